@@ -15,6 +15,11 @@ is reference-faithful ("cold"): the frozen reference-image UNet is re-run every 
 /root/reference/src/models/mvd_unet.py:287-291 does; ``--cached`` reuses its step-invariant K/V (Q5).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the ``--steps`` forwards and prints the line (``value``, ``ms_per_step``).  Everything
+else it can measure or check -- the determinism / cross-path output screens, the per-kernel-class profile and roofline, the
+CPU baseline, the attention-statistics proxy, e2e's per-phase times -- runs only with ``--full`` (each still switched off by
+its own ``--no-*`` option there).  ``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -136,6 +141,32 @@ def make_batch(pairs: int, rank: int, device, lat_hw: int = 64):
     tgt = torch.stack([look_at([45.0, 90.0, 180.0, 270.0][i % 4]) for i in range(pairs)])
     t = torch.full((pairs,), 500.0)
     return {k: v.to(device).contiguous() for k, v in dict(sample=sample, text=text, lat=lat, src=src, tgt=tgt, t=t).items()}
+
+
+# --dump-outputs: at most this many bytes of .npy files in all; the per-call random draws of the timed path (Q1's Fourier
+# projection, e2e's initial noise and posterior samples) come from torch's default generators, seeded with this before warm-up
+DUMP_BYTES_MAX = 64 << 20
+OUTPUT_SEED = 20240
+
+
+def dump_outputs(outdir: str, arrays: dict, budget: int = DUMP_BYTES_MAX) -> dict:
+    """Write each tensor as ``outdir/<name>.npy`` in float32, in its own shape.  A tensor larger than its share of ``budget``
+    is replaced by a fixed, seeded sample of its flattened elements (sorted indices, the same for the same shape), stored 1-D.
+    -> {name: [shape written, elements of the full output]}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 4096          # (room for the .npy header)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        full = a.numel()
+        if full * 4 > share:
+            g = torch.Generator().manual_seed(OUTPUT_SEED)
+            idx = torch.randint(0, full, (share // 4,), generator=g).sort().values
+            a = a.flatten()[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), a.numpy())
+        written[name] = [list(a.shape), full]
+    return written
 
 
 def cpu_baseline(timed_runs: int = 3, warmup_runs: int = 1, latent: int = 64):
@@ -287,21 +318,30 @@ def e2e_workload(args, dev):
             ts.append(time.perf_counter() - t0)
         return statistics.median(ts), out
 
+    torch.manual_seed(OUTPUT_SEED)
     for _ in range(max(1, args.warmup)):
         out = one_image()
     assert torch.isfinite(out).all() and out.shape == (1, 3, 8 * L_, 8 * L_)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_image()
+        out = one_image()
     torch.cuda.synchronize()
     per_image = (time.perf_counter() - t0) / args.steps
-    t_enc, dist = timed(lambda: vae.encode(img).latent_dist.sample(), 5)
-    lat = dist * vae.config.scaling_factor
-    t_dec, _ = timed(lambda: vae.decode(lat / vae.config.scaling_factor).sample, 5)
+    dumped = dump_outputs(args.dump_outputs, {"images": out}) if args.dump_outputs else None
     f_main, f_base = unet_flops(L_, L_, adapter=True), unet_flops(L_, L_)
     fl = nsteps * f_main + (1 if args.cached else nsteps) * f_base
-    cpu = None if args.no_cpu_baseline else cpu_baseline(1, 0, L_)
+    phases, shares, loop_tflops = None, None, None
+    if args.full:
+        t_enc, dist = timed(lambda: vae.encode(img).latent_dist.sample(), 5)
+        lat = dist * vae.config.scaling_factor
+        t_dec, _ = timed(lambda: vae.decode(lat / vae.config.scaling_factor).sample, 5)
+        phases = {"vae_encode": round(t_enc * 1e3, 2), "vae_decode": round(t_dec * 1e3, 2),
+                  "loop_and_glue": round((per_image - t_enc - t_dec) * 1e3, 2),
+                  "per_denoising_step": round((per_image - t_enc - t_dec) / nsteps * 1e3, 3)}
+        shares = {"vae": round((t_enc + t_dec) / per_image, 3), "loop": round(1 - (t_enc + t_dec) / per_image, 3)}
+        loop_tflops = round(fl / max(per_image - t_enc - t_dec, 1e-9) / 1e12, 1)
+    cpu = None if args.no_cpu_baseline or not args.full else cpu_baseline(1, 0, L_)
     line = {"metric": "images/sec end to end (VAE encode + denoising loop + VAE decode), 1 GPU", "value": round(1.0 / per_image, 4),
             "unit": "images/s", "seconds_per_image": round(per_image, 4), "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(per_image * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
@@ -310,12 +350,8 @@ def e2e_workload(args, dev):
                                    f"{'cache_reference (Q5)' if args.cached else 'reference encoder re-run every step'})",
                        "image": f"{8 * L_}x{8 * L_}", "latent": f"{L_}x{L_}x4", "denoising_steps": nsteps, "text_tokens": 77,
                        "weights": "synthetic (UNet: seeded variance-preserving; VAE: torch default init), SD-2.1 shapes"},
-            "phases_ms": {"vae_encode": round(t_enc * 1e3, 2), "vae_decode": round(t_dec * 1e3, 2),
-                          "loop_and_glue": round((per_image - t_enc - t_dec) * 1e3, 2),
-                          "per_denoising_step": round((per_image - t_enc - t_dec) / nsteps * 1e3, 3)},
-            "shares": {"vae": round((t_enc + t_dec) / per_image, 3), "loop": round(1 - (t_enc + t_dec) / per_image, 3)},
-            "unet_tflops_in_loop": round(fl / max(per_image - t_enc - t_dec, 1e-9) / 1e12, 1),
-            "cpu_baseline": cpu, "kernel_src_sha": kernel_source_sha()}
+            "phases_ms": phases, "shares": shares, "unet_tflops_in_loop": loop_tflops,
+            "cpu_baseline": cpu, "kernel_src_sha": kernel_source_sha(), "full": bool(args.full), "outputs_dumped": dumped}
     print(json.dumps(line), flush=True)
     return 0
 
@@ -385,7 +421,15 @@ def main():
     ap.add_argument("--debug-flags", type=int, default=0, help="measurement: mvd_debug_set_flags bits")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="control flow only (no GPU, gloo): process group, a small arena broadcast, barriers, max over ranks, rank 0's line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the output screens, the per-kernel-class profile and roofline, the CPU "
+                         "baseline, the attention-statistics proxy, e2e's per-phase times (each still off with its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, rank 0's shard, "
+                         "at most 64 MB: a larger output is a fixed seeded sample); inputs are seeded, the same on every run")
     args = ap.parse_args()
+    if args.shapes_out and not args.full:
+        ap.error("--shapes-out comes from the per-kernel-class profile: it needs --full")
 
     # ---- self-launch: `python bench.py --gpus N` without a launcher starts the N ranks itself.  Nothing in this process has
     # touched a GPU at this point (importing torch does not), and nothing will: the ranks are fresh children of
@@ -494,24 +538,27 @@ def main():
             return model(batch["sample"], batch["t"], batch["text"], **kw).sample
 
     out = None
+    torch.manual_seed(OUTPUT_SEED)
     for _ in range(args.warmup):
         out = step()
     torch.cuda.synchronize()
     assert out is None or torch.isfinite(out).all(), "non-finite UNet output"
-    check = None if args.no_check else output_check(model, batch, kw, step, strict_cross=args.attn_stats == "flat")
+    check = None if args.no_check or not args.full else output_check(model, batch, kw, step, strict_cross=args.attn_stats == "flat")
     D.barrier()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
     for _ in range(args.steps):
-        step()
+        out = step()
     e1.record()
     torch.cuda.synchronize()
     D.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = D.max_over_ranks(elapsed, dev)
     gpu_ms = e0.elapsed_time(e1)
+    # (before any further forward: the engine may hand back the same output buffer on the next call)
+    dumped = dump_outputs(args.dump_outputs, {"sample": out}) if args.dump_outputs and rank == 0 else None
 
     forward_kind = "base" if not use_img else ("cached" if args.cached else "cold")
     f_base, f_main = unet_flops(args.latent, args.latent), unet_flops(args.latent, args.latent, adapter=True)
@@ -524,7 +571,7 @@ def main():
     # ---- per-kernel-class timing with HIP events on the launch stream (rank 0, after the timed region)
     roofline = None
     classes = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         nprof = min(args.steps, 3)
         eng.set_profiling(True)
         for _ in range(nprof):
@@ -585,7 +632,7 @@ def main():
                               "ms_per_step_overlapped": round(overl[k]["ms"] / nprof, 3) if k in overl else None}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(3, 1)
 
     if rank == 0:
@@ -600,14 +647,14 @@ def main():
                        "weights": "synthetic seeded, SD2.1 shapes (865.9M UNet x2 + 99.2M adapter + 19.1M camera)" if args.encoder_weights == "distinct"
                        else "synthetic seeded, SD2.1 shapes; image_encoder.unet = a frozen copy of base_unet (one packed weight set for both passes)",
                        "encoder_weights": args.encoder_weights, "encoder_weights_shared": bool(getattr(model, "encoder_weights_shared", False)),
-                       "attn_stats": {"mode": args.attn_stats, **softmax_stats_proxy(q_scale)}},
+                       "attn_stats": {"mode": args.attn_stats, **(softmax_stats_proxy(q_scale) if args.full else {"q_scale": q_scale})}},
             "roofline": roofline, "cpu_baseline": cpu, "output_check": check, "kernel_src_sha": kernel_source_sha(),
             "gpu_ms_per_step_events": round(gpu_ms / args.steps, 3),
             "weight_bytes_bf16_packed": weight_bytes,
             "weight_broadcast": {"bytes": bc["bytes"], "seconds": round(bc["seconds"], 4), "buckets": bc["buckets"],
                                  "backend": D.collective_library(), "rehearsal": rehearsal},
             "ranks_seen": idents, "distinct_gpus": D.distinct_devices(idents),
-            "kernel_classes": classes,
+            "kernel_classes": classes, "full": bool(args.full), "outputs_dumped": dumped,
         }
         print(json.dumps(line), flush=True)
     D.shutdown()        # (after rank 0's line is out: a clean exit of every rank, no "process group not destroyed" noise)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Recompute roofline.frac of a bench line from a rocprofv3 --kernel-trace --stats summary of the same command:
+"""Recompute roofline.frac of a `bench.py --full` line from a rocprofv3 --kernel-trace --stats summary of the same command:
     tools/frac_from_stats.py <kernel_stats.csv> <bench line .json> [one|two]
 frac = flops_per_launch / (average duration of the dominant kernel's launches in the CSV) / peak.  `one`: the CSV is of
 `bench.py --debug-flags 16 --no-profile` (one stream: compare with roofline.avg_launch_us / frac); `two` (default): of the default
