@@ -249,6 +249,15 @@ int mvd_op_ddpm_step(const float* model_out, const float* sample, const float* n
                      float c3, float sigma, float* out, int64_t n, void* stream);
 /* classifier-free guidance combine of [uncond | cond] stacked on the batch dim (pipeline.py:156-158) */
 int mvd_op_cfg_combine(const float* uncond_cond, float guidance_scale, float* out, int64_t n_half, void* stream);
+/* One DDIM / DPM-Solver++ step (mvd_amd/scheduler.py computes the per-step scalars on the host; nothing is uploaded):
+ *   m = guided ? u + guidance_scale*(c - u) : model_out   ([uncond | cond] stacked on the batch dim: 2n floats when guided)
+ *   x0 = a0*m + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; if (x0_out) x0_out = x0 (multistep history).
+ * x0_prev may be NULL iff r == 0, noise may be NULL iff sigma == 0, n % 4 == 0; otherwise -1 (mvd_last_error).  In place is
+ * allowed for out == sample and x0_out == x0_prev (every element is read and then written by the same thread); no other
+ * argument may overlap an output. */
+int mvd_op_sampler_step(const float* model_out, int guided, float guidance_scale, const float* sample, const float* x0_prev,
+                        const float* noise, float a0, float a1, float p, float q, float r, float sigma, float* out,
+                        float* x0_out, int64_t n, void* stream);
 
 /* ---- AutoencoderKL (SD-2.1 VAE) either side of the loop ------------------------------------ */
 /* Replaces: vae.encode(x).latent_dist (pipeline.py:115) and vae.decode(z).sample (pipeline.py:171-176) of diffusers'

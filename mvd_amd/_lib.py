@@ -113,6 +113,8 @@ _SIGS = {
     "mvd_op_ddpm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "mvd_op_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvd_op_sampler_step": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mvd_vae_create": (C.c_int, [C.POINTER(mvd_vae_config_t), C.POINTER(C.c_void_p)]),
     "mvd_vae_destroy": (C.c_int, [C.c_void_p]),
     "mvd_vae_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),

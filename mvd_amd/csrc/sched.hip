@@ -1,5 +1,6 @@
-// Denoising-loop helpers around the UNet: the DDPM ancestral step and the
-// classifier-free-guidance combine as single fused elementwise kernels (fp32 latents, 16-byte vectors).
+// Denoising-loop helpers around the UNet: the DDPM ancestral step, the
+// classifier-free-guidance combine and the guided DDIM / DPM-Solver++ step as single fused elementwise kernels
+// (fp32 latents, 16-byte vectors).
 // Follows /root/reference/src/models/pipeline.py:156-161 and the diffusers-0.32.2 DDPMScheduler.step algebra;
 // the per-step scalar coefficients are computed on the host (mvd_amd/scheduler.py) so the loop never syncs.
 #include "kernels.h"
@@ -26,6 +27,25 @@ __global__ void cfg_combine_kernel(const float* __restrict__ both, float g, floa
   }
 }
 
+// The DDIM / DPM-Solver++ step (mvd_amd/scheduler.py), affine in (model output, sample, previous x0, noise):
+//   m = guided ? u + g*(c - u) : model_out ; x0 = a0*m + a1*x ; y = p*x + q*x0 + r*d + sigma*z ; x0o = x0.
+// x / y and d / x0o may alias (each element is read, then written, by the same thread): no __restrict__ on them.
+__global__ void sampler_step_kernel(const float* __restrict__ mo, int guided, float g, const float* x, const float* d,
+                                    const float* __restrict__ nz, float a0, float a1, float p, float q, float r, float sigma,
+                                    float* y, float* x0o, long n4) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    f32x4 m = reinterpret_cast<const f32x4*>(mo)[i];
+    if (guided) m = m + (reinterpret_cast<const f32x4*>(mo)[i + n4] - m) * g;
+    const f32x4 s = reinterpret_cast<const f32x4*>(x)[i];
+    const f32x4 x0 = m * a0 + s * a1;
+    f32x4 o = s * p + x0 * q;
+    if (d) o += reinterpret_cast<const f32x4*>(d)[i] * r;
+    if (nz) o += reinterpret_cast<const f32x4*>(nz)[i] * sigma;
+    reinterpret_cast<f32x4*>(y)[i] = o;
+    if (x0o) reinterpret_cast<f32x4*>(x0o)[i] = x0;
+  }
+}
+
 int grid_for(long n4) { long g = (n4 + 255) / 256; return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g)); }
 
 }  // namespace
@@ -47,5 +67,19 @@ extern "C" int mvd_op_cfg_combine(const float* uncond_cond, float guidance_scale
                      (long)(n_half / 4));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mvd_set_error("cfg_combine launch: %s", hipGetErrorString(e)); return -3; }
+  return 0;
+}
+
+extern "C" int mvd_op_sampler_step(const float* model_out, int guided, float guidance_scale, const float* sample,
+                                   const float* x0_prev, const float* noise, float a0, float a1, float p, float q, float r,
+                                   float sigma, float* out, float* x0_out, int64_t n, void* stream) {
+  if (!model_out || !sample || !out || n <= 0 || (n & 3)) { mvd_set_error("sampler_step: bad arguments (n must be a multiple of 4)"); return -1; }
+  if (!x0_prev && r != 0.f) { mvd_set_error("sampler_step: x0_prev required when r != 0"); return -1; }
+  if (!noise && sigma != 0.f) { mvd_set_error("sampler_step: noise required when sigma != 0"); return -1; }
+  hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, model_out, guided ? 1 : 0,
+                     guidance_scale, sample, r != 0.f ? x0_prev : nullptr, sigma != 0.f ? noise : nullptr, a0, a1, p, q, r, sigma,
+                     out, x0_out, (long)(n / 4));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { mvd_set_error("sampler_step launch: %s", hipGetErrorString(e)); return -3; }
   return 0;
 }

@@ -210,6 +210,23 @@ def cfg_combine(uncond_cond, guidance_scale):
     return out
 
 
+def sampler_step(model_out, sample, a0, a1, p, q, r=0.0, sigma=0.0, x0_prev=None, noise=None, guidance_scale=None,
+                 out=None, x0_out=None):
+    """fp32 DDIM / DPM-Solver++ step: m = model_out, or u + g*(c - u) of the stacked (2B, ...) [uncond | cond] when
+    ``guidance_scale`` is given; x0 = a0*m + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; x0_out = x0.
+    ``x0_prev`` may be None iff r == 0, ``noise`` iff sigma == 0.  ``out`` may be ``sample`` and ``x0_out`` may be ``x0_prev``."""
+    guided = guidance_scale is not None
+    assert model_out.dtype == torch.float32 and sample.dtype == torch.float32
+    assert model_out.numel() == sample.numel() * (2 if guided else 1), (tuple(model_out.shape), tuple(sample.shape))
+    for t in (x0_prev, noise, out, x0_out):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == sample.numel())
+    if out is None:
+        out = torch.empty_like(sample)
+    L.call("mvd_op_sampler_step", _p(model_out), int(guided), float(guidance_scale) if guided else 0.0, _p(sample), _p(x0_prev),
+           _p(noise), float(a0), float(a1), float(p), float(q), float(r), float(sigma), _p(out), _p(x0_out), sample.numel(), _s())
+    return out
+
+
 def skinny_linear(x, w, bias=None, silu_in=False):
     """fp32 linear layer of the camera / time MLPs: x (B, K) fp32, w (N, K) fp32 or bf16 -> (B, N) fp32."""
     assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 2 and w.dim() == 2 and w.shape[1] == x.shape[1]

@@ -14,7 +14,9 @@ from ``from_pretrained``.  diffusers / SD-2.1 weights do not exist in this image
   ``decode(z).sample``, ``config.scaling_factor``); ``mvd_amd.vae.AutoencoderKLHIP`` is the engine-backed one (row N3).
 
 Reference quirk Q7 is kept: ``ref_scale``, ``use_camera_embeddings`` and ``use_image_conditioning`` are accepted and
-unused (pipeline.py:34-36, 134-135); the effective switches live on the UNet.
+unused (pipeline.py:34-36, 134-135); the effective switches live on the UNet.  ``eta`` is likewise accepted and never
+forwarded (pipeline.py:161 calls ``scheduler.step`` without it), so with ``sampler="ddim"`` this pipeline runs DDIM at
+eta = 0; a caller who wants the stochastic form drives ``DDIMScheduler.step(..., eta=)`` directly.
 """
 from __future__ import annotations
 
@@ -64,18 +66,23 @@ class MVDDenoiser:
         # Q5: the reference K/V of a previous call (another object) must never be reused by this one
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
+        guided_step = getattr(self.scheduler, "step_guided", None)              # DDIM / DPM-Solver++ (DDPM has none)
         ts_host = self.scheduler.timesteps.tolist()                             # host ints for the scheduler's coefficients
         ts_dev = torch.tensor(ts_host, dtype=torch.float32, device=dev)         # ONE upload: a per-step scalar upload would make
         for i, t in enumerate(ts_host):                                         # the host wait for the previous step's kernels
             x_in = torch.cat([latents] * 2) if guidance_scale > 1.0 else latents  # pipeline.py:141
             out = self.unet(sample=x_in, timestep=ts_dev[i], encoder_hidden_states=embeds,
                             cross_attention_kwargs=cross_attention_kwargs, **extra).sample
-            if guidance_scale > 1.0:                                            # pipeline.py:156-158
-                out = ops.cfg_combine(out.float().contiguous(), guidance_scale)
             nz = None if noise_per_step is None else noise_per_step[i]
-            # pipeline.py:161 calls scheduler.step(noise_pred, t, latents) WITHOUT the generator: the ancestral noise comes from
-            # torch's global RNG (of the latents' device), the caller's generator only seeds the initial latents
-            latents = self.scheduler.step(out.float().contiguous(), t, latents, noise=nz).prev_sample
+            if guidance_scale > 1.0 and guided_step is not None:
+                # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch
+                latents = guided_step(out.float().contiguous(), guidance_scale, t, latents, noise=nz).prev_sample
+            else:
+                if guidance_scale > 1.0:                                        # pipeline.py:156-158
+                    out = ops.cfg_combine(out.float().contiguous(), guidance_scale)
+                # pipeline.py:161 calls scheduler.step(noise_pred, t, latents) WITHOUT the generator: the ancestral noise comes
+                # from torch's global RNG (of the latents' device), the caller's generator only seeds the initial latents
+                latents = self.scheduler.step(out.float().contiguous(), t, latents, noise=nz).prev_sample
             if callback is not None and i % callback_steps == 0:                # pipeline.py:165-166
                 callback(i, t, latents)
         return latents
@@ -224,6 +231,35 @@ def _scheduler_from_snapshot(path) -> "Any":
     return DDPMScheduler(**cfg)
 
 
+SAMPLERS = ("ddpm", "ddim", "dpmsolver++")
+
+
+def _sampler_config_from_snapshot(path) -> Dict[str, Any]:
+    """The fields of the snapshot's scheduler config that the DDIM / DPM-Solver++ schedulers read beyond the DDPM ones
+    (``steps_offset`` / ``timestep_spacing`` / ``set_alpha_to_one``); {} without a snapshot (the classes' defaults)."""
+    f = os.path.join(str(path), "scheduler", "scheduler_config.json") if path else ""
+    if not (f and os.path.exists(f)):
+        return {}
+    raw = json.load(open(f))
+    return {k: raw[k] for k in ("steps_offset", "timestep_spacing", "set_alpha_to_one") if k in raw}
+
+
+def _make_scheduler(path, sampler: str):
+    """The interpolated SNR shift (scale 6, mvd_unet.py:420-428) of the snapshot's schedule, handed to the chosen
+    sampler's class (``ShiftSNRScheduler.from_scheduler(..., scheduler_class=)``)."""
+    from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, ShiftSNRScheduler
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
+    base_scheduler = _scheduler_from_snapshot(path)
+    if sampler == "ddpm":
+        return ShiftSNRScheduler.from_scheduler(noise_scheduler=base_scheduler, shift_mode="interpolated", shift_scale=6.0,
+                                                scheduler_class=DDPMScheduler)
+    base_scheduler.config = SimpleNamespace(**{**vars(base_scheduler.config), **_sampler_config_from_snapshot(path)})
+    cls = DDIMScheduler if sampler == "ddim" else DPMSolverMultistepScheduler
+    return ShiftSNRScheduler.from_scheduler(noise_scheduler=base_scheduler, shift_mode="interpolated", shift_scale=6.0,
+                                            scheduler_class=cls)
+
+
 def _optional_components(path, dtype):
     """VAE / CLIP from a local diffusers snapshot when both the libraries and the files exist; None otherwise."""
     vae = text_encoder = tokenizer = None
@@ -255,19 +291,19 @@ def _optional_components(path, dtype):
 
 def build_pipeline(pretrained_model_name_or_path, dtype, use_camera_conditioning, use_image_conditioning, img_ref_scale,
                    cam_modulation_strength, cam_output_dim, cam_hidden_dim, simple_cam_encoder, cache_dir=None,
-                   unet_config=None, init: str = "default") -> MVDPipeline:
+                   unet_config=None, init: str = "default", *, sampler: str = "ddpm") -> MVDPipeline:
     """``create_mvd_pipeline`` (mvd_unet.py:388-453): scheduler swap to the interpolated SNR shift (scale 6, hard-coded
     there, :420-428), ``MultiViewUNet`` as ``pipeline.unet``, the three attributes of :449-451.  Nothing is fetched: the
-    name resolves to local snapshot files (hub.resolve_snapshot) or the call raises."""
+    name resolves to local snapshot files (hub.resolve_snapshot) or the call raises.  ``sampler``: "ddpm" (the
+    reference's ancestral DDPM, the default), "ddim" or "dpmsolver++" -- the same shifted schedule in another class."""
     from .hub import resolve_snapshot
     from .mvd_unet import MultiViewUNet
-    from .scheduler import DDPMScheduler, ShiftSNRScheduler
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
     # MVDPipeline.from_pretrained(name, cache_dir=...) (mvd_unet.py:411-415): a directory, or a hub name whose snapshot is in a
     # local huggingface cache; a name nothing local answers to raises MvdError (never a random-initialised pipeline)
     pretrained_model_name_or_path = resolve_snapshot(pretrained_model_name_or_path, cache_dir)
-    base_scheduler = _scheduler_from_snapshot(pretrained_model_name_or_path)
-    scheduler = ShiftSNRScheduler.from_scheduler(noise_scheduler=base_scheduler, shift_mode="interpolated", shift_scale=6.0,
-                                                 scheduler_class=DDPMScheduler)
+    scheduler = _make_scheduler(pretrained_model_name_or_path, sampler)
     unet = MultiViewUNet(pretrained_model_name_or_path, dtype=dtype, img_ref_scale=img_ref_scale,
                          cam_modulation_strength=cam_modulation_strength, cam_output_dim=cam_output_dim,
                          cam_hidden_dim=cam_hidden_dim, simple_cam_encoder=simple_cam_encoder,

@@ -6,12 +6,19 @@
   (``from_config(..., trained_betas=)``, ``set_timesteps``, ``step`` with ``variance_type="fixed_small"``,
   epsilon / v_prediction, no sample clipping -- the SD-2.1 scheduler config).  diffusers is not installed here, so
   this part is unpinned (checked against a numpy restatement in oracle/scheduler.py only).
+* ``DDIMScheduler`` (Song et al. 2021) and ``DPMSolverMultistepScheduler`` (Lu et al. 2022, DPM-Solver++ multistep,
+  data prediction, orders 1 / 2) restate the diffusers-0.32.2 algebra of those classes for the config subset named in
+  their docstrings; anything outside it raises ValueError.  Also unpinned against diffusers; pinned instead by
+  first-principles identities (tests/test_samplers_cpu.py: DDIM(eta=1) == the DDPM step, DDIM(eta=0) == DPM-Solver++
+  order 1, exactness on point-mass data, convergence to the exact probability-flow ODE solution on Gaussian data).
 
 Everything here is scalar / length-1000 vector math on the host; the per-step tensor update is one fused HIP
-kernel (``mvd_op_ddpm_step``) whose four coefficients are computed here, so the loop never syncs the device.
+kernel (``mvd_op_ddpm_step``, ``mvd_op_sampler_step``) whose coefficients are computed here, so the loop never syncs
+the device.
 """
 from __future__ import annotations
 
+import math
 from types import SimpleNamespace
 from typing import Any, Optional
 
@@ -114,6 +121,293 @@ class DDPMScheduler:
             noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
         prev = ops.ddpm_step(model_output, sample, noise, c0, c1, c2, c3, sigma)
         return SimpleNamespace(prev_sample=prev)
+
+
+_PREDICTION_TYPES = ("epsilon", "v_prediction")
+_SPACINGS = ("leading", "linspace", "trailing")
+
+
+def _unsupported(what: str):
+    raise ValueError(f"{what} is not implemented (supported: epsilon / v_prediction, no clipping or thresholding, "
+                     f"timestep_spacing leading / linspace / trailing); nothing is approximated")
+
+
+class _SolverSchedule:
+    """What the DDIM and DPM-Solver++ classes share: the trained schedule (built by the same torch ops as
+    ``DDPMScheduler``, so ShiftSNRScheduler's betas give bit-identical ``alphas_cumprod``), ``from_config`` and the
+    timestep grid of diffusers' ``set_timesteps``."""
+
+    order = 1                       # diffusers' attribute (one model evaluation per step)
+    init_noise_sigma = 1.0
+
+    def _init_schedule(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                       timestep_spacing):
+        if prediction_type not in _PREDICTION_TYPES:
+            _unsupported(f"prediction_type={prediction_type!r}")
+        if timestep_spacing not in _SPACINGS:
+            _unsupported(f"timestep_spacing={timestep_spacing!r}")
+        if trained_betas is not None:
+            self.betas = torch.as_tensor(np.asarray(trained_betas), dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            raise ValueError(f"unsupported beta_schedule {beta_schedule}")
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._acp = self.alphas_cumprod.double().numpy()       # host copy: the coefficients never touch a device tensor
+        self.one = torch.tensor(1.0)
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
+
+    @classmethod
+    def from_config(cls, config: Any, **overrides):
+        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
+        d.update(overrides)
+        return cls(**d)
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    def _grid(self, n: int, extra: int) -> np.ndarray:
+        """diffusers' grid of ``n`` timesteps; DPM-Solver++ (``extra`` = 1) spaces n + 1 points and drops the last."""
+        T, spacing = self.config.num_train_timesteps, self.config.timestep_spacing
+        if not 0 < n <= T:
+            raise ValueError(f"num_inference_steps={n} must be in [1, {T}]")
+        if spacing == "leading":
+            ratio = T // (n + extra)
+            ts = (np.arange(0, n + extra) * ratio).round()[::-1][:n].copy().astype(np.int64) + self.config.steps_offset
+        elif spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + extra).round()[::-1][:n].copy().astype(np.int64)
+        else:
+            ts = np.round(np.arange(T, 0, -T / n)).astype(np.int64) - 1
+        return ts
+
+    def _x0_coefficients(self, alpha: float, sigma_bar: float):
+        """x0 = a0*model_out + a1*sample, with sample = alpha*x0 + sigma_bar*eps (alpha^2 + sigma_bar^2 = 1)."""
+        if self.config.prediction_type == "epsilon":
+            return -sigma_bar / alpha, 1.0 / alpha
+        return -sigma_bar, alpha                                # v_prediction
+
+    def _launch(self, model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None):
+        from . import ops
+        a0, a1, p, q, r, sigma = coeffs
+        if sigma != 0.0 and noise is None:
+            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        return ops.sampler_step(model_out, sample, a0, a1, p, q, r, sigma, x0_prev=x0_prev if r != 0.0 else None,
+                                noise=noise if sigma != 0.0 else None, guidance_scale=guidance_scale, x0_out=x0_out)
+
+
+class DDIMScheduler(_SolverSchedule):
+    """diffusers-0.32.2 ``DDIMScheduler`` (Song et al. 2021) for epsilon / v_prediction, no sample clipping or
+    thresholding, ``timestep_spacing`` leading / linspace / trailing with ``steps_offset``, ``set_alpha_to_one``, and
+    ``eta`` as a ``step`` keyword (0: deterministic; 1: the DDPM posterior).  Defaults are SD-2.1's betas and
+    v_prediction, as ``DDPMScheduler`` here.  Fields of other schedulers' configs (``variance_type``, ...) are ignored."""
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "scaled_linear", trained_betas=None, clip_sample: bool = False,
+                 set_alpha_to_one: bool = True, steps_offset: int = 0, prediction_type: str = "v_prediction",
+                 thresholding: bool = False, timestep_spacing: str = "leading", rescale_betas_zero_snr: bool = False,
+                 **_ignored):
+        if clip_sample or thresholding or rescale_betas_zero_snr:
+            _unsupported("clip_sample / thresholding / rescale_betas_zero_snr")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
+                                      steps_offset=steps_offset, prediction_type=prediction_type, thresholding=thresholding,
+                                      timestep_spacing=timestep_spacing, rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                            timestep_spacing)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        self.num_inference_steps = num_inference_steps
+        ts = torch.from_numpy(self._grid(num_inference_steps, 0))
+        self.timesteps = ts.to(device) if device is not None else ts
+
+    def previous_timestep(self, t: int) -> int:
+        n = self.num_inference_steps or self.config.num_train_timesteps
+        return t - self.config.num_train_timesteps // n
+
+    def step_coefficients(self, t: int, eta: float = 0.0):
+        """(a0, a1, p, q, r, sigma) of one DDIM step: x0 = a0*model_out + a1*sample ;
+        prev = p*sample + q*x0 + sigma*noise (r = 0: no history).  The predicted noise is written as
+        (sample - sqrt(a_t)*x0) / sqrt(1 - a_t), which makes the update affine in (model_out, sample, noise)."""
+        t = int(t)
+        prev_t = self.previous_timestep(t)
+        a_t = float(self._acp[t])
+        a_prev = float(self._acp[prev_t]) if prev_t >= 0 else float(self.final_alpha_cumprod)
+        b_t, b_prev = 1.0 - a_t, 1.0 - a_prev
+        variance = (b_prev / b_t) * (1.0 - a_t / a_prev)
+        std = float(eta) * math.sqrt(max(variance, 0.0))
+        a0, a1 = self._x0_coefficients(math.sqrt(a_t), math.sqrt(b_t))
+        c_dir = math.sqrt(max(b_prev - std * std, 0.0))         # coefficient of the predicted noise
+        p = c_dir / math.sqrt(b_t)
+        q = math.sqrt(a_prev) - c_dir * math.sqrt(a_t) / math.sqrt(b_t)
+        return a0, a1, p, q, 0.0, std
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0,
+             use_clipped_model_output: bool = False, generator: Optional[torch.Generator] = None,
+             variance_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """One DDIM step on the GPU (one fused HIP kernel); returns an object with ``prev_sample``.  For eta > 0 the noise
+        is ``noise`` / ``variance_noise`` or a draw from ``generator`` (torch's global RNG when None)."""
+        if use_clipped_model_output:
+            _unsupported("use_clipped_model_output")
+        c = self.step_coefficients(int(timestep), eta)
+        nz = noise if noise is not None else variance_noise
+        return SimpleNamespace(prev_sample=self._launch(model_output, None, c, sample, nz, generator))
+
+    def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
+                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, eta: float = 0.0):
+        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch."""
+        c = self.step_coefficients(int(timestep), eta)
+        return SimpleNamespace(prev_sample=self._launch(uncond_cond, guidance_scale, c, sample, noise, generator))
+
+
+class DPMSolverMultistepScheduler(_SolverSchedule):
+    """diffusers-0.32.2 ``DPMSolverMultistepScheduler`` (Lu et al. 2022) for ``algorithm_type="dpmsolver++"`` (data
+    prediction), ``solver_order`` 1 / 2, ``solver_type`` midpoint / heun, ``final_sigmas_type="zero"``, epsilon /
+    v_prediction, ``timestep_spacing`` leading / linspace / trailing with ``steps_offset``, ``lower_order_final`` /
+    ``euler_at_final``.  Defaults are SD-2.1's betas and v_prediction, as ``DDPMScheduler`` here.  The sigmas are kept
+    in float64 (diffusers rounds them to float32: a relative difference below 1e-7).
+
+    The multistep history (the previous step's x0) is one device buffer per (shape, device), written in place by the
+    step kernel; ``set_timesteps`` resets the step index and the history."""
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "scaled_linear", trained_betas=None, solver_order: int = 2,
+                 prediction_type: str = "v_prediction", thresholding: bool = False, algorithm_type: str = "dpmsolver++",
+                 solver_type: str = "midpoint", lower_order_final: bool = True, euler_at_final: bool = False,
+                 use_karras_sigmas: bool = False, use_exponential_sigmas: bool = False, use_beta_sigmas: bool = False,
+                 use_lu_lambdas: bool = False, final_sigmas_type: str = "zero", lambda_min_clipped: float = -float("inf"),
+                 variance_type: Optional[str] = None, timestep_spacing: str = "linspace", steps_offset: int = 0,
+                 rescale_betas_zero_snr: bool = False, **_ignored):
+        if algorithm_type != "dpmsolver++":
+            _unsupported(f"algorithm_type={algorithm_type!r}")
+        if solver_order not in (1, 2):
+            _unsupported(f"solver_order={solver_order}")
+        if solver_type not in ("midpoint", "heun"):
+            _unsupported(f"solver_type={solver_type!r}")
+        if thresholding or use_karras_sigmas or use_exponential_sigmas or use_beta_sigmas or use_lu_lambdas:
+            _unsupported("thresholding / Karras, exponential, beta sigmas / Lu lambdas")
+        if final_sigmas_type != "zero" or lambda_min_clipped != -float("inf") or rescale_betas_zero_snr:
+            _unsupported("final_sigmas_type != 'zero' / lambda_min_clipped / rescale_betas_zero_snr")
+        if variance_type in ("learned", "learned_range"):
+            _unsupported(f"variance_type={variance_type!r}")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                                      thresholding=thresholding, algorithm_type=algorithm_type, solver_type=solver_type,
+                                      lower_order_final=lower_order_final, euler_at_final=euler_at_final,
+                                      use_karras_sigmas=use_karras_sigmas, use_exponential_sigmas=use_exponential_sigmas,
+                                      use_beta_sigmas=use_beta_sigmas, use_lu_lambdas=use_lu_lambdas,
+                                      final_sigmas_type=final_sigmas_type, lambda_min_clipped=lambda_min_clipped,
+                                      variance_type=variance_type, timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                            timestep_spacing)
+        self.sigmas = None
+        self._hist = {}             # (shape, device) -> the x0 history buffer
+        self._hist_key = None       # the buffer the previous step of this schedule wrote
+        self._step_index = None
+        self.lower_order_nums = 0
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
+        """The spaced grid of ``num_inference_steps`` timesteps, or an explicit integer grid ``timesteps``."""
+        if (num_inference_steps is None) == (timesteps is None):
+            raise ValueError("pass exactly one of num_inference_steps / timesteps")
+        T = self.config.num_train_timesteps
+        if timesteps is not None:
+            ts = np.asarray(timesteps).astype(np.int64)
+            if ts.ndim != 1 or ts.size == 0 or ts.min() < 0 or ts.max() >= T:
+                raise ValueError(f"timesteps must be a non-empty 1-D grid in [0, {T - 1}]")
+        else:
+            ts = self._grid(int(num_inference_steps), 1)
+        acp = self._acp[ts]
+        self._sig = [float(s) for s in np.sqrt((1.0 - acp) / acp)] + [0.0]       # final_sigmas_type "zero"
+        self.sigmas = torch.tensor(self._sig, dtype=torch.float64)
+        self.timesteps = torch.from_numpy(ts.copy())
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self._ts_host = ts.tolist()
+        self.num_inference_steps = len(ts)
+        self._step_index = None
+        self.lower_order_nums = 0
+        self._hist_key = None
+
+    def _order(self, i: int, lower_order_nums: int) -> int:
+        n = len(self._ts_host)
+        lower_final = i == n - 1 and (self.config.euler_at_final or (self.config.lower_order_final and n < 15)
+                                      or self.config.final_sigmas_type == "zero")
+        return 1 if self.config.solver_order == 1 or lower_order_nums < 1 or lower_final else 2
+
+    def step_coefficients(self, step_index: int, order: Optional[int] = None):
+        """(a0, a1, p, q, r, sigma) of step ``step_index``: x0 = a0*model_out + a1*sample ;
+        prev = p*sample + q*x0 + r*x0_prev (sigma = 0).  ``order`` defaults to the one a run from step 0 uses."""
+        if self.sigmas is None:
+            raise ValueError("call set_timesteps first")
+        i = int(step_index)
+        if order is None:
+            order = self._order(i, min(i, self.config.solver_order))
+        lam = lambda a, sb: math.inf if sb == 0.0 else math.log(a) - math.log(sb)      # noqa: E731
+        s0, st = self._sig[i], self._sig[i + 1]
+        alpha_s0 = 1.0 / math.sqrt(s0 * s0 + 1.0)
+        alpha_t = 1.0 / math.sqrt(st * st + 1.0)
+        sb_s0, sb_t = s0 * alpha_s0, st * alpha_t
+        a0, a1 = self._x0_coefficients(alpha_s0, sb_s0)
+        h = lam(alpha_t, sb_t) - lam(alpha_s0, sb_s0)
+        em1 = math.expm1(-h)                                    # e^{-h} - 1 (-1 at the zero final sigma, h = +inf)
+        p, q, r = sb_t / sb_s0, -alpha_t * em1, 0.0
+        if order == 2:
+            if st == 0.0:
+                raise ValueError("a second-order step onto the zero final sigma is undefined (diffusers takes order 1 there)")
+            s1 = self._sig[i - 1]
+            alpha_s1 = 1.0 / math.sqrt(s1 * s1 + 1.0)
+            r0 = (lam(alpha_s0, sb_s0) - lam(alpha_s1, s1 * alpha_s1)) / h
+            if self.config.solver_type == "midpoint":           # - 1/2 alpha_t (e^{-h} - 1) D1,  D1 = (x0 - x0_prev) / r0
+                c = -0.5 * alpha_t * em1 / r0
+            else:                                               # + alpha_t ((e^{-h} - 1)/h + 1) D1
+                c = alpha_t * (em1 / h + 1.0) / r0
+            q, r = q + c, -c
+        return a0, a1, p, q, r, 0.0
+
+    def _step(self, model_output, guidance_scale, timestep, sample):
+        if self.sigmas is None:
+            raise ValueError("call set_timesteps first")
+        if self._step_index is None:                           # diffusers' index_for_timestep
+            hits = [k for k, v in enumerate(self._ts_host) if v == int(timestep)]
+            self._step_index = len(self._ts_host) - 1 if not hits else hits[1] if len(hits) > 1 else hits[0]
+        i = self._step_index
+        if i >= len(self._ts_host):
+            raise ValueError("step called more often than the schedule has timesteps: call set_timesteps again")
+        c = self.step_coefficients(i, self._order(i, self.lower_order_nums))
+        key = (tuple(sample.shape), sample.device)
+        hist = None
+        if self.config.solver_order > 1:
+            hist = self._hist.get(key)
+            if hist is None:
+                hist = self._hist[key] = torch.empty(sample.shape, device=sample.device, dtype=torch.float32)
+        if c[4] != 0.0 and self._hist_key != key:
+            raise ValueError("a second-order step needs the previous step's x0 of the same shape and device")
+        out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist)
+        self._hist_key = key if hist is not None else None
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
+        self._step_index = i + 1
+        return out
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator: Optional[torch.Generator] = None,
+             noise: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """One DPM-Solver++ step on the GPU (one fused HIP kernel, which also stores this step's x0 for the next);
+        returns an object with ``prev_sample``.  Deterministic: ``generator`` / ``noise`` are accepted and unused."""
+        return SimpleNamespace(prev_sample=self._step(model_output, None, timestep, sample))
+
+    def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
+                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None):
+        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch."""
+        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample))
 
 
 class ShiftSNRScheduler:
