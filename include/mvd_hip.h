@@ -282,6 +282,15 @@ int mvd_vae_bind_workspace(mvd_vae_t* v, void* ws, int64_t ws_bytes);
 int mvd_vae_encode(mvd_vae_t* v, const float* image_nchw, int batch, int height, int width, float* moments, void* stream);
 /* latents [batch][latent][h][w] fp32 (already divided by the scaling factor) -> image [batch][in_channels][f*h][f*w] fp32 */
 int mvd_vae_decode(mvd_vae_t* v, const float* latents_nchw, int batch, int height, int width, float* image, void* stream);
+/* One mid-block attention (GroupNorm, q / k / v, softmax(q.k^T / sqrt(C)).v, out-projection + residual) of the encoder
+ * (decoder = 0) or the decoder (decoder = 1), with the weights set on v, on caller buffers: x, out [batch][height][width][C]
+ * bf16 NHWC, C = the deepest level's channel count; height * width must be a multiple of 64.  The same code as inside
+ * mvd_vae_encode / mvd_vae_decode.  Checks the bound workspace before it launches anything. */
+int64_t mvd_vae_mid_attention_workspace_bytes(mvd_vae_t* v, int decoder, int batch, int height, int width);
+int mvd_vae_mid_attention(mvd_vae_t* v, int decoder, const void* x_nhwc_bf16, int batch, int height, int width, void* out_nhwc_bf16,
+                          void* stream);
+/* The attention's row softmax: p[r][i] = exp(s[r][i] - max_r) / sum_r, fp32 scores [rows][n] -> bf16 probabilities */
+int mvd_op_softmax_rows(const float* s, int rows, int n, void* p_bf16, void* stream);
 /* DiagonalGaussianDistribution.sample(): out = (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scale; noise/out [batch][c][hw] */
 int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, int channels, int hw, float scale, float* out,
                            void* stream);

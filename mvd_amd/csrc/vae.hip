@@ -292,6 +292,20 @@ int encode_impl(mvd_vae* v, const float* image, int B, int H, int W_, float* mom
   return 0;
 }
 
+// one mid-block attention (the encoder's or the decoder's weights) on caller buffers: the same VCtx::attention that
+// encode_impl / decode_impl run inside mid(), for the operator-level tests
+int mid_attention_impl(mvd_vae* v, int decoder, const bf16_t* x_nhwc, int B, int H, int W_, bf16_t* out_nhwc, hipStream_t s, bool dry) {
+  if (B <= 0 || H <= 0 || W_ <= 0 || (decoder != 0 && decoder != 1)) { mvd_set_error("vae mid_attention: bad shape or coder"); return -1; }
+  v->ar.dry = dry; v->ar.off = v->ar.high = 0;
+  VCtx x{v, s, dry};
+  VAct in;
+  in.p = const_cast<bf16_t*>(x_nhwc); in.B = B; in.H = H; in.W = W_; in.C = v->cfg.block_out_channels[v->cfg.num_levels - 1];
+  VAct out = in;
+  out.p = out_nhwc;
+  VCHECK(x.attention(decoder ? "decoder.mid_block.attn" : "encoder.mid_block.attn", in, out));
+  return x.err;
+}
+
 int decode_impl(mvd_vae* v, const float* latents, int B, int h_, int w_, float* image, hipStream_t s, bool dry) {
   const mvd_vae_config_t& c = v->cfg;
   const int n = c.num_levels;
@@ -379,6 +393,26 @@ int mvd_vae_decode(mvd_vae_t* v, const float* latents_nchw, int batch, int heigh
   if (int r = decode_impl(v, nullptr, batch, height, width, nullptr, nullptr, true)) return r;
   if (v->ar.high > (size_t)v->ws_bytes) { mvd_set_error("vae_decode: workspace too small: need %zu bytes, bound %lld", v->ar.high, (long long)v->ws_bytes); return -4; }
   return decode_impl(v, latents_nchw, batch, height, width, image, (hipStream_t)stream, false);
+}
+
+int64_t mvd_vae_mid_attention_workspace_bytes(mvd_vae_t* v, int decoder, int batch, int height, int width) {
+  if (!v) { mvd_set_error("vae_mid_attention_workspace_bytes: null handle"); return -1; }
+  if (int r = mid_attention_impl(v, decoder, nullptr, batch, height, width, nullptr, nullptr, true)) return r;
+  return (int64_t)v->ar.high + 4096;
+}
+
+int mvd_vae_mid_attention(mvd_vae_t* v, int decoder, const void* x_nhwc, int batch, int height, int width, void* out_nhwc, void* stream) {
+  if (!v || !x_nhwc || !out_nhwc) { mvd_set_error("vae_mid_attention: null argument"); return -1; }
+  if (!v->ws_ptr) { mvd_set_error("vae_mid_attention: workspace not bound"); return -1; }
+  if (int r = mid_attention_impl(v, decoder, nullptr, batch, height, width, nullptr, nullptr, true)) return r;   // size first
+  if (v->ar.high > (size_t)v->ws_bytes) { mvd_set_error("vae_mid_attention: workspace too small: need %zu bytes, bound %lld", v->ar.high, (long long)v->ws_bytes); return -4; }
+  return mid_attention_impl(v, decoder, (const bf16_t*)x_nhwc, batch, height, width, (bf16_t*)out_nhwc, (hipStream_t)stream, false);
+}
+
+int mvd_op_softmax_rows(const float* s, int rows, int n, void* p_bf16, void* stream) {
+  if (!s || !p_bf16 || rows <= 0 || n <= 0) { mvd_set_error("softmax_rows: bad argument"); return -1; }
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, s, n, (bf16_t*)p_bf16);
+  return vcheck("softmax_rows");
 }
 
 int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, int channels, int hw, float scale, float* out, void* stream) {

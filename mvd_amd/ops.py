@@ -192,6 +192,14 @@ def conv_out(x, w, bias):
     return y
 
 
+def softmax_rows(s):
+    """The VAE attention's row softmax (vae.hip): s (rows, n) fp32 -> (rows, n) bf16 probabilities."""
+    assert s.dtype == torch.float32 and s.dim() == 2
+    out = torch.empty(s.shape, device=s.device, dtype=torch.bfloat16)
+    L.call("mvd_op_softmax_rows", _p(s), s.shape[0], s.shape[1], _p(out), _s())
+    return out
+
+
 def ddpm_step(model_out, sample, noise, c0, c1, c2, c3, sigma):
     """fp32: x0 = c0*model_out + c1*sample ; prev = c2*x0 + c3*sample + sigma*noise (noise may be None iff sigma == 0)."""
     assert model_out.dtype == torch.float32 and sample.dtype == torch.float32

@@ -281,6 +281,26 @@ class AutoencoderKLHIP(nn.Module):
             self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
         L.call("mvd_vae_bind_workspace", self._h, C.c_void_p(self._ws.data_ptr()), self._ws.numel())
 
+    @torch.no_grad()
+    def mid_attention(self, x: torch.Tensor, decoder: bool) -> torch.Tensor:
+        """One mid-block attention (the encoder's or the decoder's) on x (B, H, W, C) bf16 NHWC -> same shape: the code
+        encode / decode run (``mvd_vae_mid_attention``), for the operator-level tests."""
+        dev = self._sync()
+        assert x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous() and x.device == dev
+        assert x.shape[3] == self.config.block_out_channels[-1], "the mid block runs at the deepest level's channel count"
+        B, H, W, _ = x.shape
+        need = L.lib().mvd_vae_mid_attention_workspace_bytes(self._h, int(decoder), B, H, W)
+        if need < 0:
+            raise L.MvdError(f"vae mid_attention_workspace_bytes: {L.last_error()}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
+        L.call("mvd_vae_bind_workspace", self._h, C.c_void_p(self._ws.data_ptr()), self._ws.numel())
+        out = torch.empty_like(x)
+        L.call("mvd_vae_mid_attention", self._h, int(decoder), C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return out
+
     # ------------------------------------------------------------------ the diffusers protocol
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
