@@ -189,6 +189,12 @@ int mvd_op_conv3x3_ws(const void* x, int batch, int h, int w, int c, const void*
 int mvd_op_conv3x3(const void* x, int batch, int in_h, int in_w, int cin, int stride, int upsample, int asym_pad, const void* w,
                    const float* bias, const float* rowvec, int ld_rowvec, const void* res, const void* sc, const void* sc2,
                    int sc_c1, int sc_c2, void* out, int cout, int force_cfg, int splitk, float* splitk_ws, void* stream);
+/* The 3x3 conv behind a nearest-2x upsample (mvd_op_conv3x3 with upsample = 1) as four 2x2 sub-pixel convolutions of the
+ * source map: K = 4 * cin instead of 9 * cin.  w4 = mvd_amd.packing.pack_up4: [4 parities][cout][4 * cin] bf16.  256x320
+ * ping-pong tile only (force_cfg -1 or 7); cin % 64 == 0, cout % 320 == 0, source width a multiple of 16, or 8 with an even
+ * height -- anything else is an error, never another kernel.  out: (batch, 2 in_h, 2 in_w, cout) bf16. */
+int mvd_op_conv3x3_up4(const void* x, int batch, int in_h, int in_w, int cin, const void* w4, const float* bias, void* out, int cout,
+                       int force_cfg, void* stream);
 /* softmax(scale * q.k^T).v per head of 64 channels.  scale == 0 selects the engine's form: q is already multiplied
  * by softmax_scale * log2(e) (the packed to_q / to_q_ref weight rows carry that factor, DESIGN.md "Weight slots"). */
 int mvd_op_attention(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
@@ -222,6 +228,8 @@ int mvd_gemm_num_configs(void);
  * persistent multi-tile path (work items > workgroups) is what ran at the benchmarked shapes. */
 int mvd_debug_last_gemm_plan(int* out);
 int mvd_debug_last_attention_plan(int* out);
+/* Launches of the 2x2 sub-pixel upsampling convolution by this process so far (read the difference across a forward). */
+long mvd_debug_up4_launches(void);
 /* 1 when the calling thread's last small-M split-K launch used the no-wait combine (requested, or chosen because the grid
  * cannot be resident at once), else 0. */
 int mvd_debug_last_gemm_nowait(void);
@@ -239,7 +247,8 @@ int mvd_debug_set_attention_nw(int nw_log2);
 /* Measurement / bisection switches of the engine's schedule: bit 0 no LayerNorm fold through the small-M kernels, bit 1 the
  * small-M kernels never split K, bit 2 small-M kernels off, bit 3 no split-KV attention, bit 4 the reference-encoder pass on the
  * caller's stream (one stream), bit 5 the single-stream launch policy (split-K / tile choice) also while two streams run,
- * bit 6 the side stream at default instead of highest priority (read when the stream is created).  0 = the product's behaviour. */
+ * bit 6 the side stream at default instead of highest priority (read when the stream is created), bit 20 (1048576) the upsampling
+ * convolutions keep the nine-tap kernel (no 2x2 sub-pixel form).  0 = the product's behaviour. */
 int mvd_debug_set_flags(int flags);
 
 /* ---- denoising-loop helpers either side of the UNet, fp32 latents ------ */

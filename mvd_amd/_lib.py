@@ -103,6 +103,9 @@ _SIGS = {
                                         C.c_void_p, C.c_int, C.c_void_p]),
     "mvd_gemm_num_configs": (C.c_int, []),
     "mvd_debug_last_gemm_plan": (C.c_int, [C.POINTER(C.c_int)]),
+    "mvd_debug_up4_launches": (C.c_long, []),
+    "mvd_op_conv3x3_up4": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p]),
     "mvd_debug_last_gemm_nowait": (C.c_int, []),
     "mvd_debug_last_attention_plan": (C.c_int, [C.POINTER(C.c_int)]),
     "mvd_debug_pick_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -279,6 +279,22 @@ struct Ctx {
     static const bool use_sm = MVD_ENV_INT("MVD_GEMM_SM", 1) != 0;
     return use_sm && !(g_debug_flags & 4);
   }
+  // split factor and forced tile config (-1: the heuristic's) of a launch of the tiled kernels
+  void tiled_plan(const MvdGemmArgs& g, int& S, int& fc) {
+    // split-K for tile grids that cannot fill the chip: fp32 partials in scoped workspace + a reduce/epilogue pass
+    S = mvd_gemm_pick_splitk(g);
+    fc = -1;
+    // While the encoder pass runs beside the main pass (two streams, forward_impl) a launch need not fill the chip by itself --
+    // the other stream's kernels take the idle CUs -- so the two devices that exist only to fill it are dropped: the 256x320
+    // tile is not split along K at 128 tiles (16x16 level; no fp32 partials, no reduce pass), and 100+ tiles of it are preferred
+    // to 512 of the 128x160 tile (measured on one box, cfg4 cold: 65.6 -> 64.6 -> 63.5 ms per step; halving or dropping the
+    // four-way split of the 8x8 level instead: no gain / a loss; profiles/r03_probe_dual_stream_policies.log).
+    if (e->dual_now && !e->dual_late && !(g_debug_flags & 32) && !g.geglu && !g.ln_c1 && !g.out_f32 && g.N % 320 == 0 && mvd_gemm_pp_applicable(g)) {
+      const int cfg = mvd_gemm_pick_config(g);
+      const long t7 = (long)((g.M + 255) / 256) * (g.N / 320);
+      if (t7 >= 100) { S = 1; if (cfg != 7) fc = 7; }      // (below 100 tiles -- the 8x8 level -- the heuristic's tile and split stand)
+    }
+  }
   int gemm(MvdGemmArgs& g) {
     if (err) return err;
     // small problems (one image's feature maps): the latency-oriented kernels of gemm_sm.hip, split-K combined in the kernel
@@ -302,19 +318,8 @@ struct Ctx {
       e->tmp.off = mark;
       return r;
     }
-    // split-K for tile grids that cannot fill the chip: fp32 partials in scoped workspace + a reduce/epilogue pass
-    int S = mvd_gemm_pick_splitk(g);
-    // While the encoder pass runs beside the main pass (two streams, forward_impl) a launch need not fill the chip by itself --
-    // the other stream's kernels take the idle CUs -- so the two devices that exist only to fill it are dropped: the 256x320
-    // tile is not split along K at 128 tiles (16x16 level; no fp32 partials, no reduce pass), and 100+ tiles of it are preferred
-    // to 512 of the 128x160 tile (measured on one box, cfg4 cold: 65.6 -> 64.6 -> 63.5 ms per step; halving or dropping the
-    // four-way split of the 8x8 level instead: no gain / a loss; profiles/r03_probe_dual_stream_policies.log).
-    int fc = -1;
-    if (e->dual_now && !e->dual_late && !(g_debug_flags & 32) && !g.geglu && !g.ln_c1 && !g.out_f32 && g.N % 320 == 0 && mvd_gemm_pp_applicable(g)) {
-      const int cfg = mvd_gemm_pick_config(g);
-      const long t7 = (long)((g.M + 255) / 256) * (g.N / 320);
-      if (t7 >= 100) { S = 1; if (cfg != 7) fc = 7; }      // (below 100 tiles -- the 8x8 level -- the heuristic's tile and split stand)
-    }
+    int S = 1, fc = -1;
+    tiled_plan(g, S, fc);
     const size_t mark = e->tmp.off;
     if (S > 1) { g.splitk = S; g.part = talloc<float>((size_t)S * g.M * g.N); } else g.splitk = 1;   // (decided: 0 = undecided)
     static const bool trace = MVD_ENV_INT("MVD_TRACE_GEMM", 0) != 0;
@@ -452,7 +457,8 @@ struct Ctx {
   }
 
   int conv3(const Act& x, int stride, int ups, const bf16_t* w, const float* bias, const float* rowvec, int ld_rowvec,
-            const bf16_t* res, const bf16_t* sc0, const bf16_t* sc1, int scc0, int scc1, Act& out, const std::string& ws = std::string()) {
+            const bf16_t* res, const bf16_t* sc0, const bf16_t* sc1, int scc0, int scc1, Act& out, const std::string& ws = std::string(),
+            const std::string& w4 = std::string()) {
     if (!ws.empty() && stride == 1) {
       const int r = try_ws(x, ups, ws, bias, rowvec, ld_rowvec, res, sc0, sc1, scc0, scc1, out);
       if (r) return r < 0 ? r : 0;
@@ -468,6 +474,29 @@ struct Ctx {
     g.W = w; g.ldw = g.Ktot; g.M = out.rows(); g.N = out.C; g.rows_per_batch = out.hw(); g.outH = out.H; g.outW = out.W;
     g.bias = bias; g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = res; g.ldres = out.C; g.alpha = 1.f;
     g.out = out.p; g.ldo = out.C;
+    // Upsampling convolution as four 2x2 sub-pixel convolutions of the source map (gemm_pp.hip AMODE 4: K = 4 C instead of 9 C,
+    // the same result up to one bf16 rounding of the pre-summed weights), taken when the packed twin `w4` (packing.pack_up4) is
+    // registered and the schedule would put the nine-tap problem on the unsplit 256x320 ping-pong tile anyway: batch-1 forwards
+    // keep their conv_ws / small-M route, a split launch (the 8x8 -> 16x16 site outside a two-stream forward) and source widths
+    // the mode does not take (12, 24) keep the nine-tap kernel.  Debug flag 1048576 turns the route off (A/B).
+    if (!w4.empty() && !dry && !err && ups == 1 && stride == 1 && !sc0 && !res && !rowvec && !(g_debug_flags & 1048576) && has(w4)) {
+      int t_ = 0, n_ = 0, s_ = 1, S = 1, fc = -1;
+      if (!(sm_enabled() && mvd_gemm_sm_plan(g, &t_, &n_, &s_))) {
+        tiled_plan(g, S, fc);
+        MvdGemmArgs u = g;
+        u.splitk = 1;
+        if (S == 1 && (fc >= 0 ? fc : mvd_gemm_pick_config(u)) == 7 && mvd_gemm_pp_applicable(u)) {
+          u.seg[0].ups = 2; u.seg[0].ksize = 4 * x.C; u.Ktot = 4 * x.C; u.ldw = u.Ktot;
+          if (mvd_gemm_pp_up4_applicable(u)) {
+            u.W = WB(w4, (int64_t)4 * out.C * 4 * x.C);
+            if (!u.W) return err;
+            // (executed FLOPs: 4/9 of the algorithmic count of the nine-tap form; tag 140 tells the rows apart in the shape table)
+            e->prof_M = u.M; e->prof_N = u.N; e->prof_K = u.Ktot; e->prof_tag = 140;
+            return profiled(13, 2.0 * u.M * (double)u.N * u.Ktot, 0.0, [&] { return mvd_launch_gemm(u, s, 7); });
+          }
+        }
+      }
+    }
     return gemm(g);
   }
 
@@ -758,7 +787,7 @@ struct UNetPass {
       }
       if (i + 1 < n) {
         Act u = c.new_act(B, h.H * 2, h.W * 2, co, true);
-        CHECK(c.conv3(h, 1, 1, c.WB(bk + ".up.w", (int64_t)co * 9 * co), c.WF(bk + ".up.b", co), nullptr, 0, nullptr, nullptr, nullptr, 0, 0, u, bk + ".up.ws"));
+        CHECK(c.conv3(h, 1, 1, c.WB(bk + ".up.w", (int64_t)co * 9 * co), c.WF(bk + ".up.b", co), nullptr, 0, nullptr, nullptr, nullptr, 0, 0, u, bk + ".up.ws", bk + ".up.w4"));
         h = u;
       }
       if (o.film) { Act res = h; CHECK(film("up_" + std::to_string(i), h, res)); h = res; }
@@ -1536,6 +1565,20 @@ int mvd_op_conv3x3(const void* x, int batch, int in_h, int in_w, int cin, int st
     return mvd_launch_splitk_reduce(g, (hipStream_t)stream);
   }
   g.splitk = 1;            // the caller DECIDED not to split (0 would mean "undecided": the tile heuristic may then assume a deep split)
+  return mvd_launch_gemm(g, (hipStream_t)stream, force_cfg);
+}
+
+// the upsampling convolution as four 2x2 sub-pixel convolutions (w4 = packing.pack_up4: [4][cout][4 * cin] bf16); an error --
+// never another kernel -- for a problem the mode does not take (mvd_gemm_pp_up4_applicable)
+int mvd_op_conv3x3_up4(const void* x, int batch, int in_h, int in_w, int cin, const void* w4, const float* bias, void* out, int cout,
+                       int force_cfg, void* stream) {
+  if (!x || !w4 || !out || batch <= 0 || in_h <= 0 || in_w <= 0 || cin <= 0 || cout <= 0) { mvd_set_error("mvd_op_conv3x3_up4: bad argument"); return -1; }
+  MvdGemmArgs g; memset(&g, 0, sizeof(g));
+  g.seg[0].p0 = (const bf16_t*)x; g.seg[0].c0 = cin; g.seg[0].mode = MVD_A_CONV3; g.seg[0].ksize = 4 * cin;
+  g.seg[0].inH = in_h; g.seg[0].inW = in_w; g.seg[0].stride = 1; g.seg[0].ups = 2;
+  g.nseg = 1; g.Ktot = 4 * cin; g.W = (const bf16_t*)w4; g.ldw = g.Ktot;
+  g.outH = 2 * in_h; g.outW = 2 * in_w; g.rows_per_batch = g.outH * g.outW; g.M = batch * g.rows_per_batch; g.N = cout;
+  g.bias = bias; g.ldres = cout; g.alpha = 1.f; g.out = out; g.ldo = cout; g.splitk = 1;
   return mvd_launch_gemm(g, (hipStream_t)stream, force_cfg);
 }
 

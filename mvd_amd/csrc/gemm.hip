@@ -574,6 +574,11 @@ extern "C" int mvd_debug_last_gemm_plan(int* out) {
   return 0;
 }
 
+// launches of the 2x2 sub-pixel upsampling convolution (gemm_pp.hip, AMODE 4) by this process so far: tests and A/B runs read
+// the difference across a forward to see which route the upsamplers took
+std::atomic<long> g_mvd_up4_launches{0};
+extern "C" long mvd_debug_up4_launches(void) { return g_mvd_up4_launches.load(); }
+
 // 1 when the calling thread's last small-M split-K launch took the no-wait combine (asked for by the caller, or because its
 // grid exceeded what the chip holds at once: gemm_sm.hip launch_sm3), else 0
 extern "C" int mvd_debug_last_gemm_nowait(void) { return g_mvd_last_gemm.nowait; }
@@ -643,7 +648,8 @@ int mvd_launch_gemm(const MvdGemmArgs& a, hipStream_t s, int force_cfg) {
     if (g.mode == MVD_A_DENSE) {
       if (g.c0 % 64 || g.c1 % 64 || g.ksize != g.c0 + g.c1 || !g.p0 || (g.c1 && !g.p1)) { mvd_set_error("gemm: bad dense segment %d (c0=%d c1=%d ksize=%d)", i, g.c0, g.c1, g.ksize); return -1; }
     } else if (g.mode == MVD_A_CONV3) {
-      if (g.c0 % 64 || g.c1 != 0 || g.ksize != 9 * g.c0 || !g.p0 || (g.stride != 1 && g.stride != 2) || (g.ups && g.stride != 1)) { mvd_set_error("gemm: bad conv segment %d", i); return -1; }
+      if (g.ups != 0 && g.ups != 1 && g.ups != 2) { mvd_set_error("gemm: bad conv segment %d (ups=%d)", i, g.ups); return -1; }
+      if (g.c0 % 64 || g.c1 != 0 || g.ksize != (g.ups == 2 ? 4 : 9) * g.c0 || !g.p0 || (g.stride != 1 && g.stride != 2) || (g.ups && g.stride != 1)) { mvd_set_error("gemm: bad conv segment %d", i); return -1; }
       if (g.asym && (g.asym != 1 || g.stride != 2 || (g.inH & 1) || (g.inW & 1))) { mvd_set_error("gemm: bottom/right-only padding needs stride 2 and an even input size"); return -1; }
       const int eh = g.ups ? 2 * g.inH : (g.stride == 2 ? (g.inH + 1) / 2 : g.inH);
       const int ew = g.ups ? 2 * g.inW : (g.stride == 2 ? (g.inW + 1) / 2 : g.inW);
@@ -668,6 +674,16 @@ int mvd_launch_gemm(const MvdGemmArgs& a, hipStream_t s, int force_cfg) {
   static const int dbg = MVD_ENV_INT("MVD_GEMM_DEBUG", 0);
   if (dbg) const_cast<MvdGemmArgs&>(a).dbg = dbg;
 #endif
+  // the 2x2 sub-pixel form of an upsampling convolution exists in the ping-pong kernel only: no other kernel may see ups == 2
+  if (a.seg[0].mode == MVD_A_CONV3 && a.seg[0].ups == 2) {
+    if ((force_cfg >= 0 && force_cfg != 7) || (a.dbg & ~32) || !mvd_gemm_pp_up4_applicable(a)) {
+      mvd_set_error("gemm: the 2x2 sub-pixel upsampling convolution does not take this problem (in %dx%d C=%d N=%d cfg=%d): source width a multiple of 16 or 8 (even height), N %% 320 == 0, bias only, unsplit",
+                    a.seg[0].inH, a.seg[0].inW, a.seg[0].c0, a.N, force_cfg);
+      return -1;
+    }
+    g_mvd_last_gemm.cfg = 7; g_mvd_last_gemm.splitk = 1;
+    return mvd_launch_gemm_pp(a, s);
+  }
   int cfg = force_cfg;
   // force_cfg >= 100: the small-M kernels of gemm_sm.hip, 100 + 10 * tile + ring depth (0: default 4)
   if (cfg >= 1000) { const_cast<MvdGemmArgs&>(a).w_blocked = 1; cfg -= 1000; }    // (+1000: W in the blocked LDS-image layout)

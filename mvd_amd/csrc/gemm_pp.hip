@@ -72,7 +72,18 @@ MVD_DEVINL void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base,
 
 // WM x WN wave grid: 2 x 4 (wave tile 128 x 80) for plain epilogues, 4 x 2 (64 x 160: value/gate column tiles pair
 // up inside a wave) for GEGLU.  AMODE: 0 dense, 1 conv, 2 conv + dense (1x1 shortcut) segment, 3 conv behind a fused
-// nearest-2x upsample.
+// nearest-2x upsample, 4 the same convolution as four 2x2 sub-pixel convolutions of the source map (below).
+//
+// AMODE 4 (MvdASeg::ups == 2): in the nearest-2x upsampled map two of the three rows (columns) of a 3x3 window are the same
+// source row (column), so output pixel (2i+py, 2j+px) is a 2x2 convolution of the SOURCE map with the pre-summed weights of
+// its parity (packing.pack_up4: W = [4 parities][N][4*Cin]), window top-left (i+py-1, j+px-1): K = 4*Cin instead of 9*Cin.
+// One launch covers the four parities; a work item is (parity, row tile of 256 SOURCE pixels, column tile), parity major, so
+// an XCD stays on one weight panel.  The tile walk carries the parity inside the row coordinate (m0 = parity * PR + source
+// row, PR = row tiles * 256); the loader and the epilogue take it apart on the SALU.  The epilogue maps source row (b, i, j)
+// to output row (b*2H + 2i+py)*2W + 2j+px: a 16-row fragment tile is 16 consecutive source pixels, which lie in one source
+// row (source width a multiple of 16) or are two whole source rows (width 8, even height), so the lane's share of the
+// offset stays tile invariant and the rest is one (b, i, j) decode per wave tile on the SALU.  No split-K, residual or
+// row vector in this form (the launcher refuses them).
 // BM = 256 rows per tile (the default) or 128 (levels whose 256-row grid cannot fill the chip: twice the tiles, wave tile 64 x 80).
 //
 // LNF: LayerNorm of the A rows folded in (MvdGemmArgs::ln_c1; W carries gamma, the epilogue applies
@@ -94,6 +105,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   constexpr bool GEGLU = WM == 4;
   constexpr bool HAS_CONV = AMODE != 0;
   constexpr bool UPS = AMODE == 3;
+  constexpr bool UP4 = AMODE == 4;
+  static_assert(!UP4 || !SPLITK, "the sub-pixel form is unsplit");
   static_assert((WTM * 128) % 2048 == 0 && (WTN % 16) == 0, "fragment rows of a wave share one swizzle pattern");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -101,7 +114,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   const int grp = wave >> 2;                                      // ping-pong group (SIMD partners are waves w, w + 4)
   const int wm = wave / WN, wn = wave % WN;
   const int ntn = a.N / BN;
-  const int ntm = (a.M + BM - 1) / BM;
+  const int srcM = UP4 ? a.M >> 2 : a.M;                          // A rows of one pass over the source (UP4: one parity)
+  const int ntm = (srcM + BM - 1) / BM;
   const int lrow = tid >> 3;                                      // 0..63: row inside a 64-row DMA block (W loads)
   const int kc = (tid & 7) ^ ((lrow >> 1) & 7);                   // source chunk (the XOR swizzle lives on the source side)
   // A loads: EACH GROUP LOADS THE ROWS IT MULTIPLIES (group g = row block wm's half: rows 128 g .. 128 g + 127 of the tile, the
@@ -114,7 +128,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
 
   // ---- tile walk (as gemm.hip): XCD x owns a contiguous range of work items, its workgroups stride through it
   const int S = SPLITK ? a.splitk : 1;
-  const int ntiles = ntn * ntm * S;
+  const int ntiles = ntn * ntm * S * (UP4 ? 4 : 1);
   const int xcd = blockIdx.x & 7, xj = blockIdx.x >> 3;
   const int gx = (gridDim.x >> 3) + ((int)(gridDim.x & 7) > xcd ? 1 : 0);
   const int tq = ntiles >> 3, tr = ntiles & 7;
@@ -141,7 +155,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
 
   const MvdASeg& cs = a.seg[0];                       // conv segment (AMODE 1, 2)
   const MvdASeg& ds = a.seg[AMODE == 2 ? 1 : 0];      // dense segment (AMODE 0, 2)
-  const int nkt_conv = HAS_CONV ? (9 * cs.c0) / 64 : 0;
+  const int nkt_conv = HAS_CONV ? ((UP4 ? 4 : 9) * cs.c0) / 64 : 0;
   const int nkt = a.Ktot / 64;
   const int conv_c2 = cs.c0 * 2;                      // bytes per input pixel
   const int conv_rowB = cs.inW * conv_c2;             // bytes per input row
@@ -152,11 +166,11 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   // ---- buffer descriptors (scalar).  The conv descriptor starts one row + one pixel BEFORE the feature map so
   // that tap (dy, dx) is a non-negative scalar offset (dy * row + dx * pixel) from a per-lane base; nothing below
   // the map is ever dereferenced (those taps are out of the image and take the OOB offset).
-  __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.W), 0, (int)((size_t)a.N * a.ldw * 2), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.W), 0, (int)((size_t)a.N * a.ldw * 2 * (UP4 ? 4 : 1)), 0x00020000);
   __amdgpu_buffer_rsrc_t rs_c = rs_w, rs_d0 = rs_w, rs_d1 = rs_w;
   if (HAS_CONV) {
     const int shift = conv_rowB + conv_c2;
-    const size_t bytes = (size_t)(a.M / a.rows_per_batch) * cs.inH * cs.inW * conv_c2;
+    const size_t bytes = (size_t)(a.M / a.rows_per_batch) * cs.inH * cs.inW * conv_c2;      // (UP4: M and rows_per_batch both count OUTPUT pixels)
     rs_c = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(const_cast<bf16_t*>(cs.p0)) - shift, 0, (int)(bytes + shift), 0x00020000);
   }
   if (AMODE == 0 || AMODE == 2) {
@@ -176,7 +190,29 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   auto setup_loader = [&](int work) {
     const int t = S == 1 ? work : work / S;
     tile_mn(t, ld_m0, ld_n0);
-    if (HAS_CONV) {
+    if constexpr (UP4) {
+      // parity out of the row coordinate; the W panel of the parity is folded into the loader's column origin
+      const int pr = ntm * BM;
+      const int par = (ld_m0 >= pr ? 1 : 0) + (ld_m0 >= 2 * pr ? 1 : 0) + (ld_m0 >= 3 * pr ? 1 : 0);
+      ld_m0 -= par * pr; ld_n0 += par * a.N;
+      const int py = par >> 1, px = par & 1;
+      const int hw = cs.inH * cs.inW;
+#pragma unroll
+      for (int i = 0; i < A_IT; ++i) {
+        int m = ld_m0 + (2 * grp + (i & 1)) * 64 + arow + (i >> 1) * 32;
+        m = m < srcM ? m : srcM - 1;
+        const int b = m / hw;
+        const int rem = m - b * hw;
+        const int sy = rem / cs.inW, sx = rem - sy * cs.inW;
+        const int wy = sy + py - 1, wx = sx + px - 1;                  // window top-left in the source map
+        int okm = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          okm |= ((unsigned)(wy + (t >> 1)) < (unsigned)cs.inH && (unsigned)(wx + (t & 1)) < (unsigned)cs.inW) ? (1 << t) : 0;
+        a_yx[i] = okm << 22;
+        a_base[i] = (unsigned)((b * hw + (wy + 1) * cs.inW + (wx + 1)) * conv_c2 + kc * 16);
+      }
+    } else if (HAS_CONV) {
 #pragma unroll
       for (int i = 0; i < A_IT; ++i) {
         int m = ld_m0 + (2 * grp + (i & 1)) * 64 + arow + (i >> 1) * 32;
@@ -209,7 +245,16 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   auto issue_a = [&](int st, int lk, int i0, int i1) {
     // LDS image of the A operand: [64-row block][8-row slice][8 rows][128 B]; load i -> block 2g + (i & 1), slice w4 + 4 (i >> 1)
     unsigned char* sa = smem + st * STAGE_BYTES + (2 * grp) * 8192 + w4 * 1024;
-    if (HAS_CONV && (AMODE != 2 || lk < nkt_conv)) {
+    if constexpr (UP4) {
+      // K order [channel slice][tap ty*2+tx][64 channels]: a stride-1 loader with a 2x2 tap set
+      const int sl = lk >> 2, tap = lk & 3;
+      const unsigned soff = (unsigned)(sl * 128 + (tap >> 1) * conv_rowB + (tap & 1) * conv_c2);
+#pragma unroll
+      for (int i = 0; i < A_IT; ++i) {
+        const bool ok = (a_yx[i] >> (22 + tap)) & 1;
+        if (i >= i0 && i < i1) dma16(rs_c, sa + (i & 1) * 8192 + (i >> 1) * 4096, ok ? a_base[i] : OOB, soff);
+      }
+    } else if (HAS_CONV && (AMODE != 2 || lk < nkt_conv)) {
       // K order [channel slice][tap][64 channels] (gemm.hip): slice = lk / 9, tap = lk % 9
       const int sl = lk / 9, tap = lk - sl * 9;
 #ifdef PP_ABLATE_A_TAPS   // round-5 timing-only ablation (WRONG RESULTS): the A operand is fetched for tap 0 of every 64-channel slice only --
@@ -341,6 +386,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   const int pair_col = (fq & 1) * 16 + (fq >> 1) * 8;      // column of the lane's 16-byte piece inside a pair of column tiles
   auto epilogue = [&](int m0, int n0, int ks) {
     asm volatile("" : "+s"(m0), "+s"(n0));
+    int up_par = 0;
+    if constexpr (UP4) {                                   // the parity travels inside the row coordinate (setup_loader)
+      const int pr = ntm * BM;
+      up_par = (m0 >= pr ? 1 : 0) + (m0 >= 2 * pr ? 1 : 0) + (m0 >= 3 * pr ? 1 : 0);
+      m0 -= up_par * pr;
+    }
     const int row0 = m0 + wm * WTM;                        // (scalar) first row of the wave tile
     if (SPLITK) {   // raw fp32 partial tile; bias / residual are applied by the reduce kernel
       __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(a.part + (size_t)ks * a.M * a.N, 0, (int)((size_t)a.M * a.N * 4), 0x00020000);
@@ -361,6 +412,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
       const int el = fresh_lane();
       efr = el & 15; efq = el >> 4;
       vo16 = (efr * a.ldo + (efq & 1) * 16 + (efq >> 1) * 8) * 2; vo8 = (efr * a.ldo + efq * 4) * 2;
+    } else if constexpr (UP4) {
+      // row fr of a fragment tile = source pixel fr of 16 consecutive ones: one source row (width % 16 == 0) or two whole rows
+      // (width 8); source pixel (y, x) -> output pixel (2y + py, 2x + px), the tile's first pixel being the scalar part
+      const int sh = cs.inW >= 16 ? 4 : 3;
+      const int lr = (fr >> sh) * 2 * a.outW + (fr & ((1 << sh) - 1)) * 2;
+      vo16 = (lr * a.ldo + pair_col) * 2; vo8 = (lr * a.ldo + fq * 4) * 2;
     } else {
       vo16 = (fr * a.ldo + pair_col) * 2; vo8 = (fr * a.ldo + fq * 4) * 2;
       // (round 4, timing-only experiment: the same stores aimed at 8 rows x 128 B per instruction instead of 16 rows x 64 B --
@@ -439,7 +496,15 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
         if (TN & 1) __builtin_amdgcn_raw_buffer_store_b64(one(TN - 1), rs_o, vo8, so + (TN - 1) * 32, 0);
       }
     } else {
-      const bool has_res = a.res != nullptr;
+      const bool has_res = !UP4 && a.res != nullptr;
+      // UP4: (image, y, x) of the current row tile's first source pixel, decoded once per wave tile and stepped by 16 pixels
+      unsigned up_b = 0, up_y = 0, up_x = 0;
+      if constexpr (UP4) {
+        const unsigned hw = (unsigned)(cs.inH * cs.inW);
+        up_b = (unsigned)row0 / hw;
+        const unsigned rem = (unsigned)row0 - up_b * hw;
+        up_y = rem / (unsigned)cs.inW; up_x = rem - up_y * (unsigned)cs.inW;
+      }
       __amdgpu_buffer_rsrc_t rs_r = rs_o;
       if (has_res) rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.res), 0, (int)((size_t)a.M * a.ldres * 2), 0x00020000);
       const int vr16 = (fr * a.ldres + pair_col) * 2, vr8 = (fr * a.ldres + fq * 4) * 2;
@@ -465,7 +530,15 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
           const int i = i0 + g;
-          const int so = ((row0 + i * 16) * a.ldo + n0 + wn * WTN) * 2;
+          int so = ((row0 + i * 16) * a.ldo + n0 + wn * WTN) * 2;
+          if constexpr (UP4) {
+            const int orow = (int)((up_b * 2 * cs.inH + 2 * up_y + (up_par >> 1)) * a.outW + 2 * up_x + (up_par & 1));
+            // row tiles at or beyond the last source pixel: an offset at num_records, the stores are dropped
+            so = (row0 + i * 16 < srcM ? orow : a.M) * a.ldo * 2 + (n0 + wn * WTN) * 2;
+            up_x += 16;
+            if (up_x >= (unsigned)cs.inW) { up_x = 0; up_y += cs.inW >= 16 ? 1 : 2; }
+            if (up_y >= (unsigned)cs.inH) { up_y = 0; ++up_b; }
+          }
           int mrow = row0 + i * 16 + fr;
           mrow = mrow < a.M ? mrow : a.M - 1;
           const float* rvp = row_rv ? a.rowvec + (size_t)(mrow / a.rows_per_batch) * a.ld_rowvec + n0 + wn * WTN + fq * 4 : nullptr;
@@ -660,11 +733,11 @@ int launch_pp(const MvdGemmArgs& a, hipStream_t s) {
     if (e != hipSuccess) { mvd_set_error("gemm_pp: hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
     init[dev & 15] = true;
   }
-  const int ntm = (a.M + BM - 1) / BM, ntn = a.N / BN;
+  const int ntm = ((AMODE == 4 ? a.M / 4 : a.M) + BM - 1) / BM, ntn = a.N / BN;   // (AMODE 4: row tiles of SOURCE pixels, per parity)
   MvdGemmArgs b = a;
   b.walk_cg = SPLITK ? 0 : mvd_gemm_pp_walk(a);
   int grid = 256;                                         // one 144 KB (112 KB at BM = 128) workgroup per CU
-  const int ntiles = ntm * ntn * (a.splitk > 1 ? a.splitk : 1);
+  const int ntiles = ntm * ntn * (a.splitk > 1 ? a.splitk : 1) * (AMODE == 4 ? 4 : 1);
   if (ntiles < grid) grid = ((ntiles + 7) / 8) * 8;
   g_mvd_last_gemm.tiles = ntiles; g_mvd_last_gemm.grid = grid; g_mvd_last_gemm.per_cu = 1;
   hipLaunchKernelGGL((gemm_pp_kernel<BM, WM, WN, AMODE, SPLITK, LNF>), dim3(grid), dim3(NT), LDS_BYTES, s, b);
@@ -677,6 +750,11 @@ template <int BM, int WM, int WN>
 int launch_pp_mode(const MvdGemmArgs& a, hipStream_t s) {
   const bool sk = a.splitk > 1;
   if (a.seg[0].mode == MVD_A_DENSE) return sk ? launch_pp<BM, WM, WN, 0, true>(a, s) : launch_pp<BM, WM, WN, 0, false>(a, s);
+  if (a.seg[0].ups == 2) {
+    if (!mvd_gemm_pp_up4_applicable(a)) { mvd_set_error("gemm_pp: not a problem of the 2x2 sub-pixel upsampling convolution"); return -1; }
+    g_mvd_up4_launches.fetch_add(1);
+    return launch_pp<BM, WM, WN, 4, false>(a, s);
+  }
   if (a.seg[0].ups) {
     if (a.nseg != 1) { mvd_set_error("gemm_pp: an upsampling convolution takes no shortcut segment"); return -1; }
     return sk ? launch_pp<BM, WM, WN, 3, true>(a, s) : launch_pp<BM, WM, WN, 3, false>(a, s);
@@ -727,6 +805,24 @@ bool mvd_gemm_pp_applicable(const MvdGemmArgs& a) {
     }
   }
   return true;
+}
+
+// The 2x2 sub-pixel form of the upsampling convolution (AMODE 4; MvdASeg::ups == 2, W = packing.pack_up4, Ktot = 4 * c0,
+// M / outH / outW / rows_per_batch describe the OUTPUT as for ups == 1).  Takes: one conv segment, bias only (no residual, row
+// vector, split-K), and a source map whose 16-pixel runs map to output rows the same way in every tile: width a multiple of
+// 16, or width 8 with an even height.  Other widths (12, 24) would need per-lane offsets per row tile: refused, the caller
+// keeps the nine-tap form.
+bool mvd_gemm_pp_up4_applicable(const MvdGemmArgs& a) {
+  const MvdASeg& g = a.seg[0];
+  if (a.nseg != 1 || g.mode != MVD_A_CONV3 || g.ups != 2 || g.stride != 1 || g.asym || g.c1) return false;
+  if (a.res || a.rowvec || a.splitk > 1 || a.geglu || a.ln_c1 || a.out_f32) return false;
+  if (g.c0 <= 0 || g.c0 % 64 || g.ksize != 4 * g.c0 || a.Ktot != 4 * g.c0 || a.ldw != a.Ktot) return false;
+  if (g.inH <= 0 || g.inW <= 0 || a.outH != 2 * g.inH || a.outW != 2 * g.inW || a.rows_per_batch != a.outH * a.outW || a.M % a.rows_per_batch) return false;
+  if (!(g.inW % 16 == 0 || (g.inW == 8 && g.inH % 2 == 0))) return false;
+  const size_t lim = (size_t)1 << 31;
+  if ((size_t)4 * a.N * a.ldw * 2 >= lim) return false;                                           // the four weight panels
+  if ((size_t)(a.M + 2 * a.outW + 16 + 256) * a.ldo * 2 >= lim) return false;                     // scalar row + the lane's share
+  return mvd_gemm_pp_applicable(a);
 }
 
 // geglu selects the 4 x 2 wave grid (arguments already validated by mvd_launch_gemm).

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "common.h"
 
 // ---------------------------------------------------------------- GEMM / implicit conv
@@ -18,7 +19,8 @@ struct MvdASeg {          // one K segment of the A operand
   int ksize;              // K extent: dense c0+c1, conv 9*c0
   int inH, inW;           // conv: stored input spatial size
   int stride;             // conv: 1 or 2
-  int ups;                // conv: 1 = nearest 2x upsample fused in front of the conv
+  int ups;                // conv: 1 = nearest 2x upsample fused in front of the conv; 2 = the same result as four 2x2 sub-pixel
+                          // convolutions of the source map (ksize 4*c0, W = packing.pack_up4; gemm_pp.hip AMODE 4 only)
   int asym;               // conv, stride 2 only: 1 = zero padding on the bottom/right edge only (diffusers' VAE
                           // Downsample2D(padding=0): F.pad(x, (0,1,0,1)) then a pad-0 conv), 0 = the usual pad 1 all round
 };
@@ -67,9 +69,11 @@ int mvd_gemm_pick_config(const MvdGemmArgs& a);   // tile config the heuristic g
 // what the calling thread's last mvd_launch_gemm launched (tests assert that the persistent multi-tile path ran)
 struct MvdLaunchPlan { int cfg, splitk, tiles, grid, per_cu, nowait; };
 extern thread_local MvdLaunchPlan g_mvd_last_gemm;
+extern std::atomic<long> g_mvd_up4_launches;       // launches of the 2x2 sub-pixel upsampling convolution (mvd_debug_up4_launches)
 // 256x320 "ping-pong" kernels (gemm_pp.hip): buffer-addressed LDS-DMA, two wave groups one phase apart.  Used for tile
 // configs 6 (GEGLU) and 7 whenever every byte offset fits 32-bit buffer addressing; arguments validated by mvd_launch_gemm.
 bool mvd_gemm_pp_applicable(const MvdGemmArgs& a);
+bool mvd_gemm_pp_up4_applicable(const MvdGemmArgs& a);   // the 2x2 sub-pixel form of an upsampling convolution (seg[0].ups == 2)
 int mvd_gemm_pp_walk(const MvdGemmArgs& a);        // column tiles per group of the ping-pong kernel's tile walk (0: row-major)
 int mvd_debug_flags();                             // engine.hip: the measurement switches of mvd_debug_set_flags
 // true when a problem with a.ln_c1 set can run (one dense source spanning the whole row, no residual / row vector /

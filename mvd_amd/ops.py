@@ -111,6 +111,24 @@ def conv3x3(x, w_packed, bias=None, stride=1, upsample=False, rowvec=None, res=N
     return out
 
 
+def conv3x3_up4(x, w4, bias=None, force_cfg=-1):
+    """conv3x3(upsample=True) as four 2x2 sub-pixel convolutions of the source map (gemm_pp.hip AMODE 4).  x: (B,H,W,Cin) bf16;
+    w4: packing.pack_up4 of the fp32 [Cout][Cin][3][3] weight, (4, Cout, 4*Cin) bf16.  Raises for a shape the mode does not take
+    (W % 16 != 0 other than W == 8 with even H, Cout % 320, Cin % 64)."""
+    _bf16(x, w4)
+    B, H, W, Cin = x.shape
+    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * Cin and w4.is_contiguous() and x.is_contiguous(), tuple(w4.shape)
+    cout = w4.shape[1]
+    out = torch.empty(B, 2 * H, 2 * W, cout, device=x.device, dtype=torch.bfloat16)
+    L.call("mvd_op_conv3x3_up4", _p(x), B, H, W, Cin, _p(w4), _p(bias), _p(out), cout, force_cfg, _s())
+    return out
+
+
+def up4_launches() -> int:
+    """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
+    return int(L.lib().mvd_debug_up4_launches())
+
+
 def attention(q, k, v, heads, scale=0.125):
     """q: (B,Nq,heads*64) bf16, k/v: (B,Nk,heads*64); row strides may exceed heads*64 (views of fused buffers).
     scale=0 selects the engine's form: q already multiplied by 64^-0.5 * log2(e) (packing.QSCALE)."""

@@ -134,6 +134,33 @@ def pack_ws(w4: torch.Tensor, wsc=None, device=None) -> torch.Tensor:
     return torch.cat(parts, 1).to(torch.bfloat16).contiguous().reshape(-1)
 
 
+def up4_weights(w: torch.Tensor) -> torch.Tensor:
+    """3x3 weight ``[Cout][Cin][3][3]`` of a convolution behind a nearest-2x upsample -> the four 2x2 sub-pixel weights
+    ``[parity py*2+px][Cout][Cin][ty][tx]`` (unrounded, fp32 or wider as ``w`` is).  In the upsampled map two of the three rows
+    a window touches are the same source row, so output pixel (2i+py, 2j+px) is a 2x2 convolution of the SOURCE map whose
+    window starts at (i+py-1, j+px-1): py = 0 weighs source rows (i-1, i) by (w[0], w[1]+w[2]), py = 1 weighs (i, i+1) by
+    (w[0]+w[1], w[2]); the same along x.  Taps outside the source map are zero, as the padding of the upsampled map is."""
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (3, 3), tuple(w.shape)
+    w = w.detach()
+    if w.dtype not in (torch.float32, torch.float64):
+        w = w.float()
+    r = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=w.dtype, device=w.device)   # [parity][tap][k]
+    w4 = torch.einsum("pty,qsx,oiyx->pqoits", r, r, w)                        # [py][px][Cout][Cin][ty][tx]
+    return w4.reshape(4, w.shape[0], w.shape[1], 2, 2)
+
+
+def pack_up4(w: torch.Tensor, device=None) -> torch.Tensor:
+    """``[Cout][Cin][3][3]`` (the fp32 master) -> the ``.up.w4`` slot of the 2x2 sub-pixel upsampler (gemm_pp.hip, AMODE 4):
+    ``[4 parities][Cout][K = 4*Cin]`` bf16, summed in fp32 and rounded once, K ordered like every conv slot of that kernel:
+    ``[Cin/64][tap ty*2+tx][64]``."""
+    device = device if device is not None else w.device
+    w4 = up4_weights(w.detach().to(device=device, dtype=torch.float32))
+    co, ci = w4.shape[1], w4.shape[2]
+    assert ci % 64 == 0, ci
+    k = w4.reshape(4, co, ci // 64, 64, 2, 2).permute(0, 1, 2, 4, 5, 3).reshape(4, co, 4 * ci)
+    return k.to(torch.bfloat16).contiguous()
+
+
 # LayerNorm fold: only the 64x64 / 32x32 levels (C = 320 / 640 in SD-2.1) ever reach the fused kernel (it needs >= 200
 # tiles of 256x320, i.e. many rows); deeper levels keep ln_kernel + the plain GEMM and get no folded twin
 LN_FOLD_MAX_C = 1 << 30     # every level: the small-M kernels (batch 1) fold at C = 1280 too (the M = 32-images kernels stop at 640)
@@ -277,6 +304,8 @@ def pack_unet(sd: Dict[str, torch.Tensor], cfg: UNetConfig, device, adapter: boo
         wu = sd[f"up_blocks.{i}.upsamplers.0.conv.weight"]
         if small_batch_twins and wu.shape[0] > cfg.block_out_channels[0] and wu.shape[0] % 128 == 0 and wu.shape[1] % 128 == 0:
             out[f"up_blocks.{i}.up.ws"] = pack_ws(wu, None, device)            # conv_ws.hip with the 2x upsampling in front
+        if wu.shape[1] % 64 == 0:
+            out[f"up_blocks.{i}.up.w4"] = pack_up4(wu, device)                 # many-image batches: four 2x2 sub-pixel convolutions
         out[f"up_blocks.{i}.up.b"] = _f32(sd[f"up_blocks.{i}.upsamplers.0.conv.bias"], device)
     out["conv_norm_out.g"] = _f32(sd["conv_norm_out.weight"], device)
     out["conv_norm_out.b"] = _f32(sd["conv_norm_out.bias"], device)

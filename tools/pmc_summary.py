@@ -7,7 +7,7 @@ import collections, csv, glob, json, re, sys
 
 CLASSES = {
     "gemm_pp_256x320_dense": r"gemm_pp_kernel<256, 2, 4, 0, false, false>", "gemm_pp_256x320_ln_dense": r"gemm_pp_kernel<256, 2, 4, 0, false, true>",
-    "gemm_pp_256x320_conv3x3": r"gemm_pp_kernel<256, 2, 4, [123], false, false>",
+    "gemm_pp_256x320_conv3x3": r"gemm_pp_kernel<256, 2, 4, [1234], false, false>",
     "gemm_pp_256x320_splitk": r"gemm_pp_kernel<256, 2, 4, \d, true, false>", "gemm_pp_256x320_geglu": r"gemm_pp_kernel<256, 4, 2, 0, false, (false|true)>",
     "gemm_sm_64x64": "gemm_sm_kernel<64, 64,", "gemm_sm_128x64": "gemm_sm_kernel<128, 64,", "gemm_sm_64x128": "gemm_sm_kernel<64, 128,",
     "gemm_sm_128x128": "gemm_sm_kernel<128, 128,", "gemm_sm_64x160": "gemm_sm_kernel<64, 160,", "gemm_sm_128x160": "gemm_sm_kernel<128, 160,",
