@@ -304,6 +304,39 @@ int mvd_op_softmax_rows(const float* s, int rows, int n, void* p_bf16, void* str
 int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, int channels, int hw, float scale, float* out,
                            void* stream);
 
+/* ---- CLIP text encoder in front of the loop ------------------------------------------------ */
+/* Replaces: text_encoder(tokenizer(prompt).input_ids)[0] of transformers' CLIPTextModel (pipeline.py:52-75): the
+ * last_hidden_state only (no pooler, no attention mask: the reference passes input_ids alone, pipeline.py:62, 72).
+ * SD-2.1 values in comments.  Slot names / layouts: DESIGN.md "Text-encoder weight slots" (mvd_amd/text_encoder.py packs a
+ * transformers state dict). */
+typedef struct {
+  int vocab_size;          /* 49408 */
+  int hidden_size;         /* 1024 */
+  int intermediate_size;   /* 4096 */
+  int num_layers;          /* 23 */
+  int num_heads;           /* 16 (head dimension 64) */
+  int max_positions;       /* 77 */
+  float layer_norm_eps;    /* 1e-5 */
+  int act;                 /* 0 gelu (erf), 1 quick_gelu = x * sigmoid(1.702 x) */
+} mvd_text_config_t;
+typedef struct mvd_text mvd_text_t;
+/* rejects hidden_size / num_heads != 64, hidden_size % 64 (or > 2048), intermediate_size % 64, max_positions > 96, an unknown act */
+int mvd_text_create(const mvd_text_config_t* cfg, mvd_text_t** out);
+int mvd_text_destroy(mvd_text_t* t);
+int mvd_text_set_weight(mvd_text_t* t, const char* slot, const void* ptr, int64_t numel, int dtype);
+int64_t mvd_text_workspace_bytes(mvd_text_t* t, int batch, int seq_len);
+int mvd_text_bind_workspace(mvd_text_t* t, void* ws, int64_t bytes);
+/* ids [batch][seq_len] int32 (clamped into the vocabulary for address safety only: validate on the host) ->
+ * out [batch][seq_len][hidden_size] fp32.  A missing weight slot, an unbound or too small workspace and seq_len >
+ * max_positions return < 0 before anything is launched.  No allocation, no host synchronisation; everything on `stream`. */
+int mvd_text_encode(mvd_text_t* t, const int32_t* ids, int batch, int seq_len, float* out, void* stream);
+/* The encoder's attention (CLIPAttention with the causal mask of CLIPTextTransformer, reached through pipeline.py:62, 72):
+ * softmax(scale * q.k^T + causal).v per head of 64 channels, nq == nk == n <= 96, key j visible to query i iff j <= i; one
+ * workgroup per (batch, head) with the whole problem in LDS.  scale == 0: q is prescaled by scale * log2(e), as for
+ * mvd_op_attention.  q / k / v 16-byte aligned with row strides that are multiples of 8 (views of one fused QKV buffer). */
+int mvd_op_attention_causal(const void* q, const void* k, const void* v, void* o, int batch, int heads, int n, int ldq, int ldk,
+                            int ldv, int ldo, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,13 @@ class mvd_vae_config_t(C.Structure):
     ]
 
 
+class mvd_text_config_t(C.Structure):
+    _fields_ = [
+        ("vocab_size", C.c_int), ("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_layers", C.c_int),
+        ("num_heads", C.c_int), ("max_positions", C.c_int), ("layer_norm_eps", C.c_float), ("act", C.c_int),
+    ]
+
+
 class mvd_forward_args_t(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("height", C.c_int), ("width", C.c_int), ("text_len", C.c_int),
@@ -129,6 +136,14 @@ _SIGS = {
     "mvd_vae_mid_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_gaussian_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "mvd_text_create": (C.c_int, [C.POINTER(mvd_text_config_t), C.POINTER(C.c_void_p)]),
+    "mvd_text_destroy": (C.c_int, [C.c_void_p]),
+    "mvd_text_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mvd_text_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "mvd_text_bind_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "mvd_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_op_attention_causal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1,0 +1,460 @@
+// CLIP text transformer (the `last_hidden_state` of transformers' CLIPTextModel) on the hot path's kernels -- SURVEY.md 8f
+// row N5: the first stage of MVDPipeline.__call__ (/root/reference/src/models/pipeline.py:52-75, tokenise + text-encode).
+//
+//   x   = token_embedding[ids] + position_embedding[0:T]
+//   per layer:  h = LN1(x); q,k,v = h.Wqkv^T + b;  a = softmax(q.k^T / sqrt(64) + causal).v  per head of 64 channels
+//               x = x + a.Wo^T + bo;  h = LN2(x); h = act(h.W1^T + b1); x = x + h.W2^T + b2
+//   out = final_layer_norm(x)
+//
+// The residual stream x stays in fp32 (23 pre-LN layers add into it); GEMM operands are bf16 with fp32 accumulation.  The
+// GEMMs are the existing kernels, untouched: a projection that feeds the residual writes its fp32 result (`out_f32`) to a
+// delta buffer, and the NEXT kernel -- residual add + LayerNorm in one pass -- folds it into x, so the fp32 residual costs no
+// launch of its own and no epilogue mode of the GEMM kernels changes.  fc1 writes fp32 pre-activations, one pass applies
+// GELU (erf) / quick-GELU and rounds to the bf16 operand of fc2.  Per layer: add+LN, QKV GEMM, causal attention,
+// out-projection, add+LN, fc1, activation, fc2 = 8 launches (plus in-kernel split-K where the small-M planner asks for it).
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <unordered_map>
+
+#include "../../include/mvd_hip.h"
+#include "kernels.h"
+
+namespace {
+
+struct TWeight { const void* p; int64_t numel; int dtype; };
+
+int tcheck(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
+  return 0;
+}
+
+// ---------------------------------------------------------------- embedding gather + position add
+// one wave per row, 16-byte loads; the id is clamped for address safety only (range validation is the caller's, host side)
+__global__ __launch_bounds__(256) void text_embed_kernel(const int* __restrict__ ids, const float* __restrict__ tok, const float* __restrict__ pos,
+                                                         int rows, int T, int H, int vocab, float* __restrict__ x) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  int id = ids[row];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const f32x4* tp = reinterpret_cast<const f32x4*>(tok + (size_t)id * H);
+  const f32x4* pp = reinterpret_cast<const f32x4*>(pos + (size_t)(row % T) * H);
+  f32x4* xp = reinterpret_cast<f32x4*>(x + (size_t)row * H);
+  for (int c = lane; c < H / 4; c += 64) xp[c] = tp[c] + pp[c];
+}
+
+// ---------------------------------------------------------------- residual add + LayerNorm
+// x[row] += delta[row] (fp32, in place; delta may be null), then y = LN(x) as bf16 (y_bf) or fp32 (y_f32).  One wave per
+// row, the row in registers (H <= 2048), two-pass variance.
+constexpr int LN_MAXCH = 8;     // float4 chunks per lane
+__global__ __launch_bounds__(256) void text_add_ln_kernel(float* __restrict__ x, const float* __restrict__ delta, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int rows, int H, float eps, bf16_t* __restrict__ y_bf,
+                                                          float* __restrict__ y_f32) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int nch = H / 4;
+  f32x4* xp = reinterpret_cast<f32x4*>(x + (size_t)row * H);
+  const f32x4* dp = delta ? reinterpret_cast<const f32x4*>(delta + (size_t)row * H) : nullptr;
+  f32x4 v[LN_MAXCH];
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < LN_MAXCH; ++c) {
+    const int ch = c * 64 + lane;
+    v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (ch < nch) {
+      v[c] = xp[ch];
+      if (dp) { v[c] += dp[ch]; xp[ch] = v[c]; }
+      sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
+    }
+  }
+  const float mean = wave_sum(sum) / (float)H;
+  float sq = 0.f;
+#pragma unroll
+  for (int c = 0; c < LN_MAXCH; ++c) {
+    if (c * 64 + lane < nch) {
+      const f32x4 d = v[c] - mean;
+      sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / (float)H + eps);
+#pragma unroll
+  for (int c = 0; c < LN_MAXCH; ++c) {
+    const int ch = c * 64 + lane;
+    if (ch < nch) {
+      const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[ch], b = reinterpret_cast<const f32x4*>(beta)[ch];
+      const f32x4 r = (v[c] - mean) * rstd * g + b;
+      if (y_f32) reinterpret_cast<f32x4*>(y_f32 + (size_t)row * H)[ch] = r;
+      else {
+        const u32x2 o = {pack2bf(r[0], r[1]), pack2bf(r[2], r[3])};
+        reinterpret_cast<u32x2*>(y_bf + (size_t)row * H)[ch] = o;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- activation pass: fp32 pre-activations -> bf16
+// act 0: gelu (erf form), 1: quick_gelu = x * sigmoid(1.702 x).  8 elements per thread (2 x 16-byte loads, one 16-byte store).
+MVD_DEVINL float text_act(float x, int act) {
+  return act ? x / (1.0f + __expf(-1.702f * x)) : 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+}
+__global__ __launch_bounds__(256) void text_act_kernel(const float* __restrict__ x, long n8, int act, bf16_t* __restrict__ y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const f32x4 a = reinterpret_cast<const f32x4*>(x)[2 * i], b = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
+  const u32x4 o = {pack2bf(text_act(a[0], act), text_act(a[1], act)), pack2bf(text_act(a[2], act), text_act(a[3], act)),
+                   pack2bf(text_act(b[0], act), text_act(b[1], act)), pack2bf(text_act(b[2], act), text_act(b[3], act))};
+  reinterpret_cast<u32x4*>(y)[i] = o;
+}
+
+// ---------------------------------------------------------------- causal attention, n <= 96 keys, d = 64
+// One workgroup (4 waves) per (batch, head): q, k and v^T of the whole problem sit in LDS (61 KB with the probability tile),
+// zero filled up to the MFMA tile.  Wave w owns the 16-query row tiles w and w + 4: scores of the tiles at or left of the
+// diagonal by v_mfma_f32_16x16x32_bf16 (A = q rows, B = k rows: D[query][key], a lane holds 4 queries x 1 key per tile), the
+// causal mask on the diagonal tile, fp32 softmax in the exp2 domain with the row reductions across the 16 lanes that share
+// a query, P as bf16 through LDS (A operand of P.V wants keys along k), P.V against v^T rows, 1 / denominator applied to
+// the fp32 result.  Keys beyond the query never reach a result: masked scores become exactly 0 and v is zero beyond n, so
+// 0 * v adds nothing (padded keys j >= n are > every live query and fall under the same mask); padded query rows are
+// computed and never stored.
+constexpr int CA_NP = 96, CA_LDQ = 72, CA_LDP = 104;     // row strides (bf16) padded off the 128-byte bank period, 16-byte multiples
+__global__ __launch_bounds__(256) void text_attn_causal_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                               bf16_t* __restrict__ o, int heads, int n, int ldq, int ldk, int ldv, int ldo,
+                                                               float scale_log2) {
+  __shared__ __attribute__((aligned(16))) bf16_t sQ[CA_NP * CA_LDQ];
+  __shared__ __attribute__((aligned(16))) bf16_t sK[CA_NP * CA_LDQ];
+  __shared__ __attribute__((aligned(16))) bf16_t sVt[64 * CA_LDP];
+  __shared__ __attribute__((aligned(16))) bf16_t sP[CA_NP * CA_LDP];
+  const int b = blockIdx.x / heads, hd = blockIdx.x - b * heads;
+  const size_t row0 = (size_t)b * n;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nt = (n + 15) >> 4;                 // live 16-row tiles (<= 6)
+  const int np32 = ((nt + 1) >> 1) * 32;        // rows staged: P.V walks the keys 32 at a time (<= 96)
+  for (int c = tid; c < np32 * 8; c += 256) {
+    const int r = c >> 3, c8 = (c & 7) * 8;
+    u32x4 qv = {0u, 0u, 0u, 0u}, kv = qv, vv = qv;
+    if (r < n) {
+      qv = *reinterpret_cast<const u32x4*>(q + (row0 + r) * ldq + hd * 64 + c8);
+      kv = *reinterpret_cast<const u32x4*>(k + (row0 + r) * ldk + hd * 64 + c8);
+      vv = *reinterpret_cast<const u32x4*>(v + (row0 + r) * ldv + hd * 64 + c8);
+    }
+    *reinterpret_cast<u32x4*>(sQ + r * CA_LDQ + c8) = qv;
+    *reinterpret_cast<u32x4*>(sK + r * CA_LDQ + c8) = kv;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sVt[(c8 + e) * CA_LDP + r] = (bf16_t)(vv[e >> 1] >> ((e & 1) * 16));
+  }
+  __syncthreads();
+  const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll 1
+  for (int it = 0; it < 2; ++it) {
+    const int i = wave + 4 * it;                // this wave's row tile (wave-uniform)
+    const bool live = i < nt;
+    float inv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+      bf16x8 qa[2];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) qa[kk] = *reinterpret_cast<const bf16x8*>(sQ + (i * 16 + fr) * CA_LDQ + kk * 32 + fq * 8);
+      f32x4 s[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (j <= i) {
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            const bf16x8 kb = *reinterpret_cast<const bf16x8*>(sK + (j * 16 + fr) * CA_LDQ + kk * 32 + fq * 8);
+            s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kk], kb, s[j], 0, 0, 0);
+          }
+        }
+      }
+      // s[j][r]: query i*16 + fq*4 + r, key j*16 + fr
+      float mx[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        if (j <= i) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float t = s[j][r] * scale_log2;
+            if (j == i && fr > fq * 4 + r) t = -3.0e38f;
+            s[j][r] = t;
+            mx[r] = fmaxf(mx[r], t);
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], d, 64));
+      }
+      float sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        if (j <= i) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float p = exp2f(s[j][r] - mx[r]);
+            sum[r] += p;
+            sP[(i * 16 + fq * 4 + r) * CA_LDP + j * 16 + fr] = f2bf(p);
+          }
+        }
+      }
+      if (!(i & 1)) {                           // an odd number of key tiles: the second half of the last 32-key step is zero
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sP[(i * 16 + fq * 4 + r) * CA_LDP + (i + 1) * 16 + fr] = 0;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) sum[r] += __shfl_xor(sum[r], d, 64);
+        inv[r] = 1.0f / sum[r];
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const int nks = (i + 2) >> 1;             // 32-key steps covering keys 0 .. 16 (i + 1) - 1
+      f32x4 acc[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) {
+        if (ks < nks) {
+          const bf16x8 pa = *reinterpret_cast<const bf16x8*>(sP + (i * 16 + fr) * CA_LDP + ks * 32 + fq * 8);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const bf16x8 vb = *reinterpret_cast<const bf16x8*>(sVt + (c * 16 + fr) * CA_LDP + ks * 32 + fq * 8);
+            acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, acc[c], 0, 0, 0);
+          }
+        }
+      }
+      // acc[c][r]: query i*16 + fq*4 + r, channel c*16 + fr
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = i * 16 + fq * 4 + r;
+        if (row < n) {
+          bf16_t* op = o + (row0 + row) * ldo + hd * 64 + fr;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) op[c * 16] = f2bf(acc[c][r] * inv[r]);
+        }
+      }
+    }
+  }
+}
+
+int launch_attn_causal(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, int batch, int heads, int n, int ldq, int ldk, int ldv,
+                       int ldo, float scale, hipStream_t s) {
+  if (!q || !k || !v || !o || batch <= 0 || heads <= 0 || n <= 0) { mvd_set_error("attention_causal: bad argument"); return -1; }
+  if (n > CA_NP) { mvd_set_error("attention_causal: n = %d exceeds %d keys", n, CA_NP); return -1; }
+  if ((ldq | ldk | ldv) % 8 || ldq < heads * 64 || ldk < heads * 64 || ldv < heads * 64 || ldo < heads * 64) {
+    mvd_set_error("attention_causal: row strides must cover heads * 64 channels (q / k / v: multiples of 8)"); return -1;
+  }
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) { mvd_set_error("attention_causal: q / k / v must be 16-byte aligned"); return -1; }
+  if ((long)batch * heads > 0x7fffffffL) { mvd_set_error("attention_causal: grid too large"); return -1; }
+  // scale == 0: q already carries softmax_scale * log2(e) (the packed q rows, as for mvd_op_attention)
+  const float sl = scale == 0.f ? 1.0f : scale * 1.4426950408889634f;
+  hipLaunchKernelGGL(text_attn_causal_kernel, dim3(batch * heads), dim3(256), 0, s, q, k, v, o, heads, n, ldq, ldk, ldv, ldo, sl);
+  return tcheck("attention_causal");
+}
+
+}  // namespace
+
+struct mvd_text {
+  mvd_text_config_t cfg;
+  std::unordered_map<std::string, TWeight> w;
+  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
+};
+
+namespace {
+
+#define TCHECK(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+struct TCtx {
+  mvd_text* t;
+  hipStream_t s;
+  bool dry;
+  bool check_w = true;        // false (sizing only): weight slots are not looked at
+  char* base = nullptr;       // activations start here (behind the split-K tile counters)
+  size_t off = 0, high = 0;
+  unsigned int* cnt_base = nullptr;
+  int cnt_used = 0;
+  int err = 0;
+
+  void* alloc_bytes(size_t bytes) {
+    off = (off + 255) & ~size_t(255);
+    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
+    off += bytes;
+    if (off > high) high = off;
+    return p;
+  }
+  template <class T> T* alloc(size_t n) { return (T*)alloc_bytes(n * sizeof(T)); }
+
+  const TWeight* W(const std::string& name, int dtype, int64_t numel) {
+    if (!check_w) return nullptr;
+    auto it = t->w.find(name);
+    if (it == t->w.end()) { mvd_set_error("text: missing weight slot '%s'", name.c_str()); err = -10; return nullptr; }
+    if (it->second.dtype != dtype || it->second.numel != numel) {
+      mvd_set_error("text: weight slot '%s': expected dtype %d numel %lld, got dtype %d numel %lld", name.c_str(), dtype, (long long)numel,
+                    it->second.dtype, (long long)it->second.numel);
+      err = -11; return nullptr;
+    }
+    return &it->second;
+  }
+  const bf16_t* WB(const std::string& n, int64_t numel) { auto* w = W(n, 1, numel); return w ? (const bf16_t*)w->p : nullptr; }
+  const float* WF(const std::string& n, int64_t numel) { auto* w = W(n, 0, numel); return w ? (const float*)w->p : nullptr; }
+
+  // out[M][N] = a[M][K] . w[N][K]^T + bias: the small-M kernels (split-K combined in the kernel) where their planner takes
+  // the shape, else the tiled kernels (+ split-K reduce) -- the same routing as the UNet engine's
+  int linear(const bf16_t* a, int K, int M, const bf16_t* w, const float* bias, int N, void* out, bool out_f32) {
+    if (err) return err;
+    MvdGemmArgs g; memset(&g, 0, sizeof(g));
+    g.seg[0].p0 = a; g.seg[0].c0 = K; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = K; g.nseg = 1;
+    g.W = w; g.ldw = K; g.M = M; g.N = N; g.Ktot = K; g.rows_per_batch = M; g.outH = 1; g.outW = M;
+    g.bias = bias; g.ldres = N; g.alpha = 1.f; g.out = out; g.ldo = N; g.out_f32 = out_f32 ? 1 : 0;
+    const size_t mark = off;
+    int r = 0;
+    int tile = 0, ns = 0, S = 1;
+    if (mvd_gemm_sm_plan(g, &tile, &ns, &S)) {
+      if (S > 1) {
+        g.splitk = S; g.part = alloc<float>((size_t)S * M * N);
+        g.tile_cnt = cnt_base + cnt_used;
+        cnt_used += ((M + 63) / 64) * (N / 64);       // (an upper bound for every tile shape)
+      }
+      if (!dry) r = mvd_launch_gemm_sm(g, s, tile, ns);
+    } else {
+      S = mvd_gemm_pick_splitk(g);
+      if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * M * N); } else g.splitk = 1;
+      if (!dry) {
+        r = mvd_launch_gemm(g, s);
+        if (!r && S > 1) r = mvd_launch_splitk_reduce(g, s);
+      }
+    }
+    off = mark;
+    return r;
+  }
+  int add_ln(float* x, const float* delta, const float* g, const float* b, int rows, int H, bf16_t* y_bf, float* y_f32) {
+    if (err) return err;
+    if (dry) return 0;
+    hipLaunchKernelGGL(text_add_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, delta, g, b, rows, H, t->cfg.layer_norm_eps, y_bf, y_f32);
+    return tcheck("text add+layernorm");
+  }
+};
+
+size_t cnt_bytes(int cnt) { return ((size_t)cnt * 4 + 255) & ~size_t(255); }
+
+// dry: sizes only (x.high, x.cnt_used); otherwise `cnt` = the counter words the dry run asked for
+int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream_t s, bool dry, int cnt, size_t* high_out, int* cnt_out,
+                bool check_w = true) {
+  const mvd_text_config_t& c = t->cfg;
+  const int H = c.hidden_size, I = c.intermediate_size, M = B * T;
+  TCtx x{t, s, dry};
+  x.check_w = check_w;
+  if (!dry) {
+    x.cnt_base = reinterpret_cast<unsigned int*>(t->ws_ptr);
+    x.base = reinterpret_cast<char*>(t->ws_ptr) + cnt_bytes(cnt);
+    if (cnt > 0 && hipMemsetAsync(x.cnt_base, 0, (size_t)cnt * 4, s) != hipSuccess) { mvd_set_error("text_encode: hipMemsetAsync failed"); return -3; }
+  }
+  float* xs = x.alloc<float>((size_t)M * H);          // residual stream
+  float* dl = x.alloc<float>((size_t)M * H);          // fp32 result of the projection that feeds it
+  bf16_t* h = x.alloc<bf16_t>((size_t)M * H);
+  bf16_t* qkv = x.alloc<bf16_t>((size_t)M * 3 * H);
+  bf16_t* at = x.alloc<bf16_t>((size_t)M * H);
+  float* f1 = x.alloc<float>((size_t)M * I);
+  bf16_t* g1 = x.alloc<bf16_t>((size_t)M * I);
+  const float* tok = x.WF("tok", (int64_t)c.vocab_size * H);
+  const float* pos = x.WF("pos", (int64_t)c.max_positions * H);
+  if (x.err) return x.err;
+  if (!dry) {
+    hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, tok, pos, M, T, H, c.vocab_size, xs);
+    TCHECK(tcheck("text embedding"));
+  }
+  for (int l = 0; l < c.num_layers; ++l) {
+    const std::string p = "layers." + std::to_string(l);
+    const float *g1w = x.WF(p + ".ln1.g", H), *b1w = x.WF(p + ".ln1.b", H), *g2w = x.WF(p + ".ln2.g", H), *b2w = x.WF(p + ".ln2.b", H);
+    const bf16_t *wqkv = x.WB(p + ".qkv.w", (int64_t)3 * H * H), *wo = x.WB(p + ".out.w", (int64_t)H * H);
+    const bf16_t *w1 = x.WB(p + ".fc1.w", (int64_t)I * H), *w2 = x.WB(p + ".fc2.w", (int64_t)H * I);
+    const float *bqkv = x.WF(p + ".qkv.b", 3 * H), *bo = x.WF(p + ".out.b", H), *bf1 = x.WF(p + ".fc1.b", I), *bf2 = x.WF(p + ".fc2.b", H);
+    if (x.err) return x.err;
+    TCHECK(x.add_ln(xs, l ? dl : nullptr, g1w, b1w, M, H, h, nullptr));
+    TCHECK(x.linear(h, H, M, wqkv, bqkv, 3 * H, qkv, false));
+    if (!dry) TCHECK(launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s));   // q rows prescaled at pack time
+    TCHECK(x.linear(at, H, M, wo, bo, H, dl, true));
+    TCHECK(x.add_ln(xs, dl, g2w, b2w, M, H, h, nullptr));
+    TCHECK(x.linear(h, H, M, w1, bf1, I, f1, true));
+    if (!dry) {
+      const long n8 = (long)M * I / 8;
+      hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, f1, n8, c.act, g1);
+      TCHECK(tcheck("text activation"));
+    }
+    TCHECK(x.linear(g1, I, M, w2, bf2, H, dl, true));
+  }
+  const float *gf = x.WF("final_ln.g", H), *bf = x.WF("final_ln.b", H);
+  if (x.err) return x.err;
+  TCHECK(x.add_ln(xs, c.num_layers ? dl : nullptr, gf, bf, M, H, nullptr, out));
+  if (high_out) *high_out = x.high;
+  if (cnt_out) *cnt_out = x.cnt_used;
+  return x.err;
+}
+
+int check_shape(mvd_text* t, int batch, int seq_len, const char* who) {
+  if (batch <= 0 || seq_len <= 0) { mvd_set_error("%s: bad shape (batch %d, seq_len %d)", who, batch, seq_len); return -1; }
+  if (seq_len > t->cfg.max_positions) { mvd_set_error("%s: seq_len %d exceeds max_positions %d", who, seq_len, t->cfg.max_positions); return -1; }
+  if ((long)batch * seq_len > (1L << 20)) { mvd_set_error("%s: batch %d x seq_len %d rows is beyond what one call takes", who, batch, seq_len); return -1; }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvd_text_create(const mvd_text_config_t* cfg, mvd_text_t** out) {
+  if (!cfg || !out) { mvd_set_error("text_create: null argument"); return -1; }
+  if (cfg->num_heads <= 0 || cfg->hidden_size != cfg->num_heads * 64) { mvd_set_error("text_create: hidden_size %d / num_heads %d: the head dimension must be 64", cfg->hidden_size, cfg->num_heads); return -1; }
+  if (cfg->hidden_size % 64 || cfg->hidden_size > LN_MAXCH * 256) { mvd_set_error("text_create: hidden_size %d must be a multiple of 64, at most %d", cfg->hidden_size, LN_MAXCH * 256); return -1; }
+  if (cfg->intermediate_size <= 0 || cfg->intermediate_size % 64) { mvd_set_error("text_create: intermediate_size %d must be a multiple of 64", cfg->intermediate_size); return -1; }
+  if (cfg->max_positions <= 0 || cfg->max_positions > CA_NP) { mvd_set_error("text_create: max_positions %d must be in 1..%d", cfg->max_positions, CA_NP); return -1; }
+  if (cfg->act != 0 && cfg->act != 1) { mvd_set_error("text_create: act %d (0 gelu, 1 quick_gelu)", cfg->act); return -1; }
+  if (cfg->vocab_size <= 0 || cfg->num_layers < 0 || !(cfg->layer_norm_eps > 0.f)) { mvd_set_error("text_create: bad vocab_size / num_layers / layer_norm_eps"); return -1; }
+  mvd_text* t = new mvd_text();
+  t->cfg = *cfg;
+  *out = t;
+  return 0;
+}
+int mvd_text_destroy(mvd_text_t* t) { delete t; return 0; }
+
+int mvd_text_set_weight(mvd_text_t* t, const char* slot, const void* ptr, int64_t numel, int dtype) {
+  if (!t || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("text_set_weight: bad argument"); return -1; }
+  if ((uintptr_t)ptr & 15) { mvd_set_error("text_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
+  t->w[slot] = TWeight{ptr, numel, dtype};
+  return 0;
+}
+
+int64_t mvd_text_workspace_bytes(mvd_text_t* t, int batch, int seq_len) {
+  if (!t) { mvd_set_error("text_workspace_bytes: null handle"); return -1; }
+  if (int r = check_shape(t, batch, seq_len, "text_workspace_bytes")) return r;
+  size_t high = 0; int cnt = 0;
+  if (int r = encode_impl(t, nullptr, batch, seq_len, nullptr, nullptr, true, 0, &high, &cnt, false)) return r;   // (sizes do not depend on the weights)
+  return (int64_t)(cnt_bytes(cnt) + high + 4096);
+}
+
+int mvd_text_bind_workspace(mvd_text_t* t, void* ws, int64_t bytes) {
+  if (!t || !ws || bytes <= 0 || ((uintptr_t)ws & 255)) { mvd_set_error("text_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
+  t->ws_ptr = ws; t->ws_bytes = bytes;
+  return 0;
+}
+
+int mvd_text_encode(mvd_text_t* t, const int32_t* ids, int batch, int seq_len, float* out, void* stream) {
+  if (!t || !ids || !out) { mvd_set_error("text_encode: null argument"); return -1; }
+  if (int r = check_shape(t, batch, seq_len, "text_encode")) return r;
+  size_t high = 0; int cnt = 0;
+  if (int r = encode_impl(t, nullptr, batch, seq_len, nullptr, nullptr, true, 0, &high, &cnt)) return r;   // weights and sizes first: nothing is launched on a failure
+  if (!t->ws_ptr) { mvd_set_error("text_encode: workspace not bound"); return -1; }
+  if (cnt_bytes(cnt) + high > (size_t)t->ws_bytes) { mvd_set_error("text_encode: workspace too small: need %zu bytes, bound %lld", cnt_bytes(cnt) + high, (long long)t->ws_bytes); return -4; }
+  return encode_impl(t, ids, batch, seq_len, out, (hipStream_t)stream, false, cnt, nullptr, nullptr);
+}
+
+int mvd_op_attention_causal(const void* q, const void* k, const void* v, void* o, int batch, int heads, int n, int ldq, int ldk, int ldv,
+                            int ldo, float scale, void* stream) {
+  return launch_attn_causal((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, batch, heads, n, ldq, ldk, ldv, ldo, scale,
+                            (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -368,13 +368,16 @@ def create_mvd_pipeline(pretrained_model_name_or_path: str, dtype: torch.dtype =
                         img_ref_scale: float = 0.25, cam_modulation_strength: float = 1.0, cam_output_dim: int = 1024,
                         cam_hidden_dim: int = 512, simple_cam_encoder: bool = False, cache_dir=None,
                         scheduler_config: Optional[Dict[str, Any]] = None, *, unet_config: Optional[UNetConfig] = None,
-                        init: str = "default", sampler: str = "ddpm"):
+                        init: str = "default", sampler: str = "ddpm", text_encoder: str = "transformers"):
     """mvd_unet.py:388-453: returns an ``MVDPipeline`` whose ``unet`` is this ``MultiViewUNet`` and whose scheduler is the
     interpolated SNR-shifted DDPM scheduler (``scheduler_config`` is accepted and ignored like the reference, :401,
     420-421).  Text encoder / VAE are attached when a local snapshot directory provides them; nothing is downloaded.
     ``unet_config`` / ``init`` are keyword-only extensions for checkpoint-free construction (tests, synthetic weights);
-    ``sampler`` (keyword-only) picks the scheduler class of the shifted schedule: "ddpm" (default), "ddim", "dpmsolver++"."""
+    ``sampler`` (keyword-only) picks the scheduler class of the shifted schedule: "ddpm" (default), "ddim", "dpmsolver++";
+    ``text_encoder`` (keyword-only): "transformers" (default, today's optional component) or "hip" (``CLIPTextModelHIP`` and the
+    native CLIP tokenizer from the snapshot: prompt strings without the transformers package; missing files are an error)."""
     from .pipeline import build_pipeline
     return build_pipeline(pretrained_model_name_or_path, dtype, use_camera_conditioning, use_image_conditioning,
                           img_ref_scale, cam_modulation_strength, cam_output_dim, cam_hidden_dim, simple_cam_encoder,
-                          cache_dir, unet_config=unet_config, init=init, sampler=sampler)
+                          cache_dir, unet_config=unet_config, init=init, sampler=sampler,
+                          text_encoder=text_encoder)

@@ -143,6 +143,20 @@ def attention(q, k, v, heads, scale=0.125):
     return out
 
 
+def attention_causal(q, k, v, heads, scale=0.125):
+    """The CLIP text encoder's attention: q, k, v (B, n, heads*64) bf16 with n <= 96, key j visible to query i iff j <= i; row
+    strides may exceed heads*64 (views of one fused QKV buffer).  scale=0: q already carries 64^-0.5 * log2(e)."""
+    _bf16(q, k, v)
+    B, n, _ = q.shape
+    assert k.shape[1] == n and v.shape[1] == n
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    assert q.stride(0) == n * q.stride(1) and k.stride(0) == n * k.stride(1) and v.stride(0) == n * v.stride(1)
+    out = torch.empty(B, n, heads * 64, device=q.device, dtype=torch.bfloat16)
+    L.call("mvd_op_attention_causal", C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), _p(out),
+           B, heads, n, q.stride(1), k.stride(1), v.stride(1), heads * 64, float(scale), _s())
+    return out
+
+
 def attention_split(q, k, v, heads, nsplit):
     """Split-KV attention (engine form: q carries softmax_scale * log2 e); the keys are cut into ``nsplit`` ranges."""
     _bf16(q, k, v)

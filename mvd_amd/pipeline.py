@@ -260,9 +260,40 @@ def _make_scheduler(path, sampler: str):
                                             scheduler_class=cls)
 
 
-def _optional_components(path, dtype):
-    """VAE / CLIP from a local diffusers snapshot when both the libraries and the files exist; None otherwise."""
+TEXT_ENCODERS = ("transformers", "hip")
+
+
+def _native_text_components(path):
+    """``CLIPTextModelHIP`` + ``CLIPTokenizerLite`` from the snapshot's ``text_encoder/`` and ``tokenizer/`` (row N5).  Missing
+    or unloadable files raise ``MvdError`` -- asking for the native encoder never yields ``None``.  No transformers import."""
+    from .clip_tokenizer import CLIPTokenizerLite
+    from .text_encoder import CLIPTextModelHIP
+    if not path or not os.path.isdir(str(path)):
+        raise L.MvdError(f"text_encoder='hip' needs a local snapshot directory with text_encoder/ and tokenizer/ (got {path!r})")
+    te_dir, tok_dir = os.path.join(str(path), "text_encoder"), os.path.join(str(path), "tokenizer")
+    need = [os.path.join(te_dir, "config.json"), os.path.join(te_dir, "model.safetensors"), os.path.join(tok_dir, "vocab.json"),
+            os.path.join(tok_dir, "merges.txt")]
+    missing = [f for f in need if not os.path.exists(f)]
+    if missing:
+        raise L.MvdError(f"text_encoder='hip': snapshot {path} lacks {', '.join(missing)}")
+    try:
+        tokenizer = CLIPTokenizerLite.from_pretrained(tok_dir)
+        text_encoder = CLIPTextModelHIP.from_snapshot(te_dir)
+    except L.MvdError:
+        raise
+    except Exception as e:
+        raise L.MvdError(f"text encoder / tokenizer under {path} failed to load: {type(e).__name__}: {e}") from e
+    if torch.cuda.is_available():
+        text_encoder = text_encoder.to("cuda")
+    return text_encoder, tokenizer
+
+
+def _optional_components(path, dtype, text_encoder_kind: str = "transformers"):
+    """VAE / CLIP from a local diffusers snapshot when both the libraries and the files exist; None otherwise.
+    ``text_encoder_kind="hip"``: the native encoder and tokenizer instead of transformers' (an error when they cannot load)."""
     vae = text_encoder = tokenizer = None
+    if text_encoder_kind == "hip" and (not path or not os.path.isdir(str(path))):
+        _native_text_components(path)       # raises
     if not path or not os.path.isdir(str(path)):
         return vae, text_encoder, tokenizer
     try:
@@ -274,6 +305,9 @@ def _optional_components(path, dtype):
             vae = AutoencoderKLHIP.from_snapshot(os.path.join(str(path), "vae"))
         except Exception as e:   # a snapshot that is there but does not load is an error, not "no VAE"
             raise L.MvdError(f"VAE snapshot under {os.path.join(str(path), 'vae')} failed to load: {type(e).__name__}: {e}") from e
+    if text_encoder_kind == "hip":
+        text_encoder, tokenizer = _native_text_components(path)
+        return vae, text_encoder, tokenizer
     te_dir, tok_dir = os.path.join(str(path), "text_encoder"), os.path.join(str(path), "tokenizer")
     if os.path.isdir(te_dir) and os.path.isdir(tok_dir):
         try:
@@ -291,15 +325,20 @@ def _optional_components(path, dtype):
 
 def build_pipeline(pretrained_model_name_or_path, dtype, use_camera_conditioning, use_image_conditioning, img_ref_scale,
                    cam_modulation_strength, cam_output_dim, cam_hidden_dim, simple_cam_encoder, cache_dir=None,
-                   unet_config=None, init: str = "default", *, sampler: str = "ddpm") -> MVDPipeline:
+                   unet_config=None, init: str = "default", *, sampler: str = "ddpm",
+                   text_encoder: str = "transformers") -> MVDPipeline:
     """``create_mvd_pipeline`` (mvd_unet.py:388-453): scheduler swap to the interpolated SNR shift (scale 6, hard-coded
     there, :420-428), ``MultiViewUNet`` as ``pipeline.unet``, the three attributes of :449-451.  Nothing is fetched: the
     name resolves to local snapshot files (hub.resolve_snapshot) or the call raises.  ``sampler``: "ddpm" (the
-    reference's ancestral DDPM, the default), "ddim" or "dpmsolver++" -- the same shifted schedule in another class."""
+    reference's ancestral DDPM, the default), "ddim" or "dpmsolver++" -- the same shifted schedule in another class.
+    ``text_encoder``: "transformers" (the default: transformers' CLIP when the package and the snapshot files exist, else none)
+    or "hip" (``CLIPTextModelHIP`` + the native tokenizer from the snapshot; an error when they are missing)."""
     from .hub import resolve_snapshot
     from .mvd_unet import MultiViewUNet
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
+    if text_encoder not in TEXT_ENCODERS:
+        raise ValueError(f"text_encoder={text_encoder!r}: expected one of {TEXT_ENCODERS}")
     # MVDPipeline.from_pretrained(name, cache_dir=...) (mvd_unet.py:411-415): a directory, or a hub name whose snapshot is in a
     # local huggingface cache; a name nothing local answers to raises MvdError (never a random-initialised pipeline)
     pretrained_model_name_or_path = resolve_snapshot(pretrained_model_name_or_path, cache_dir)
@@ -311,7 +350,7 @@ def build_pipeline(pretrained_model_name_or_path, dtype, use_camera_conditioning
                          unet_config=unet_config, init=init)
     if torch.cuda.is_available():
         unet = unet.to(device="cuda", dtype=dtype)
-    vae, text_encoder, tokenizer = _optional_components(pretrained_model_name_or_path, dtype)
+    vae, text_encoder, tokenizer = _optional_components(pretrained_model_name_or_path, dtype, text_encoder)
     # (StableDiffusionPipeline.__init__: vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1))
     vsf = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
     pipe = MVDPipeline(unet, scheduler, vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, vae_scale_factor=vsf)
