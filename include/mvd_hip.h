@@ -244,11 +244,35 @@ int mvd_debug_pick_splitk_conv(int m, int n, int k);
 int mvd_gemm_sm_num_tiles(void);
 /* Measurement hook: log2(waves per attention workgroup) for every later launch of this process; -1 = heuristic. */
 int mvd_debug_set_attention_nw(int nw_log2);
-/* Measurement / bisection switches of the engine's schedule: bit 0 no LayerNorm fold through the small-M kernels, bit 1 the
- * small-M kernels never split K, bit 2 small-M kernels off, bit 3 no split-KV attention, bit 4 the reference-encoder pass on the
- * caller's stream (one stream), bit 5 the single-stream launch policy (split-K / tile choice) also while two streams run,
- * bit 6 the side stream at default instead of highest priority (read when the stream is created), bit 20 (1048576) the upsampling
- * convolutions keep the nine-tap kernel (no 2x2 sub-pixel form).  0 = the product's behaviour. */
+/* Measurement / bisection switches (bench.py --debug-flags, tools/, A/B tests): OR them into mvd_debug_set_flags.  Every switch
+ * is read per launch or per forward unless it says otherwise, so 0 restores the product's behaviour.  The values are quoted
+ * by DESIGN.md and profiles/ and never change; mvd_amd/_lib.py DebugFlag mirrors them (tests/test_cabi_cpu.py compares). */
+typedef enum {
+  MVD_DBG_NO_SM_LN_FOLD = 1,            /* no LayerNorm fold through the small-M kernels */
+  MVD_DBG_SM_NO_SPLITK = 2,             /* small-M kernels never split K */
+  MVD_DBG_NO_SM = 4,                    /* small-M kernels off */
+  MVD_DBG_NO_SPLIT_KV = 8,              /* no split-KV attention */
+  MVD_DBG_ONE_STREAM = 16,              /* encoder pass on the caller's stream */
+  MVD_DBG_SINGLE_STREAM_POLICY = 32,    /* single-stream launch policy (split-K / tile choice) also while two streams run */
+  MVD_DBG_SIDE_DEFAULT_PRIORITY = 64,   /* side stream at default instead of highest priority (read when the stream is created) */
+  MVD_DBG_NO_XS = 128,                  /* X-stationary kernels off */
+  MVD_DBG_NO_WS = 256,                  /* conv_ws off */
+  MVD_DBG_WS_SMALL_MAPS = 512,          /* conv_ws only for maps of at most 256 pixels */
+  MVD_DBG_WS_BLOCK64 = 1024,            /* conv_ws 64-pixel blocks everywhere */
+  MVD_DBG_WS_NO_SHORTCUT = 2048,        /* conv_ws not with a fused shortcut */
+  MVD_DBG_WS_NOT_IN_ENCODER = 4096,     /* conv_ws not in the encoder pass of a two-stream forward */
+  MVD_DBG_WS_ONLY_IN_ENCODER = 8192,    /* conv_ws only in the encoder pass of a two-stream forward */
+  MVD_DBG_WS_THEN_TILED = 16384,        /* conv_ws, and then the tiled kernel over it */
+  MVD_DBG_WS_CHECK = 32768,             /* probe builds: compare conv_ws with the tiled kernel */
+  MVD_DBG_GRAPH_ONE_STREAM = 65536,     /* graph capture on one stream */
+  MVD_DBG_PP_ROW_MAJOR = 131072,        /* ping-pong kernels: row-major tile walk (gemm_pp.hip) */
+  MVD_DBG_NO_DEEP_CONV_SPLIT = 262144,  /* no deep-conv split rule (gemm.hip deep_conv_split) */
+  MVD_DBG_LATE_FROM_UP1 = 524288,       /* main pass back to the single-stream policy from up_blocks.1 on */
+  MVD_DBG_NO_UP4 = 1048576,             /* upsamplers keep the nine-tap kernel (no 2x2 sub-pixel form) */
+  MVD_DBG_GN_ONE_PASS = 2097152,        /* one-pass GroupNorm also for few big slices (norm.hip) */
+  MVD_DBG_FORK_LATE = 4194304,          /* front matter of both passes first, the stream fork behind it */
+  MVD_DBG_SKINNY_VECTOR = 8388608       /* skinny linear: vector form instead of the fp32 matrix pipe (misc.hip) */
+} mvd_debug_flag_t;
 int mvd_debug_set_flags(int flags);
 
 /* ---- denoising-loop helpers either side of the UNet, fp32 latents ------ */

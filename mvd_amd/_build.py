@@ -1,4 +1,5 @@
 """Build libmvd_hip.so (gfx950) in-tree with hipcc.  No JIT cache: the .so travels with the repo snapshot."""
+import glob
 import os
 import subprocess
 import sys
@@ -33,7 +34,7 @@ def _stale(out, deps):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "kernels.h")] + [os.path.join(HERE, "..", "include", "mvd_hip.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "mvd_hip.h")]
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = []

@@ -5,6 +5,7 @@ There is NO fallback: if the library is missing or a call fails, an exception is
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,6 +18,35 @@ MVD_USE_CAMERA, MVD_USE_IMAGE, MVD_REUSE_REF, MVD_KEEP_FEATURES = 1, 2, 4, 8
 
 class MvdError(RuntimeError):
     pass
+
+
+class DebugFlag(enum.IntFlag):
+    """mvd_debug_set_flags switches: mvd_debug_flag_t of include/mvd_hip.h without the MVD_DBG_ prefix (the meanings are there;
+    tests/test_cabi_cpu.py keeps the two in step).  0 = the product's behaviour."""
+    NO_SM_LN_FOLD = 1
+    SM_NO_SPLITK = 2
+    NO_SM = 4
+    NO_SPLIT_KV = 8
+    ONE_STREAM = 16
+    SINGLE_STREAM_POLICY = 32
+    SIDE_DEFAULT_PRIORITY = 64
+    NO_XS = 128
+    NO_WS = 256
+    WS_SMALL_MAPS = 512
+    WS_BLOCK64 = 1024
+    WS_NO_SHORTCUT = 2048
+    WS_NOT_IN_ENCODER = 4096
+    WS_ONLY_IN_ENCODER = 8192
+    WS_THEN_TILED = 16384
+    WS_CHECK = 32768
+    GRAPH_ONE_STREAM = 65536
+    PP_ROW_MAJOR = 131072
+    NO_DEEP_CONV_SPLIT = 262144
+    LATE_FROM_UP1 = 524288
+    NO_UP4 = 1048576
+    GN_ONE_PASS = 2097152
+    FORK_LATE = 4194304
+    SKINNY_VECTOR = 8388608
 
 
 class mvd_config_t(C.Structure):

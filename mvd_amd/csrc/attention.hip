@@ -36,6 +36,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
 
@@ -160,9 +161,8 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
   const unsigned ld_vo = ((unsigned)ld_row * (unsigned)ldv + ld_kc * 8) * 2u;
   const char* kp_b = reinterpret_cast<const char*>(kp);
   const char* vp_b = reinterpret_cast<const char*>(vp);
-  typedef __attribute__((address_space(3))) void lds_void_t;
-  __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(kp), 0, (nk - 1) * ldk * 2 + 128, 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(vp), 0, (nk - 1) * ldv * 2 + 128, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_k = buf_rsrc(kp, (nk - 1) * ldk * 2 + 128);
+  __amdgpu_buffer_rsrc_t rs_v = buf_rsrc(vp, (nk - 1) * ldv * 2 + 128);
   const unsigned dma_ko = (unsigned)ld_row * (unsigned)ldk * 2u + ((ld_kc ^ ((ld_row >> 1) & 7)) << 4);
   const unsigned dma_vo = (unsigned)ld_row * (unsigned)ldv * 2u + ((ld_kc ^ (((ld_row >> 1) & 1) << 2)) << 4);
   auto dma_tile = [&](int kb, int st) {            // tile kb -> stage st (lane-linear LDS image, swizzled source chunk)
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
 #pragma unroll
     for (int i = 0; i < LD_IT; ++i) {
       const int row0 = kb * KV_TILE + i * (NT / 8);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_void_t*)(dk + i * (NT / 8) * 128), 16, (int)dma_ko, row0 * ldk * 2, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lds_void_t*)(dv + i * (NT / 8) * 128), 16, (int)dma_vo, row0 * ldv * 2, 0, 0);
+      dma16(rs_k, dk + i * (NT / 8) * 128, dma_ko, row0 * ldk * 2);
+      dma16(rs_v, dv + i * (NT / 8) * 128, dma_vo, row0 * ldv * 2);
     }
   };
   u32x4 rk[DMA ? 1 : LD_IT], rv[DMA ? 1 : LD_IT];
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
       const size_t grp = (size_t)pair * nqb + qb_;                         // (pair, query block)
       bf16_t* wo = reinterpret_cast<bf16_t*>(a.split_ws) + (grp * nsplit + sp) * (size_t)(QB * 64);
       float2* wml = reinterpret_cast<float2*>(reinterpret_cast<bf16_t*>(a.split_ws) + (size_t)gridDim.x * (QB * 64)) + (grp * nsplit + sp) * QB;
-      __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(wo, 0, QB * 128, 0x00020000);
+      __amdgpu_buffer_rsrc_t rs_o = buf_rsrc(wo, QB * 128);
       const int ql = wave * 32 + lq;                                       // query inside the block
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
       const int mrow = qblk0 + mq;
       const bf16_t* wo0 = reinterpret_cast<const bf16_t*>(a.split_ws) + grp * nsplit * (size_t)(QB * 64);
       const float2* wml0 = reinterpret_cast<const float2*>(reinterpret_cast<const bf16_t*>(a.split_ws) + (size_t)gridDim.x * (QB * 64)) + grp * nsplit * QB;
-      __amdgpu_buffer_rsrc_t rs_i = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(wo0), 0, nsplit * QB * 128, 0x00020000);
+      __amdgpu_buffer_rsrc_t rs_i = buf_rsrc(wo0, nsplit * QB * 128);
       typedef __attribute__((address_space(1))) unsigned long long gu64c;
       float mmax = -3.0e38f;
       float ms[8], ls[8];

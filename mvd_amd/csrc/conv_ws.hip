@@ -30,14 +30,10 @@
 #include "../../include/mvd_hip.h"
 #include <type_traits>
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-MVD_DEVINL void ws_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
 #ifdef WS_LAG_TEST     // diagnosis builds: idle cycles between the counted wait and the first read of what it waited for
 #define WS_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)\n\ts_sleep 16" ::"n"(n) : "memory")
 #else
@@ -81,10 +77,10 @@ MVD_DEVINL void ws_pass(const __amdgpu_buffer_rsrc_t rs_x, const unsigned (&svo)
     unsigned char* dst = slabs + (rd & 1) * SLAB;
     const unsigned so = (unsigned)rd * xstep;
 #pragma unroll
-    for (int i = 0; i < NSL; ++i) ws_dma16(rs_x, dst + i * 1024, svo[i], so);
+    for (int i = 0; i < NSL; ++i) dma16(rs_x, dst + i * 1024, svo[i], so);
   };
   auto issue_w = [&](int rd, int t, int slot) {
-    ws_dma16(rs_w, ring + slot * 1024, (unsigned)lane * 16u, wso + (unsigned)((rd * 4 * T + t) * 1024));
+    dma16(rs_w, ring + slot * 1024, (unsigned)lane * 16u, wso + (unsigned)((rd * 4 * T + t) * 1024));
   };
   auto round = [&](int rd, auto la_tag) {
     constexpr int LA = decltype(la_tag)::value;            // how many of the rounds rd + 1, rd + 2 exist
@@ -168,14 +164,14 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(const MvdWsArgs a) {
 
   const int Rc = a.C / 128, Rs0 = a.scc0 / 128, Rs1 = a.scc1 / 128;
   const unsigned tile_bytes = (unsigned)((Rc * 9 + Rs0 + Rs1) * 4) * 1024u;            // packed bytes of one column tile
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.w), 0, (int)((size_t)nct * tile_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(a.w, (int)((size_t)nct * tile_bytes));
   f32x4 acc[RB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- the convolution: rounds of 128 channels x 9 taps
   {
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)((size_t)a.B * a.H * G::WI * a.C * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buf_rsrc(a.x, (int)((size_t)a.B * a.H * G::WI * a.C * 2));
     unsigned svo[NSL];
 #pragma unroll
     for (int i = 0; i < NSL; ++i) {
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(256) void conv_ws_kernel(const MvdWsArgs a) {
     const bf16_t* p = sgm ? a.sc1 : a.sc0;
     const int cc = sgm ? a.scc1 : a.scc0, Rs = sgm ? Rs1 : Rs0;
     if (!p || !Rs) continue;
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p), 0, (int)((size_t)a.M * cc * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_s = buf_rsrc(p, (int)((size_t)a.M * cc * 2));
     unsigned svo[RB];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {

@@ -15,42 +15,16 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/mvd_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 
 int mvd_launch_silu_to_bf16(const float* x, int64_t n, bf16_t* y, hipStream_t s);
 
-// measurement / bisection switches (bench.py --debug-flags, tools/): bit 0 = no LayerNorm fold through the small-M kernels,
-// bit 1 = small-M kernels never split K, bit 2 = small-M kernels off, bit 3 = no split-KV attention, bit 4 = no side stream,
-// bit 7 (128) = X-stationary kernels off
+// measurement / bisection switches (bench.py --debug-flags, tools/): mvd_debug_flag_t of include/mvd_hip.h
 static int g_debug_flags = 0;
 extern "C" int mvd_debug_set_flags(int flags) { g_debug_flags = flags; return 0; }
 int mvd_debug_flags() { return g_debug_flags; }
 
 namespace {
-
-struct Weight { const void* p; int64_t numel; int dtype; };
-
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, off = 0, high = 0;
-  bool dry = false;
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
-    off += bytes;
-    if (off > high) high = off;
-    return p;
-  }
-  bool overflow() const { return !dry && high > cap; }
-};
-
-struct Act {  // NHWC bf16 activation
-  bf16_t* p = nullptr;
-  int B = 0, H = 0, W = 0, C = 0;
-  int hw() const { return H * W; }
-  int rows() const { return B * H * W; }
-};
 
 struct FeatureInfo { std::string name; int level; int C; int heads; std::string key; /* weight-slot prefix of the block */ };
 constexpr int MVD_REF_ONLY_INTERNAL = 1 << 30;   // set by mvd_engine_reference_encode only (rejected on the public entry)
@@ -59,7 +33,7 @@ constexpr int MVD_REF_ONLY_INTERNAL = 1 << 30;   // set by mvd_engine_reference_
 
 struct mvd_engine {
   mvd_config_t cfg;
-  std::unordered_map<std::string, Weight> w[2];
+  WeightTable w[2];
   Arena tmp, act, persist;
   void* ws_ptr = nullptr; int64_t ws_bytes = 0;
   void* rc_ptr = nullptr; int64_t rc_bytes = 0;
@@ -89,10 +63,10 @@ struct mvd_engine {
     {
       // the side stream gets the HIGHEST priority: the encoder pass is the producer of every adapter attention's K/V, and with it
       // ahead the main pass fills the gaps (cfg4 cold, same box: default priority 63.06 / 62.83 ms, lowest 62.92 / 62.78, highest
-      // 62.69 / 62.58; batch 1 indifferent; mvd_debug_set_flags bit 64 = default priority, for A/B)
+      // 62.69 / 62.58; batch 1 indifferent; MVD_DBG_SIDE_DEFAULT_PRIORITY, for A/B)
       int lo = 0, hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      const int pr = (g_debug_flags & 64) ? 0 : hi;
+      const int pr = (g_debug_flags & MVD_DBG_SIDE_DEFAULT_PRIORITY) ? 0 : hi;
       if (hipStreamCreateWithPriority(&side, hipStreamNonBlocking, pr) != hipSuccess) { mvd_set_error("engine: hipStreamCreate failed"); return -3; }
     }
     feat_ev.resize(feats.size());
@@ -114,7 +88,6 @@ struct mvd_engine {
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
-  int dual_late_from = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);   // up-block index from which that holds (99: never)
   bool graph_on = false;
   std::vector<GraphEntry> graphs;
   std::vector<std::string> graph_seen;      // keys that ran once un-captured (first-use initialisation happens there)
@@ -147,22 +120,15 @@ struct mvd_engine {
   }
 };
 
-// profiling classes: 0..5 = gemm tile config, 8..11 = attention NW (1,2,4,8), 16 groupnorm, 17 layernorm, 18 other
-// profile class of a GEMM launch = the KERNEL that runs it (each is a distinct rocprof kernel name): tile config for the
-// lock-step kernels of gemm.hip; for the ping-pong kernels of gemm_pp.hip 7 = dense A operand, 13 = implicit-GEMM 3x3
-// convolution (incl. the fused 1x1 shortcut / upsample forms), 14 = their split-K forms, 15 = dense with the LayerNorm fold,
-// 6 = GEGLU (with or without the fold).  (8..11 are attention.)  30..33 = the X-stationary kernels of gemm_xs.hip (dense, residual,
-// LayerNorm, GEGLU).
+// profiling class (MvdProfClass, kernels.h) of a launch of the tiled kernels with tile config `cfg`
 static inline int gemm_class(const MvdGemmArgs& g, int cfg, int splitk) {
-  if (cfg == 8) return 12;
-  if (cfg == 7) return splitk > 1 ? 14 : (g.seg[0].mode == MVD_A_CONV3 ? 13 : (g.ln_c1 ? 15 : 7));
-  return cfg;
+  if (cfg == 8) return MVD_PC_GEMM_128X320;
+  if (cfg == 7) return splitk > 1 ? MVD_PC_PP_SPLITK : (g.seg[0].mode == MVD_A_CONV3 ? MVD_PC_PP_CONV3 : (g.ln_c1 ? MVD_PC_PP_LN_DENSE : MVD_PC_PP_DENSE));
+  return MVD_PC_GEMM_256X160 + cfg;       // (configs 0..5 of gemm.hip, 6 = MVD_PC_PP_GEGLU)
 }
 int mvd_attention_pick_nw(const MvdAttnArgs& a);
 
 namespace {
-
-#define CHECK(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 #ifdef MVD_PROBE
 struct WsCheckRec { std::string slot; int set; bool side; const char* p[4]; size_t n[4]; };
@@ -197,14 +163,8 @@ extern "C" void mvd_debug_ws_check_report(void) {
   int nbad = 0;
   for (size_t i = 0; i < g_ws_recs.size(); ++i)
     if (g_ws_cnt[2 * i]) { ++nbad; fprintf(stderr, "ws check: launch %zu %s (set %d, %s stream): %llu of %llu elements beyond tolerance\n", i, g_ws_recs[i].slot.c_str(), g_ws_recs[i].set, g_ws_recs[i].side ? "side" : "main", g_ws_cnt[2 * i], g_ws_cnt[2 * i + 1]); }
-  {   // where the mismatches sit: (launch, row m, channel n) histogram by row block of 64 and channel tile of 16
+  {   // where the mismatches sit
     const unsigned long long nlog = g_ws_cnt[8192 * 2 - 1] < 4096 ? g_ws_cnt[8192 * 2 - 1] : 4096;
-    std::unordered_map<unsigned long long, int> tiles;
-    for (unsigned long long k = 0; k < nlog; ++k) {
-      const unsigned long long v = g_ws_cnt[8192 * 2 + 2 * k], launch = v >> 40, idx = v & ((1ull << 40) - 1);
-      const int N = 0; (void)N;
-      tiles[(launch << 40) | idx] = 1;
-    }
     // print the first 24 raw entries (index decoded by the reader: idx = m * N + n)
     for (unsigned long long k = 0; k < nlog && k < 24; ++k) {
       const unsigned long long v = g_ws_cnt[8192 * 2 + 2 * k], w = g_ws_cnt[8192 * 2 + 2 * k + 1];
@@ -239,29 +199,18 @@ struct Ctx {
   int err = 0;
   bool nowait = false;   // split-K combines must not wait for other workgroups (kernels of two streams share the chip)
 
-  const Weight* W(const std::string& name, int dtype, int64_t numel, int set_override = -1) {
+  const void* W(const std::string& name, int dtype, int64_t numel, int set_override = -1) {
     if (dry) return nullptr;  // sizing run: weights need not be registered
     const int st = set_override >= 0 ? set_override : set;
-    auto it = e->w[st].find(name);
-    if (it == e->w[st].end()) { mvd_set_error("missing weight slot '%s' in set %d", name.c_str(), st); err = -10; return nullptr; }
-    if (it->second.dtype != dtype || it->second.numel != numel) {
-      mvd_set_error("weight slot '%s' (set %d): expected dtype %d numel %lld, got dtype %d numel %lld", name.c_str(), st, dtype,
-                    (long long)numel, it->second.dtype, (long long)it->second.numel);
-      err = -11; return nullptr;
-    }
-    return &it->second;
+    return e->w[st].find(name, dtype, numel, &err, "", st);
   }
-  const bf16_t* WB(const std::string& n, int64_t numel, int so = -1) { auto* w = W(n, 1, numel, so); return w ? (const bf16_t*)w->p : nullptr; }
-  const float* WF(const std::string& n, int64_t numel, int so = -1) { auto* w = W(n, 0, numel, so); return w ? (const float*)w->p : nullptr; }
-  bool has(const std::string& n, int so = -1) { const int st = so >= 0 ? so : set; return e->w[st].count(n) != 0; }
+  const bf16_t* WB(const std::string& n, int64_t numel, int so = -1) { return (const bf16_t*)W(n, 1, numel, so); }
+  const float* WF(const std::string& n, int64_t numel, int so = -1) { return (const float*)W(n, 0, numel, so); }
+  bool has(const std::string& n, int so = -1) { return e->w[so >= 0 ? so : set].has(n); }
 
-  template <class T> T* talloc(size_t n) { return (T*)e->tmp.alloc(n * sizeof(T)); }
-  template <class T> T* aalloc(size_t n) { return (T*)e->act.alloc(n * sizeof(T)); }
-  Act new_act(int B, int H, int W_, int C, bool longlived) {
-    Act a; a.B = B; a.H = H; a.W = W_; a.C = C;
-    a.p = longlived ? aalloc<bf16_t>((size_t)B * H * W_ * C) : talloc<bf16_t>((size_t)B * H * W_ * C);
-    return a;
-  }
+  template <class T> T* talloc(size_t n) { return e->tmp.alloc_n<T>(n); }
+  template <class T> T* aalloc(size_t n) { return e->act.alloc_n<T>(n); }
+  Act new_act(int B, int H, int W_, int C, bool longlived) { return arena_act(longlived ? e->act : e->tmp, B, H, W_, C); }
 
   // ------------------------------------------------------------------ op wrappers
   template <class F> int profiled(int cls, double flops, double bytes, F&& launch) {
@@ -277,7 +226,7 @@ struct Ctx {
   // "the fold is available through them" test (a kill switch must make the forward fall back, not fail)
   static bool sm_enabled() {
     static const bool use_sm = MVD_ENV_INT("MVD_GEMM_SM", 1) != 0;
-    return use_sm && !(g_debug_flags & 4);
+    return use_sm && !(g_debug_flags & MVD_DBG_NO_SM);
   }
   // split factor and forced tile config (-1: the heuristic's) of a launch of the tiled kernels
   void tiled_plan(const MvdGemmArgs& g, int& S, int& fc) {
@@ -289,7 +238,7 @@ struct Ctx {
     // tile is not split along K at 128 tiles (16x16 level; no fp32 partials, no reduce pass), and 100+ tiles of it are preferred
     // to 512 of the 128x160 tile (measured on one box, cfg4 cold: 65.6 -> 64.6 -> 63.5 ms per step; halving or dropping the
     // four-way split of the 8x8 level instead: no gain / a loss; profiles/r03_probe_dual_stream_policies.log).
-    if (e->dual_now && !e->dual_late && !(g_debug_flags & 32) && !g.geglu && !g.ln_c1 && !g.out_f32 && g.N % 320 == 0 && mvd_gemm_pp_applicable(g)) {
+    if (e->dual_now && !e->dual_late && !(g_debug_flags & MVD_DBG_SINGLE_STREAM_POLICY) && !g.geglu && !g.ln_c1 && !g.out_f32 && g.N % 320 == 0 && mvd_gemm_pp_applicable(g)) {
       const int cfg = mvd_gemm_pick_config(g);
       const long t7 = (long)((g.M + 255) / 256) * (g.N / 320);
       if (t7 >= 100) { S = 1; if (cfg != 7) fc = 7; }      // (below 100 tiles -- the 8x8 level -- the heuristic's tile and split stand)
@@ -300,7 +249,7 @@ struct Ctx {
     // small problems (one image's feature maps): the latency-oriented kernels of gemm_sm.hip, split-K combined in the kernel
     int sm_tile = 0, sm_ns = 0, sm_S = 1;
     if (sm_enabled() && mvd_gemm_sm_plan(g, &sm_tile, &sm_ns, &sm_S)) {
-      if (g_debug_flags & 2) sm_S = 1;
+      if (g_debug_flags & MVD_DBG_SM_NO_SPLITK) sm_S = 1;
       const size_t mark = e->tmp.off;
       if (sm_S > 1) {
         g.splitk = sm_S; g.splitk_nowait = nowait ? 1 : 0; g.part = talloc<float>((size_t)sm_S * g.M * g.N);
@@ -313,7 +262,7 @@ struct Ctx {
       if (!dry) {
         const double fl = 2.0 * g.M * (double)g.N * g.Ktot;
         e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = g.seg[0].mode * 100 + g.geglu * 10 + (sm_S > 1 ? sm_S : 0);
-        r = profiled(20 + sm_tile, fl, 0.0, [&] { return mvd_launch_gemm_sm(g, s, sm_tile, sm_ns); });
+        r = profiled(MVD_PC_SM_64X64 + sm_tile, fl, 0.0, [&] { return mvd_launch_gemm_sm(g, s, sm_tile, sm_ns); });
       }
       e->tmp.off = mark;
       return r;
@@ -328,8 +277,7 @@ struct Ctx {
     if (!dry) {
       const double fl = 2.0 * g.M * (double)g.N * g.Ktot;
       e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = g.seg[0].mode * 100 + g.geglu * 10 + (S > 1 ? S : 0);
-      r = profiled(e->prof ? gemm_class(g, mvd_gemm_pick_config(g), S) : 0, fl, 0.0, [&] { return mvd_launch_gemm(g, s, fc); });
-      if (!r && S > 1) r = mvd_launch_splitk_reduce(g, s);
+      r = launch_tiled(g, s, fc, [&](auto&& launch) { return profiled(e->prof ? gemm_class(g, mvd_gemm_pick_config(g), S) : 0, fl, 0.0, launch); });
     }
     e->tmp.off = mark;
     return r;
@@ -342,7 +290,7 @@ struct Ctx {
   int try_xs(const bf16_t* x, int K, int M, const std::string& slot, int64_t n_full, int N, bool geglu, bool ln,
              const bf16_t* res, int ldres, void* out, int ldo, int set_override = -1) {
     if (err) return err;
-    if (dry || (g_debug_flags & 128) || K != 320 || slot.empty() || !has(slot, set_override)) return 0;
+    if (dry || (g_debug_flags & MVD_DBG_NO_XS) || K != 320 || slot.empty() || !has(slot, set_override)) return 0;
     MvdXsArgs a; memset(&a, 0, sizeof(a));
     a.x = x; a.ldx = K; a.M = M; a.K = K; a.units = N / 32; a.geglu = geglu; a.ln = ln; a.ln_eps = 1e-5f;
     a.res = res; a.ldres = ldres; a.out = (bf16_t*)out; a.ldo = ldo;
@@ -353,7 +301,7 @@ struct Ctx {
     a.w = WB(slot, (n_full / 32) * 21 * 512, set_override);
     if (!a.w) return err;
     e->prof_M = M; e->prof_N = N; e->prof_K = K; e->prof_tag = geglu * 10 + (ln ? 1 : 0);
-    const int r = profiled(geglu ? 33 : (res ? 31 : (ln ? 32 : 30)), 2.0 * M * (double)N * K, 0.0, [&] { return mvd_launch_gemm_xs(a, s); });
+    const int r = profiled(geglu ? MVD_PC_XS_GEGLU : (res ? MVD_PC_XS_RESIDUAL : (ln ? MVD_PC_XS_LN_DENSE : MVD_PC_XS_DENSE)), 2.0 * M * (double)N * K, 0.0, [&] { return mvd_launch_gemm_xs(a, s); });
     return r ? r : 1;
   }
 
@@ -365,11 +313,8 @@ struct Ctx {
       const int r = try_xs(a, k1, M, xs, N, N, false, false, res, ldres, out, ldo, xs_set);
       if (r) return r < 0 ? r : 0;
     }
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.ldw = ldw ? ldw : k1 + k2;
-    g.seg[0].p0 = a; g.seg[0].p1 = a2; g.seg[0].c0 = k1; g.seg[0].c1 = k2; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k1 + k2;
-    g.nseg = 1; g.W = w; g.M = M; g.N = N; g.Ktot = k1 + k2; g.rows_per_batch = M; g.outH = 1; g.outW = M;
-    g.bias = bias; g.res = res; g.ldres = ldres; g.alpha = 1.f; g.geglu = geglu; g.out = out; g.ldo = ldo; g.out_f32 = out_f32;
+    MvdGemmArgs g = gemm_dense(a, a2, k1, k2, M, w, ldw, bias, N, out, ldo);
+    g.res = res; g.ldres = ldres; g.geglu = geglu; g.out_f32 = out_f32;
     return gemm(g);
   }
 
@@ -378,9 +323,8 @@ struct Ctx {
   // the un-normalised rows; otherwise ln_kernel into `ln_tmp` and the plain GEMM.
   int ln_linear(const bf16_t* x, int M, int C, const std::string& ln_key, const std::string& slot, int64_t n_full, int N,
                 const float* bias, bf16_t* ln_tmp, void* out, int ldo, bool geglu) {
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.ldw = C; g.seg[0].p0 = x; g.seg[0].c0 = C; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = C; g.nseg = 1;
-    g.M = M; g.N = N; g.Ktot = C; g.rows_per_batch = M; g.outH = 1; g.outW = M; g.alpha = 1.f; g.geglu = geglu; g.out = out; g.ldo = ldo;
+    MvdGemmArgs g = gemm_dense(x, nullptr, C, 0, M, nullptr, 0, nullptr, N, out, ldo);    // (W and bias: below, per route)
+    g.geglu = geglu;
     {
       const int r = try_xs(x, C, M, slot + ".wx", n_full, N, geglu, true, nullptr, 0, out, ldo);
       if (r) return r < 0 ? r : 0;
@@ -391,7 +335,7 @@ struct Ctx {
       static const float dummy = 0.f;
       t.ln_c1 = &dummy; t.bias = &dummy; t.W = reinterpret_cast<const bf16_t*>(&dummy);
       int a_, b_, c_;
-      return sm_enabled() && !(g_debug_flags & 1) && mvd_gemm_sm_plan(t, &a_, &b_, &c_);
+      return sm_enabled() && !(g_debug_flags & MVD_DBG_NO_SM_LN_FOLD) && mvd_gemm_sm_plan(t, &a_, &b_, &c_);
     };
     if (use_fold && !dry && has(slot + ".wf") && has(slot + ".cf") && (mvd_gemm_ln_fold_ok(g) || sm_fold_ok())) {
       const float* cf = WF(slot + ".cf", 2 * n_full);
@@ -411,17 +355,17 @@ struct Ctx {
   int try_ws(const Act& x, int ups, const std::string& slot, const float* bias, const float* rowvec, int ld_rowvec, const bf16_t* res,
              const bf16_t* sc0, const bf16_t* sc1, int scc0, int scc1, Act& out) {
     if (err) return err;
-    if (dry || (g_debug_flags & 256) || slot.empty() || !has(slot)) return 0;
+    if (dry || (g_debug_flags & MVD_DBG_NO_WS) || slot.empty() || !has(slot)) return 0;
     MvdWsArgs a; memset(&a, 0, sizeof(a));
     a.x = x.p; a.B = x.B; a.H = x.H; a.W = x.W; a.C = x.C; a.ups = ups; a.sc0 = sc0; a.sc1 = sc1; a.scc0 = scc0; a.scc1 = scc1;
     a.bias = bias; a.rowvec = rowvec; a.ld_rowvec = ld_rowvec; a.res = res; a.ldres = out.C; a.out = out.p; a.ldo = out.C;
     a.M = out.rows(); a.N = out.C;
-    // (debug flags, A/B only: 512 = maps of at most 256 pixels, 1024 = 64-pixel blocks everywhere, 2048 = no fused shortcut)
-    if ((g_debug_flags & 512) && a.M > 256) return 0;
-    if (g_debug_flags & 1024) a.variant = 1;
-    if ((g_debug_flags & 2048) && scc0) return 0;
-    if ((g_debug_flags & 4096) && nowait) return 0;             // (4096: not in the encoder pass of a two-stream forward; 8192: only there)
-    if ((g_debug_flags & 8192) && !nowait) return 0;
+    // (debug flags, A/B only; nowait = the encoder pass of a two-stream forward)
+    if ((g_debug_flags & MVD_DBG_WS_SMALL_MAPS) && a.M > 256) return 0;
+    if (g_debug_flags & MVD_DBG_WS_BLOCK64) a.variant = 1;
+    if ((g_debug_flags & MVD_DBG_WS_NO_SHORTCUT) && scc0) return 0;
+    if ((g_debug_flags & MVD_DBG_WS_NOT_IN_ENCODER) && nowait) return 0;
+    if ((g_debug_flags & MVD_DBG_WS_ONLY_IN_ENCODER) && !nowait) return 0;
     if (out.H != (ups ? 2 : 1) * x.H || out.W != (ups ? 2 : 1) * x.W || out.B != x.B || a.M > 1024) return 0;
     // every 64-pixel row block streams its column tile's whole weight panel (from L2 at best): with 16 row blocks x 80 column tiles
     // (the 16 -> 32 upsampling convolution, N = 1280) that is a tie with the tiled kernel (62.9 vs 60.5 us) -- not taken
@@ -431,17 +375,17 @@ struct Ctx {
     a.w = WB(slot, (int64_t)mvd_conv_ws_packed_elems(x.C, scc0 + scc1, out.C));
     if (!a.w) return err;
     e->prof_M = a.M; e->prof_N = a.N; e->prof_K = 9 * x.C + scc0 + scc1; e->prof_tag = 100 + (scc0 ? 1 : 0);
-    const int r = profiled(34, 2.0 * a.M * (double)a.N * (9.0 * x.C + scc0 + scc1), 0.0, [&] { return mvd_launch_conv_ws(a, s); });
-    if (!r && (g_debug_flags & 16384)) return 0;              // (16384, A/B only: the tiled kernel runs as well and overwrites the result)
+    const int r = profiled(MVD_PC_CONV_WS, 2.0 * a.M * (double)a.N * (9.0 * x.C + scc0 + scc1), 0.0, [&] { return mvd_launch_conv_ws(a, s); });
+    if (!r && (g_debug_flags & MVD_DBG_WS_THEN_TILED)) return 0;   // (A/B only: the tiled kernel runs as well and overwrites the result)
 #ifdef MVD_PROBE
-    // probe builds, flag 32768: the tiled kernel computes the same launch into a scratch tensor and a compare kernel counts the
+    // probe builds, MVD_DBG_WS_CHECK: the tiled kernel computes the same launch into a scratch tensor and a compare kernel counts the
     // elements that differ by more than rounding into pinned host memory -- no synchronise; mvd_debug_ws_check_report() prints
-    if (!r && (g_debug_flags & 32768)) {
+    if (!r && (g_debug_flags & MVD_DBG_WS_CHECK)) {
       const size_t mark = e->tmp.off;
       Act chk = new_act(out.B, out.H, out.W, out.C, false);
       const bf16_t* wold = WB(slot.substr(0, slot.size() - 1), (int64_t)out.C * (9 * x.C + scc0 + scc1));   // "<..>.convN.ws" -> "<..>.convN.w"
       if (wold) {
-        const int saved = g_debug_flags; g_debug_flags |= 256;
+        const int saved = g_debug_flags; g_debug_flags |= MVD_DBG_NO_WS;
         conv3(x, 1, ups, wold, bias, rowvec, ld_rowvec, res, sc0, sc1, scc0, scc1, chk);
         g_debug_flags = saved;
         g_ws_ptrs[0] = (const char*)x.p; g_ws_lens[0] = (size_t)x.rows() * x.C * 2;   // (input rows)
@@ -463,36 +407,27 @@ struct Ctx {
       const int r = try_ws(x, ups, ws, bias, rowvec, ld_rowvec, res, sc0, sc1, scc0, scc1, out);
       if (r) return r < 0 ? r : 0;
     }
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.seg[0].p0 = x.p; g.seg[0].c0 = x.C; g.seg[0].mode = MVD_A_CONV3; g.seg[0].ksize = 9 * x.C;
-    g.seg[0].inH = x.H; g.seg[0].inW = x.W; g.seg[0].stride = stride; g.seg[0].ups = ups;
-    g.nseg = 1; g.Ktot = 9 * x.C;
-    if (sc0) {
-      g.seg[1].p0 = sc0; g.seg[1].p1 = sc1; g.seg[1].c0 = scc0; g.seg[1].c1 = scc1; g.seg[1].mode = MVD_A_DENSE;
-      g.seg[1].ksize = scc0 + scc1; g.nseg = 2; g.Ktot += scc0 + scc1;
-    }
-    g.W = w; g.ldw = g.Ktot; g.M = out.rows(); g.N = out.C; g.rows_per_batch = out.hw(); g.outH = out.H; g.outW = out.W;
-    g.bias = bias; g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = res; g.ldres = out.C; g.alpha = 1.f;
-    g.out = out.p; g.ldo = out.C;
+    MvdGemmArgs g = gemm_conv3(x.p, x.H, x.W, x.C, stride, ups, 0, sc0, sc1, scc0, scc1, w, bias, out.B, out.H, out.W, out.C, out.p);
+    g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = res;
     // Upsampling convolution as four 2x2 sub-pixel convolutions of the source map (gemm_pp.hip AMODE 4: K = 4 C instead of 9 C,
     // the same result up to one bf16 rounding of the pre-summed weights), taken when the packed twin `w4` (packing.pack_up4) is
     // registered and the schedule would put the nine-tap problem on the unsplit 256x320 ping-pong tile anyway: batch-1 forwards
     // keep their conv_ws / small-M route, a split launch (the 8x8 -> 16x16 site outside a two-stream forward) and source widths
-    // the mode does not take (12, 24) keep the nine-tap kernel.  Debug flag 1048576 turns the route off (A/B).
-    if (!w4.empty() && !dry && !err && ups == 1 && stride == 1 && !sc0 && !res && !rowvec && !(g_debug_flags & 1048576) && has(w4)) {
+    // the mode does not take (12, 24) keep the nine-tap kernel.  MVD_DBG_NO_UP4 turns the route off (A/B).
+    if (!w4.empty() && !dry && !err && ups == 1 && stride == 1 && !sc0 && !res && !rowvec && !(g_debug_flags & MVD_DBG_NO_UP4) && has(w4)) {
       int t_ = 0, n_ = 0, s_ = 1, S = 1, fc = -1;
       if (!(sm_enabled() && mvd_gemm_sm_plan(g, &t_, &n_, &s_))) {
         tiled_plan(g, S, fc);
         MvdGemmArgs u = g;
         u.splitk = 1;
         if (S == 1 && (fc >= 0 ? fc : mvd_gemm_pick_config(u)) == 7 && mvd_gemm_pp_applicable(u)) {
-          u.seg[0].ups = 2; u.seg[0].ksize = 4 * x.C; u.Ktot = 4 * x.C; u.ldw = u.Ktot;
+          gemm_conv3_to_up4(u);
           if (mvd_gemm_pp_up4_applicable(u)) {
             u.W = WB(w4, (int64_t)4 * out.C * 4 * x.C);
             if (!u.W) return err;
             // (executed FLOPs: 4/9 of the algorithmic count of the nine-tap form; tag 140 tells the rows apart in the shape table)
             e->prof_M = u.M; e->prof_N = u.N; e->prof_K = u.Ktot; e->prof_tag = 140;
-            return profiled(13, 2.0 * u.M * (double)u.N * u.Ktot, 0.0, [&] { return mvd_launch_gemm(u, s, 7); });
+            return profiled(MVD_PC_PP_CONV3, 2.0 * u.M * (double)u.N * u.Ktot, 0.0, [&] { return mvd_launch_gemm(u, s, 7); });
           }
         }
       }
@@ -508,18 +443,18 @@ struct Ctx {
     if (dry) return 0;
     const double by = 3.0 * B * (double)hw * (c0 + c1) * 2;   // 2 reads + 1 write of the activation
     e->prof_M = B * hw; e->prof_N = c0 + c1; e->prof_K = 0; e->prof_tag = 2000 + silu;
-    return profiled(16, 0.0, by, [&] { return mvd_launch_groupnorm(x0, x1, c0, c1, B, hw, groups, eps, g, b, silu, y, ws, s); });
+    return profiled(MVD_PC_GROUPNORM, 0.0, by, [&] { return mvd_launch_groupnorm(x0, x1, c0, c1, B, hw, groups, eps, g, b, silu, y, ws, s); });
   }
   int layernorm(const bf16_t* x, int rows, int c, const float* g, const float* b, bf16_t* y) {
     if (err) return err; if (dry) return 0;
     e->prof_M = rows; e->prof_N = c; e->prof_K = 0; e->prof_tag = 3000;
-    return profiled(17, 0.0, 2.0 * rows * (double)c * 2, [&] { return mvd_launch_layernorm(x, rows, c, 1e-5f, g, b, y, s); });
+    return profiled(MVD_PC_LAYERNORM, 0.0, 2.0 * rows * (double)c * 2, [&] { return mvd_launch_layernorm(x, rows, c, 1e-5f, g, b, y, s); });
   }
   int attention(MvdAttnArgs& a) {
     if (err) return err;
     // batch 1: split the keys over several workgroups (partials + counters from the scoped workspace / the call's counter block)
     const size_t mark = e->tmp.off;
-    const int ns = (g_debug_flags & 8) ? 1 : mvd_attention_pick_split(a);
+    const int ns = (g_debug_flags & MVD_DBG_NO_SPLIT_KV) ? 1 : mvd_attention_pick_split(a);
     if (ns > 1) {
       a.nsplit = ns;
       a.split_ws = e->tmp.alloc(mvd_attention_split_ws_bytes(a, ns));
@@ -532,7 +467,7 @@ struct Ctx {
     double fl = 0;
     for (int i = 0; i < a.nprob; ++i) fl += 4.0 * a.batch * a.heads * (double)a.p[i].nq * a.p[i].nk * 64;
     e->prof_M = a.p[0].nq; e->prof_N = a.p[0].nk; e->prof_K = a.heads; e->prof_tag = 1000 + a.nprob;
-    return profiled(e->prof ? 8 + mvd_attention_pick_nw(a) : 8, fl, 0.0, [&] { return mvd_launch_attention(a, s); });
+    return profiled(MVD_PC_ATTN_1WAVE + (e->prof ? mvd_attention_pick_nw(a) : 0), fl, 0.0, [&] { return mvd_launch_attention(a, s); });
   }
 };
 
@@ -585,6 +520,7 @@ struct PassOpts {
   bool defer_norm = false;    // capture, global-statistics form: per-pixel local (mean, M2) go to `stats`, the features are
   float* stats = nullptr;     // kept raw and normalisation + K/V projection wait for mvd_engine_reference_finish
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
+  int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
 
@@ -625,7 +561,6 @@ struct UNetPass {
 
   int transformer(const std::string& key, const Act& x, int heads, Act& out) {
     const int C = x.C, M = x.rows(), hw = x.hw(), B_ = x.B;
-    const FeatureInfo& fi = c.e->feats[feat_idx];
     const bool ad = o.adapter;
     // set 0 may carry the adapter rows/columns even when this pass does not use them (no image conditioning):
     // q/k/v rows are a prefix of the fused matrix, the out-projection is addressed with its packed row stride.
@@ -659,8 +594,6 @@ struct UNetPass {
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
       CHECK(c.attention(a));
-      const int kout = ad ? 2 * C : C;
-      (void)kout;
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn1.out.wx"));
     }
@@ -676,8 +609,6 @@ struct UNetPass {
       a.p[0] = {q2, kv2, kv2 + C, o_self, nq, ldkv, ldkv, C, (int64_t)hw * nq, (int64_t)L * ldkv, (int64_t)L * ldkv, (int64_t)hw * C, hw, L};
       if (ad) a.p[1] = {q2 + C, rkv + 2 * C, rkv + 3 * C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
       CHECK(c.attention(a));
-      const int kout = ad ? 2 * C : C;
-      (void)kout;
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn2.out.w", (int64_t)C * ld_out), c.WF(key + ".attn2" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn2.out.wx"));
     }
@@ -705,7 +636,6 @@ struct UNetPass {
         CHECK((int)hipMemcpyAsync(c.e->feat_keep[feat_idx], out.p, (size_t)M * C * sizeof(bf16_t), hipMemcpyDeviceToDevice, c.s));
       c.e->tmp.off = mk;
     }
-    (void)fi;
     ++feat_idx;
     return c.err;
   }
@@ -770,9 +700,9 @@ struct UNetPass {
     for (int i = 0; i < n; ++i) {
       const int co = cfg.block_out_channels[n - 1 - i];
       const std::string bk = "up_blocks." + std::to_string(i);
-      // main pass of a two-stream forward: from up block `dual_late_from` on the encoder pass (41 % of the work, ahead by design
+      // main pass of a two-stream forward: from up block `late_from` on the encoder pass (41 % of the work, ahead by design
       // and on the higher-priority stream) has normally drained -- launches must fill the chip by themselves again
-      if (!o.capture && i >= c.e->dual_late_from) c.e->dual_late = true;
+      if (!o.capture && i >= o.late_from) c.e->dual_late = true;
       for (int j = 0; j <= Lb; ++j) {
         Act skip = skips.back(); skips.pop_back();
         if (skip.H != h.H || skip.W != h.W) { mvd_set_error("up block %d: skip %dx%d vs hidden %dx%d (odd latent size unsupported)", i, skip.H, skip.W, h.H, h.W); return -13; }
@@ -1003,9 +933,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   // error in the reference and would read past the [B][4] scale/shift rows here -- reject before any launch
   if (!dry && use_cam && cfg.in_channels != 4) { mvd_set_error("forward: camera conditioning needs in_channels == 4 (the 'output' modulator is 4 wide), got %d", cfg.in_channels); return -1; }
 
-  e->tmp.dry = e->act.dry = dry;
-  e->tmp.off = e->tmp.high = 0;
-  e->act.off = e->act.high = 0;
+  e->tmp.reset(dry); e->act.reset(dry);
   Ctx c{e, s, 0, dry};
   CHECK(setup_tile_counters(e, (unsigned int*)e->act.alloc(MVD_TILE_COUNTERS * sizeof(unsigned int)), s, dry));
   const int B = a.batch, H = a.height, Wd = a.width, L = a.text_len, xd = cfg.cross_attention_dim;
@@ -1016,7 +944,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
     if (reuse) {
       if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
     } else {
-      e->persist.dry = dry; e->persist.off = e->persist.high = 0;
+      e->persist.reset(dry);
       e->refkv.assign(e->feats.size(), nullptr);
       e->feat_keep.assign(e->feats.size(), nullptr);
       for (size_t i = 0; i < e->feats.size(); ++i) {
@@ -1037,21 +965,20 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   // the sizing runs too; whether the side stream is really used also needs: no per-launch profiling.
   const bool dual = use_img && !reuse && !ref_only;
   e->dual_late = false;
-  if (g_debug_flags & (3 << 19)) e->dual_late_from = (g_debug_flags >> 19) & 3;      // (A/B: debug-flag bits 19-20 = 1..3)
   // (Round 5: under hipGraph capture too.  The fork event is recorded on the capturing stream and waited for by the side stream,
   //  which thereby joins the capture; the per-feature events and the join event become edges of the graph, so a replayed
-  //  forward keeps the two-branch schedule instead of serialising the passes.  Debug flag 65536 restores the one-stream capture.)
-  e->dual_now = dual && !dry && !(e->graph_on && (g_debug_flags & 65536)) && (!e->prof || e->prof_overlap) && !(g_debug_flags & 16);
+  //  forward keeps the two-branch schedule instead of serialising the passes.  MVD_DBG_GRAPH_ONE_STREAM restores the one-stream capture.)
+  e->dual_now = dual && !dry && !(e->graph_on && (g_debug_flags & MVD_DBG_GRAPH_ONE_STREAM)) && (!e->prof || e->prof_overlap) && !(g_debug_flags & MVD_DBG_ONE_STREAM);
   // Where the side stream forks: in front of everything (the encoder pass needs nothing of the camera path).  Round 5's two-stream
   // kernel stats showed what that does to the ~30 latency-bound launches in front of the main pass (camera MLPs, time MLPs): the
   // encoder's persistent 256-workgroup kernels fill every CU's register file, so a small kernel of the other stream waits for
   // a whole big kernel to retire -- 145 us per time-MLP launch, 390 us for the grouped modulator layer, ~1.6 ms before the main
-  // pass (the step's critical path) can start.  The alternative `early` (debug flag 4194304: those launches of BOTH passes first,
+  // pass (the step's critical path) can start.  The alternative `early` (MVD_DBG_FORK_LATE: those launches of BOTH passes first,
   // on an otherwise idle chip, the fork behind them) was measured and LOSES: cfg4 60.19 -> 60.96 ms, cfg3 6.46 -> 6.67 ms (three /
   // two same-box alternations) -- an idle chip for 0.75 ms costs more than the slowed-down front matter.  What helped instead is
   // making those launches cheap (misc.hip skinny_mfma_kernel).  `early` is a function of the call's flags only, so the sizing run
   // allocates in the same order.
-  const bool early = dual && (g_debug_flags & 4194304);
+  const bool early = dual && (g_debug_flags & MVD_DBG_FORK_LATE);
   auto fork = [&]() -> int {
     if (!e->dual_now) return 0;
     CHECK(e->ensure_side_stream());
@@ -1136,6 +1063,10 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
     CHECK(mvd_launch_im2col_in(a.sample, B, cfg.in_channels, H, Wd, sc, sh, 4, xin.p, s));
   }
   PassOpts po; po.adapter = use_img; po.film = use_cam; po.ref_batch = a.ref_batch; po.film_ss = &film_ss;
+  // (decided per forward, not kept on the engine: clearing the flag restores the product's schedule.  "From up_blocks.2"
+  //  measured no difference and has no switch.)
+  static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
+  po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   CHECK(pass.run(xin, a.out));
   if (e->dual_now) {   // join: everything the side stream did (kept features included) precedes whatever follows on s
@@ -1162,8 +1093,7 @@ int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
 // Second half of the global-statistics path: normalise the kept raw features with the merged per-pixel (mean, k) and
 // project them to the adapter K/V -- the same two launches per feature the encoder pass makes in the local form.
 int reference_finish_impl(mvd_engine* e, const float* mean_k, hipStream_t s, bool dry) {
-  e->tmp.dry = dry;
-  e->tmp.off = e->tmp.high = 0;
+  e->tmp.reset(dry);
   Ctx c{e, s, 0, dry};
   CHECK(setup_tile_counters(e, (unsigned int*)e->tmp.alloc(MVD_TILE_COUNTERS * sizeof(unsigned int)), s, dry));
   c.set = 0;                                         // the adapter's ref_kv weights live with the base set
@@ -1225,13 +1155,13 @@ int mvd_engine_set_weight(mvd_engine_t* e, int set, const char* slot, const void
   if (e) e->drop_graphs();
   if (!e || set < 0 || set > 1 || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("set_weight: bad argument"); return -1; }
   if ((uintptr_t)ptr & 15) { mvd_set_error("set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  e->w[set][slot] = Weight{ptr, numel, dtype};
+  e->w[set].m[slot] = Weight{ptr, numel, dtype};
   return 0;
 }
 int mvd_engine_clear_weights(mvd_engine_t* e, int set) {
   if (e) e->drop_graphs();
   if (!e || set < 0 || set > 1) { mvd_set_error("clear_weights: bad argument"); return -1; }
-  e->w[set].clear();
+  e->w[set].m.clear();
   return 0;
 }
 
@@ -1244,11 +1174,9 @@ static void fill_dry_args(mvd_forward_args_t& a, int batch, int h, int w, int L,
 int64_t mvd_engine_workspace_bytes(mvd_engine_t* e, int batch, int height, int width, int text_len, int ref_batch) {
   if (!e) { mvd_set_error("workspace_bytes: null engine"); return -1; }
   mvd_forward_args_t a; fill_dry_args(a, batch, height, width, text_len, ref_batch);
-  const bool valid = e->rc_valid;
-  std::vector<bf16_t*> kv = e->refkv, fk = e->feat_keep;
-  const bool keep = e->rc_keep; const int rb = e->rc_batch, rh = e->rc_h, rw = e->rc_w;
+  const mvd_engine::HostState before = e->host_state();     // (a sizing call leaves no dry pointers behind)
   int r = forward_impl(e, a, nullptr, true);
-  e->rc_valid = valid; e->refkv = kv; e->feat_keep = fk; e->rc_keep = keep; e->rc_batch = rb; e->rc_h = rh; e->rc_w = rw;
+  e->set_host_state(before);
   if (r) return r;
   // act and tmp arenas share one buffer: [act | tmp]
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
@@ -1321,11 +1249,9 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
   if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
   // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
-  const bool valid = e->rc_valid;
-  std::vector<bf16_t*> kv = e->refkv, fk = e->feat_keep;
-  const bool keep = e->rc_keep; const int rb = e->rc_batch, rh = e->rc_h, rw = e->rc_w;
+  const mvd_engine::HostState before = e->host_state();
   int r = forward_impl(e, *args, nullptr, true);
-  e->rc_valid = valid; e->refkv = kv; e->feat_keep = fk; e->rc_keep = keep; e->rc_batch = rb; e->rc_h = rh; e->rc_w = rw;
+  e->set_host_state(before);
   if (r) return r;
   const size_t act_bytes = (e->act.high + 255) & ~size_t(255);
   if (!e->ws_ptr || act_bytes + e->tmp.high > (size_t)e->ws_bytes) {
@@ -1452,12 +1378,12 @@ int mvd_engine_encode_cameras(mvd_engine_t* e, const float* source_camera, const
   if (!e || !source_camera || !target_camera || !fourier_proj || !out_emb || batch <= 0 || (cam_rows != 3 && cam_rows != 4)) { mvd_set_error("encode_cameras: bad argument"); return -1; }
   if (!e->ws_ptr) { mvd_set_error("encode_cameras: workspace not bound"); return -1; }
   {   // size the scratch with a dry pass: nothing is launched into a workspace that is too small
-    e->tmp.dry = true; e->tmp.off = e->tmp.high = 0;
+    e->tmp.reset(true);
     Ctx d{e, nullptr, 0, true};
     if (int r = camera_embed(d, source_camera, target_camera, cam_rows, fourier_proj, batch, out_emb)) return r;
     if (e->tmp.high > (size_t)e->ws_bytes) { mvd_set_error("encode_cameras: workspace too small (%zu > %lld bytes)", e->tmp.high, (long long)e->ws_bytes); return -4; }
   }
-  e->tmp.dry = false; e->tmp.base = (char*)e->ws_ptr; e->tmp.cap = (size_t)e->ws_bytes; e->tmp.off = e->tmp.high = 0;
+  e->tmp.reset(false); e->tmp.base = (char*)e->ws_ptr; e->tmp.cap = (size_t)e->ws_bytes;
   Ctx c{e, (hipStream_t)stream, 0, false};
   return camera_embed(c, source_camera, target_camera, cam_rows, fourier_proj, batch, out_emb);
 }
@@ -1473,14 +1399,14 @@ int mvd_engine_apply_modulation(mvd_engine_t* e, const char* name, const float* 
   if (dim < 0) return 1;
   if (dim != channels) { mvd_set_error("apply_modulation: modulator '%s' has %d channels, tensor has %d", name, dim, channels); return -1; }
   {   // dry sizing pass first (see encode_cameras)
-    e->tmp.dry = true; e->tmp.off = e->tmp.high = 0;
+    e->tmp.reset(true);
     Ctx d{e, nullptr, 0, true};
     float* sc0 = d.talloc<float>((size_t)batch * dim);
     float* sh0 = d.talloc<float>((size_t)batch * dim);
     if (int r = modulator(d, name, dim, emb, batch, sc0, sh0)) return r;
     if (e->tmp.high > (size_t)e->ws_bytes) { mvd_set_error("apply_modulation: workspace too small (%zu > %lld bytes)", e->tmp.high, (long long)e->ws_bytes); return -4; }
   }
-  e->tmp.dry = false; e->tmp.base = (char*)e->ws_ptr; e->tmp.cap = (size_t)e->ws_bytes; e->tmp.off = e->tmp.high = 0;
+  e->tmp.reset(false); e->tmp.base = (char*)e->ws_ptr; e->tmp.cap = (size_t)e->ws_bytes;
   Ctx c{e, (hipStream_t)stream, 0, false};
   float* sc = c.talloc<float>((size_t)batch * dim);
   float* sh = c.talloc<float>((size_t)batch * dim);
@@ -1503,34 +1429,28 @@ static int op_sm_splitk(MvdGemmArgs& g, hipStream_t s, int force_cfg) {
   if ((long)((g.M + 63) / 64) * (g.N / 64) > MVD_OP_SPLITK_COUNTERS) { mvd_set_error("op split-K: more than %d output tiles", MVD_OP_SPLITK_COUNTERS); return -1; }
   return mvd_launch_gemm(g, s, force_cfg);
 }
+// splitk <= 1: the caller DECIDED not to split (g.splitk = 1; 0 would mean "undecided": the tile heuristic may then assume a
+// deep split)
+static int op_launch(MvdGemmArgs& g, int force_cfg, int splitk, float* splitk_ws, hipStream_t s) {
+  g.part = splitk_ws;      // (also the stamp buffer of probe builds)
+  g.splitk = splitk > 1 ? splitk : 1;
+  if (splitk > 1 && force_cfg >= 100) return op_sm_splitk(g, s, force_cfg);
+  return launch_tiled(g, s, force_cfg);
+}
 int mvd_op_linear(const void* a, const void* a2, int k1, int k2, const void* w, const float* bias, const float* rowvec,
                   int ld_rowvec, int rows_per_batch, const void* res, float alpha, int geglu, void* out, int out_f32, int m,
                   int n, int force_cfg, int splitk, float* splitk_ws, void* stream) {
-  MvdGemmArgs g; memset(&g, 0, sizeof(g));
-  g.seg[0].p0 = (const bf16_t*)a; g.seg[0].p1 = (const bf16_t*)a2; g.seg[0].c0 = k1; g.seg[0].c1 = k2;
-  g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k1 + k2; g.nseg = 1;
-  g.W = (const bf16_t*)w; g.M = m; g.N = n; g.Ktot = k1 + k2; g.ldw = k1 + k2;
-  g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : m; g.outH = 1; g.outW = g.rows_per_batch;
-  g.bias = bias; g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res;
   const int on = geglu ? n / 2 : n;
-  g.ldres = on; g.alpha = alpha; g.geglu = geglu; g.out = out; g.ldo = on; g.out_f32 = out_f32;
-  g.part = splitk_ws;      // (also the stamp buffer of probe builds)
-  if (splitk > 1) {
-    g.splitk = splitk; g.part = splitk_ws;
-    if (force_cfg >= 100) return op_sm_splitk(g, (hipStream_t)stream, force_cfg);
-    if (int r = mvd_launch_gemm(g, (hipStream_t)stream, force_cfg)) return r;
-    return mvd_launch_splitk_reduce(g, (hipStream_t)stream);
-  }
-  g.splitk = 1;            // the caller DECIDED not to split (0 would mean "undecided": the tile heuristic may then assume a deep split)
-  return mvd_launch_gemm(g, (hipStream_t)stream, force_cfg);
+  MvdGemmArgs g = gemm_dense((const bf16_t*)a, (const bf16_t*)a2, k1, k2, m, (const bf16_t*)w, 0, bias, n, out, on);
+  if (rows_per_batch > 0) g.rows_per_batch = g.outW = rows_per_batch;
+  g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res; g.ldres = on; g.alpha = alpha; g.geglu = geglu; g.out_f32 = out_f32;
+  return op_launch(g, force_cfg, splitk, splitk_ws, (hipStream_t)stream);
 }
 
 int mvd_op_ln_linear(const void* x, int k, const void* w_folded, const float* c1, const float* c2, float eps, int geglu,
                      void* out, int m, int n, void* stream) {
-  MvdGemmArgs g; memset(&g, 0, sizeof(g));
-  g.seg[0].p0 = (const bf16_t*)x; g.seg[0].c0 = k; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k; g.nseg = 1;
-  g.W = (const bf16_t*)w_folded; g.M = m; g.N = n; g.Ktot = k; g.ldw = k; g.rows_per_batch = m; g.outH = 1; g.outW = m;
-  g.bias = c2; g.ln_c1 = c1; g.ln_eps = eps; g.alpha = 1.f; g.geglu = geglu; g.out = out; g.ldo = geglu ? n / 2 : n; g.ldres = g.ldo;
+  MvdGemmArgs g = gemm_dense((const bf16_t*)x, nullptr, k, 0, m, (const bf16_t*)w_folded, 0, c2, n, out, geglu ? n / 2 : n);
+  g.ln_c1 = c1; g.ln_eps = eps; g.geglu = geglu; g.ldres = g.ldo;
   if (!c1 || !c2) { mvd_set_error("mvd_op_ln_linear: c1 and c2 are required"); return -1; }
   if (!mvd_gemm_ln_fold_ok(g)) {
     int tile = 0, ns = 0, S = 1;           // small problems (batch 1): the fold of the small-M kernels
@@ -1544,28 +1464,12 @@ int mvd_op_ln_linear(const void* x, int k, const void* w_folded, const float* c1
 int mvd_op_conv3x3(const void* x, int batch, int in_h, int in_w, int cin, int stride, int upsample, int asym_pad, const void* w,
                    const float* bias, const float* rowvec, int ld_rowvec, const void* res, const void* sc, const void* sc2,
                    int sc_c1, int sc_c2, void* out, int cout, int force_cfg, int splitk, float* splitk_ws, void* stream) {
-  MvdGemmArgs g; memset(&g, 0, sizeof(g));
   const int oh = upsample ? in_h * 2 : (stride == 2 ? (in_h + 1) / 2 : in_h);
   const int ow = upsample ? in_w * 2 : (stride == 2 ? (in_w + 1) / 2 : in_w);
-  g.seg[0].p0 = (const bf16_t*)x; g.seg[0].c0 = cin; g.seg[0].mode = MVD_A_CONV3; g.seg[0].ksize = 9 * cin;
-  g.seg[0].inH = in_h; g.seg[0].inW = in_w; g.seg[0].stride = stride; g.seg[0].ups = upsample; g.seg[0].asym = asym_pad;
-  g.nseg = 1; g.Ktot = 9 * cin;
-  if (sc) {
-    g.seg[1].p0 = (const bf16_t*)sc; g.seg[1].p1 = (const bf16_t*)sc2; g.seg[1].c0 = sc_c1; g.seg[1].c1 = sc_c2;
-    g.seg[1].mode = MVD_A_DENSE; g.seg[1].ksize = sc_c1 + sc_c2; g.nseg = 2; g.Ktot += sc_c1 + sc_c2;
-  }
-  g.W = (const bf16_t*)w; g.ldw = g.Ktot; g.M = batch * oh * ow; g.N = cout; g.rows_per_batch = oh * ow; g.outH = oh; g.outW = ow;
-  g.bias = bias; g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res; g.ldres = cout; g.alpha = 1.f;
-  g.out = out; g.ldo = cout;
-  g.part = splitk_ws;      // (also the stamp buffer of probe builds)
-  if (splitk > 1) {
-    g.splitk = splitk; g.part = splitk_ws;
-    if (force_cfg >= 100) return op_sm_splitk(g, (hipStream_t)stream, force_cfg);
-    if (int r = mvd_launch_gemm(g, (hipStream_t)stream, force_cfg)) return r;
-    return mvd_launch_splitk_reduce(g, (hipStream_t)stream);
-  }
-  g.splitk = 1;            // the caller DECIDED not to split (0 would mean "undecided": the tile heuristic may then assume a deep split)
-  return mvd_launch_gemm(g, (hipStream_t)stream, force_cfg);
+  MvdGemmArgs g = gemm_conv3((const bf16_t*)x, in_h, in_w, cin, stride, upsample, asym_pad, (const bf16_t*)sc, (const bf16_t*)sc2, sc_c1, sc_c2,
+                             (const bf16_t*)w, bias, batch, oh, ow, cout, out);
+  g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res;
+  return op_launch(g, force_cfg, splitk, splitk_ws, (hipStream_t)stream);
 }
 
 // the upsampling convolution as four 2x2 sub-pixel convolutions (w4 = packing.pack_up4: [4][cout][4 * cin] bf16); an error --
@@ -1573,12 +1477,10 @@ int mvd_op_conv3x3(const void* x, int batch, int in_h, int in_w, int cin, int st
 int mvd_op_conv3x3_up4(const void* x, int batch, int in_h, int in_w, int cin, const void* w4, const float* bias, void* out, int cout,
                        int force_cfg, void* stream) {
   if (!x || !w4 || !out || batch <= 0 || in_h <= 0 || in_w <= 0 || cin <= 0 || cout <= 0) { mvd_set_error("mvd_op_conv3x3_up4: bad argument"); return -1; }
-  MvdGemmArgs g; memset(&g, 0, sizeof(g));
-  g.seg[0].p0 = (const bf16_t*)x; g.seg[0].c0 = cin; g.seg[0].mode = MVD_A_CONV3; g.seg[0].ksize = 4 * cin;
-  g.seg[0].inH = in_h; g.seg[0].inW = in_w; g.seg[0].stride = 1; g.seg[0].ups = 2;
-  g.nseg = 1; g.Ktot = 4 * cin; g.W = (const bf16_t*)w4; g.ldw = g.Ktot;
-  g.outH = 2 * in_h; g.outW = 2 * in_w; g.rows_per_batch = g.outH * g.outW; g.M = batch * g.rows_per_batch; g.N = cout;
-  g.bias = bias; g.ldres = cout; g.alpha = 1.f; g.out = out; g.ldo = cout; g.splitk = 1;
+  MvdGemmArgs g = gemm_conv3((const bf16_t*)x, in_h, in_w, cin, 1, 1, 0, nullptr, nullptr, 0, 0, (const bf16_t*)w4, bias, batch, 2 * in_h, 2 * in_w,
+                             cout, out);
+  gemm_conv3_to_up4(g);
+  g.splitk = 1;
   return mvd_launch_gemm(g, (hipStream_t)stream, force_cfg);
 }
 

@@ -33,14 +33,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
 
 constexpr int BN = 320, NT = 512;
 constexpr int B_BYTES = BN * 128, B_IT = BN * 8 / NT;   // 5 W-side DMA instructions per wave-slice per slab
-constexpr unsigned OOB = 0x80000000u;                   // voffset of a load that must return zeros (>= num_records)
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 // lane id computed on the spot (2 vector ops) and opaque to the optimiser: whatever is derived from it is neither hoisted
 // out of a loop nor kept live across one
@@ -50,25 +48,7 @@ MVD_DEVINL int fresh_lane() {
   return l;
 }
 
-// 16-byte buffer store + the wait states hipcc does not insert.  A store of more than 64 bits reads its data registers
-// over several cycles; overwriting them in the next instruction corrupts the last lanes' data.  hipcc's hazard
-// recognizer skips this case whenever the store's soffset is an SGPR -- as it always is here -- which the older ISAs
-// allowed; on gfx950 it is not safe: in the LayerNorm-fold epilogue a v_pk_mul_f32 directly behind a
-// buffer_store_dwordx4 replaced bf16 pairs of lanes 12..15 / 28..31 / ... by halves of the fp32 product (NaNs in the
-// output).  The asm READS the data registers, so whatever overwrites them is ordered behind the two wait states.
-MVD_DEVINL void store16(u32x4 v, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-  // (default cache policy: with the non-temporal hint, aux = 2, the L2 stops merging the four waves' 160-byte row pieces into
-  //  whole lines -- dense class 10.1 -> 12.2 ms/step, fused-LayerNorm 3.4 -> 5.5, 460 -> 425 fwd/s on the same box)
-  __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, soff, 0);
-  asm volatile("s_nop 1" :: "v"(v));
-}
-
 MVD_DEVINL int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// one 16-byte-per-lane LDS-DMA: LDS destination = wave-uniform base + lane * 16
-MVD_DEVINL void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
 
 // WM x WN wave grid: 2 x 4 (wave tile 128 x 80) for plain epilogues, 4 x 2 (64 x 160: value/gate column tiles pair
 // up inside a wave) for GEGLU.  AMODE: 0 dense, 1 conv, 2 conv + dense (1x1 shortcut) segment, 3 conv behind a fused
@@ -166,16 +146,16 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   // ---- buffer descriptors (scalar).  The conv descriptor starts one row + one pixel BEFORE the feature map so
   // that tap (dy, dx) is a non-negative scalar offset (dy * row + dx * pixel) from a per-lane base; nothing below
   // the map is ever dereferenced (those taps are out of the image and take the OOB offset).
-  __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.W), 0, (int)((size_t)a.N * a.ldw * 2 * (UP4 ? 4 : 1)), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(a.W, (int)((size_t)a.N * a.ldw * 2 * (UP4 ? 4 : 1)));
   __amdgpu_buffer_rsrc_t rs_c = rs_w, rs_d0 = rs_w, rs_d1 = rs_w;
   if (HAS_CONV) {
     const int shift = conv_rowB + conv_c2;
     const size_t bytes = (size_t)(a.M / a.rows_per_batch) * cs.inH * cs.inW * conv_c2;      // (UP4: M and rows_per_batch both count OUTPUT pixels)
-    rs_c = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(const_cast<bf16_t*>(cs.p0)) - shift, 0, (int)(bytes + shift), 0x00020000);
+    rs_c = buf_rsrc(reinterpret_cast<const char*>(cs.p0) - shift, (int)(bytes + shift));
   }
   if (AMODE == 0 || AMODE == 2) {
-    rs_d0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ds.p0), 0, (int)((size_t)a.M * dc0 * 2), 0x00020000);
-    if (dc1) rs_d1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ds.p1), 0, (int)((size_t)a.M * dc1 * 2), 0x00020000);
+    rs_d0 = buf_rsrc(ds.p0, (int)((size_t)a.M * dc0 * 2));
+    if (dc1) rs_d1 = buf_rsrc(ds.p1, (int)((size_t)a.M * dc1 * 2));
   }
   // loop-invariant per-lane offsets: row-in-block * pitch + chunk.  Rows >= M of a dense source lie beyond num_records
   // and read as zeros (their outputs are never stored).
@@ -328,7 +308,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
   auto issue_consts = [&](int n0) {
     if constexpr (LNF) {
       if (wave < 2) {
-        __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wave == 0 ? a.ln_c1 : a.bias), 0, a.N * 4, 0x00020000);
+        __amdgpu_buffer_rsrc_t rs_k = buf_rsrc(wave == 0 ? a.ln_c1 : a.bias, a.N * 4);
         unsigned char* dst = xch + (wave == 0 ? XCH_C1 : XCH_C2);
         const unsigned vo = (unsigned)fresh_lane() * 16u;
         dma16(rs_k, dst, vo, n0 * 4);
@@ -394,7 +374,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
     }
     const int row0 = m0 + wm * WTM;                        // (scalar) first row of the wave tile
     if (SPLITK) {   // raw fp32 partial tile; bias / residual are applied by the reduce kernel
-      __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(a.part + (size_t)ks * a.M * a.N, 0, (int)((size_t)a.M * a.N * 4), 0x00020000);
+      __amdgpu_buffer_rsrc_t rs_p = buf_rsrc(a.part + (size_t)ks * a.M * a.N, (int)((size_t)a.M * a.N * 4));
       const int vo = (fr * a.N + fq * 4) * 4;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -403,7 +383,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
           store16(__builtin_bit_cast(u32x4, acc[i][j]), rs_p, vo, ((row0 + i * 16) * a.N + n0 + wn * WTN + j * 16) * 4);
       return;
     }
-    __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)((size_t)a.M * a.ldo * 2), 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_o = buf_rsrc(a.out, (int)((size_t)a.M * a.ldo * 2));
     // (LNF is out of registers: its per-lane epilogue offsets are re-derived here from an opaque copy of the lane id so that
     //  they are not hoisted out of the tile loop -- a hoisted value gets spilled, and a scratch reload inside the slab loop
     //  comes with a vmcnt(0) that drains the DMA stream)
@@ -506,7 +486,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(const MvdGemmArgs a) {
         up_y = rem / (unsigned)cs.inW; up_x = rem - up_y * (unsigned)cs.inW;
       }
       __amdgpu_buffer_rsrc_t rs_r = rs_o;
-      if (has_res) rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.res), 0, (int)((size_t)a.M * a.ldres * 2), 0x00020000);
+      if (has_res) rs_r = buf_rsrc(a.res, (int)((size_t)a.M * a.ldres * 2));
       const int vr16 = (fr * a.ldres + pair_col) * 2, vr8 = (fr * a.ldres + fq * 4) * 2;
       constexpr int NP = TN / 2;                           // column-tile pairs (+ one single tile when TN is odd)
       f32x4 cb[TN];
@@ -773,7 +753,7 @@ int launch_pp_mode(const MvdGemmArgs& a, hipStream_t s) {
 // MVD_GEMM_PP_WALK=0 / debug flag 131072 turn it off (A/B).
 int mvd_gemm_pp_walk(const MvdGemmArgs& a) {
   static const int on = MVD_ENV_INT("MVD_GEMM_PP_WALK", 1);
-  if (!on || (mvd_debug_flags() & 131072) || a.walk_cg < 0) return 0;
+  if (!on || (mvd_debug_flags() & MVD_DBG_PP_ROW_MAJOR) || a.walk_cg < 0) return 0;
   if (a.walk_cg > 0) return a.walk_cg;                         // forced (tests / probes)
   if (a.seg[0].mode != MVD_A_DENSE || a.nseg != 1 || a.splitk > 1) return 0;
   const int ntm = (a.M + 255) / 256, ntn = a.N / BN;

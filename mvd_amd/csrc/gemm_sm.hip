@@ -24,15 +24,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
-
-constexpr unsigned OOB = 0x80000000u;                   // voffset of a load that must return zeros (>= num_records)
-typedef __attribute__((address_space(3))) void lds_void;
-
-MVD_DEVINL void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
 
 template <int N> MVD_DEVINL void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // at most `ahead` groups of L loads each may still be in flight (the counter is 6 bits: a smaller number waits for more)
@@ -97,16 +91,16 @@ __global__ __launch_bounds__(256) void gemm_sm_kernel(const MvdGemmArgs a, const
 
   // ---- buffer descriptors (scalar).  The conv descriptor starts one row + one pixel BEFORE the feature map so that tap
   // (dy, dx) is a non-negative scalar offset from a per-lane base; nothing below the map is ever dereferenced.
-  __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.W), 0, (int)((size_t)a.N * a.ldw * 2), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(a.W, (int)((size_t)a.N * a.ldw * 2));
   __amdgpu_buffer_rsrc_t rs_c = rs_w, rs_d0 = rs_w, rs_d1 = rs_w;
   if (HAS_CONV) {
     const int shift = conv_rowB + conv_c2;
     const size_t bytes = (size_t)(a.M / a.rows_per_batch) * cs.inH * cs.inW * conv_c2;
-    rs_c = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(const_cast<bf16_t*>(cs.p0)) - shift, 0, (int)(bytes + shift), 0x00020000);
+    rs_c = buf_rsrc(reinterpret_cast<const char*>(cs.p0) - shift, (int)(bytes + shift));
   }
   if (AMODE == 0 || AMODE == 2) {
-    rs_d0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ds.p0), 0, (int)((size_t)a.M * dc0 * 2), 0x00020000);
-    if (dc1) rs_d1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ds.p1), 0, (int)((size_t)a.M * dc1 * 2), 0x00020000);
+    rs_d0 = buf_rsrc(ds.p0, (int)((size_t)a.M * dc0 * 2));
+    if (dc1) rs_d1 = buf_rsrc(ds.p1, (int)((size_t)a.M * dc1 * 2));
   }
   // per-lane offsets, fixed for the whole work item.  Rows >= M are clamped to the last row (their outputs are not stored);
   // the row term lives in the VGPR offset, so every access stays inside its tensor whatever the range check covers.
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(256) void gemm_sm_kernel(const MvdGemmArgs a, const
   // ---- split-K: publish the partial tile, take a ticket; the last slice to arrive combines all of them in slice order
   if constexpr (SPLITK) {
     const size_t slab = (size_t)a.M * a.N;                              // floats per slice
-    __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(a.part, 0, (int)((size_t)S * slab * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_p = buf_rsrc(a.part, (int)((size_t)S * slab * 4));
     unsigned pvo[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -305,8 +299,7 @@ __global__ __launch_bounds__(256) void gemm_sm_kernel(const MvdGemmArgs a, const
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const u32x4 v = __builtin_bit_cast(u32x4, acc[i][j]);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs_p, (int)pvo[i] + j * 64, (int)pso, 16);   // aux 16 = sc1: write-through
-        asm volatile("s_nop 1" ::"v"(v));
+        store16<16>(v, rs_p, (int)pvo[i] + j * 64, (int)pso);   // aux 16 = sc1: write-through
       }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // every storing wave drains its own stores
     __builtin_amdgcn_s_barrier();

@@ -36,22 +36,9 @@
 #include <string.h>
 #include "../../include/mvd_hip.h"
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-MVD_DEVINL void xs_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
-MVD_DEVINL void xs_dma4(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_wave_base, 4, (int)voff, (int)soff, 0, 0);
-}
-// 16-byte buffer store + the wait states hipcc does not insert for an SGPR soffset (see store16() in gemm_pp.hip)
-MVD_DEVINL void xs_store16(u32x4 v, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, soff, 0);
-  asm volatile("s_nop 1" :: "v"(v));
-}
 
 #define XS_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
@@ -90,20 +77,20 @@ __global__ __launch_bounds__(256, 2) void gemm_xs_kernel(const MvdXsArgs a) {
   const int u0 = cp * upp, nit = upp;
   const int row_w = rb * 256 + wave * (RT * 32);        // first token of the wave
 
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.w), 0, a.units * UNIT, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(a.w, a.units * UNIT);
   auto issue_unit = [&](int it, int stage) {
     unsigned char* dst = smem + stage * UNIT;
     const unsigned so = (unsigned)(u0 + it) * (unsigned)UNIT;
     if (dbg & 4) return;
 #pragma unroll
-    for (int i = 0; i < P; ++i) xs_dma16(rs_w, dst + (wave * P + i) * 1024, (unsigned)lane * 16u, so + (unsigned)((wave * P + i) * 1024));
-    xs_dma4(rs_w, dst + KS * 1024 + wave * 256, (unsigned)lane * 4u, so + (unsigned)(KS * 1024 + wave * 256));
+    for (int i = 0; i < P; ++i) dma16(rs_w, dst + (wave * P + i) * 1024, (unsigned)lane * 16u, so + (unsigned)((wave * P + i) * 1024));
+    dma4(rs_w, dst + KS * 1024 + wave * 256, (unsigned)lane * 4u, so + (unsigned)(KS * 1024 + wave * 256));
   };
   issue_unit(0, 0);
   if (NS == 3 && nit > 1) issue_unit(1, 1);
 
   // ---- the wave's 64 tokens -> B-operand fragments (rows >= M lie beyond num_records and read as zeros)
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)((size_t)a.M * a.ldx * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buf_rsrc(a.x, (int)((size_t)a.M * a.ldx * 2));
   u32x4 x[RT][KS];
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
@@ -144,9 +131,9 @@ __global__ __launch_bounds__(256, 2) void gemm_xs_kernel(const MvdXsArgs a) {
   // B operand of the bias k-step: 1.0 at k = 0, 1 (lanes of half 0, elements 0 and 1), zero elsewhere
   const u32x4 one_frag = {h == 0 ? 0x3f803f80u : 0u, 0u, 0u, 0u};
 
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)((size_t)a.M * a.ldo * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_o = buf_rsrc(a.out, (int)((size_t)a.M * a.ldo * 2));
   __amdgpu_buffer_rsrc_t rs_r = rs_o;
-  if (RES) rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.res), 0, (int)((size_t)a.M * a.ldres * 2), 0x00020000);
+  if (RES) rs_r = buf_rsrc(a.res, (int)((size_t)a.M * a.ldres * 2));
   int vo_r[RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
@@ -285,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void gemm_xs_kernel(const MvdXsArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
-      if (!(dbg & 1) || v[j].x == 0x12345678u) xs_store16(v[j], rs_o, vo_l[t], so + j * so_j);
+      if (!(dbg & 1) || v[j].x == 0x12345678u) store16(v[j], rs_o, vo_l[t], so + j * so_j);
   };
   auto pack8 = [&](const f32x16& o, int b) -> u32x4 {
     return u32x4{pack2bf(o[8 * b], o[8 * b + 1]), pack2bf(o[8 * b + 2], o[8 * b + 3]), pack2bf(o[8 * b + 4], o[8 * b + 5]), pack2bf(o[8 * b + 6], o[8 * b + 7])};

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <atomic>
 #include "common.h"
+#include "../../include/mvd_hip.h"    // mvd_debug_flag_t: the switches mvd_debug_flags() returns
 
 // ---------------------------------------------------------------- GEMM / implicit conv
 enum { MVD_A_DENSE = 0, MVD_A_CONV3 = 1 };
@@ -75,7 +76,7 @@ extern std::atomic<long> g_mvd_up4_launches;       // launches of the 2x2 sub-pi
 bool mvd_gemm_pp_applicable(const MvdGemmArgs& a);
 bool mvd_gemm_pp_up4_applicable(const MvdGemmArgs& a);   // the 2x2 sub-pixel form of an upsampling convolution (seg[0].ups == 2)
 int mvd_gemm_pp_walk(const MvdGemmArgs& a);        // column tiles per group of the ping-pong kernel's tile walk (0: row-major)
-int mvd_debug_flags();                             // engine.hip: the measurement switches of mvd_debug_set_flags
+int mvd_debug_flags();                             // engine.hip: what mvd_debug_set_flags set (MVD_DBG_* of the public header)
 // true when a problem with a.ln_c1 set can run (one dense source spanning the whole row, no residual / row vector /
 // split-K, and a shape the heuristic gives to the ping-pong kernels); the engine falls back to ln_kernel + plain GEMM otherwise
 bool mvd_gemm_ln_fold_ok(const MvdGemmArgs& a);
@@ -220,3 +221,28 @@ int mvd_launch_film_nchw_f32(const float* x, int batch, int c, int hw, const flo
                              hipStream_t s);
 
 void mvd_set_error(const char* fmt, ...);
+
+// ---------------------------------------------------------------- profiling classes (mvd_engine_set_profiling)
+// The class of a launch is the KERNEL that runs it (each is a distinct rocprof kernel name).  The values are what
+// mvd_engine_profile_summary reports; their names in bench lines and profiles/ come from MVDEngine.PROFILE_CLASSES
+// (mvd_amd/engine.py; tests/test_cabi_cpu.py checks that every enumerator has one).
+enum MvdProfClass {
+  // lock-step kernels of gemm.hip: class = tile config 0..5
+  MVD_PC_GEMM_256X160 = 0, MVD_PC_GEMM_256X128 = 1, MVD_PC_GEMM_128X160 = 2, MVD_PC_GEMM_128X128 = 3, MVD_PC_GEMM_128X64 = 4,
+  MVD_PC_GEMM_64X64 = 5,
+  // ping-pong kernels of gemm_pp.hip (tile configs 6, 7): GEGLU (with or without the LayerNorm fold), dense A operand
+  MVD_PC_PP_GEGLU = 6, MVD_PC_PP_DENSE = 7,
+  // attention: MVD_PC_ATTN_1WAVE + log2(waves per workgroup)
+  MVD_PC_ATTN_1WAVE = 8, MVD_PC_ATTN_2WAVE = 9, MVD_PC_ATTN_4WAVE = 10, MVD_PC_ATTN_8WAVE = 11,
+  MVD_PC_GEMM_128X320 = 12,   // tile config 8
+  // ping-pong again: implicit-GEMM 3x3 convolution (incl. the fused 1x1 shortcut / upsample forms), the split-K forms, dense
+  // with the LayerNorm fold
+  MVD_PC_PP_CONV3 = 13, MVD_PC_PP_SPLITK = 14, MVD_PC_PP_LN_DENSE = 15,
+  MVD_PC_GROUPNORM = 16, MVD_PC_LAYERNORM = 17,
+  // small-M kernels of gemm_sm.hip: MVD_PC_SM_64X64 + tile
+  MVD_PC_SM_64X64 = 20, MVD_PC_SM_128X64 = 21, MVD_PC_SM_64X128 = 22, MVD_PC_SM_128X128 = 23, MVD_PC_SM_64X160 = 24,
+  MVD_PC_SM_128X160 = 25, MVD_PC_SM_64X320 = 26,
+  // X-stationary kernels of gemm_xs.hip
+  MVD_PC_XS_DENSE = 30, MVD_PC_XS_RESIDUAL = 31, MVD_PC_XS_LN_DENSE = 32, MVD_PC_XS_GEGLU = 33,
+  MVD_PC_CONV_WS = 34         // conv_ws.hip
+};

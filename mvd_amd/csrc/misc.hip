@@ -571,7 +571,7 @@ int mvd_launch_skinny_linear(const float* x, int ldx, int batch, int k, const vo
   // stream) the 32-row front matter of a forward drops from ~0.75 to ~0.35 ms; beside the encoder pass a launch's time is the wait
   // for a CU whose register file a persistent kernel has filled (grouped layer 389 -> 81 us, time MLPs 145 -> 70 us in situ) and the
   // two-stream step gains nothing measurable (60.85 -> 60.72 ms, noise); at one row the vector form is 0.6 % of a cfg3 step faster
-  if (vec && batch >= 8 && !(mvd_debug_flags() & 8388608)) {
+  if (vec && batch >= 8 && !(mvd_debug_flags() & MVD_DBG_SKINNY_VECTOR)) {
     const MvdSegTable none{};
     if (wbf16) hipLaunchKernelGGL((skinny_mfma_kernel<true, false>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy, none, 0);
     else hipLaunchKernelGGL((skinny_mfma_kernel<false, false>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy, none, 0);
@@ -594,7 +594,7 @@ int mvd_launch_skinny_linear_grouped(const float* x, int ldx, int xseg, int batc
   if (!x || !w || !y || batch <= 0 || batch > 4096 || k <= 0 || (k % 4) || (ldx % 4) || n <= 0 || ldy < n || seg.n < 1 || seg.n > 16 ||
       seg.end[seg.n - 1] != n || (((uintptr_t)x | (uintptr_t)w) & 15) || (xseg % 4)) { mvd_set_error("skinny_linear_grouped: bad arguments"); return -1; }
   for (int g = 0; g < seg.n; ++g) if (seg.end[g] % 2) { mvd_set_error("skinny_linear_grouped: segment ends must be even"); return -1; }
-  bool tiles_ok = batch >= 8 && !(mvd_debug_flags() & 8388608);    // a 32-feature tile must not straddle two segments
+  bool tiles_ok = batch >= 8 && !(mvd_debug_flags() & MVD_DBG_SKINNY_VECTOR);    // a 32-feature tile must not straddle two segments
   for (int g = 0; g + 1 < seg.n; ++g) tiles_ok = tiles_ok && seg.end[g] % 32 == 0;
   if (tiles_ok) {
     hipLaunchKernelGGL((skinny_mfma_kernel<false, true>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, (const void*)w, bias, n, 0, y, ldy, seg, xseg);

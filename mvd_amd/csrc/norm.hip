@@ -3,6 +3,7 @@
 // normalisation (per pixel over batch x channel, attention.py:95-103 of the reference).
 #include <stdlib.h>
 #include "kernels.h"
+#include "bufaddr.h"
 
 namespace {
 
@@ -196,15 +197,14 @@ __global__ __launch_bounds__(1024) void gn_slice_kernel(const bf16_t* __restrict
   // Buffer addressing: one descriptor per source image, a loop-invariant per-thread byte offset, the pixel step as a
   // scalar offset -- no per-vector 64-bit addresses (they would double the registers a vector costs).  Pixels >= hw and the
   // threads beyond npl * nvec fall outside num_records: their loads return zeros, their stores are dropped.
-  constexpr unsigned OOB = 0x80000000u;
-  __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(x0 + (size_t)b * hw * c0), 0, hw * c0 * 2, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs0 = buf_rsrc(x0 + (size_t)b * hw * c0, hw * c0 * 2);
   const unsigned vo0 = active && ch < c0 ? (unsigned)(pl * c0 + ch) * 2u : OOB;
   const int st0 = npl * c0 * 2;                           // (scalar) byte step between a thread's consecutive pixels
   u32x4 d[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) d[i] = __builtin_amdgcn_raw_buffer_load_b128(rs0, vo0, i * st0, 0);
   if (c1 && ch >= c0) {      // threads whose channels lie in the second source: same registers, loads under their exec mask
-    __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(x1 + (size_t)b * hw * c1), 0, hw * c1 * 2, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs1 = buf_rsrc(x1 + (size_t)b * hw * c1, hw * c1 * 2);
     const unsigned vo1 = active ? (unsigned)(pl * c1 + ch - c0) * 2u : OOB;
     const int st1 = npl * c1 * 2;
 #pragma unroll
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(1024) void gn_slice_kernel(const bf16_t* __restrict
       gb[j] = bt - (j < kb ? m0 : m1) * ga[j];
     }
   }
-  __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)b * hw * C, 0, hw * C * 2, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_y = buf_rsrc(y + (size_t)b * hw * C, hw * C * 2);
   const unsigned voy = (unsigned)(pl * C + ch) * 2u;
   const int sty = npl * C * 2;
 #pragma unroll
@@ -297,8 +297,7 @@ __global__ __launch_bounds__(1024) void gn_slice_kernel(const bf16_t* __restrict
         if (silu) { lo = silu_f(lo); hi = silu_f(hi); }
         o[k] = pack2bf(lo, hi);
       }
-      __builtin_amdgcn_raw_buffer_store_b128(o, rs_y, voy, i * sty, 0);
-      asm volatile("s_nop 1" :: "v"(o));       // wait states hipcc leaves out behind a 16-byte store with an SGPR soffset (see gemm_pp.hip store16)
+      store16(o, rs_y, voy, i * sty);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -513,7 +512,7 @@ static bool launch_gn_slice(const bf16_t* x0, const bf16_t* x1, int c0, int c1, 
   // few big slices: the two-kernel form has more parallelism.  (Round 5 re-measured the one-pass form for one image's 64x64 map --
   // 8 slices of 327 KB, 13 launches fewer per pass: debug flag 2097152 -- on one box, three alternations: cfg2 4.27 -> 4.39 ms,
   // cfg3 cold 6.50 -> 6.61 ms.  Fewer launches, more time: the floor stays.)
-  const long min_wg = (mvd_debug_flags() & 2097152) ? 8 : 128;
+  const long min_wg = (mvd_debug_flags() & MVD_DBG_GN_ONE_PASS) ? 8 : 128;
   if (slice_bytes > 96 * 1024 && nwg < min_wg) return false;
   const dim3 grid((unsigned)nwg), blk((unsigned)threads);
 #define GN_SLICE(NVT) hipLaunchKernelGGL(gn_slice_kernel<NVT>, grid, blk, 0, s, x0, x1, c0, c1, batch, hw, groups, gpw, eps, gamma, beta, silu, y)

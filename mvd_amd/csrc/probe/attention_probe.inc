@@ -51,9 +51,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_q64_kernel(const MvdAttnArgs 
 
   const int ld_kc = tid & 7, ld_row = tid >> 3;
   const int ldk = P.ldk, ldv = P.ldv;
-  typedef __attribute__((address_space(3))) void lds_void_t;
-  __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(kp), 0, (nk - 1) * ldk * 2 + 128, 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(vp), 0, (nk - 1) * ldv * 2 + 128, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_k = buf_rsrc(kp, (nk - 1) * ldk * 2 + 128);
+  __amdgpu_buffer_rsrc_t rs_v = buf_rsrc(vp, (nk - 1) * ldv * 2 + 128);
   const unsigned dma_ko = (unsigned)ld_row * (unsigned)ldk * 2u + ((ld_kc ^ ((ld_row >> 1) & 7)) << 4);
   const unsigned dma_vo = (unsigned)ld_row * (unsigned)ldv * 2u + ((ld_kc ^ (((ld_row >> 1) & 1) << 2)) << 4);
   auto dma_tile = [&](int kb, int st) {
@@ -63,8 +62,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_q64_kernel(const MvdAttnArgs 
 #pragma unroll
     for (int i = 0; i < LD_IT; ++i) {
       const int row0 = kb * KV_TILE + i * (NT / 8);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_void_t*)(dk + i * (NT / 8) * 128), 16, (int)dma_ko, row0 * ldk * 2, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lds_void_t*)(dv + i * (NT / 8) * 128), 16, (int)dma_vo, row0 * ldv * 2, 0, 0);
+      dma16(rs_k, dk + i * (NT / 8) * 128, dma_ko, row0 * ldk * 2);
+      dma16(rs_v, dv + i * (NT / 8) * 128, dma_vo, row0 * ldv * 2);
     }
   };
 
@@ -459,7 +458,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_pipe_kernel(const MvdAttnArgs
 __global__ __launch_bounds__(512, 2) void attn_pp_kernel(const MvdAttnArgs a) {
   constexpr int QB = 256, KV_TILE = 64, TILE_BYTES = KV_TILE * 128, NSTG = 3;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * NSTG * TILE_BYTES];   // K ring | V ring
-  typedef __attribute__((address_space(3))) void lds_void;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -486,8 +484,8 @@ __global__ __launch_bounds__(512, 2) void attn_pp_kernel(const MvdAttnArgs a) {
   // ---- K/V loader: buffer descriptors over this batch element's rows; per-lane offset = key-in-piece row + head + chunk
   // (the XOR swizzles of k_off / v_off live on the SOURCE side: the DMA writes lane-linear)
   const int ldk2 = P.ldk * 2, ldv2 = P.ldv * 2;
-  __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(P.k + (size_t)bz * P.bsk), 0, (int)((size_t)nk * ldk2), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(P.v + (size_t)bz * P.bsv), 0, (int)((size_t)nk * ldv2), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_k = buf_rsrc(P.k + (size_t)bz * P.bsk, (int)((size_t)nk * ldk2));
+  __amdgpu_buffer_rsrc_t rs_v = buf_rsrc(P.v + (size_t)bz * P.bsv, (int)((size_t)nk * ldv2));
   const int ld_key = wave * 8 + (lane >> 3);                          // key row inside the tile this lane fetches
   const unsigned vo_k = (unsigned)ld_key * (unsigned)ldk2 + head * 128 + (((lane & 7) ^ ((ld_key >> 1) & 7)) << 4);
   const unsigned vo_v = (unsigned)ld_key * (unsigned)ldv2 + head * 128 + (((lane & 7) ^ (((ld_key >> 1) & 1) << 2)) << 4);

@@ -19,12 +19,9 @@
 #include <string>
 #include <unordered_map>
 
-#include "../../include/mvd_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 
 namespace {
-
-struct TWeight { const void* p; int64_t numel; int dtype; };
 
 int tcheck(const char* what) {
   hipError_t e = hipGetLastError();
@@ -259,57 +256,34 @@ int launch_attn_causal(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t
 
 struct mvd_text {
   mvd_text_config_t cfg;
-  std::unordered_map<std::string, TWeight> w;
+  WeightTable w;
   void* ws_ptr = nullptr; int64_t ws_bytes = 0;
 };
 
 namespace {
-
-#define TCHECK(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 struct TCtx {
   mvd_text* t;
   hipStream_t s;
   bool dry;
   bool check_w = true;        // false (sizing only): weight slots are not looked at
-  char* base = nullptr;       // activations start here (behind the split-K tile counters)
-  size_t off = 0, high = 0;
+  Arena ar;                   // activations (ar.base: behind the split-K tile counters)
   unsigned int* cnt_base = nullptr;
   int cnt_used = 0;
   int err = 0;
 
-  void* alloc_bytes(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
-    off += bytes;
-    if (off > high) high = off;
-    return p;
-  }
-  template <class T> T* alloc(size_t n) { return (T*)alloc_bytes(n * sizeof(T)); }
-
-  const TWeight* W(const std::string& name, int dtype, int64_t numel) {
-    if (!check_w) return nullptr;
-    auto it = t->w.find(name);
-    if (it == t->w.end()) { mvd_set_error("text: missing weight slot '%s'", name.c_str()); err = -10; return nullptr; }
-    if (it->second.dtype != dtype || it->second.numel != numel) {
-      mvd_set_error("text: weight slot '%s': expected dtype %d numel %lld, got dtype %d numel %lld", name.c_str(), dtype, (long long)numel,
-                    it->second.dtype, (long long)it->second.numel);
-      err = -11; return nullptr;
-    }
-    return &it->second;
-  }
-  const bf16_t* WB(const std::string& n, int64_t numel) { auto* w = W(n, 1, numel); return w ? (const bf16_t*)w->p : nullptr; }
-  const float* WF(const std::string& n, int64_t numel) { auto* w = W(n, 0, numel); return w ? (const float*)w->p : nullptr; }
+  template <class T> T* alloc(size_t n) { return ar.alloc_n<T>(n); }
+  const void* W(const std::string& name, int dtype, int64_t numel) { return check_w ? t->w.find(name, dtype, numel, &err, "text: ") : nullptr; }
+  const bf16_t* WB(const std::string& n, int64_t numel) { return (const bf16_t*)W(n, 1, numel); }
+  const float* WF(const std::string& n, int64_t numel) { return (const float*)W(n, 0, numel); }
 
   // out[M][N] = a[M][K] . w[N][K]^T + bias: the small-M kernels (split-K combined in the kernel) where their planner takes
   // the shape, else the tiled kernels (+ split-K reduce) -- the same routing as the UNet engine's
   int linear(const bf16_t* a, int K, int M, const bf16_t* w, const float* bias, int N, void* out, bool out_f32) {
     if (err) return err;
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.seg[0].p0 = a; g.seg[0].c0 = K; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = K; g.nseg = 1;
-    g.W = w; g.ldw = K; g.M = M; g.N = N; g.Ktot = K; g.rows_per_batch = M; g.outH = 1; g.outW = M;
-    g.bias = bias; g.ldres = N; g.alpha = 1.f; g.out = out; g.ldo = N; g.out_f32 = out_f32 ? 1 : 0;
-    const size_t mark = off;
+    MvdGemmArgs g = gemm_dense(a, nullptr, K, 0, M, w, 0, bias, N, out, N);
+    g.ldres = N; g.out_f32 = out_f32 ? 1 : 0;
+    const size_t mark = ar.off;
     int r = 0;
     int tile = 0, ns = 0, S = 1;
     if (mvd_gemm_sm_plan(g, &tile, &ns, &S)) {
@@ -322,12 +296,9 @@ struct TCtx {
     } else {
       S = mvd_gemm_pick_splitk(g);
       if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * M * N); } else g.splitk = 1;
-      if (!dry) {
-        r = mvd_launch_gemm(g, s);
-        if (!r && S > 1) r = mvd_launch_splitk_reduce(g, s);
-      }
+      if (!dry) r = launch_tiled(g, s);
     }
-    off = mark;
+    ar.off = mark;
     return r;
   }
   int add_ln(float* x, const float* delta, const float* g, const float* b, int rows, int H, bf16_t* y_bf, float* y_f32) {
@@ -340,16 +311,16 @@ struct TCtx {
 
 size_t cnt_bytes(int cnt) { return ((size_t)cnt * 4 + 255) & ~size_t(255); }
 
-// dry: sizes only (x.high, x.cnt_used); otherwise `cnt` = the counter words the dry run asked for
+// dry: sizes only (x.ar.high, x.cnt_used); otherwise `cnt` = the counter words the dry run asked for
 int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream_t s, bool dry, int cnt, size_t* high_out, int* cnt_out,
                 bool check_w = true) {
   const mvd_text_config_t& c = t->cfg;
   const int H = c.hidden_size, I = c.intermediate_size, M = B * T;
   TCtx x{t, s, dry};
-  x.check_w = check_w;
+  x.check_w = check_w; x.ar.dry = dry;
   if (!dry) {
     x.cnt_base = reinterpret_cast<unsigned int*>(t->ws_ptr);
-    x.base = reinterpret_cast<char*>(t->ws_ptr) + cnt_bytes(cnt);
+    x.ar.base = reinterpret_cast<char*>(t->ws_ptr) + cnt_bytes(cnt);
     if (cnt > 0 && hipMemsetAsync(x.cnt_base, 0, (size_t)cnt * 4, s) != hipSuccess) { mvd_set_error("text_encode: hipMemsetAsync failed"); return -3; }
   }
   float* xs = x.alloc<float>((size_t)M * H);          // residual stream
@@ -364,7 +335,7 @@ int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream
   if (x.err) return x.err;
   if (!dry) {
     hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, tok, pos, M, T, H, c.vocab_size, xs);
-    TCHECK(tcheck("text embedding"));
+    CHECK(tcheck("text embedding"));
   }
   for (int l = 0; l < c.num_layers; ++l) {
     const std::string p = "layers." + std::to_string(l);
@@ -373,23 +344,23 @@ int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream
     const bf16_t *w1 = x.WB(p + ".fc1.w", (int64_t)I * H), *w2 = x.WB(p + ".fc2.w", (int64_t)H * I);
     const float *bqkv = x.WF(p + ".qkv.b", 3 * H), *bo = x.WF(p + ".out.b", H), *bf1 = x.WF(p + ".fc1.b", I), *bf2 = x.WF(p + ".fc2.b", H);
     if (x.err) return x.err;
-    TCHECK(x.add_ln(xs, l ? dl : nullptr, g1w, b1w, M, H, h, nullptr));
-    TCHECK(x.linear(h, H, M, wqkv, bqkv, 3 * H, qkv, false));
-    if (!dry) TCHECK(launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s));   // q rows prescaled at pack time
-    TCHECK(x.linear(at, H, M, wo, bo, H, dl, true));
-    TCHECK(x.add_ln(xs, dl, g2w, b2w, M, H, h, nullptr));
-    TCHECK(x.linear(h, H, M, w1, bf1, I, f1, true));
+    CHECK(x.add_ln(xs, l ? dl : nullptr, g1w, b1w, M, H, h, nullptr));
+    CHECK(x.linear(h, H, M, wqkv, bqkv, 3 * H, qkv, false));
+    if (!dry) CHECK(launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s));   // q rows prescaled at pack time
+    CHECK(x.linear(at, H, M, wo, bo, H, dl, true));
+    CHECK(x.add_ln(xs, dl, g2w, b2w, M, H, h, nullptr));
+    CHECK(x.linear(h, H, M, w1, bf1, I, f1, true));
     if (!dry) {
       const long n8 = (long)M * I / 8;
       hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, f1, n8, c.act, g1);
-      TCHECK(tcheck("text activation"));
+      CHECK(tcheck("text activation"));
     }
-    TCHECK(x.linear(g1, I, M, w2, bf2, H, dl, true));
+    CHECK(x.linear(g1, I, M, w2, bf2, H, dl, true));
   }
   const float *gf = x.WF("final_ln.g", H), *bf = x.WF("final_ln.b", H);
   if (x.err) return x.err;
-  TCHECK(x.add_ln(xs, c.num_layers ? dl : nullptr, gf, bf, M, H, nullptr, out));
-  if (high_out) *high_out = x.high;
+  CHECK(x.add_ln(xs, c.num_layers ? dl : nullptr, gf, bf, M, H, nullptr, out));
+  if (high_out) *high_out = x.ar.high;
   if (cnt_out) *cnt_out = x.cnt_used;
   return x.err;
 }
@@ -423,7 +394,7 @@ int mvd_text_destroy(mvd_text_t* t) { delete t; return 0; }
 int mvd_text_set_weight(mvd_text_t* t, const char* slot, const void* ptr, int64_t numel, int dtype) {
   if (!t || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("text_set_weight: bad argument"); return -1; }
   if ((uintptr_t)ptr & 15) { mvd_set_error("text_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  t->w[slot] = TWeight{ptr, numel, dtype};
+  t->w.m[slot] = Weight{ptr, numel, dtype};
   return 0;
 }
 

@@ -21,27 +21,9 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/mvd_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 
 namespace {
-
-struct VWeight { const void* p; int64_t numel; int dtype; };
-
-struct VArena {
-  char* base = nullptr;
-  size_t cap = 0, off = 0, high = 0;
-  bool dry = false;
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
-    off += bytes;
-    if (off > high) high = off;
-    return p;
-  }
-};
-
-struct VAct { bf16_t* p = nullptr; int B = 0, H = 0, W = 0, C = 0; int hw() const { return H * W; } int rows() const { return B * H * W; } };
 
 // fp32 row softmax -> bf16 probabilities; one workgroup per row
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ s, int n, bf16_t* __restrict__ p) {
@@ -104,14 +86,12 @@ int vcheck(const char* what) {
 
 struct mvd_vae {
   mvd_vae_config_t cfg;
-  std::unordered_map<std::string, VWeight> w;
-  VArena ar;
+  WeightTable w;
+  Arena ar;
   void* ws_ptr = nullptr; int64_t ws_bytes = 0;
 };
 
 namespace {
-
-#define VCHECK(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 struct VCtx {
   mvd_vae* v;
@@ -119,59 +99,36 @@ struct VCtx {
   bool dry;
   int err = 0;
 
-  const VWeight* W(const std::string& name, int dtype, int64_t numel) {
-    if (dry) return nullptr;
-    auto it = v->w.find(name);
-    if (it == v->w.end()) { mvd_set_error("vae: missing weight slot '%s'", name.c_str()); err = -10; return nullptr; }
-    if (it->second.dtype != dtype || it->second.numel != numel) {
-      mvd_set_error("vae: weight slot '%s': expected dtype %d numel %lld, got dtype %d numel %lld", name.c_str(), dtype, (long long)numel,
-                    it->second.dtype, (long long)it->second.numel);
-      err = -11; return nullptr;
-    }
-    return &it->second;
-  }
-  const bf16_t* WB(const std::string& n, int64_t numel) { auto* w = W(n, 1, numel); return w ? (const bf16_t*)w->p : nullptr; }
-  const float* WF(const std::string& n, int64_t numel) { auto* w = W(n, 0, numel); return w ? (const float*)w->p : nullptr; }
-  template <class T> T* alloc(size_t n) { return (T*)v->ar.alloc(n * sizeof(T)); }
-  VAct act(int B, int H, int W_, int C) { VAct a; a.B = B; a.H = H; a.W = W_; a.C = C; a.p = alloc<bf16_t>((size_t)B * H * W_ * C); return a; }
+  const void* W(const std::string& name, int dtype, int64_t numel) { return dry ? nullptr : v->w.find(name, dtype, numel, &err, "vae: "); }
+  const bf16_t* WB(const std::string& n, int64_t numel) { return (const bf16_t*)W(n, 1, numel); }
+  const float* WF(const std::string& n, int64_t numel) { return (const float*)W(n, 0, numel); }
+  template <class T> T* alloc(size_t n) { return v->ar.alloc_n<T>(n); }
+  Act act(int B, int H, int W_, int C) { return arena_act(v->ar, B, H, W_, C); }
 
+  // the tiled kernels only (never the small-M kernels); an unsplit launch leaves splitk = 0, "undecided"
   int gemm(MvdGemmArgs& g) {
     if (err) return err;
     const int S = mvd_gemm_pick_splitk(g);
     const size_t mark = v->ar.off;
     if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * g.M * g.N); }
-    int r = 0;
-    if (!dry) {
-      r = mvd_launch_gemm(g, s);
-      if (!r && S > 1) r = mvd_launch_splitk_reduce(g, s);
-    }
+    const int r = dry ? 0 : launch_tiled(g, s);
     v->ar.off = mark;
     return r;
   }
   int linear(const bf16_t* a, int k, int M, const bf16_t* w, const float* bias, int N, const bf16_t* res, void* out, float alpha = 1.f,
              bool out_f32 = false) {
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.ldw = k;
-    g.seg[0].p0 = a; g.seg[0].c0 = k; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k;
-    g.nseg = 1; g.W = w; g.M = M; g.N = N; g.Ktot = k; g.rows_per_batch = M; g.outH = 1; g.outW = M;
-    g.bias = bias; g.res = res; g.ldres = N; g.alpha = alpha; g.out = out; g.ldo = N; g.out_f32 = out_f32;
+    MvdGemmArgs g = gemm_dense(a, nullptr, k, 0, M, w, 0, bias, N, out, N);
+    g.res = res; g.ldres = N; g.alpha = alpha; g.out_f32 = out_f32;
     return gemm(g);
   }
   // 3x3 conv (pad 1; stride 2 = the VAE's bottom/right-padded downsampler; ups = nearest 2x in front), optional residual
   // or fused 1x1 shortcut on `sc`
-  int conv3(const VAct& x, int stride, int ups, const bf16_t* w, const float* bias, const bf16_t* res, const bf16_t* sc, int scc, VAct& out) {
-    MvdGemmArgs g; memset(&g, 0, sizeof(g));
-    g.seg[0].p0 = x.p; g.seg[0].c0 = x.C; g.seg[0].mode = MVD_A_CONV3; g.seg[0].ksize = 9 * x.C;
-    g.seg[0].inH = x.H; g.seg[0].inW = x.W; g.seg[0].stride = stride; g.seg[0].ups = ups; g.seg[0].asym = stride == 2 ? 1 : 0;
-    g.nseg = 1; g.Ktot = 9 * x.C;
-    if (sc) {
-      g.seg[1].p0 = sc; g.seg[1].c0 = scc; g.seg[1].mode = MVD_A_DENSE; g.seg[1].ksize = scc; g.nseg = 2; g.Ktot += scc;
-    }
-    g.W = w; g.ldw = g.Ktot; g.M = out.rows(); g.N = out.C; g.rows_per_batch = out.hw(); g.outH = out.H; g.outW = out.W;
-    g.bias = bias; g.res = res; g.ldres = out.C; g.alpha = 1.f; g.out = out.p; g.ldo = out.C;
+  int conv3(const Act& x, int stride, int ups, const bf16_t* w, const float* bias, const bf16_t* res, const bf16_t* sc, int scc, Act& out) {
+    MvdGemmArgs g = gemm_conv3(x.p, x.H, x.W, x.C, stride, ups, stride == 2 ? 1 : 0, sc, nullptr, scc, 0, w, bias, out.B, out.H, out.W, out.C, out.p);
+    g.res = res;
     return gemm(g);
   }
-  int groupnorm(const VAct& x, const float* g, const float* b, int silu, bf16_t* y) {
+  int groupnorm(const Act& x, const float* g, const float* b, int silu, bf16_t* y) {
     if (err) return err;
     float* ws = alloc<float>((size_t)x.B * MVD_GN_MAXCHUNK * v->cfg.norm_num_groups * 2);
     if (dry) return 0;
@@ -179,36 +136,36 @@ struct VCtx {
   }
 
   // ResnetBlock2D without a time embedding: GN+SiLU -> conv1 -> GN+SiLU -> conv2 (+ x, or || 1x1 conv_shortcut(x))
-  int resnet(const std::string& key, const VAct& x, int cout, VAct& out) {
+  int resnet(const std::string& key, const Act& x, int cout, Act& out) {
     const int cin = x.C;
     const size_t mark = v->ar.off;
-    VAct t1 = act(x.B, x.H, x.W, cin);
-    VCHECK(groupnorm(x, WF(key + ".norm1.g", cin), WF(key + ".norm1.b", cin), 1, t1.p));
-    VAct h1 = act(x.B, x.H, x.W, cout);
-    VCHECK(conv3(t1, 1, 0, WB(key + ".conv1.w", (int64_t)cout * 9 * cin), WF(key + ".conv1.b", cout), nullptr, nullptr, 0, h1));
-    VAct t2 = act(x.B, x.H, x.W, cout);
-    VCHECK(groupnorm(h1, WF(key + ".norm2.g", cout), WF(key + ".norm2.b", cout), 1, t2.p));
+    Act t1 = act(x.B, x.H, x.W, cin);
+    CHECK(groupnorm(x, WF(key + ".norm1.g", cin), WF(key + ".norm1.b", cin), 1, t1.p));
+    Act h1 = act(x.B, x.H, x.W, cout);
+    CHECK(conv3(t1, 1, 0, WB(key + ".conv1.w", (int64_t)cout * 9 * cin), WF(key + ".conv1.b", cout), nullptr, nullptr, 0, h1));
+    Act t2 = act(x.B, x.H, x.W, cout);
+    CHECK(groupnorm(h1, WF(key + ".norm2.g", cout), WF(key + ".norm2.b", cout), 1, t2.p));
     if (cin != cout) {
-      VCHECK(conv3(t2, 1, 0, WB(key + ".conv2.w", (int64_t)cout * (9 * cout + cin)), WF(key + ".conv2.b", cout), nullptr, x.p, cin, out));
+      CHECK(conv3(t2, 1, 0, WB(key + ".conv2.w", (int64_t)cout * (9 * cout + cin)), WF(key + ".conv2.b", cout), nullptr, x.p, cin, out));
     } else {
-      VCHECK(conv3(t2, 1, 0, WB(key + ".conv2.w", (int64_t)cout * 9 * cout), WF(key + ".conv2.b", cout), x.p, nullptr, 0, out));
+      CHECK(conv3(t2, 1, 0, WB(key + ".conv2.w", (int64_t)cout * 9 * cout), WF(key + ".conv2.b", cout), x.p, nullptr, 0, out));
     }
     v->ar.off = mark;
     return err;
   }
 
   // mid-block attention: one head of C channels over the H*W positions of each image
-  int attention(const std::string& key, const VAct& x, VAct& out) {
+  int attention(const std::string& key, const Act& x, Act& out) {
     const int C = x.C, hw = x.hw(), M = x.rows();
     if (hw % 64 || C % 64) { mvd_set_error("vae attention: %d positions x %d channels must be multiples of 64", hw, C); return -1; }
     const size_t mark = v->ar.off;
     bf16_t* xn = alloc<bf16_t>((size_t)M * C);
-    VCHECK(groupnorm(x, WF(key + ".norm.g", C), WF(key + ".norm.b", C), 0, xn));
+    CHECK(groupnorm(x, WF(key + ".norm.g", C), WF(key + ".norm.b", C), 0, xn));
     bf16_t* q = alloc<bf16_t>((size_t)M * C);
     bf16_t* k = alloc<bf16_t>((size_t)M * C);
     bf16_t* o = alloc<bf16_t>((size_t)M * C);
-    VCHECK(linear(xn, C, M, WB(key + ".q.w", (int64_t)C * C), WF(key + ".q.b", C), C, nullptr, q));
-    VCHECK(linear(xn, C, M, WB(key + ".k.w", (int64_t)C * C), WF(key + ".k.b", C), C, nullptr, k));
+    CHECK(linear(xn, C, M, WB(key + ".q.w", (int64_t)C * C), WF(key + ".q.b", C), C, nullptr, q));
+    CHECK(linear(xn, C, M, WB(key + ".k.w", (int64_t)C * C), WF(key + ".k.b", C), C, nullptr, k));
     bf16_t* vt = alloc<bf16_t>((size_t)C * hw);
     float* sc = alloc<float>((size_t)hw * hw);
     bf16_t* pr = alloc<bf16_t>((size_t)hw * hw);
@@ -217,36 +174,36 @@ struct VCtx {
     const float scale = 1.0f / sqrtf((float)C);
     for (int b = 0; b < x.B && !err; ++b) {
       const size_t o0 = (size_t)b * hw * C;
-      VCHECK(linear(wv, C, C, xn + o0, nullptr, hw, nullptr, vt));                          // V^T = W_v . x^T   [C][hw]
-      VCHECK(linear(q + o0, C, hw, k + o0, nullptr, hw, nullptr, sc, scale, true));          // S = q.k^T / sqrt(C)  fp32
-      if (!dry) { hipLaunchKernelGGL(softmax_rows_kernel, dim3(hw), dim3(256), 0, s, sc, hw, pr); VCHECK(vcheck("vae softmax")); }
-      VCHECK(linear(pr, hw, hw, vt, bv, C, nullptr, o + o0));                                // P.V + b_v
+      CHECK(linear(wv, C, C, xn + o0, nullptr, hw, nullptr, vt));                          // V^T = W_v . x^T   [C][hw]
+      CHECK(linear(q + o0, C, hw, k + o0, nullptr, hw, nullptr, sc, scale, true));          // S = q.k^T / sqrt(C)  fp32
+      if (!dry) { hipLaunchKernelGGL(softmax_rows_kernel, dim3(hw), dim3(256), 0, s, sc, hw, pr); CHECK(vcheck("vae softmax")); }
+      CHECK(linear(pr, hw, hw, vt, bv, C, nullptr, o + o0));                                // P.V + b_v
     }
-    VCHECK(linear(o, C, M, WB(key + ".out.w", (int64_t)C * C), WF(key + ".out.b", C), C, x.p, out.p));   // to_out + residual
+    CHECK(linear(o, C, M, WB(key + ".out.w", (int64_t)C * C), WF(key + ".out.b", C), C, x.p, out.p));   // to_out + residual
     v->ar.off = mark;
     return err;
   }
 
-  int mid(const std::string& p, const VAct& x, VAct& out) {
+  int mid(const std::string& p, const Act& x, Act& out) {
     const int C = x.C;
-    VAct r0 = act(x.B, x.H, x.W, C), a0 = act(x.B, x.H, x.W, C);
-    VCHECK(resnet(p + ".resnets.0", x, C, r0));
-    VCHECK(attention(p + ".attn", r0, a0));
-    VCHECK(resnet(p + ".resnets.1", a0, C, out));
+    Act r0 = act(x.B, x.H, x.W, C), a0 = act(x.B, x.H, x.W, C);
+    CHECK(resnet(p + ".resnets.0", x, C, r0));
+    CHECK(attention(p + ".attn", r0, a0));
+    CHECK(resnet(p + ".resnets.1", a0, C, out));
     return err;
   }
   // conv_in: NCHW fp32 -> im2col rows (K padded to 64) -> GEMM
-  int conv_in(const std::string& key, const float* x_nchw, int B, int cin, int H, int W_, int cout, VAct& out) {
+  int conv_in(const std::string& key, const float* x_nchw, int B, int cin, int H, int W_, int cout, Act& out) {
     bf16_t* col = alloc<bf16_t>((size_t)B * H * W_ * 64);
-    if (!dry && !err) VCHECK(mvd_launch_im2col_in(x_nchw, B, cin, H, W_, nullptr, nullptr, 0, col, s));
+    if (!dry && !err) CHECK(mvd_launch_im2col_in(x_nchw, B, cin, H, W_, nullptr, nullptr, 0, col, s));
     return linear(col, 64, B * H * W_, WB(key + ".w", (int64_t)cout * 64), WF(key + ".b", cout), cout, nullptr, out.p);
   }
-  int norm_conv_out(const std::string& pfx, const VAct& x, int cout, float* y_nchw) {
+  int norm_conv_out(const std::string& pfx, const Act& x, int cout, float* y_nchw) {
     bf16_t* t = alloc<bf16_t>((size_t)x.rows() * x.C);
-    VCHECK(groupnorm(x, WF(pfx + ".norm_out.g", x.C), WF(pfx + ".norm_out.b", x.C), 1, t));
+    CHECK(groupnorm(x, WF(pfx + ".norm_out.g", x.C), WF(pfx + ".norm_out.b", x.C), 1, t));
     const bf16_t* w = WB(pfx + ".conv_out.w", (int64_t)cout * 9 * x.C);
     const float* b = WF(pfx + ".conv_out.b", cout);
-    if (!dry && !err) VCHECK(mvd_launch_conv_out(t, x.B, x.H, x.W, x.C, w, b, cout, y_nchw, s));
+    if (!dry && !err) CHECK(mvd_launch_conv_out(t, x.B, x.H, x.W, x.C, w, b, cout, y_nchw, s));
     return err;
   }
   int pointwise(const std::string& key, const float* x, int B, int cin, int cout, int hw, float* y) {
@@ -263,30 +220,30 @@ int encode_impl(mvd_vae* v, const float* image, int B, int H, int W_, float* mom
   const mvd_vae_config_t& c = v->cfg;
   const int n = c.num_levels, div = 1 << (n - 1);
   if (B <= 0 || H <= 0 || W_ <= 0 || H % div || W_ % div) { mvd_set_error("vae encode: image %dx%d must be divisible by %d", H, W_, div); return -1; }
-  v->ar.dry = dry; v->ar.off = v->ar.high = 0;
+  v->ar.reset(dry);
   VCtx x{v, s, dry};
-  VAct h = x.act(B, H, W_, c.block_out_channels[0]);
-  VCHECK(x.conv_in("encoder.conv_in", image, B, c.in_channels, H, W_, c.block_out_channels[0], h));
+  Act h = x.act(B, H, W_, c.block_out_channels[0]);
+  CHECK(x.conv_in("encoder.conv_in", image, B, c.in_channels, H, W_, c.block_out_channels[0], h));
   for (int i = 0; i < n; ++i) {
     const int co = c.block_out_channels[i];
     const std::string bk = "encoder.down_blocks." + std::to_string(i);
     for (int j = 0; j < c.layers_per_block; ++j) {
-      VAct r = x.act(B, h.H, h.W, co);
-      VCHECK(x.resnet(bk + ".resnets." + std::to_string(j), h, co, r));
+      Act r = x.act(B, h.H, h.W, co);
+      CHECK(x.resnet(bk + ".resnets." + std::to_string(j), h, co, r));
       h = r;
     }
     if (i + 1 < n) {
-      VAct d = x.act(B, h.H / 2, h.W / 2, co);
-      VCHECK(x.conv3(h, 2, 0, x.WB(bk + ".down.w", (int64_t)co * 9 * co), x.WF(bk + ".down.b", co), nullptr, nullptr, 0, d));
+      Act d = x.act(B, h.H / 2, h.W / 2, co);
+      CHECK(x.conv3(h, 2, 0, x.WB(bk + ".down.w", (int64_t)co * 9 * co), x.WF(bk + ".down.b", co), nullptr, nullptr, 0, d));
       h = d;
     }
   }
-  VAct m = x.act(B, h.H, h.W, h.C);
-  VCHECK(x.mid("encoder.mid_block", h, m));
+  Act m = x.act(B, h.H, h.W, h.C);
+  CHECK(x.mid("encoder.mid_block", h, m));
   const int L2 = 2 * c.latent_channels, hw = m.hw();
   float* pre = x.alloc<float>((size_t)B * L2 * hw);
-  VCHECK(x.norm_conv_out("encoder", m, L2, pre));
-  VCHECK(x.pointwise("quant_conv", pre, B, L2, L2, hw, moments));
+  CHECK(x.norm_conv_out("encoder", m, L2, pre));
+  CHECK(x.pointwise("quant_conv", pre, B, L2, L2, hw, moments));
   if (x.err) return x.err;
   if (!dry && v->ar.high > (size_t)v->ws_bytes) { mvd_set_error("vae encode: workspace too small"); return -4; }
   return 0;
@@ -296,13 +253,13 @@ int encode_impl(mvd_vae* v, const float* image, int B, int H, int W_, float* mom
 // encode_impl / decode_impl run inside mid(), for the operator-level tests
 int mid_attention_impl(mvd_vae* v, int decoder, const bf16_t* x_nhwc, int B, int H, int W_, bf16_t* out_nhwc, hipStream_t s, bool dry) {
   if (B <= 0 || H <= 0 || W_ <= 0 || (decoder != 0 && decoder != 1)) { mvd_set_error("vae mid_attention: bad shape or coder"); return -1; }
-  v->ar.dry = dry; v->ar.off = v->ar.high = 0;
+  v->ar.reset(dry);
   VCtx x{v, s, dry};
-  VAct in;
+  Act in;
   in.p = const_cast<bf16_t*>(x_nhwc); in.B = B; in.H = H; in.W = W_; in.C = v->cfg.block_out_channels[v->cfg.num_levels - 1];
-  VAct out = in;
+  Act out = in;
   out.p = out_nhwc;
-  VCHECK(x.attention(decoder ? "decoder.mid_block.attn" : "encoder.mid_block.attn", in, out));
+  CHECK(x.attention(decoder ? "decoder.mid_block.attn" : "encoder.mid_block.attn", in, out));
   return x.err;
 }
 
@@ -310,31 +267,31 @@ int decode_impl(mvd_vae* v, const float* latents, int B, int h_, int w_, float* 
   const mvd_vae_config_t& c = v->cfg;
   const int n = c.num_levels;
   if (B <= 0 || h_ <= 0 || w_ <= 0) { mvd_set_error("vae decode: bad shape"); return -1; }
-  v->ar.dry = dry; v->ar.off = v->ar.high = 0;
+  v->ar.reset(dry);
   VCtx x{v, s, dry};
   const int L = c.latent_channels, cm = c.block_out_channels[n - 1];
   float* z = x.alloc<float>((size_t)B * L * h_ * w_);
-  VCHECK(x.pointwise("post_quant_conv", latents, B, L, L, h_ * w_, z));
-  VAct h = x.act(B, h_, w_, cm);
-  VCHECK(x.conv_in("decoder.conv_in", z, B, L, h_, w_, cm, h));
-  VAct m = x.act(B, h_, w_, cm);
-  VCHECK(x.mid("decoder.mid_block", h, m));
+  CHECK(x.pointwise("post_quant_conv", latents, B, L, L, h_ * w_, z));
+  Act h = x.act(B, h_, w_, cm);
+  CHECK(x.conv_in("decoder.conv_in", z, B, L, h_, w_, cm, h));
+  Act m = x.act(B, h_, w_, cm);
+  CHECK(x.mid("decoder.mid_block", h, m));
   h = m;
   for (int i = 0; i < n; ++i) {
     const int co = c.block_out_channels[n - 1 - i];
     const std::string bk = "decoder.up_blocks." + std::to_string(i);
     for (int j = 0; j <= c.layers_per_block; ++j) {
-      VAct r = x.act(B, h.H, h.W, co);
-      VCHECK(x.resnet(bk + ".resnets." + std::to_string(j), h, co, r));
+      Act r = x.act(B, h.H, h.W, co);
+      CHECK(x.resnet(bk + ".resnets." + std::to_string(j), h, co, r));
       h = r;
     }
     if (i + 1 < n) {
-      VAct u = x.act(B, h.H * 2, h.W * 2, co);
-      VCHECK(x.conv3(h, 1, 1, x.WB(bk + ".up.w", (int64_t)co * 9 * co), x.WF(bk + ".up.b", co), nullptr, nullptr, 0, u));
+      Act u = x.act(B, h.H * 2, h.W * 2, co);
+      CHECK(x.conv3(h, 1, 1, x.WB(bk + ".up.w", (int64_t)co * 9 * co), x.WF(bk + ".up.b", co), nullptr, nullptr, 0, u));
       h = u;
     }
   }
-  VCHECK(x.norm_conv_out("decoder", h, c.in_channels, image));
+  CHECK(x.norm_conv_out("decoder", h, c.in_channels, image));
   if (x.err) return x.err;
   if (!dry && v->ar.high > (size_t)v->ws_bytes) { mvd_set_error("vae decode: workspace too small"); return -4; }
   return 0;
@@ -360,7 +317,7 @@ int mvd_vae_destroy(mvd_vae_t* v) { delete v; return 0; }
 int mvd_vae_set_weight(mvd_vae_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
   if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("vae_set_weight: bad argument"); return -1; }
   if ((uintptr_t)ptr & 15) { mvd_set_error("vae_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w[slot] = VWeight{ptr, numel, dtype};
+  v->w.m[slot] = Weight{ptr, numel, dtype};
   return 0;
 }
 

@@ -72,3 +72,30 @@ def test_forward_without_workspace_or_weights_fails_loudly(lib):
     assert lib.mvd_unet_forward(h, C.byref(a), None) != 0
     assert L.last_error()
     lib.mvd_engine_destroy(h)
+
+
+def test_debug_flags_and_profile_classes_are_named_once():
+    """The header's mvd_debug_flag_t and mvd_amd._lib.DebugFlag agree name by name, and no two switches share a bit (1048576 once
+    meant both "upsamplers keep the nine-tap kernel" and the high bit of a two-bit field); every profiling class the C++ side
+    can report (MvdProfClass, csrc/kernels.h) has a name in MVDEngine.PROFILE_CLASSES."""
+    from mvd_amd.engine import MVDEngine
+    hdr = open(os.path.join(ROOT, "include", "mvd_hip.h")).read()
+    body = re.search(r"typedef enum \{(.*?)\} mvd_debug_flag_t;", hdr, re.S).group(1)
+    flags = {n: int(v) for n, v in re.findall(r"\bMVD_DBG_(\w+) = (\d+)", body)}
+    assert len(flags) == 24 and flags == {f.name: f.value for f in L.DebugFlag}
+    seen = 0
+    for name, v in flags.items():
+        assert v > 0 and v & (v - 1) == 0, f"{name} = {v} is not a single bit"
+        assert not seen & v, f"{name} = {v} shares its bit with another switch"
+        seen |= v
+    kern = open(os.path.join(ROOT, "mvd_amd", "csrc", "kernels.h")).read()
+    body = re.search(r"enum MvdProfClass \{(.*?)\};", kern, re.S).group(1)
+    classes = {n: int(v) for n, v in re.findall(r"\bMVD_PC_(\w+) = (\d+)", body)}
+    assert len(classes) == 30 and len(set(classes.values())) == len(classes)
+    for name, v in classes.items():
+        assert v in MVDEngine.PROFILE_CLASSES, f"MVD_PC_{name} = {v} has no name in MVDEngine.PROFILE_CLASSES"
+    # every literal left in the sources would be a switch without a name
+    for f in os.listdir(os.path.join(ROOT, "mvd_amd", "csrc")):
+        if f.endswith((".hip", ".h")):
+            src = open(os.path.join(ROOT, "mvd_amd", "csrc", f)).read()
+            assert not re.search(r"debug_flags(\(\))? *& *\(?\d", src), f

@@ -120,7 +120,7 @@ def test_column_group_tile_walk_is_bit_identical(ops, n, geglu):
     if geglu:
         w, bias = _geglu_rows(w).contiguous(), _geglu_rows(bias).contiguous()
     got = ops.linear(a, w, bias, geglu=geglu)
-    L.lib().mvd_debug_set_flags(131072)
+    L.lib().mvd_debug_set_flags(L.DebugFlag.PP_ROW_MAJOR)
     try:
         plain = ops.linear(a, w, bias, geglu=geglu)
     finally:

@@ -289,14 +289,14 @@ def test_bf16_drift_over_a_real_schedule(tiny, steps, gs, final_tol, growth):
 
 
 def test_small_m_kill_switch_falls_back_instead_of_failing():
-    """with the small-M kernels switched off (mvd_debug_set_flags bit 2) a batch-1 forward at SD-2.1 widths must fall
+    """with the small-M kernels switched off (mvd_debug_set_flags NO_SM) a batch-1 forward at SD-2.1 widths must fall
     back -- ln_kernel + the general GEMMs at C = 1280, where the ping-pong LayerNorm fold does not apply -- not stop with
     "LayerNorm fold not available".  32 x 32 latents keep the CPU oracle short; the base UNet only (no adapter, no camera)."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from mvd_amd import _lib as L
     from tests.parity_util import run_tiny_parity
-    L.lib().mvd_debug_set_flags(4)
+    L.lib().mvd_debug_set_flags(L.DebugFlag.NO_SM)
     try:
         stats = run_tiny_parity(batch=1, verbose=True, cfg_name="sd21", hw=32, text_len=77, cam=False, img=False)
     finally:

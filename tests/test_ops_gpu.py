@@ -613,7 +613,7 @@ def test_skinny_linear_matrix_pipe_form(ops, batch, k, n, wbf16, silu):
     err = (got.cpu() - want).abs().max().item()
     assert err <= 2e-5 * max(1.0, want.abs().max().item()), err
     assert torch.equal(got, ops.skinny_linear(x.cuda(), w.cuda(), bias.cuda(), silu_in=silu))
-    L.lib().mvd_debug_set_flags(8388608)
+    L.lib().mvd_debug_set_flags(L.DebugFlag.SKINNY_VECTOR)
     try:
         old = ops.skinny_linear(x.cuda(), w.cuda(), bias.cuda(), silu_in=silu)
     finally:

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from mvd_amd._lib import DebugFlag
 from tests.test_cfg4_shapes_gpu import _pack, close, grnd      # the bounds of the cfg4 shape tests, exactly as defined there
 
 pytestmark = pytest.mark.gpu
@@ -88,7 +89,7 @@ def test_up4_refuses_channel_counts_and_forced_tiles(ops):
 
 
 # ------------------------------------------------------------------------------- the engine route
-ROUTE_OFF = 1048576      # mvd_debug_set_flags: the upsamplers keep the nine-tap kernel
+ROUTE_OFF = DebugFlag.NO_UP4      # mvd_debug_set_flags: the upsamplers keep the nine-tap kernel
 
 
 def _forward(model, inp):
@@ -139,3 +140,30 @@ def test_engine_keeps_nine_taps_for_widths_the_mode_refuses():
     n_on, n_off, rel = _on_off(8, 96)
     assert n_on == 2 and n_off == 0, (n_on, n_off)
     assert rel <= 3e-2, rel
+
+
+def test_route_switch_is_read_per_forward_and_leaves_nothing_behind():
+    """Setting and clearing a debug switch must leave the product's schedule behind: after NO_UP4 was set and cleared the cfg4-shape
+    forward takes the sub-pixel form again (6 launches) and equals, bit for bit, the forward taken before the switch was ever set.
+    (1048576 once doubled as the high bit of a launch-policy field whose value stayed on the engine for every later forward.)"""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from mvd_amd import _lib as L, ops as O
+    from tests.parity_util import make_inputs, shared_pair
+    ocfg, _params, model = shared_pair("sd21")
+    inp = make_inputs(ocfg, 32, 64, 77, 0, 1024)
+    model.fourier_projection = inp["proj"]
+    L.lib().mvd_debug_set_flags(0)
+    before = _forward(model, inp)
+    n0 = O.up4_launches()
+    L.lib().mvd_debug_set_flags(ROUTE_OFF)
+    try:
+        _forward(model, inp)
+    finally:
+        L.lib().mvd_debug_set_flags(0)
+    n_off = O.up4_launches() - n0
+    after = _forward(model, inp)
+    n_after = O.up4_launches() - n0 - n_off
+    print(f"route off: {n_off} sub-pixel launches, cleared: {n_after}; max |after - before| {(after - before).abs().max().item():.3g}")
+    assert n_off == 0 and n_after == 6, (n_off, n_after)
+    assert torch.equal(before, after)

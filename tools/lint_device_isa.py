@@ -18,7 +18,7 @@ silently undo:
  I4  attention.hip: an MFMA issued from an asm statement (`mfma_from`: D = A.B + C with a live C tile; the hazard recognizer
      does not see an MFMA inside an asm statement) is directly preceded, inside the statement, by its own `s_nop 1`.
  I5  a 16-byte buffer store with an SGPR soffset is followed by >= 2 wait states before anything writes its data registers
-     (gfx950 hazard hipcc does not cover; `store16()` carries an `s_nop 1`).
+     (gfx950 hazard hipcc does not cover; `store16()` of mvd_amd/csrc/bufaddr.h carries an `s_nop 1`).
 """
 import json
 import os

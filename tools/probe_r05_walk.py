@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Round 5: same-process A/B of (1) the column-group tile walk of the ping-pong GEMM (gemm_pp.hip walk_cg; off = debug flag
-131072) at the 32x32-level shapes whose weights exceed an XCD's L2, and (2) the 8x8-level convolution rule (256x320 tile at
+PP_ROW_MAJOR, 131072) at the 32x32-level shapes whose weights exceed an XCD's L2, and (2) the 8x8-level convolution rule (256x320 tile at
 split 8; off = MVD_GEMM_DEEP_CONV_SPLIT=0 needs a second process, so the old choice is forced through force_cfg / splitk).
 PMC_MODE=1: three launches per variant and nothing else (for `rocprofv3 --pmc FETCH_SIZE` / WRITE_SIZE passes)."""
 import math
@@ -15,6 +15,7 @@ from mvd_amd import ops
 from mvd_amd.packing import _geglu_rows
 
 PMC = os.environ.get("PMC_MODE") == "1"
+ROW_MAJOR = int(L.DebugFlag.PP_ROW_MAJOR)
 rnd = lambda *s: (torch.randn(*s, device="cuda") * 0.5).to(torch.bfloat16)
 
 
@@ -33,20 +34,20 @@ def time_fn(fn, iters=20):
 
 def ab(name, fn, flops, rounds=3):
     if PMC:
-        for flag in (131072, 0):
+        for flag in (ROW_MAJOR, 0):
             L.lib().mvd_debug_set_flags(flag)
             for _ in range(3):
                 fn()
         L.lib().mvd_debug_set_flags(0)
         torch.cuda.synchronize()
         return
-    res = {0: [], 131072: []}
+    res = {0: [], ROW_MAJOR: []}
     for _ in range(rounds):
-        for flag in (131072, 0):
+        for flag in (ROW_MAJOR, 0):
             L.lib().mvd_debug_set_flags(flag)
             res[flag].append(time_fn(fn))
     L.lib().mvd_debug_set_flags(0)
-    old, new = min(res[131072]), min(res[0])
+    old, new = min(res[ROW_MAJOR]), min(res[0])
     print(f"{name:46s} row-major walk {old:7.1f} us ({flops / old * 1e-6:5.0f} TF)   column groups {new:7.1f} us ({flops / new * 1e-6:5.0f} TF)   "
           f"{(old / new - 1) * 100:+5.1f} %   plan {ops.last_gemm_plan()}", flush=True)
 
