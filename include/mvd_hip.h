@@ -292,6 +292,43 @@ int mvd_op_sampler_step(const float* model_out, int guided, float guidance_scale
                         const float* noise, float a0, float a1, float p, float q, float r, float sigma, float* out,
                         float* x0_out, int64_t n, void* stream);
 
+/* ---- checkpoint scoring around the UNet, fp32 ------------------------------------------------ */
+/* Conventions of the helpers above; in addition every quantity that depends on a sample's timestep is read ON THE DEVICE
+ * from fp32 tables of num_train_timesteps entries indexed by the int32 device vector timesteps[batch] (clamped to the table
+ * for address safety only: range checks are the caller's), so nothing is uploaded per call.  Reductions are fixed-order
+ * (one partial per workgroup in the caller's workspace, summed in index order by a finalize kernel; no float atomics):
+ * two launches on the same input give the same bits.  Inputs and outputs must not overlap.
+ *
+ * Forward diffusion of x0[batch][per_sample] (diffusers' add_noise / get_velocity; training.py:208, losses.py:168):
+ *   noisy = a x0 + s noise ; velocity = a noise - s x0 ; a = sqrt_ac[t_b], s = sqrt_1mac[t_b].  Either output may be NULL
+ * (not both); per_sample % 4 == 0, batch <= 65535. */
+int mvd_op_add_noise(const float* x0, const float* noise, const int32_t* timesteps, const float* sqrt_ac, const float* sqrt_1mac,
+                     int num_train_timesteps, float* noisy, float* velocity, int batch, int64_t per_sample, void* stream);
+/* The forward-only core of compute_losses (losses.py:128-238) in one pass over (pred, noise, x0, noisy):
+ *   prediction_type 0 epsilon:      target = noise ;            denoised = (noisy - s pred) / a
+ *                   1 v_prediction: target = a noise - s x0 ;   denoised = a noisy - s pred
+ *                   2 sample:       target = x0 ;               denoised = pred
+ *   result[0] = mse = mean (pred - target)^2            result[1] = mse * mean_b w_b,  w_b = min(snr_b, snr_gamma) / snr_b
+ *   result[2] = mean (denoised - x0)^2                  result[3] = mean_b snr_b       result[4] = mean_b w_b
+ * with snr_b = snr[t_b] (a table of its own: the reference takes it from another scheduler object than a and s).  x0 may be
+ * NULL for epsilon; without x0 and noisy (noisy is not read for sample) result[2] = 0 and `denoised` must be NULL; otherwise
+ * `denoised`, when given, receives the denoised latents.  Workspace: the _ws_bytes function below, or more. */
+int64_t mvd_op_noise_loss_ws_bytes(int batch, int64_t per_sample);
+int mvd_op_noise_loss(const float* pred, const float* noise, const float* x0, const float* noisy, const int32_t* timesteps,
+                      const float* sqrt_ac, const float* sqrt_1mac, const float* snr, int num_train_timesteps, int prediction_type,
+                      float snr_gamma, float* denoised, float* result, int batch, int64_t per_sample, void* ws, int64_t ws_bytes,
+                      void* stream);
+/* Mean squared error and, with want_ssim, SSIM of two NCHW batches x, y [n][c][h][w] from one read of both:
+ *   result[0] = mse over all elements   result[1] = SSIM (0 without want_ssim)   result[2] = PSNR = 10 log10(R^2 / mse)
+ *   per_image (may be NULL) [n][2] = each image's (mse, SSIM); their means over n are result[0], result[1].
+ * R = data_range.  SSIM is pytorch_msssim 1.0.0 with its defaults: 11-tap Gaussian window (sigma 1.5, sum 1) applied
+ * separably without padding to x, y, x^2, y^2, x y; C1 = (0.01 R)^2, C2 = (0.03 R)^2; the map's mean per (image, channel),
+ * then the mean of those.  PSNR is torchmetrics' PeakSignalNoiseRatio(data_range=R) (+inf on identical inputs).
+ * Any c, any h, w >= 11 (smaller: -1, never an unfiltered comparison); n c h w < 2^31. */
+int64_t mvd_op_image_metrics_ws_bytes(int n, int c, int h, int w, int want_ssim);
+int mvd_op_image_metrics(const float* x, const float* y, int n, int c, int h, int w, float data_range, int want_ssim, float* result,
+                         float* per_image, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- AutoencoderKL (SD-2.1 VAE) either side of the loop ------------------------------------ */
 /* Replaces: vae.encode(x).latent_dist (pipeline.py:115) and vae.decode(z).sample (pipeline.py:171-176) of diffusers'
  * AutoencoderKL.  Slot names / layouts: DESIGN.md "VAE weight slots" (mvd_amd/vae.py packs a diffusers state dict). */

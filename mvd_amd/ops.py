@@ -267,6 +267,79 @@ def sampler_step(model_out, sample, a0, a1, p, q, r=0.0, sigma=0.0, x0_prev=None
     return out
 
 
+PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")       # prediction_type of mvd_op_noise_loss, by index
+
+
+def _f32_same(*ts):
+    first = next(t for t in ts if t is not None)
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == first.shape):
+            raise L.MvdError(f"expected contiguous fp32 CUDA tensors of shape {tuple(first.shape)}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _timesteps_i32(timesteps, batch, device):
+    t = torch.as_tensor(timesteps, device=device)
+    if t.dim() == 0:
+        t = t.expand(batch)
+    if t.dim() != 1 or t.shape[0] != batch or t.is_floating_point():
+        raise L.MvdError(f"timesteps: expected {batch} integers, got {t.dtype} {tuple(t.shape)}")
+    return t.to(torch.int32).contiguous()
+
+
+def add_noise(x0, noise, timesteps, sqrt_ac, sqrt_1mac, noisy=True, velocity=False):
+    """fp32 (B, ...): noisy = a*x0 + s*noise and / or velocity = a*noise - s*x0 with a = sqrt_ac[t_b], s = sqrt_1mac[t_b]; the
+    tables are fp32 device vectors, ``timesteps`` B integers (a device tensor is not range-checked: no sync).  Returns
+    (noisy or None, velocity or None)."""
+    _f32_same(x0, noise)
+    b = x0.shape[0]
+    ts = _timesteps_i32(timesteps, b, x0.device)
+    assert sqrt_ac.dtype == torch.float32 and sqrt_1mac.dtype == torch.float32 and sqrt_ac.numel() == sqrt_1mac.numel()
+    yn = torch.empty_like(x0) if noisy else None
+    yv = torch.empty_like(x0) if velocity else None
+    L.call("mvd_op_add_noise", _p(x0), _p(noise), _p(ts), _p(sqrt_ac), _p(sqrt_1mac), sqrt_ac.numel(), _p(yn), _p(yv), b,
+           x0.numel() // b, _s())
+    return yn, yv
+
+
+def noise_loss(pred, noise, timesteps, sqrt_ac, sqrt_1mac, snr, prediction_type="v_prediction", x0=None, noisy=None,
+               snr_gamma=5.0, want_denoised=False):
+    """One pass over (pred, noise, x0, noisy), fp32 (B, ...): returns (result, denoised or None) with the device vector
+    result = [mse(pred, target), mse * mean_b(min(snr_b, gamma) / snr_b), mse(denoised, x0), mean_b snr_b, mean_b weight_b]
+    (mvd_hip.h has the formulas per ``prediction_type``).  Nothing is synchronised or uploaded."""
+    _f32_same(pred, noise, x0, noisy)
+    if prediction_type not in PREDICTION_TYPES:
+        raise L.MvdError(f"prediction_type={prediction_type!r}: expected one of {PREDICTION_TYPES}")
+    b = pred.shape[0]
+    per = pred.numel() // b
+    ts = _timesteps_i32(timesteps, b, pred.device)
+    for t in (sqrt_ac, sqrt_1mac, snr):
+        assert t.dtype == torch.float32 and t.numel() == sqrt_ac.numel()
+    nbytes = L.check(L.lib().mvd_op_noise_loss_ws_bytes(b, per), "mvd_op_noise_loss_ws_bytes")
+    ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+    result = torch.empty(5, device=pred.device, dtype=torch.float32)
+    den = torch.empty_like(pred) if want_denoised else None
+    L.call("mvd_op_noise_loss", _p(pred), _p(noise), _p(x0), _p(noisy), _p(ts), _p(sqrt_ac), _p(sqrt_1mac), _p(snr), sqrt_ac.numel(),
+           PREDICTION_TYPES.index(prediction_type), float(snr_gamma), _p(den), _p(result), b, per, _p(ws), nbytes, _s())
+    return result, den
+
+
+def image_metrics(x, y, data_range, ssim=True, per_image=False):
+    """fp32 NCHW batches: returns (result, per-image or None) with the device vectors result = [mse, ssim, psnr] and
+    per-image (N, 2) = each image's (mse, ssim).  SSIM as pytorch_msssim 1.0.0's defaults, PSNR = 10 log10(R^2 / mse)
+    (mvd_hip.h); ``ssim=False`` leaves result[1] = 0.  H, W >= 11."""
+    _f32_same(x, y)
+    if x.dim() != 4:
+        raise L.MvdError(f"image_metrics: expected (N, C, H, W), got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    nbytes = L.check(L.lib().mvd_op_image_metrics_ws_bytes(n, c, h, w, int(ssim)), "mvd_op_image_metrics_ws_bytes")
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    result = torch.empty(3, device=x.device, dtype=torch.float32)
+    pi = torch.empty(n, 2, device=x.device, dtype=torch.float32) if per_image else None
+    L.call("mvd_op_image_metrics", _p(x), _p(y), n, c, h, w, float(data_range), int(ssim), _p(result), _p(pi), _p(ws), nbytes, _s())
+    return result, pi
+
+
 def skinny_linear(x, w, bias=None, silu_in=False):
     """fp32 linear layer of the camera / time MLPs: x (B, K) fp32, w (N, K) fp32 or bf16 -> (B, N) fp32."""
     assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 2 and w.dim() == 2 and w.shape[1] == x.shape[1]

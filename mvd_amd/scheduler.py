@@ -40,7 +40,46 @@ def SNR_to_betas(snr):
     return 1 - alphas
 
 
-class DDPMScheduler:
+class _ForwardDiffusion:
+    """diffusers' ``add_noise`` / ``get_velocity`` (the forward process q(x_t | x_0) of the scheduler's own ``alphas_cumprod``)
+    through ``mvd_op_add_noise``: one fused pass, the per-sample coefficients looked up on the device."""
+
+    def noise_tables(self, device):
+        """(sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)) as fp32 vectors on ``device``: built once per (scheduler, device)."""
+        device = torch.device(device)
+        cache = self.__dict__.setdefault("_noise_tables", {})
+        if device not in cache:
+            acp = self.alphas_cumprod.to(torch.float32)
+            cache[device] = ((acp ** 0.5).to(device).contiguous(), ((1.0 - acp) ** 0.5).to(device).contiguous())
+        return cache[device]
+
+    def _forward_diffusion(self, x0, noise, timesteps, velocity: bool):
+        from . import ops
+        from ._lib import MvdError
+        if not (isinstance(x0, torch.Tensor) and isinstance(noise, torch.Tensor) and x0.is_cuda and noise.is_cuda):
+            raise MvdError("add_noise / get_velocity run on the GPU only (mvd_op_add_noise): pass CUDA tensors; there is no CPU path")
+        if not (isinstance(timesteps, torch.Tensor) and timesteps.is_cuda):        # host-side values: checked here
+            host = torch.as_tensor(timesteps)
+            T = int(self.alphas_cumprod.shape[0])
+            if host.is_floating_point() or host.numel() == 0 or int(host.min()) < 0 or int(host.max()) >= T:
+                raise ValueError(f"timesteps must be integers in [0, {T - 1}]")
+        a, s = self.noise_tables(x0.device)
+        noisy, vel = ops.add_noise(x0.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(), timesteps, a, s,
+                                   noisy=not velocity, velocity=velocity)
+        return vel if velocity else noisy
+
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
+        """sqrt(acp_t) * original_samples + sqrt(1 - acp_t) * noise, one timestep per row of the batch (fp32, on the GPU).
+        ``timesteps``: an int64 / int32 tensor or a list.  Values that live on the host are range-checked; a DEVICE tensor is
+        not (that would synchronise): the kernel clamps it into the table for address safety only."""
+        return self._forward_diffusion(original_samples, noise, timesteps, False)
+
+    def get_velocity(self, sample: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
+        """sqrt(acp_t) * noise - sqrt(1 - acp_t) * sample (the v-prediction target); arguments as ``add_noise``."""
+        return self._forward_diffusion(sample, noise, timesteps, True)
+
+
+class DDPMScheduler(_ForwardDiffusion):
     """Minimal DDPM scheduler with the diffusers attribute names the reference touches."""
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
@@ -132,7 +171,7 @@ def _unsupported(what: str):
                      f"timestep_spacing leading / linspace / trailing); nothing is approximated")
 
 
-class _SolverSchedule:
+class _SolverSchedule(_ForwardDiffusion):
     """What the DDIM and DPM-Solver++ classes share: the trained schedule (built by the same torch ops as
     ``DDPMScheduler``, so ShiftSNRScheduler's betas give bit-identical ``alphas_cumprod``), ``from_config`` and the
     timestep grid of diffusers' ``set_timesteps``."""
