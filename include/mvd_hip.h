@@ -398,6 +398,70 @@ int mvd_text_encode(mvd_text_t* t, const int32_t* ids, int batch, int seq_len, f
 int mvd_op_attention_causal(const void* q, const void* k, const void* v, void* o, int batch, int heads, int n, int ldq, int ldk,
                             int ldv, int ldo, float scale, void* stream);
 
+/* ---- CLIP image tower and CLIP score for checkpoint validation ------------------------------ */
+/* Replaces: the CLIP half of torchmetrics' CLIPScore / transformers' CLIPModel + CLIPImageProcessor as the reference's
+ * validation uses them (val.py:60-196, losses.py:59-98): image preprocessing, get_image_features, the pooled and
+ * projected text features, and the cosine.  ViT-L/14 values in comments.  Slot names / layouts: DESIGN.md "Vision-encoder
+ * weight slots" (mvd_amd/vision_encoder.py packs a transformers state dict). */
+typedef struct {
+  int image_size;          /* 224 */
+  int patch_size;          /* 14: 256 patches + the class token = 257 tokens */
+  int hidden_size;         /* 1024 */
+  int intermediate_size;   /* 4096 */
+  int num_layers;          /* 24 */
+  int num_heads;           /* 16 (head dimension 64) */
+  int projection_dim;      /* 768 */
+  float layer_norm_eps;    /* 1e-5 */
+  int act;                 /* 0 gelu (erf), 1 quick_gelu = x * sigmoid(1.702 x) */
+} mvd_vision_config_t;
+typedef struct mvd_vision mvd_vision_t;
+/* rejects hidden_size / num_heads != 64, hidden_size % 64 (or > 2048), intermediate_size % 64, projection_dim % 64 (or > 2048),
+ * image_size % patch_size, an unknown act */
+int mvd_vision_create(const mvd_vision_config_t* cfg, mvd_vision_t** out);
+int mvd_vision_destroy(mvd_vision_t* v);
+int mvd_vision_set_weight(mvd_vision_t* v, const char* slot, const void* ptr, int64_t numel, int dtype);
+/* bytes for preprocessing `batch` images of h x w (resize_to: the shortest edge after the resize) and encoding them;
+ * h = w = 0: encode only.  The workspace holds [resampling tables | bf16 patch rows | scratch]. */
+int64_t mvd_vision_workspace_bytes(mvd_vision_t* v, int batch, int h, int w, int resize_to);
+int mvd_vision_bind_workspace(mvd_vision_t* v, void* ws, int64_t bytes);
+/* CLIPImageProcessor on the device.  images [batch][3][h][w] fp32: in [-1, 1] with quantize = 1, where the first step is
+ * ((x.clamp(-1, 1) + 1) / 2 * 255).to(uint8) of losses.py:11-13 (the same fp32 operations, truncation), or integral values in
+ * [0, 255] with quantize = 0.  Then PIL's 8-bit BICUBIC Image.resize to the shortest-edge size (resize_to, int(resize_to *
+ * long / short)) -- a horizontal and a vertical pass in 2^22 fixed point, each rounded to uint8, a pass between equal sizes
+ * skipped: integer arithmetic, so the result equals PIL's byte for byte -- the centre crop (top = (oh - crop) / 2, left alike),
+ * u8 / 255 and (x - mean) / std.  want_patches: bf16 patch rows [batch * (crop / patch)^2][roundup(3 patch^2, 64)] in (c, py,
+ * px) order with zero pad columns stay in the workspace for mvd_vision_encode (crop must be the model's image_size);
+ * pixel_values (nullable) [batch][3][crop][crop] fp32 is what the processor returns.  The coefficient tables are built on the
+ * host once per (h, w, resize_to) and uploaded on the first call of that geometry on the bound workspace; later calls upload
+ * nothing.  A resized image smaller than the crop is an error (no padding).  No allocation, no host synchronisation. */
+int mvd_vision_preprocess(mvd_vision_t* v, const float* images_nchw, int batch, int h, int w, int quantize, int resize_to, int crop,
+                          const float* mean, const float* std_, int want_patches, float* pixel_values, void* stream);
+/* byte offset in the bound workspace of the patch rows the last mvd_vision_preprocess(want_patches) left there ([batch *
+ * patches][Kp] bf16), < 0 when there are none: lets a test read what the encoder will read */
+int64_t mvd_vision_patch_rows_offset(mvd_vision_t* v);
+/* pixel_values [batch][3][image_size][image_size] fp32, or NULL: the patch rows the last mvd_vision_preprocess(want_patches)
+ * of the same batch left in the workspace.  last_hidden_out (nullable) [batch][tokens][hidden_size]: the encoder output
+ * before post_layernorm (transformers' last_hidden_state); embeds_out / embeds_norm_out (either nullable) [batch][projection_dim]:
+ * visual_projection(post_layernorm(token 0)) -- get_image_features -- and the same rows L2-normalised.  A missing weight slot
+ * and an unbound or too small workspace return < 0 before anything is launched.  No allocation, no host synchronisation;
+ * everything on `stream`. */
+int mvd_vision_encode(mvd_vision_t* v, const float* pixel_values, int batch, float* last_hidden_out, float* embeds_out,
+                      float* embeds_norm_out, void* stream);
+/* One pooled row per batch element -> [LayerNorm] -> bias-free projection proj_w [proj_dim][hidden_size] fp32 (fp32
+ * accumulation) -> embeds (raw) and embeds_norm (divided by the L2 norm); either output nullable.  row = hidden[b][tok]
+ * (+ delta[b][tok] when delta is given).  ids NULL: tok = 0 (the image tower: give post_layernorm as ln_gamma / ln_beta).  ids
+ * [batch][tokens] int32 (the text tower: hidden = mvd_text_encode's output, already behind final_layer_norm, ln NULL): tok =
+ * the argmax of the ids when eos_token_id == 2 (transformers' legacy rule), else the first position equal to eos_token_id
+ * (0 when there is none), found on the device.  Two launches: one workgroup per (row, 64 output features), then the L2
+ * normalisation of embeds_norm in place (skipped without it).  hidden_size % 4 == 0; hidden_size, proj_dim <= 2048. */
+int mvd_op_clip_pool_project(const float* hidden, const float* delta, const int32_t* ids, int batch, int tokens, int hidden_size,
+                             int eos_token_id, const float* ln_gamma, const float* ln_beta, float eps, const float* proj_w, int proj_dim,
+                             float* embeds, float* embeds_norm, void* stream);
+/* per_row_out[b] = sum_c a[b][c] b[b][c] and mean_out[0] = their mean (either nullable): the cosine of L2-normalised rows.
+ * One workgroup, sums in a fixed order, the mean finished in fp64: two launches give the same bits.  The caller applies
+ * CLIPScore's 100 x and max(., 0). */
+int mvd_op_clip_cosine(const float* a, const float* b, int batch, int dim, float* per_row_out, float* mean_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

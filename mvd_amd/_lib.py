@@ -74,6 +74,13 @@ class mvd_text_config_t(C.Structure):
     ]
 
 
+class mvd_vision_config_t(C.Structure):
+    _fields_ = [
+        ("image_size", C.c_int), ("patch_size", C.c_int), ("hidden_size", C.c_int), ("intermediate_size", C.c_int),
+        ("num_layers", C.c_int), ("num_heads", C.c_int), ("projection_dim", C.c_int), ("layer_norm_eps", C.c_float), ("act", C.c_int),
+    ]
+
+
 class mvd_forward_args_t(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("height", C.c_int), ("width", C.c_int), ("text_len", C.c_int),
@@ -183,6 +190,18 @@ _SIGS = {
     "mvd_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_attention_causal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "mvd_vision_create": (C.c_int, [C.POINTER(mvd_vision_config_t), C.POINTER(C.c_void_p)]),
+    "mvd_vision_destroy": (C.c_int, [C.c_void_p]),
+    "mvd_vision_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mvd_vision_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvd_vision_bind_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "mvd_vision_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_vision_patch_rows_offset": (C.c_int64, [C.c_void_p]),
+    "mvd_vision_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_clip_pool_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_clip_cosine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

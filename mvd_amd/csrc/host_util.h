@@ -1,7 +1,7 @@
-// Host-side plumbing shared by the three schedules (engine.hip, vae.hip, text.hip) and the operator-level entry points:
+// Host-side plumbing shared by the schedules (engine.hip, vae.hip, text.hip / vision.hip) and the operator-level entry points:
 // weight slots, the bump arena, activations, the two shapes of MvdGemmArgs and the tiled launch with its reduce pass.
 // What is NOT here is routing: which kernel family a problem goes to differs per schedule on purpose (the VAE never takes
-// the small-M kernels, text asks mvd_gemm_sm_plan first, the engine adds the xs / ws / up4 / two-stream policy).
+// the small-M kernels, the CLIP towers (clip_layer.h) ask mvd_gemm_sm_plan first, the engine adds the xs / ws / up4 / two-stream policy).
 #pragma once
 #include <stdio.h>
 #include <string.h>

@@ -12,6 +12,7 @@
 // launch of its own and no epilogue mode of the GEMM kernels changes.  fc1 writes fp32 pre-activations, one pass applies
 // GELU (erf) / quick-GELU and rounds to the bf16 operand of fc2.  Per layer: add+LN, QKV GEMM, causal attention,
 // out-projection, add+LN, fc1, activation, fc2 = 8 launches (plus in-kernel split-K where the small-M planner asks for it).
+// The layer schedule and its two elementwise kernels live in clip_layer.h, shared with the image tower (vision.hip).
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -19,15 +20,9 @@
 #include <string>
 #include <unordered_map>
 
-#include "host_util.h"
+#include "clip_layer.h"     // add + LayerNorm, the activation pass and the layer schedule, shared with vision.hip
 
 namespace {
-
-int tcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
 
 // ---------------------------------------------------------------- embedding gather + position add
 // one wave per row, 16-byte loads; the id is clamped for address safety only (range validation is the caller's, host side)
@@ -41,69 +36,6 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int* __restrict__
   const f32x4* pp = reinterpret_cast<const f32x4*>(pos + (size_t)(row % T) * H);
   f32x4* xp = reinterpret_cast<f32x4*>(x + (size_t)row * H);
   for (int c = lane; c < H / 4; c += 64) xp[c] = tp[c] + pp[c];
-}
-
-// ---------------------------------------------------------------- residual add + LayerNorm
-// x[row] += delta[row] (fp32, in place; delta may be null), then y = LN(x) as bf16 (y_bf) or fp32 (y_f32).  One wave per
-// row, the row in registers (H <= 2048), two-pass variance.
-constexpr int LN_MAXCH = 8;     // float4 chunks per lane
-__global__ __launch_bounds__(256) void text_add_ln_kernel(float* __restrict__ x, const float* __restrict__ delta, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, int rows, int H, float eps, bf16_t* __restrict__ y_bf,
-                                                          float* __restrict__ y_f32) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const int nch = H / 4;
-  f32x4* xp = reinterpret_cast<f32x4*>(x + (size_t)row * H);
-  const f32x4* dp = delta ? reinterpret_cast<const f32x4*>(delta + (size_t)row * H) : nullptr;
-  f32x4 v[LN_MAXCH];
-  float sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < LN_MAXCH; ++c) {
-    const int ch = c * 64 + lane;
-    v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (ch < nch) {
-      v[c] = xp[ch];
-      if (dp) { v[c] += dp[ch]; xp[ch] = v[c]; }
-      sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
-    }
-  }
-  const float mean = wave_sum(sum) / (float)H;
-  float sq = 0.f;
-#pragma unroll
-  for (int c = 0; c < LN_MAXCH; ++c) {
-    if (c * 64 + lane < nch) {
-      const f32x4 d = v[c] - mean;
-      sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)H + eps);
-#pragma unroll
-  for (int c = 0; c < LN_MAXCH; ++c) {
-    const int ch = c * 64 + lane;
-    if (ch < nch) {
-      const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[ch], b = reinterpret_cast<const f32x4*>(beta)[ch];
-      const f32x4 r = (v[c] - mean) * rstd * g + b;
-      if (y_f32) reinterpret_cast<f32x4*>(y_f32 + (size_t)row * H)[ch] = r;
-      else {
-        const u32x2 o = {pack2bf(r[0], r[1]), pack2bf(r[2], r[3])};
-        reinterpret_cast<u32x2*>(y_bf + (size_t)row * H)[ch] = o;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------- activation pass: fp32 pre-activations -> bf16
-// act 0: gelu (erf form), 1: quick_gelu = x * sigmoid(1.702 x).  8 elements per thread (2 x 16-byte loads, one 16-byte store).
-MVD_DEVINL float text_act(float x, int act) {
-  return act ? x / (1.0f + __expf(-1.702f * x)) : 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-}
-__global__ __launch_bounds__(256) void text_act_kernel(const float* __restrict__ x, long n8, int act, bf16_t* __restrict__ y) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n8) return;
-  const f32x4 a = reinterpret_cast<const f32x4*>(x)[2 * i], b = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
-  const u32x4 o = {pack2bf(text_act(a[0], act), text_act(a[1], act)), pack2bf(text_act(a[2], act), text_act(a[3], act)),
-                   pack2bf(text_act(b[0], act), text_act(b[1], act)), pack2bf(text_act(b[2], act), text_act(b[3], act))};
-  reinterpret_cast<u32x4*>(y)[i] = o;
 }
 
 // ---------------------------------------------------------------- causal attention, n <= 96 keys, d = 64
@@ -262,104 +194,33 @@ struct mvd_text {
 
 namespace {
 
-struct TCtx {
-  mvd_text* t;
-  hipStream_t s;
-  bool dry;
-  bool check_w = true;        // false (sizing only): weight slots are not looked at
-  Arena ar;                   // activations (ar.base: behind the split-K tile counters)
-  unsigned int* cnt_base = nullptr;
-  int cnt_used = 0;
-  int err = 0;
-
-  template <class T> T* alloc(size_t n) { return ar.alloc_n<T>(n); }
-  const void* W(const std::string& name, int dtype, int64_t numel) { return check_w ? t->w.find(name, dtype, numel, &err, "text: ") : nullptr; }
-  const bf16_t* WB(const std::string& n, int64_t numel) { return (const bf16_t*)W(n, 1, numel); }
-  const float* WF(const std::string& n, int64_t numel) { return (const float*)W(n, 0, numel); }
-
-  // out[M][N] = a[M][K] . w[N][K]^T + bias: the small-M kernels (split-K combined in the kernel) where their planner takes
-  // the shape, else the tiled kernels (+ split-K reduce) -- the same routing as the UNet engine's
-  int linear(const bf16_t* a, int K, int M, const bf16_t* w, const float* bias, int N, void* out, bool out_f32) {
-    if (err) return err;
-    MvdGemmArgs g = gemm_dense(a, nullptr, K, 0, M, w, 0, bias, N, out, N);
-    g.ldres = N; g.out_f32 = out_f32 ? 1 : 0;
-    const size_t mark = ar.off;
-    int r = 0;
-    int tile = 0, ns = 0, S = 1;
-    if (mvd_gemm_sm_plan(g, &tile, &ns, &S)) {
-      if (S > 1) {
-        g.splitk = S; g.part = alloc<float>((size_t)S * M * N);
-        g.tile_cnt = cnt_base + cnt_used;
-        cnt_used += ((M + 63) / 64) * (N / 64);       // (an upper bound for every tile shape)
-      }
-      if (!dry) r = mvd_launch_gemm_sm(g, s, tile, ns);
-    } else {
-      S = mvd_gemm_pick_splitk(g);
-      if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * M * N); } else g.splitk = 1;
-      if (!dry) r = launch_tiled(g, s);
-    }
-    ar.off = mark;
-    return r;
-  }
-  int add_ln(float* x, const float* delta, const float* g, const float* b, int rows, int H, bf16_t* y_bf, float* y_f32) {
-    if (err) return err;
-    if (dry) return 0;
-    hipLaunchKernelGGL(text_add_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, delta, g, b, rows, H, t->cfg.layer_norm_eps, y_bf, y_f32);
-    return tcheck("text add+layernorm");
-  }
-};
-
-size_t cnt_bytes(int cnt) { return ((size_t)cnt * 4 + 255) & ~size_t(255); }
-
 // dry: sizes only (x.ar.high, x.cnt_used); otherwise `cnt` = the counter words the dry run asked for
 int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream_t s, bool dry, int cnt, size_t* high_out, int* cnt_out,
                 bool check_w = true) {
   const mvd_text_config_t& c = t->cfg;
   const int H = c.hidden_size, I = c.intermediate_size, M = B * T;
-  TCtx x{t, s, dry};
+  ClipCtx x{&t->w, "text: ", c.layer_norm_eps, s, dry};
   x.check_w = check_w; x.ar.dry = dry;
   if (!dry) {
     x.cnt_base = reinterpret_cast<unsigned int*>(t->ws_ptr);
     x.ar.base = reinterpret_cast<char*>(t->ws_ptr) + cnt_bytes(cnt);
     if (cnt > 0 && hipMemsetAsync(x.cnt_base, 0, (size_t)cnt * 4, s) != hipSuccess) { mvd_set_error("text_encode: hipMemsetAsync failed"); return -3; }
   }
-  float* xs = x.alloc<float>((size_t)M * H);          // residual stream
-  float* dl = x.alloc<float>((size_t)M * H);          // fp32 result of the projection that feeds it
-  bf16_t* h = x.alloc<bf16_t>((size_t)M * H);
-  bf16_t* qkv = x.alloc<bf16_t>((size_t)M * 3 * H);
-  bf16_t* at = x.alloc<bf16_t>((size_t)M * H);
-  float* f1 = x.alloc<float>((size_t)M * I);
-  bf16_t* g1 = x.alloc<bf16_t>((size_t)M * I);
+  ClipBufs b;
+  b.alloc(x, M, H, I);
   const float* tok = x.WF("tok", (int64_t)c.vocab_size * H);
   const float* pos = x.WF("pos", (int64_t)c.max_positions * H);
   if (x.err) return x.err;
   if (!dry) {
-    hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, tok, pos, M, T, H, c.vocab_size, xs);
+    hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, tok, pos, M, T, H, c.vocab_size, b.xs);
     CHECK(tcheck("text embedding"));
   }
-  for (int l = 0; l < c.num_layers; ++l) {
-    const std::string p = "layers." + std::to_string(l);
-    const float *g1w = x.WF(p + ".ln1.g", H), *b1w = x.WF(p + ".ln1.b", H), *g2w = x.WF(p + ".ln2.g", H), *b2w = x.WF(p + ".ln2.b", H);
-    const bf16_t *wqkv = x.WB(p + ".qkv.w", (int64_t)3 * H * H), *wo = x.WB(p + ".out.w", (int64_t)H * H);
-    const bf16_t *w1 = x.WB(p + ".fc1.w", (int64_t)I * H), *w2 = x.WB(p + ".fc2.w", (int64_t)H * I);
-    const float *bqkv = x.WF(p + ".qkv.b", 3 * H), *bo = x.WF(p + ".out.b", H), *bf1 = x.WF(p + ".fc1.b", I), *bf2 = x.WF(p + ".fc2.b", H);
-    if (x.err) return x.err;
-    CHECK(x.add_ln(xs, l ? dl : nullptr, g1w, b1w, M, H, h, nullptr));
-    CHECK(x.linear(h, H, M, wqkv, bqkv, 3 * H, qkv, false));
-    if (!dry) CHECK(launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s));   // q rows prescaled at pack time
-    CHECK(x.linear(at, H, M, wo, bo, H, dl, true));
-    CHECK(x.add_ln(xs, dl, g2w, b2w, M, H, h, nullptr));
-    CHECK(x.linear(h, H, M, w1, bf1, I, f1, true));
-    if (!dry) {
-      const long n8 = (long)M * I / 8;
-      hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, f1, n8, c.act, g1);
-      CHECK(tcheck("text activation"));
-    }
-    CHECK(x.linear(g1, I, M, w2, bf2, H, dl, true));
-  }
+  CHECK(clip_layers(x, b, c.num_layers, H, I, M, c.act, [&](const bf16_t* qkv, bf16_t* at) {
+    return launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s);   // q rows prescaled at pack time
+  }));
   const float *gf = x.WF("final_ln.g", H), *bf = x.WF("final_ln.b", H);
   if (x.err) return x.err;
-  CHECK(x.add_ln(xs, c.num_layers ? dl : nullptr, gf, bf, M, H, nullptr, out));
+  CHECK(x.add_ln(b.xs, c.num_layers ? b.dl : nullptr, gf, bf, M, H, nullptr, out));
   if (high_out) *high_out = x.ar.high;
   if (cnt_out) *cnt_out = x.cnt_used;
   return x.err;

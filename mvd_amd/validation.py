@@ -16,8 +16,9 @@ no fallback.  Two behaviours of the reference are kept on purpose (DESIGN.md sec
     latents from ``scheduler``'s.
 
 One behaviour is NOT kept: the reference wraps its auxiliary block in ``try / except`` and reports zeros when anything in it
-raises; here the exception reaches the caller.  LPIPS, the VGG perceptual loss, CLIP score and FID need pretrained networks
-this project does not ship: they are accepted as callables / metric objects and called the way the reference calls them.
+raises; here the exception reaches the caller.  LPIPS, the VGG perceptual loss and FID need pretrained networks this project
+does not ship: they are accepted as callables / metric objects and called the way the reference calls them.  So is a CLIP
+score object of another library; ``mvd_amd.clip_score.CLIPScore`` (row N7) takes the fused route ``image_similarity``.
 """
 from __future__ import annotations
 
@@ -121,6 +122,9 @@ def _clip_score(metric, denoised, target, device, zero):
     object's own processor and model)."""
     if metric is None:
         return zero
+    from .clip_score import CLIPScore
+    if isinstance(metric, CLIPScore):       # this project's metric: quantise + preprocess + encode + cosine on its own kernels
+        return metric.to(device).image_similarity(denoised, target)
     metric = metric.to(device)
     if not hasattr(metric, "model") or not hasattr(metric, "processor"):
         return zero
