@@ -153,7 +153,11 @@ int mvd_engine_apply_modulation(mvd_engine_t* e, const char* name, const float* 
 int mvd_engine_get_camera_embedding(mvd_engine_t* e, float* out, void* stream);
 
 /* ---- operator-level entry points (same kernels the engine schedules; used by tests) -- */
-/* out[M][N] = alpha*(A[M][K] . W[N][K]^T + bias + rowvec[m/rows_per_batch]) + res ; bf16 A/W/res */
+/* out[M][N] = alpha*(A[M][K] . W[N][K]^T + bias + rowvec[m/rows_per_batch]) + res ; bf16 A/W/res
+ * Rounding contract: the sum and the whole epilogue are fp32 and the result is rounded ONCE, to nearest even, when it is stored
+ * as bf16 (out_f32: not at all) -- in every tile config, the split-K forms (separate reduce and in-kernel combine), the small-M
+ * kernels with either weight layout, the X-stationary form and the convolutions below; no form adds res, bias or rowvec behind
+ * a rounding.  tests/test_exact_gemm_gpu.py and tests/test_exact_conv_gpu.py compare bitwise against exactly this order. */
 int mvd_op_linear(const void* a, const void* a2, int k1, int k2, const void* w, const float* bias, const float* rowvec,
                   int ld_rowvec, int rows_per_batch, const void* res, float alpha, int geglu, void* out, int out_f32,
                   int m, int n, int force_cfg, int splitk, float* splitk_ws /* splitk*m*n floats when splitk > 1 */,

@@ -30,14 +30,26 @@ def _bf16(*ts):
             assert t.dtype == torch.bfloat16, "expected bf16"
 
 
+def _blocked(w, blocked, k, force_cfg):
+    """``blocked=(n, k)``: ``w`` holds packing.block_weight of the [n][k] weight (the small-M kernels' LDS-image layout, read
+    with force_cfg + 1000).  Returns (n, force_cfg)."""
+    if blocked is None:
+        return w.shape[0], force_cfg
+    n, kb = blocked
+    assert kb == k and w.numel() == n * k and n % 32 == 0 and k % 64 == 0, (tuple(w.shape), blocked, k)
+    assert force_cfg >= 100, "the blocked weight layout is read by the small-M kernels only (force_cfg = 100 + 10 * tile + depth)"
+    return n, force_cfg + 1000
+
+
 def linear(a, w, bias=None, a2=None, rowvec=None, rows_per_batch=0, res=None, alpha=1.0, geglu=False,
-           out_f32=False, force_cfg=-1, splitk=1):
-    """out = alpha*( [a|a2] @ w.T + bias + rowvec[row // rows_per_batch] ) + res"""
+           out_f32=False, force_cfg=-1, splitk=1, blocked=None):
+    """out = alpha*( [a|a2] @ w.T + bias + rowvec[row // rows_per_batch] ) + res.  ``blocked=(n, k)``: ``w`` is
+    packing.block_weight of the [n][k] weight (small-M kernels only)."""
     _bf16(a, a2, w, res)
     m, k1 = a.shape
     k2 = a2.shape[1] if a2 is not None else 0
-    n = w.shape[0]
-    assert w.shape[1] == k1 + k2
+    assert blocked is not None or w.shape[1] == k1 + k2
+    n, force_cfg = _blocked(w, blocked, k1 + k2, force_cfg)
     on = n // 2 if geglu else n
     out = torch.empty(m, on, device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
     # (+ 4096 words: the tile counters of the small-M kernels' in-kernel split-K combine, MVD_OP_SPLITK_COUNTERS)
@@ -93,12 +105,14 @@ def conv3x3_ws(x, w_packed, bias, n, rowvec=None, res=None, shortcut=None, short
 
 
 def conv3x3(x, w_packed, bias=None, stride=1, upsample=False, rowvec=None, res=None, shortcut=None,
-            shortcut2=None, force_cfg=-1, splitk=1, asym_pad=False):
+            shortcut2=None, force_cfg=-1, splitk=1, asym_pad=False, blocked=None):
     """x: (B,H,W,Cin) bf16; w_packed: (Cout, 9*Cin [+ Csc]) bf16 tap-major.  asym_pad (stride 2): zero padding on the
-    bottom/right edge only (the VAE's Downsample2D(padding=0))."""
+    bottom/right edge only (the VAE's Downsample2D(padding=0)).  ``blocked=(n, k)``: ``w_packed`` is packing.block_weight of
+    the [n][k] packed weight (small-M kernels only)."""
     _bf16(x, w_packed, res, shortcut, shortcut2)
     B, H, W, Cin = x.shape
-    cout = w_packed.shape[0]
+    ktot = 9 * Cin + (shortcut.shape[-1] if shortcut is not None else 0) + (shortcut2.shape[-1] if shortcut2 is not None else 0)
+    cout, force_cfg = _blocked(w_packed, blocked, ktot, force_cfg)
     oh = H * 2 if upsample else (H + 1) // 2 if stride == 2 else H
     ow = W * 2 if upsample else (W + 1) // 2 if stride == 2 else W
     out = torch.empty(B, oh, ow, cout, device=x.device, dtype=torch.bfloat16)
@@ -355,6 +369,23 @@ def nchw_to_nhwc(x, scale=None, shift=None):
     B, c, H, W = x.shape
     y = torch.empty(B, H, W, c, device=x.device, dtype=torch.bfloat16)
     L.call("mvd_op_nchw_to_nhwc", _p(x), B, c, H * W, _p(scale), _p(shift), _p(y), _s())
+    return y
+
+
+def nhwc_to_nchw(x):
+    """x (B, H, W, C) bf16 -> (B, C, H, W) fp32 (the engine's output layout change)."""
+    _bf16(x)
+    B, H, W, c = x.shape
+    y = torch.empty(B, c, H, W, device=x.device, dtype=torch.float32)
+    L.call("mvd_op_nhwc_to_nchw", _p(x), B, H * W, c, _p(y), _s())
+    return y
+
+
+def f32_to_bf16(x):
+    """fp32 tensor -> bf16 of the same shape, round to nearest even."""
+    assert x.dtype == torch.float32
+    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    L.call("mvd_op_f32_to_bf16", _p(x), x.numel(), _p(y), _s())
     return y
 
 
