@@ -466,6 +466,47 @@ int mvd_op_clip_pool_project(const float* hidden, const float* delta, const int3
  * CLIPScore's 100 x and max(., 0). */
 int mvd_op_clip_cosine(const float* a, const float* b, int batch, int dim, float* per_row_out, float* mean_out, void* stream);
 
+/* ---- VGG-16 perceptual loss for checkpoint validation --------------------------------------- */
+/* Replaces: PerceptualLoss of the reference (src/training/losses.py:21-56): torchvision's vgg16().features[:29] on both image
+ * batches and the mean squared difference of the two conv5_3 maps.  Thirteen 3x3 pad-1 convolutions (features.0, 2, 5, 7, 10,
+ * 12, 14, 17, 19, 21, 24, 26, 28) with a ReLU behind all but the last, 2x2 max-pools at features.4, 9, 16, 23.
+ * Weight slots: "features.N.weight" bf16 in the packed conv layout [cout][cin/64][ky][kx][64] ("features.0.weight": [64][64],
+ * column tap * 3 + channel, zero padded from 27), "features.N.bias" fp32 [cout] (mvd_amd/perceptual.py packs a torchvision state
+ * dict).  A slot that is missing when a pass runs is error -10, one of another dtype or size -11. */
+typedef struct mvd_vgg mvd_vgg_t;
+int mvd_vgg_create(mvd_vgg_t** out);
+int mvd_vgg_destroy(mvd_vgg_t* v);
+int mvd_vgg_set_weight(mvd_vgg_t* v, const char* slot, const void* ptr, int64_t numel, int dtype);
+/* bytes for one feature pass over `images` images of h x w (a loss pass over images / 2 pairs), the internal fp32 feature
+ * buffer included; found by a dry run of the schedule.  h, w >= 16; images * h * w must stay below 2^31 rows. */
+int64_t mvd_vgg_workspace_bytes(mvd_vgg_t* v, int images, int h, int w);
+int mvd_vgg_bind_workspace(mvd_vgg_t* v, void* ws, int64_t bytes);
+/* images_nchw [images][3][h][w] fp32 in [-1, 1], as PerceptualLoss receives them: (x + 1) / 2, then Normalize(ImageNet mean,
+ * std), folded into one affine map per channel in front of conv1_1 (the padding of conv1_1 stays zero).  feat_out_nhwc [images]
+ * [h / 16][w / 16][512] fp32: features.28's output, not rounded to bf16.  taps: NULL, or four nullable bf16 NHWC buffers that
+ * receive relu1_2 [images][h][w][64], relu2_2 [h/2][w/2][128], relu3_3 [h/4][w/4][256], relu4_3 [h/8][w/8][512] -- the maps in
+ * front of the pools.  Pools drop an odd trailing row / column.  No allocation, no host synchronisation; everything on `stream`. */
+int mvd_vgg_features(mvd_vgg_t* v, const float* images_nchw, int images, int h, int w, float* feat_out_nhwc, void* const* taps, void* stream);
+/* loss_out[0] = mean over pairs and elements of (f(x) - f(y))^2, per_pair_out[p] (nullable) = the mean of pair p; x, y [pairs][3]
+ * [h][w] fp32 in [-1, 1].  As many pairs per pass as the bound workspace holds (one pair must fit: -4 otherwise); x and y of a
+ * pair are rows of the same launches, so x == y gives exactly 0.  Sums in fp64 in a fixed order: two calls, same bits. */
+int mvd_vgg_perceptual(mvd_vgg_t* v, const float* x, const float* y, int pairs, int h, int w, float* loss_out, float* per_pair_out, void* stream);
+/* The tower's operators one by one.  conv3x3_relu: mvd_op_conv3x3 restricted to stride 1, no shortcut, row vector or residual,
+ * plus relu (out = max(acc + bias, 0) before the one rounding) and out_f32, on the lock-step tiles only (force_cfg -1, 2..5,
+ * 10..13; relu = 1: tiles 3, 4, 5 / 11, 12, 13); splitk > 1 needs splitk * M * cout floats of splitk_ws.  linear_relu: the same
+ * epilogue behind a dense out[m][n] = a[m][k] . w[n][k]^T + bias (k, n multiples of 64). */
+int mvd_op_conv3x3_relu(const void* x, int batch, int in_h, int in_w, int cin, const void* w, const float* bias, void* out, int cout, int relu,
+                        int out_f32, int force_cfg, int splitk, float* splitk_ws, void* stream);
+int mvd_op_linear_relu(const void* a, int k, const void* w, const float* bias, void* out, int m, int n, int relu, int out_f32, int force_cfg,
+                       int splitk, float* splitk_ws, void* stream);
+/* NHWC bf16 [batch][h][w][c] -> [batch][h / 2][w / 2][c], 2x2 windows, stride 2 (floor); c a multiple of 8 */
+int mvd_op_maxpool2x2(const void* x, int batch, int h, int w, int c, void* y, void* stream);
+/* a, b [pairs][n] fp32 (n a multiple of 4): per_pair_out[p] = mean_i (a[p][i] - b[p][i])^2, mean_out[0] = the mean over everything
+ * (either nullable).  fp64 sums in a fixed order, no atomics.  ws: the bytes the _ws_bytes query gives, 256-byte aligned. */
+int64_t mvd_op_sqdiff_mean_ws_bytes(int pairs, int64_t n);
+int mvd_op_sqdiff_mean(const float* a, const float* b, int pairs, int64_t n, float* mean_out, float* per_pair_out, void* ws, int64_t ws_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

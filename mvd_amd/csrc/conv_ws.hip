@@ -292,7 +292,7 @@ static int ws_variant(const MvdWsArgs& a) {
 }
 
 bool mvd_conv_ws_applicable(const MvdWsArgs& a) {
-  if (!a.x || !a.w || !a.bias || !a.out || a.B <= 0 || a.H <= 0 || a.W <= 0) return false;
+  if (!a.x || !a.w || !a.bias || !a.out || a.B <= 0 || a.H <= 0 || a.W <= 0 || a.relu) return false;
   const int hw = (a.ups ? 4 : 1) * a.H * a.W;
   if (a.M != a.B * hw || a.M > 1024 || !ws_variant(a)) return false;
   if (a.ups && (a.scc0 || a.scc1)) return false;

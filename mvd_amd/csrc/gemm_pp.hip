@@ -771,6 +771,7 @@ bool mvd_gemm_pp_applicable(const MvdGemmArgs& a) {
   constexpr int BM = 256;
   const size_t lim = (size_t)1 << 31;
   if (a.N % BN || a.Ktot % 64 || a.out_f32) return false;      // (fp32 outputs exist at M = batch only: gemm.hip)
+  if (a.relu) return false;                                     // (no ReLU epilogue here: the lock-step tiles of gemm.hip have it)
   if ((size_t)a.N * a.ldw * 2 >= lim) return false;
   if ((size_t)(a.M + BM) * a.ldo * 2 >= lim || (a.res && (size_t)(a.M + BM) * a.ldres * 2 >= lim)) return false;
   if (a.splitk > 1 && (size_t)(a.M + BM) * a.N * 4 >= lim) return false;

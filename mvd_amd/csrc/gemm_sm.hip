@@ -527,6 +527,7 @@ bool mvd_gemm_sm_applicable(const MvdGemmArgs& a, int tile) {
   if (tile < 0 || tile >= kNumSmTiles) return false;
   const size_t lim = (size_t)1 << 31;
   if (a.N % kSmTiles[tile].bn || a.Ktot % 64) return false;
+  if (a.relu) return false;          // (no ReLU epilogue here: the lock-step tiles of gemm.hip have it)
   if (a.ln_c1) {   // LayerNorm fold: one dense source spanning the whole row, a bias (c2), no residual / row vector / split-K
     const MvdASeg& g = a.seg[0];
     if (a.nseg != 1 || g.mode != MVD_A_DENSE || g.c1 || a.splitk > 1 || a.res || a.rowvec || a.out_f32 || !a.bias || a.Ktot != g.c0) return false;

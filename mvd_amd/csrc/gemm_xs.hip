@@ -395,7 +395,7 @@ int launch_xs(const MvdXsArgs& a, hipStream_t s) {
 
 bool mvd_gemm_xs_applicable(const MvdXsArgs& a) {
   const size_t lim = (size_t)1 << 31;
-  if (a.K != 320 || a.units <= 0 || a.M <= 0) return false;
+  if (a.K != 320 || a.units <= 0 || a.M <= 0 || a.relu) return false;
   if (a.units % (a.geglu ? 4 : 2)) return false;        // store groups: two units = 128 bytes per token (GEGLU: gate | value | gate | value)
   if ((a.geglu || a.ln) && a.res) return false;
   if ((size_t)(a.M + 256) * a.ldx * 2 >= lim || (size_t)(a.M + 256) * a.ldo * 2 >= lim) return false;

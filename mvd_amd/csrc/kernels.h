@@ -53,6 +53,10 @@ struct MvdGemmArgs {
   unsigned int* tile_cnt; // gemm_sm.hip split-K only: one ZEROED word per output tile (arrival count in bits 0-7, one claim bit per
                           // share above: the slices combine the partials in the kernel, no reduce launch; splitk <= 24)
   int dbg;                // probe builds only (-DMVD_PROBE, env MVD_GEMM_DEBUG): bit0 skip the output stores, bit1 skip the MFMAs
+  int relu;               // 1: out = max(alpha*(acc + bias + rowvec) + res, 0) before the one rounding: the lock-step tiles 3, 4, 5 of
+                          // gemm.hip (compile-time variants; no kernel reads this field) and the split-K reduce pass; every other
+                          // kernel family refuses it.  It sits in what was alignment padding in front of ln_c1, so the struct's
+                          // size -- and with it the hidden-argument offsets every shipped GEMM kernel reads -- stays what it was
   // LayerNorm fold (ping-pong kernels only, see mvd_gemm_ln_fold_ok): A holds the UN-normalised rows x, W holds
   // W.diag(gamma), ln_c1[n] = sum_k W[n][k] (of the bf16 values), bias[n] = sum_k beta[k].W0[n][k] + b[n]; the kernel
   // accumulates the row sums / sums of squares of the A fragments it multiplies and its epilogue applies
@@ -64,9 +68,14 @@ struct MvdGemmArgs {
   // group's weight panels stay in the XCD's L2 while the rows stream past (short-K GEMMs whose W exceeds the 4 MB L2)
   int walk_cg;
 };
+static_assert(sizeof(MvdGemmArgs) == 280, "MvdGemmArgs is a kernel argument: a size change moves the hidden arguments of every GEMM kernel");
 
 int mvd_launch_gemm(const MvdGemmArgs& a, hipStream_t s, int force_cfg = -1);
 int mvd_gemm_pick_config(const MvdGemmArgs& a);   // tile config the heuristic gives this problem
+// gemm_relu.hip: the ReLU forms (a.relu == 1) of tile configs 3, 4, 5, unsplit, and the reduce pass of a split ReLU launch;
+// called by mvd_launch_gemm / mvd_launch_splitk_reduce, which validate the arguments
+int mvd_launch_gemm_relu(const MvdGemmArgs& a, hipStream_t s, int cfg, bool glds);
+int mvd_launch_splitk_reduce_relu(const MvdGemmArgs& a, hipStream_t s, int grid);
 // what the calling thread's last mvd_launch_gemm launched (tests assert that the persistent multi-tile path ran)
 struct MvdLaunchPlan { int cfg, splitk, tiles, grid, per_cu, nowait; };
 extern thread_local MvdLaunchPlan g_mvd_last_gemm;
@@ -101,6 +110,7 @@ struct MvdXsArgs {
   const bf16_t* res; int ldres; // residual [M][ldres] bf16 or null (not with geglu)
   bf16_t* out; int ldo;
   int csplit;                   // column parts per row block (<= 0: mvd_gemm_xs_pick_csplit)
+  int relu;                     // must be 0: the kernel has no ReLU form (mvd_gemm_xs_applicable refuses it)
 };
 bool mvd_gemm_xs_applicable(const MvdXsArgs& a);
 int mvd_gemm_xs_pick_csplit(const MvdXsArgs& a);
@@ -119,6 +129,7 @@ struct MvdWsArgs {
   bf16_t* out; int ldo;
   int M, N;                                   // M = output pixels = B * H * W (x 4 with ups)
   int variant;                                // 0: the launcher's choice; 1 / 2: force 64- / 128-pixel blocks (tests, probes; conv_ws.hip)
+  int relu;                                   // must be 0: the kernel has no ReLU form (mvd_conv_ws_applicable refuses it)
 };
 bool mvd_conv_ws_applicable(const MvdWsArgs& a);
 size_t mvd_conv_ws_packed_elems(int C, int sc, int N);
@@ -188,6 +199,8 @@ int mvd_launch_im2col_in(const float* x, int batch, int c, int h, int w, const f
 // fp32 -> bf16 copy
 int mvd_launch_f32_to_bf16(const float* x, int64_t n, bf16_t* y, hipStream_t s);
 int mvd_launch_nhwc_to_nchw_f32(const bf16_t* x, int batch, int hw, int c, float* y, hipStream_t s);
+// 2x2 max-pool, stride 2, floor: NHWC bf16 [batch][h][w][c] -> [batch][h/2][w/2][c]; c % 8 == 0, h, w >= 2 (vgg.hip)
+int mvd_launch_maxpool2x2(const bf16_t* x, int batch, int h, int w, int c, bf16_t* y, hipStream_t s);
 
 // skinny fp32 linear: y[b][n] = act_out( sum_k act_in(x[b][k]) * W[n][k] + bias[n] ), b < 256
 // W is fp32 (wbf16 == 0) or bf16 (wbf16 == 1).  act: 0 none, 1 SiLU

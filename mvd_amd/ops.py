@@ -138,6 +138,58 @@ def conv3x3_up4(x, w4, bias=None, force_cfg=-1):
     return out
 
 
+def conv3x3_relu(x, w_packed, bias=None, relu=True, out_f32=False, force_cfg=-1, splitk=1):
+    """The VGG tower's convolution (gemm_relu.hip): x (B, H, W, Cin) bf16, w_packed (Cout, 9 * Cin) bf16 in the packed conv
+    layout; stride 1, padding 1; out = max(conv + bias, 0) (``relu``) rounded once to bf16, or kept in fp32 (``out_f32``).  The
+    lock-step tiles only: force_cfg -1, 3 / 4 / 5 (register staging) or 11 / 12 / 13 (LDS-DMA)."""
+    _bf16(x, w_packed)
+    B, H, W, Cin = x.shape
+    cout = w_packed.shape[0]
+    assert w_packed.shape[1] == 9 * Cin, (tuple(w_packed.shape), Cin)
+    out = torch.empty(B, H, W, cout, device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    ws = torch.empty(splitk * B * H * W * cout, device=x.device, dtype=torch.float32) if splitk > 1 else None
+    L.call("mvd_op_conv3x3_relu", _p(x), B, H, W, Cin, _p(w_packed), _p(bias), _p(out), cout, int(relu), int(out_f32), force_cfg,
+           splitk, _p(ws), _s())
+    return out
+
+
+def linear_relu(a, w, bias=None, relu=True, out_f32=False, force_cfg=-1, splitk=1):
+    """out = max(a @ w.T + bias, 0) on the lock-step tiles (conv1_1 of the VGG tower runs this way over im2col rows)."""
+    _bf16(a, w)
+    m, k = a.shape
+    n = w.shape[0]
+    assert w.shape[1] == k
+    out = torch.empty(m, n, device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    ws = torch.empty(splitk * m * n, device=a.device, dtype=torch.float32) if splitk > 1 else None
+    L.call("mvd_op_linear_relu", _p(a), k, _p(w), _p(bias), _p(out), m, n, int(relu), int(out_f32), force_cfg, splitk, _p(ws), _s())
+    return out
+
+
+def maxpool2x2(x, out=None):
+    """x (B, H, W, C) bf16, C % 8 == 0 -> (B, H // 2, W // 2, C): 2x2 windows, stride 2, an odd trailing row / column dropped.
+    ``out``: a buffer whose first B * (H // 2) * (W // 2) * C elements are written."""
+    _bf16(x)
+    B, H, W, c = x.shape
+    if out is None:
+        out = torch.empty(B, H // 2, W // 2, c, device=x.device, dtype=torch.bfloat16)
+    L.call("mvd_op_maxpool2x2", _p(x), B, H, W, c, _p(out), _s())
+    return out
+
+
+def sqdiff_mean(a, b, per_pair=False):
+    """a, b (pairs, ...) fp32: (mean of (a - b)^2 over everything as a 0-d device tensor, per-pair means (pairs,) or None); fp64
+    sums in a fixed order."""
+    _f32_same(a, b)
+    pairs = a.shape[0]
+    n = a.numel() // pairs
+    nbytes = L.check(L.lib().mvd_op_sqdiff_mean_ws_bytes(pairs, n), "mvd_op_sqdiff_mean_ws_bytes")
+    ws = torch.empty(nbytes, device=a.device, dtype=torch.uint8)
+    mean = torch.empty((), device=a.device, dtype=torch.float32)
+    pp = torch.empty(pairs, device=a.device, dtype=torch.float32) if per_pair else None
+    L.call("mvd_op_sqdiff_mean", _p(a), _p(b), pairs, n, _p(mean), _p(pp), _p(ws), nbytes, _s())
+    return mean, pp
+
+
 def up4_launches() -> int:
     """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
     return int(L.lib().mvd_debug_up4_launches())

@@ -328,3 +328,49 @@ def pack_camera(sd: Dict[str, torch.Tensor], device, num_levels: int = 4) -> Dic
         out["cam.modcat.g1"], out["cam.modcat.be1"] = _f32(cat(1, "weight"), device), _f32(cat(1, "bias"), device)
         out["cam.modcat.w3"], out["cam.modcat.b3"] = _f32(cat(3, "weight"), device), _f32(cat(3, "bias"), device)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- VGG-16 (perceptual loss, row N8)
+# torchvision's vgg16().features[:29]: (index, cin, cout) of the thirteen 3x3 pad-1 convolutions; a ReLU follows every one but
+# the last (features.28), a 2x2 max-pool sits at VGG16_POOLS (behind relu1_2, relu2_2, relu3_3, relu4_3)
+VGG16_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
+               (17, 256, 512), (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512))
+VGG16_POOLS = (4, 9, 16, 23)
+VGG16_PARAMS = 14_714_688          # over the 26 tensors
+
+
+def normalize_vgg_keys(sd) -> Dict[str, torch.Tensor]:
+    """A torchvision ``vgg16`` state dict (``features.N.*``; ``classifier.*`` and anything else is ignored) or the one of the
+    sliced ``Sequential`` (``N.*``) -> the 26 tensors as ``features.N.weight`` / ``features.N.bias``.  A missing key or a wrong
+    shape raises ``MvdError``."""
+    from ._lib import MvdError
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"VGG-16 weights: expected a state dict, got {type(sd).__name__}")
+    out = {}
+    for idx, cin, cout in VGG16_CONVS:
+        for leaf, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+            t = sd.get(f"features.{idx}.{leaf}", sd.get(f"{idx}.{leaf}"))
+            if t is None:
+                raise MvdError(f"VGG-16 weights: key 'features.{idx}.{leaf}' (or '{idx}.{leaf}') is missing")
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise MvdError(f"VGG-16 weights: 'features.{idx}.{leaf}' has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+            out[f"features.{idx}.{leaf}"] = t
+    return out
+
+
+def pack_vgg_conv(w: torch.Tensor) -> torch.Tensor:
+    """[cout][cin][3][3] -> the packed fp32 [cout][K] of one tower convolution: the implicit-GEMM layout [cin/64][ky][kx][64] of
+    ``_conv_w``, or for conv1_1 (cin = 3) the im2col order of ``im2col_in_kernel``, column tap * 3 + channel, zero padded 27 -> 64."""
+    if w.shape[1] == 3:
+        return torch.nn.functional.pad(_conv_w(w, tap_major=True), (0, 64 - 27))
+    return _conv_w(w)
+
+
+def pack_vgg(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """``mvd_vgg_set_weight`` slots: ``features.N.weight`` bf16 (``pack_vgg_conv``), ``features.N.bias`` fp32."""
+    sd = normalize_vgg_keys(sd)
+    out = {}
+    for idx, _, _ in VGG16_CONVS:
+        out[f"features.{idx}.weight"] = _bf(pack_vgg_conv(sd[f"features.{idx}.weight"]), device)
+        out[f"features.{idx}.bias"] = _f32(sd[f"features.{idx}.bias"], device)
+    return out
