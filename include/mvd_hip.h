@@ -507,6 +507,56 @@ int64_t mvd_op_sqdiff_mean_ws_bytes(int pairs, int64_t n);
 int mvd_op_sqdiff_mean(const float* a, const float* b, int pairs, int64_t n, float* mean_out, float* per_pair_out, void* ws, int64_t ws_bytes,
                        void* stream);
 
+/* ---- LPIPS v0.1 for checkpoint validation ---------------------------------------------------- */
+/* Replaces: lpips.LPIPS(net="alex") of the reference's val.py:87.  The tower is torchvision's alexnet().features[:12]: conv
+ * 3->64 11x11 stride 4 pad 2 (features.0), conv 64->192 5x5 pad 2 (features.3), conv 192->384, 384->256, 256->256 3x3 pad 1
+ * (features.6, .8, .10), a ReLU behind each (the five taps), a 3x3 stride-2 max-pool behind the first two.  In front of it the
+ * scaling layer (x - shift) / scale, shift (-.030, -.088, -.188), scale (.458, .448, .450); behind it, per tap, the maps divided
+ * by their channel norm (+ 1e-10), the squared difference weighted by lin_k >= 0, the mean over pixels; the sum over the taps.
+ * Weight slots: "features.0.weight" bf16 [64][384], column (ky * 11 + kx) * 3 + c, zero padded from 363; "features.3.weight"
+ * bf16 [192][1600], column (ky * 5 + kx) * 64 + c; "features.{6,8,10}.weight" bf16 in the packed conv layout [cout][cin/64]
+ * [ky][kx][64]; "features.N.bias" fp32 [cout]; "lin{0..4}.weight" fp32 [C] (mvd_amd/lpips.py packs torchvision / lpips state
+ * dicts).  A slot that is missing when a pass runs is error -10, one of another dtype or size -11; nothing is launched then. */
+typedef struct mvd_lpips mvd_lpips_t;
+int mvd_lpips_create(mvd_lpips_t** out);
+int mvd_lpips_destroy(mvd_lpips_t* v);
+int mvd_lpips_set_weight(mvd_lpips_t* v, const char* slot, const void* ptr, int64_t numel, int dtype);
+/* bytes for one pass over `images` images of h x w (a distance pass over images / 2 pairs), the five taps and the head's partial
+ * sums included; found by a dry run of the schedule (no GPU needed); never smaller than the bytes of a pass over fewer images of the
+ * same size.  h, w >= 31: below that the second pool has no output. */
+int64_t mvd_lpips_workspace_bytes(mvd_lpips_t* v, int images, int h, int w);
+int mvd_lpips_bind_workspace(mvd_lpips_t* v, void* ws, int64_t bytes);
+/* images_nchw [images][3][h][w] fp32 in [-1, 1].  taps: five bf16 NHWC buffers (an entry may be NULL: that map stays in the
+ * workspace) for the post-ReLU maps [images][h1][w1][64], [h2][w2][192], [h3][w3][384], [h3][w3][256], [h3][w3][256] with
+ * h1 = (h - 7) / 4 + 1, h2 = (h1 - 3) / 2 + 1, h3 = (h2 - 3) / 2 + 1 -- the maps in front of the pools.  No allocation, no host
+ * synchronisation; everything on `stream`. */
+int mvd_lpips_features(mvd_lpips_t* v, const float* images_nchw, int images, int h, int w, void* const* taps, void* stream);
+/* per_pair_out[p] = d(x[p], y[p]); per_layer_out (nullable) [pairs][5] = the five terms of each; mean_out (nullable) = the mean
+ * over the pairs (one of per_pair_out / mean_out must be given); x, y [pairs][3][h][w] fp32 in [-1, 1].  max_pairs_per_pass pairs
+ * per pass (<= 0: no cap), fewer where the bound workspace holds fewer (one pair must fit: -4 otherwise); every pass that will run,
+ * the shorter last one included, is sized by a dry run before anything is launched.  The pass size decides the split-K of the
+ * convolutions and with it the last bits of the result: give the same cap to get the same bits.  x and y of a pair are rows of
+ * the same launches, so x == y gives exactly 0.  Sums in fp64 in a fixed order: two calls, same bits. */
+int mvd_lpips_distance(mvd_lpips_t* v, const float* x, const float* y, int pairs, int h, int w, int max_pairs_per_pass, float* per_pair_out,
+                       float* per_layer_out, float* mean_out, void* stream);
+/* The new operators one by one.  im2col_patch, form 0: src fp32 NCHW [batch][3][h][w] -> rows [batch * oh * ow][384] bf16 of the
+ * 11x11 stride-4 pad-2 windows, oh = (h - 7) / 4 + 1, column (ky * 11 + kx) * 3 + c, columns 363.. zero; scale / shift: HOST
+ * arrays of three floats (both or neither), applied as x * scale[c] + shift[c] to in-image taps only.  Form 1: src bf16 NHWC
+ * [batch][h][w][64] -> rows [batch * h * w][1600] of the 5x5 pad-2 windows, column (ky * 5 + kx) * 64 + c (no affine map). */
+int mvd_op_im2col_patch(const void* src, int form, int batch, int h, int w, const float* scale, const float* shift, void* rows_out, void* stream);
+/* NHWC bf16 [batch][h][w][c] -> [batch][(h - 3) / 2 + 1][(w - 3) / 2 + 1][c], 3x3 windows, stride 2, no padding (floor); c a
+ * multiple of 8, h, w >= 3 */
+int mvd_op_maxpool3x3s2(const void* x, int batch, int h, int w, int c, void* y, void* stream);
+/* The LPIPS head over `layers` <= 8 layers in ONE launch (+ a one-workgroup finish).  Layer l: x[l], y[l] [pairs][pixels[l]]
+ * [channels[l]] of dtype[l] (1 bf16, 0 fp32; relu_in[l] = 1 applies max(., 0) to an fp32 map on the way in), lin_w[l] fp32
+ * [channels[l]] >= 0; channels a multiple of 64.  per_pair_out[p] = sum_l mean_pixels sum_c w_c (x_c / |x| - y_c / |y|)^2,
+ * per_layer_out (nullable) [pairs][layers] the terms, mean_out (nullable) the mean over pairs.  A pixel of zeros on both sides
+ * contributes exactly 0.  fp64 sums in a fixed order, no atomics.  ws: the bytes the _ws_bytes query gives, 256-byte aligned. */
+int64_t mvd_op_lpips_head_ws_bytes(int layers, const int* pixels, int pairs);
+int mvd_op_lpips_head(int layers, const void* const* x, const void* const* y, const int* dtype, const int* relu_in, const int* pixels, const int* channels,
+                      const float* const* lin_w, int pairs, float* per_pair_out, float* per_layer_out, float* mean_out, void* ws, int64_t ws_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,21 @@ _SIGS = {
     "mvd_op_maxpool2x2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_sqdiff_mean_ws_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "mvd_op_sqdiff_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvd_lpips_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "mvd_lpips_destroy": (C.c_int, [C.c_void_p]),
+    "mvd_lpips_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mvd_lpips_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mvd_lpips_bind_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "mvd_lpips_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mvd_lpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "mvd_op_im2col_patch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                      C.c_void_p]),
+    "mvd_op_maxpool3x3s2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_op_lpips_head_ws_bytes": (C.c_int64, [C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "mvd_op_lpips_head": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

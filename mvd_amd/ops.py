@@ -190,6 +190,46 @@ def sqdiff_mean(a, b, per_pair=False):
     return mean, pp
 
 
+def im2col_patch(src, scale=None, shift=None, out=None):
+    """The im2col rows of the AlexNet front ends (lpips.hip).  ``src`` fp32 (B, 3, H, W): the 11x11 stride-4 pad-2 windows,
+    (B * oh * ow, 384) bf16 with oh = (H - 7) // 4 + 1, column (ky * 11 + kx) * 3 + c, columns 363.. zero; ``scale`` / ``shift``
+    (three floats each) are applied as x * scale[c] + shift[c] to in-image taps only.  ``src`` bf16 (B, H, W, 64): the 5x5 pad-2
+    windows, (B * H * W, 1600), column (ky * 5 + kx) * 64 + c.  ``out``: a buffer whose first rows * columns elements are written."""
+    if src.dtype == torch.float32:
+        B, c, H, W = src.shape
+        assert c == 3
+        rows, cols, form = B * ((H - 7) // 4 + 1) * ((W - 7) // 4 + 1), 384, 0
+    else:
+        _bf16(src)
+        B, H, W, c = src.shape
+        assert c == 64 and scale is None
+        rows, cols, form = B * H * W, 1600, 1
+    if out is None:
+        out = torch.empty(rows, cols, device=src.device, dtype=torch.bfloat16)
+    f3 = lambda v: None if v is None else (C.c_float * 3)(*[float(e) for e in v])      # noqa: E731
+    L.call("mvd_op_im2col_patch", _p(src), form, B, H, W, f3(scale), f3(shift), _p(out), _s())
+    return out
+
+
+def maxpool3x3s2(x, out=None):
+    """x (B, H, W, C) bf16, C % 8 == 0 -> (B, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C): 3x3 windows, stride 2, no padding.
+    ``out``: a buffer whose first output elements are written."""
+    _bf16(x)
+    B, H, W, c = x.shape
+    if out is None:
+        out = torch.empty(B, (H - 3) // 2 + 1, (W - 3) // 2 + 1, c, device=x.device, dtype=torch.bfloat16)
+    L.call("mvd_op_maxpool3x3s2", _p(x), B, H, W, c, _p(out), _s())
+    return out
+
+
+def lpips_head(xs, ys, lin_w, relu_in=None, per_layer=False, mean=False):
+    """The LPIPS head over up to 8 layers in one launch: see ``mvd_amd.lpips.lpips_head`` -> (per-pair (pairs,) -- ``mean``: their
+    mean, 0-d, with no per-pair output -- , per-layer (pairs, layers) or None)."""
+    from .lpips import lpips_head as head
+    d, dl, _ = head(xs, ys, lin_w, relu_in=relu_in, per_layer=per_layer, mean=mean)
+    return d, dl
+
+
 def up4_launches() -> int:
     """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
     return int(L.lib().mvd_debug_up4_launches())

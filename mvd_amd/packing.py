@@ -374,3 +374,86 @@ def pack_vgg(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
         out[f"features.{idx}.weight"] = _bf(pack_vgg_conv(sd[f"features.{idx}.weight"]), device)
         out[f"features.{idx}.bias"] = _f32(sd[f"features.{idx}.bias"], device)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- LPIPS (AlexNet / VGG-16 backbones, row N9)
+# torchvision's alexnet().features[:12]: (index, cin, cout, kernel, stride, padding) of the five convolutions; a ReLU follows
+# every one (the five LPIPS taps, at index + 1), a 3x3 stride-2 max-pool sits at ALEX_POOLS
+ALEX_CONVS = ((0, 3, 64, 11, 4, 2), (3, 64, 192, 5, 1, 2), (6, 192, 384, 3, 1, 1), (8, 384, 256, 3, 1, 1), (10, 256, 256, 3, 1, 1))
+ALEX_POOLS = (2, 5)
+ALEX_TAP_CHANNELS = (64, 192, 384, 256, 256)
+ALEX_CONV1_COLS = 384              # 11 * 11 * 3 = 363 columns of the im2col rows, zero padded to a multiple of 64
+# the taps of the VGG variant: relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 of vgg16().features[:30]
+VGG_LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+
+
+def normalize_backbone_keys(sd, convs, what: str) -> Dict[str, torch.Tensor]:
+    """The convolutions ``convs`` ((index, cin, cout, kernel, ...) or (index, cin, cout) with kernel 3) out of a state dict under
+    torchvision's keys (``features.N.*``), those of the sliced ``Sequential`` (``N.*``) or lpips' (``net.sliceK.N.*``; a full
+    ``lpips.LPIPS`` state dict carries them beside the linear heads) -> ``features.N.weight`` / ``features.N.bias``.  A missing key
+    or a wrong shape raises ``MvdError``."""
+    import re
+    from ._lib import MvdError
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"{what} weights: expected a state dict, got {type(sd).__name__}")
+    found = {}
+    for key in sd.keys():
+        m = re.match(r"^(?:features\.|net\.slice\d+\.)?(\d+)\.(weight|bias)$", key)
+        if m:
+            found[(int(m.group(1)), m.group(2))] = sd[key]
+    out = {}
+    for conv in convs:
+        idx, cin, cout = conv[:3]
+        k = conv[3] if len(conv) > 3 else 3
+        for leaf, shape in (("weight", (cout, cin, k, k)), ("bias", (cout,))):
+            t = found.get((idx, leaf))
+            if t is None:
+                raise MvdError(f"{what} weights: key 'features.{idx}.{leaf}' (or '{idx}.{leaf}', 'net.sliceK.{idx}.{leaf}') is missing")
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise MvdError(f"{what} weights: 'features.{idx}.{leaf}' has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+            out[f"features.{idx}.{leaf}"] = t
+    return out
+
+
+def normalize_lpips_lin_keys(sd, channels, what: str = "LPIPS") -> Dict[str, torch.Tensor]:
+    """lpips' linear heads (``lin{k}.model.1.weight`` or ``lins.{k}.model.1.weight``, shape (1, C, 1, 1)) -> ``lin{k}.weight`` fp32
+    (C,).  A negative weight raises ``MvdError``: the shipped heads have none, and the head kernel's contract is w >= 0."""
+    from ._lib import MvdError
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"{what} linear heads: expected a state dict, got {type(sd).__name__}")
+    out = {}
+    for k, c in enumerate(channels):
+        t = sd.get(f"lin{k}.model.1.weight", sd.get(f"lins.{k}.model.1.weight"))
+        if t is None:
+            raise MvdError(f"{what} linear heads: key 'lin{k}.model.1.weight' (or 'lins.{k}.model.1.weight') is missing")
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (1, c, 1, 1):
+            raise MvdError(f"{what} linear heads: 'lin{k}.model.1.weight' has shape {tuple(getattr(t, 'shape', ()))}, expected {(1, c, 1, 1)}")
+        t = t.detach().float().reshape(c)
+        if bool((t < 0).any()):
+            raise MvdError(f"{what} linear heads: 'lin{k}.model.1.weight' has a negative weight ({float(t.min()):.3e}); the head takes w >= 0 only")
+        out[f"lin{k}.weight"] = t
+    return out
+
+
+def pack_alex_conv(w: torch.Tensor) -> torch.Tensor:
+    """[cout][cin][k][k] -> the packed fp32 [cout][K] of one AlexNet convolution: conv1 (11x11) and conv2 (5x5) in the im2col
+    order of ``im2col_patch_*_kernel``, column (ky * k + kx) * cin + c (conv1 zero padded 363 -> 384); the 3x3 ones in the
+    implicit-GEMM layout [cin/64][ky][kx][64] of ``_conv_w``."""
+    if w.shape[2] == 3:
+        return _conv_w(w)
+    flat = w.detach().float().permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    return torch.nn.functional.pad(flat, (0, -flat.shape[1] % 64))
+
+
+def pack_alex(backbone: Dict[str, torch.Tensor], lins: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """``mvd_lpips_set_weight`` slots: ``features.N.weight`` bf16 (``pack_alex_conv``), ``features.N.bias`` fp32, ``lin{k}.weight`` fp32"""
+    sd = normalize_backbone_keys(backbone, ALEX_CONVS, "AlexNet")
+    out = {}
+    for conv in ALEX_CONVS:
+        idx = conv[0]
+        out[f"features.{idx}.weight"] = _bf(pack_alex_conv(sd[f"features.{idx}.weight"]), device)
+        out[f"features.{idx}.bias"] = _f32(sd[f"features.{idx}.bias"], device)
+    for k in range(5):
+        out[f"lin{k}.weight"] = _f32(lins[f"lin{k}.weight"], device)
+    return out
