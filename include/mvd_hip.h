@@ -232,6 +232,10 @@ int mvd_gemm_num_configs(void);
  * persistent multi-tile path (work items > workgroups) is what ran at the benchmarked shapes. */
 int mvd_debug_last_gemm_plan(int* out);
 int mvd_debug_last_attention_plan(int* out);
+/* The calling thread's last GroupNorm launch, out[6].  One-pass slice kernel: {1, vectors per thread of the instantiation
+ * (2, 4, 8, 16 or 21), threads, groups per workgroup, pixels per pass, 0}; two-kernel form: {2, rows in flight of the
+ * statistics kernel, its threads, chunks per image, rows per chunk, rows per block of the apply kernel}. */
+int mvd_debug_last_groupnorm_plan(int* out);
 /* Launches of the 2x2 sub-pixel upsampling convolution by this process so far (read the difference across a forward). */
 long mvd_debug_up4_launches(void);
 /* 1 when the calling thread's last small-M split-K launch used the no-wait combine (requested, or chosen because the grid

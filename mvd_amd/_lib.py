@@ -152,6 +152,7 @@ _SIGS = {
                                      C.c_void_p]),
     "mvd_debug_last_gemm_nowait": (C.c_int, []),
     "mvd_debug_last_attention_plan": (C.c_int, [C.POINTER(C.c_int)]),
+    "mvd_debug_last_groupnorm_plan": (C.c_int, [C.POINTER(C.c_int)]),
     "mvd_debug_pick_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_debug_pick_splitk_conv": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvd_gemm_sm_num_tiles": (C.c_int, []),

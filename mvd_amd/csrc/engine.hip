@@ -1454,7 +1454,10 @@ int mvd_op_ln_linear(const void* x, int k, const void* w_folded, const float* c1
   if (!c1 || !c2) { mvd_set_error("mvd_op_ln_linear: c1 and c2 are required"); return -1; }
   if (!mvd_gemm_ln_fold_ok(g)) {
     int tile = 0, ns = 0, S = 1;           // small problems (batch 1): the fold of the small-M kernels
-    if (mvd_gemm_sm_plan(g, &tile, &ns, &S) && S == 1) return mvd_launch_gemm_sm(g, (hipStream_t)stream, tile, ns);
+    if (mvd_gemm_sm_plan(g, &tile, &ns, &S) && S == 1) {
+      g_mvd_last_gemm.cfg = 100 + 10 * tile + ns; g_mvd_last_gemm.splitk = 1;    // as mvd_launch_gemm records a forced small-M launch
+      return mvd_launch_gemm_sm(g, (hipStream_t)stream, tile, ns);
+    }
     mvd_set_error("mvd_op_ln_linear: M=%d N=%d K=%d geglu=%d is not a shape of the fused LayerNorm GEMMs", m, n, k, geglu);
     return -1;
   }

@@ -482,6 +482,9 @@ __global__ __launch_bounds__(256) void ln_f32_kernel(const float* __restrict__ x
 
 }  // namespace
 
+// what the calling thread's last mvd_launch_groupnorm launched: {form, ...} as mvd_debug_last_groupnorm_plan documents
+static thread_local int g_last_gn[6] = {0, 0, 0, 0, 0, 0};
+
 static int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
@@ -515,7 +518,9 @@ static bool launch_gn_slice(const bf16_t* x0, const bf16_t* x1, int c0, int c1, 
   const long min_wg = (mvd_debug_flags() & MVD_DBG_GN_ONE_PASS) ? 8 : 128;
   if (slice_bytes > 96 * 1024 && nwg < min_wg) return false;
   const dim3 grid((unsigned)nwg), blk((unsigned)threads);
-#define GN_SLICE(NVT) hipLaunchKernelGGL(gn_slice_kernel<NVT>, grid, blk, 0, s, x0, x1, c0, c1, batch, hw, groups, gpw, eps, gamma, beta, silu, y)
+  g_last_gn[0] = 1; g_last_gn[2] = threads; g_last_gn[3] = gpw; g_last_gn[4] = threads / nvec; g_last_gn[5] = 0;
+#define GN_SLICE(NVT) do { g_last_gn[1] = NVT; \
+    hipLaunchKernelGGL(gn_slice_kernel<NVT>, grid, blk, 0, s, x0, x1, c0, c1, batch, hw, groups, gpw, eps, gamma, beta, silu, y); } while (0)
   if (nv <= 2) GN_SLICE(2); else if (nv <= 4) GN_SLICE(4); else if (nv <= 8) GN_SLICE(8); else if (nv <= 16) GN_SLICE(16); else GN_SLICE(21);
 #undef GN_SLICE
   return true;
@@ -564,9 +569,19 @@ int mvd_launch_groupnorm(const bf16_t* x0, const bf16_t* x1, int c0, int c1, int
   if (rows_per_blk > hw) rows_per_blk = hw;
   const int nblk = (hw + rows_per_blk - 1) / rows_per_blk;
   const size_t sh2 = (size_t)(2 * groups + 2 * C) * sizeof(float);
+  g_last_gn[0] = 2; g_last_gn[1] = R; g_last_gn[2] = threads; g_last_gn[3] = nchunk; g_last_gn[4] = rpc; g_last_gn[5] = rows_per_blk;
   hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, batch), dim3(256), sh2, s, x0, x1, c0, c1, hw, groups, nchunk, rpc, eps, gamma,
                      beta, silu, ws, rows_per_blk, y);
   return check_launch("gn_apply");
+}
+
+// out[6] of the calling thread's last GroupNorm launch.  One-pass slice kernel: {1, NV (vectors per thread of the instantiation),
+// threads, groups per workgroup, pixels per pass, 0}; two-kernel form: {2, R (rows in flight of the statistics kernel), its
+// threads, chunks per image, rows per chunk, rows per block of the apply kernel}
+extern "C" int mvd_debug_last_groupnorm_plan(int* out) {
+  if (!out) { mvd_set_error("last_groupnorm_plan: null argument"); return -1; }
+  for (int i = 0; i < 6; ++i) out[i] = g_last_gn[i];
+  return 0;
 }
 
 int mvd_launch_layernorm(const bf16_t* x, int rows, int c, float eps, const float* gamma, const float* beta, bf16_t* y,

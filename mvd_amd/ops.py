@@ -494,6 +494,19 @@ def last_attention_plan():
     return dict(waves=out[0], workgroups=out[1])
 
 
+def last_groupnorm_plan():
+    """This thread's last GroupNorm launch.  One-pass slice kernel: dict(form="slice", nv, threads, gpw, npl) -- the instantiation's
+    vectors per thread, groups per workgroup, pixels per pass; two-kernel form: dict(form="two_kernel", R, threads, nchunk,
+    rows_per_chunk, apply_rows) -- rows in flight of gn_stats, its chunks per image, and gn_apply's rows per block."""
+    out = (C.c_int * 6)()
+    L.call("mvd_debug_last_groupnorm_plan", out)
+    if out[0] == 1:
+        return dict(form="slice", nv=out[1], threads=out[2], gpw=out[3], npl=out[4])
+    if out[0] == 2:
+        return dict(form="two_kernel", R=out[1], threads=out[2], nchunk=out[3], rows_per_chunk=out[4], apply_rows=out[5])
+    return dict(form="none")
+
+
 def engine_splitk(m, n, k, geglu=False, conv=False):
     """The split-K factor the engine's schedule uses for this GEMM (or, ``conv=True``, 3x3 convolution) size."""
     if conv:
