@@ -561,6 +561,54 @@ int mvd_op_lpips_head(int layers, const void* const* x, const void* const* y, co
                       const float* const* lin_w, int pairs, float* per_pair_out, float* per_layer_out, float* mean_out, void* ws, int64_t ws_bytes,
                       void* stream);
 
+/* ---- FID: Inception-v3 pool3 features and their statistics, for checkpoint validation ---------- */
+/* Replaces: the network inside torchmetrics' FrechetInceptionDistance(feature=2048) of the reference's val.py -- the FID variant
+ * of Inception-v3 (torch-fidelity's FeatureExtractorInceptionV3, pytorch-fid's pt_inception-2015-12-05) up to pool3.
+ * The layer table lives in ONE place, mvd_amd/packing.py INCEPTION_FID_LAYERS; mvd_fid_create receives it compiled into a
+ * program: n_ops records of 13 ints {kind (0 conv, 1 3x3 pool), src buffer, dst buffer, c_off (first channel written in dst),
+ * cin (all channels of src), cout, kh, kw, stride, pad_h, pad_w, conv index (0, 1, ... in program order), pool mode}; n_buffers
+ * records {channels, is_fp32}: buffer 0 is the front end's output (299 x 299, 16 channels: r, g, b, zeros), final_buffer the fp32
+ * map whose mean over the pixels is the feature vector (channels a multiple of 64).  conv_names[k]: convolution k reads the
+ * weight slots "<name>.weight" bf16 [cout][kh kw][cin rounded up to 32] (BatchNorm folded, the padding zeros) and "<name>.bias"
+ * fp32 [cout].  max_images_per_pass (0: 8) is the pass size: more images run as several passes within one call, whatever earlier
+ * calls left bound.  K is never split and its order is fixed: an image's features do not depend on the batch it is part of. */
+typedef struct mvd_fid mvd_fid_t;
+int mvd_fid_create(const int* program, int n_ops, const int* buffers, int n_buffers, const char* const* conv_names, int n_convs, int final_buffer,
+                   int max_images_per_pass, mvd_fid_t** out);
+int mvd_fid_destroy(mvd_fid_t* v);
+int mvd_fid_set_weight(mvd_fid_t* v, const char* slot, const void* ptr, int64_t numel, int dtype);
+int mvd_fid_feature_dim(mvd_fid_t* v);
+/* bytes for a call over `images` images of any size (the tower always runs at 299 x 299): a dry run of the schedule over one pass
+ * of min(images, max_images_per_pass) images plus the feature rows of mvd_fid_update; never smaller for more images. */
+int64_t mvd_fid_workspace_bytes(mvd_fid_t* v, int images);
+int mvd_fid_bind_workspace(mvd_fid_t* v, void* ws, int64_t bytes);
+/* images [n][3][h][w], dtype 0: uint8, 1: fp32 in [0, 1] (quantised as trunc(clamp(x, 0, 1) * 255)) -> feat_out [n][D] fp32.
+ * Weights (-10 / -11) and every pass size that will run, the shorter last one included (-4), are checked before anything is
+ * launched.  No allocation, no host synchronisation; everything on `stream`. */
+int mvd_fid_features(mvd_fid_t* v, const void* images, int dtype, int n, int h, int w, float* feat_out, void* stream);
+/* the same, then sum[D] += sum_i f_i and cov_sum[D][D] += sum_i f_i f_i^T in fp64 (mvd_op_feature_stats over all n rows at once) */
+int mvd_fid_update(mvd_fid_t* v, const void* images, int dtype, int n, int h, int w, double* sum, double* cov_sum, void* stream);
+/* The new operators one by one.  conv_relu_slice: x bf16 NHWC [batch][h][w][ld_in], channels [cin_off, cin_off + cin) ->
+ * out[batch][oh][ow][ld_out], channels [c_off, c_off + cout) = max(conv + bias, 0), rounded once (bf16, or fp32 with out_f32);
+ * nothing outside the slice is written.  (kh, kw) one of 1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1; stride 1 or 2; oh = (h + 2 pad_h -
+ * kh) / stride + 1; taps outside the image are exact zeros.  w_packed as above.  Every channel count, offset and row stride is a
+ * multiple of 16.  bf16 MFMA, fp32 accumulation over K = kh kw cin in (ky, kx, c) order, no split-K. */
+int mvd_op_conv_relu_slice(const void* x, int batch, int h, int w, int ld_in, int cin_off, int cin, const void* w_packed, const float* bias, int kh, int kw,
+                           int stride, int pad_h, int pad_w, int cout, void* out, int ld_out, int c_off, int out_f32, void* stream);
+/* 3x3 pool of channels [cin_off, cin_off + c) of x bf16 NHWC into channels [c_off, c_off + c) of out.  mode 0: average, stride
+ * 1, pad 1, over the in-image taps only (fp32 sum in tap order, a true division by their count, one rounding); 1: maximum,
+ * stride 1, pad 1; 2: maximum, stride 2, no padding, floor.  Multiples of 8 channels. */
+int mvd_op_pool3x3_slice(const void* x, int batch, int h, int w, int ld_in, int cin_off, int c, int mode, void* out, int ld_out, int c_off, void* stream);
+/* the front end: src [batch][3][h][w] (dtype as above) -> out bf16 NHWC [batch][299][299][16], channels 3.. zero: TF1-legacy
+ * bilinear resize (src = dst * float32(in / out), i0 = floor, i1 = min(i0 + 1, in - 1), top = tl + (tr - tl) wx, out = top +
+ * (bot - top) wy, every operation rounded as written), then (v - 128) / 128 */
+int mvd_op_resize_tf1(const void* src, int dtype, int batch, int h, int w, void* out, void* stream);
+/* x fp32 [batch][pixels][c] -> out[batch][c] = (sum over the pixels in order) / pixels */
+int mvd_op_global_mean(const float* x, int batch, int pixels, int c, float* out, void* stream);
+/* f fp32 [n][d], d a multiple of 64: sum[d] += sum_i f_i, cov_sum[d][d] += sum_i f_i f_i^T, converted to fp64 first, on
+ * v_mfma_f64_16x16x4_f64 with the images as K (zero padded to a multiple of 4), in image order; no atomics. */
+int mvd_op_feature_stats(const float* f, int n, int d, double* sum, double* cov_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

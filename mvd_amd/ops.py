@@ -230,6 +230,69 @@ def lpips_head(xs, ys, lin_w, relu_in=None, per_layer=False, mean=False):
     return d, dl
 
 
+def conv_relu_slice(x, w_packed, bias, kh, kw, stride=1, pad=(0, 0), cin_off=0, cin=None, out=None, c_off=0, out_f32=False):
+    """``mvd_op_conv_relu_slice`` (fid.hip): channels [cin_off, cin_off + cin) of x (B, H, W, ld_in) bf16 -> max(conv + bias, 0) in
+    channels [c_off, c_off + cout) of ``out`` (B, oh, ow, ld_out), bf16 or (``out_f32``) fp32; ``out=None``: a buffer of cout
+    channels.  w_packed (cout, kh * kw * cin_pad) bf16 (``packing.pack_slice_conv``), bias (cout,) fp32."""
+    _bf16(x, w_packed)
+    B, H, W, ld_in = x.shape
+    cin = ld_in - cin_off if cin is None else cin
+    cout = w_packed.shape[0]
+    assert w_packed.shape[1] == kh * kw * ((cin + 31) // 32 * 32) and bias.dtype == torch.float32 and bias.numel() == cout
+    oh, ow = (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
+    if out is None:
+        out = torch.empty(B, oh, ow, cout, device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16) and tuple(out.shape[:3]) == (B, oh, ow)
+    L.call("mvd_op_conv_relu_slice", _p(x), B, H, W, ld_in, cin_off, cin, _p(w_packed), _p(bias), kh, kw, stride, pad[0], pad[1], cout, _p(out),
+           out.shape[3], c_off, int(out_f32), _s())
+    return out
+
+
+POOL3_MODES = {"avg": 0, "max1": 1, "max2": 2}
+
+
+def pool3x3_slice(x, mode, cin_off=0, c=None, out=None, c_off=0):
+    """``mvd_op_pool3x3_slice``: 3x3 pool of channels [cin_off, cin_off + c) of x (B, H, W, ld_in) bf16 into channels [c_off, c_off + c)
+    of ``out``.  mode "avg": stride 1, pad 1, the mean over the in-image taps; "max1": stride 1, pad 1; "max2": stride 2, no padding."""
+    _bf16(x)
+    B, H, W, ld_in = x.shape
+    c = ld_in - cin_off if c is None else c
+    oh, ow = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == "max2" else (H, W)
+    if out is None:
+        out = torch.empty(B, oh, ow, c, device=x.device, dtype=torch.bfloat16)
+    _bf16(out)
+    assert tuple(out.shape[:3]) == (B, oh, ow)
+    L.call("mvd_op_pool3x3_slice", _p(x), B, H, W, ld_in, cin_off, c, POOL3_MODES[mode], _p(out), out.shape[3], c_off, _s())
+    return out
+
+
+def resize_tf1(images):
+    """``mvd_op_resize_tf1``: (B, 3, H, W) uint8, or fp32 in [0, 1] (quantised as trunc(clamp(x, 0, 1) * 255)) -> (B, 299, 299, 16)
+    bf16: the TF1-legacy bilinear resize, (v - 128) / 128, channels 3.. zero."""
+    assert images.dtype in (torch.uint8, torch.float32) and images.dim() == 4 and images.shape[1] == 3
+    B, _, H, W = images.shape
+    out = torch.empty(B, 299, 299, 16, device=images.device, dtype=torch.bfloat16)
+    L.call("mvd_op_resize_tf1", _p(images), int(images.dtype == torch.float32), B, H, W, _p(out), _s())
+    return out
+
+
+def global_mean(x):
+    """x (B, pixels..., C) fp32 -> (B, C): the sum over the pixels in order, divided by their number"""
+    assert x.dtype == torch.float32
+    B, c = x.shape[0], x.shape[-1]
+    out = torch.empty(B, c, device=x.device, dtype=torch.float32)
+    L.call("mvd_op_global_mean", _p(x), B, x.numel() // (B * c), c, _p(out), _s())
+    return out
+
+
+def feature_stats(f, total, cov_sum):
+    """``mvd_op_feature_stats``: f (n, d) fp32, d % 64 == 0; in place total (d,) += sum_i f_i, cov_sum (d, d) += sum_i f_i f_i^T, fp64"""
+    assert f.dtype == torch.float32 and f.dim() == 2 and total.dtype == torch.float64 and cov_sum.dtype == torch.float64
+    n, d = f.shape
+    assert total.shape == (d,) and cov_sum.shape == (d, d)
+    L.call("mvd_op_feature_stats", _p(f), n, d, _p(total), _p(cov_sum), _s())
+
+
 def up4_launches() -> int:
     """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
     return int(L.lib().mvd_debug_up4_launches())

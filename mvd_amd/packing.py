@@ -16,7 +16,7 @@ One-time host work (torch is used as plumbing for the permutes / casts).  Slot l
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Tuple
 
 
 import torch
@@ -456,4 +456,219 @@ def pack_alex(backbone: Dict[str, torch.Tensor], lins: Dict[str, torch.Tensor], 
         out[f"features.{idx}.bias"] = _f32(sd[f"features.{idx}.bias"], device)
     for k in range(5):
         out[f"lin{k}.weight"] = _f32(lins[f"lin{k}.weight"], device)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- FID: Inception-v3 up to pool3 (row N10)
+# The FID variant of Inception-v3 (torch-fidelity's FeatureExtractorInceptionV3 / pytorch-fid's pt_inception-2015-12-05) as ONE
+# table that the schedule (``fid_program`` -> mvd_fid_create), the packer (``pack_inception_fid``) and the tests' restatement
+# (tests/fid_ref.py) all read.  Entries, in execution order:
+#   ("conv", name, src, dst, c_off, cin, cout, kh, kw, stride, pad_h, pad_w)   BasicConv2d ``name``: conv (no bias) + BN(eps 1e-3) + ReLU
+#   ("pool", mode, src, dst, c_off, c)                                         3x3 pool: "avg" (stride 1, pad 1, count_include_pad=False),
+#                                                                              "max1" (stride 1, pad 1), "max2" (stride 2, no padding)
+# ``src`` is read whole; the result goes to channels [c_off, c_off + cout) of ``dst`` -- a block's output buffer is its
+# concatenation, in torch-fidelity's branch order.  "img" is the front end's output, FID_FEATURE_BUFFER the map pool3 averages.
+FID_INPUT_SIZE = 299
+FID_INPUT_CHANNELS = 16            # the front end writes r, g, b and 13 zero channels: the convolution reads multiples of 16
+FID_BN_EPS = 1e-3
+FID_FEATURE_BUFFER = "Mixed_7c"
+FID_POOL_MODES = {"avg": 0, "max1": 1, "max2": 2}
+
+
+def _inception_fid_layers():
+    T = []
+
+    def conv(name, src, dst, c_off, cin, cout, k=(1, 1), stride=1, pad=(0, 0)):
+        T.append(("conv", name, src, dst, c_off, cin, cout, k[0], k[1], stride, pad[0], pad[1]))
+
+    def pool(mode, src, dst, c_off, c):
+        T.append(("pool", mode, src, dst, c_off, c))
+
+    conv("Conv2d_1a_3x3", "img", "Conv2d_1a", 0, 3, 32, (3, 3), 2)
+    conv("Conv2d_2a_3x3", "Conv2d_1a", "Conv2d_2a", 0, 32, 32, (3, 3))
+    conv("Conv2d_2b_3x3", "Conv2d_2a", "Conv2d_2b", 0, 32, 64, (3, 3), 1, (1, 1))
+    pool("max2", "Conv2d_2b", "MaxPool_1", 0, 64)
+    conv("Conv2d_3b_1x1", "MaxPool_1", "Conv2d_3b", 0, 64, 80)
+    conv("Conv2d_4a_3x3", "Conv2d_3b", "Conv2d_4a", 0, 80, 192, (3, 3))
+    pool("max2", "Conv2d_4a", "MaxPool_2", 0, 192)
+    x = "MaxPool_2"
+    for blk, cin, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):                 # A
+        conv(f"{blk}.branch1x1", x, blk, 0, cin, 64)
+        conv(f"{blk}.branch5x5_1", x, f"{blk}.t5", 0, cin, 48)
+        conv(f"{blk}.branch5x5_2", f"{blk}.t5", blk, 64, 48, 64, (5, 5), 1, (2, 2))
+        conv(f"{blk}.branch3x3dbl_1", x, f"{blk}.t3a", 0, cin, 64)
+        conv(f"{blk}.branch3x3dbl_2", f"{blk}.t3a", f"{blk}.t3b", 0, 64, 96, (3, 3), 1, (1, 1))
+        conv(f"{blk}.branch3x3dbl_3", f"{blk}.t3b", blk, 128, 96, 96, (3, 3), 1, (1, 1))
+        pool("avg", x, f"{blk}.tp", 0, cin)
+        conv(f"{blk}.branch_pool", f"{blk}.tp", blk, 224, cin, pf)
+        x = blk
+    blk = "Mixed_6a"                                                                                            # B
+    conv(f"{blk}.branch3x3", x, blk, 0, 288, 384, (3, 3), 2)
+    conv(f"{blk}.branch3x3dbl_1", x, f"{blk}.t3a", 0, 288, 64)
+    conv(f"{blk}.branch3x3dbl_2", f"{blk}.t3a", f"{blk}.t3b", 0, 64, 96, (3, 3), 1, (1, 1))
+    conv(f"{blk}.branch3x3dbl_3", f"{blk}.t3b", blk, 384, 96, 96, (3, 3), 2)
+    pool("max2", x, blk, 480, 288)
+    x = blk
+    for blk, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):                # C
+        conv(f"{blk}.branch1x1", x, blk, 0, 768, 192)
+        conv(f"{blk}.branch7x7_1", x, f"{blk}.t7a", 0, 768, c7)
+        conv(f"{blk}.branch7x7_2", f"{blk}.t7a", f"{blk}.t7b", 0, c7, c7, (1, 7), 1, (0, 3))
+        conv(f"{blk}.branch7x7_3", f"{blk}.t7b", blk, 192, c7, 192, (7, 1), 1, (3, 0))
+        conv(f"{blk}.branch7x7dbl_1", x, f"{blk}.d1", 0, 768, c7)
+        conv(f"{blk}.branch7x7dbl_2", f"{blk}.d1", f"{blk}.d2", 0, c7, c7, (7, 1), 1, (3, 0))
+        conv(f"{blk}.branch7x7dbl_3", f"{blk}.d2", f"{blk}.d3", 0, c7, c7, (1, 7), 1, (0, 3))
+        conv(f"{blk}.branch7x7dbl_4", f"{blk}.d3", f"{blk}.d4", 0, c7, c7, (7, 1), 1, (3, 0))
+        conv(f"{blk}.branch7x7dbl_5", f"{blk}.d4", blk, 384, c7, 192, (1, 7), 1, (0, 3))
+        pool("avg", x, f"{blk}.tp", 0, 768)
+        conv(f"{blk}.branch_pool", f"{blk}.tp", blk, 576, 768, 192)
+        x = blk
+    blk = "Mixed_7a"                                                                                            # D
+    conv(f"{blk}.branch3x3_1", x, f"{blk}.t3", 0, 768, 192)
+    conv(f"{blk}.branch3x3_2", f"{blk}.t3", blk, 0, 192, 320, (3, 3), 2)
+    conv(f"{blk}.branch7x7x3_1", x, f"{blk}.s1", 0, 768, 192)
+    conv(f"{blk}.branch7x7x3_2", f"{blk}.s1", f"{blk}.s2", 0, 192, 192, (1, 7), 1, (0, 3))
+    conv(f"{blk}.branch7x7x3_3", f"{blk}.s2", f"{blk}.s3", 0, 192, 192, (7, 1), 1, (3, 0))
+    conv(f"{blk}.branch7x7x3_4", f"{blk}.s3", blk, 320, 192, 192, (3, 3), 2)
+    pool("max2", x, blk, 512, 768)
+    x = blk
+    for blk, cin, mode in (("Mixed_7b", 1280, "avg"), ("Mixed_7c", 2048, "max1")):                              # E
+        conv(f"{blk}.branch1x1", x, blk, 0, cin, 320)
+        conv(f"{blk}.branch3x3_1", x, f"{blk}.t3", 0, cin, 384)
+        conv(f"{blk}.branch3x3_2a", f"{blk}.t3", blk, 320, 384, 384, (1, 3), 1, (0, 1))
+        conv(f"{blk}.branch3x3_2b", f"{blk}.t3", blk, 704, 384, 384, (3, 1), 1, (1, 0))
+        conv(f"{blk}.branch3x3dbl_1", x, f"{blk}.d1", 0, cin, 448)
+        conv(f"{blk}.branch3x3dbl_2", f"{blk}.d1", f"{blk}.d2", 0, 448, 384, (3, 3), 1, (1, 1))
+        conv(f"{blk}.branch3x3dbl_3a", f"{blk}.d2", blk, 1088, 384, 384, (1, 3), 1, (0, 1))
+        conv(f"{blk}.branch3x3dbl_3b", f"{blk}.d2", blk, 1472, 384, 384, (3, 1), 1, (1, 0))
+        pool(mode, x, f"{blk}.tp", 0, cin)
+        conv(f"{blk}.branch_pool", f"{blk}.tp", blk, 1856, cin, 192)
+        x = blk
+    return tuple(T)
+
+
+INCEPTION_FID_LAYERS = _inception_fid_layers()
+INCEPTION_FID_CONVS = tuple(e for e in INCEPTION_FID_LAYERS if e[0] == "conv")
+
+
+def fid_buffer_channels(layers=INCEPTION_FID_LAYERS) -> Dict[str, int]:
+    """logical channels of every buffer of the table: the widest slice anything writes ("img": 3)"""
+    ch = {"img": 3}
+    for e in layers:
+        dst, end = e[3], e[4] + (e[6] if e[0] == "conv" else e[5])
+        ch[dst] = max(ch.get(dst, 0), end)
+    return ch
+
+
+def fid_geometry(layers=INCEPTION_FID_LAYERS, size: int = FID_INPUT_SIZE) -> Dict[str, Tuple[int, int]]:
+    """(h, w) of every buffer for a ``size`` x ``size`` input"""
+    hw = {"img": (size, size)}
+    for e in layers:
+        h, w = hw[e[2]]
+        if e[0] == "conv":
+            _, _, _, dst, _, _, _, kh, kw, s, ph, pw = e
+            o = ((h + 2 * ph - kh) // s + 1, (w + 2 * pw - kw) // s + 1)
+        else:
+            dst = e[3]
+            o = ((h - 3) // 2 + 1, (w - 3) // 2 + 1) if e[1] == "max2" else (h, w)
+        assert hw.setdefault(dst, o) == o, f"{dst}: {hw[dst]} and {o}"
+    return hw
+
+
+def fid_parameter_count(layers=INCEPTION_FID_LAYERS) -> int:
+    """convolution weights plus the four BatchNorm vectors of every BasicConv2d of the table"""
+    return sum(e[6] * e[5] * e[7] * e[8] + 4 * e[6] for e in layers if e[0] == "conv")
+
+
+def fid_program(layers=INCEPTION_FID_LAYERS):
+    """The table compiled for ``mvd_fid_create``: (program ints, 13 per entry; buffer ints, (channels, is_fp32) per buffer; the
+    convolutions' names; the index of the feature buffer).  Buffer 0 is "img" with its ``FID_INPUT_CHANNELS`` physical channels;
+    the feature buffer alone is fp32."""
+    ch = fid_buffer_channels(layers)
+    ch["img"] = FID_INPUT_CHANNELS
+    ids = {name: i for i, name in enumerate(ch)}
+    prog, names = [], []
+    for e in layers:
+        if e[0] == "conv":
+            _, name, src, dst, c_off, cin, cout, kh, kw, s, ph, pw = e
+            prog += [0, ids[src], ids[dst], c_off, ch[src], cout, kh, kw, s, ph, pw, len(names), 0]
+            names.append(name)
+        else:
+            _, mode, src, dst, c_off, c = e
+            prog += [1, ids[src], ids[dst], c_off, c, c, 3, 3, 2 if mode == "max2" else 1, 0 if mode == "max2" else 1, 0 if mode == "max2" else 1, -1,
+                     FID_POOL_MODES[mode]]
+    bufs = []
+    for name, c in ch.items():
+        bufs += [c, int(name == FID_FEATURE_BUFFER)]
+    return prog, bufs, names, ids[FID_FEATURE_BUFFER]
+
+
+def fold_batchnorm(w: torch.Tensor, gamma, beta, mean, var, eps: float = FID_BN_EPS):
+    """conv (no bias) + BatchNorm (eval) as one convolution, in fp32: w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)"""
+    s = gamma.detach().float() / torch.sqrt(var.detach().float() + eps)
+    return w.detach().float() * s.view(-1, 1, 1, 1), beta.detach().float() - mean.detach().float() * s
+
+
+def fid_cin_pad(cin: int) -> int:
+    return (cin + 31) // 32 * 32
+
+
+def pack_slice_conv(w: torch.Tensor, cin_phys: int = 0) -> torch.Tensor:
+    """[cout][cin][kh][kw] -> [cout][kh kw cin_pad] of ``mvd_op_conv_relu_slice``: column (ky kw + kx) cin_pad + c with cin_pad =
+    max(cin, cin_phys) rounded up to 32 and zeros in the padding (dtype kept)."""
+    cout, cin, kh, kw = w.shape
+    pad = fid_cin_pad(max(cin, cin_phys))
+    t = torch.nn.functional.pad(w.detach().permute(0, 2, 3, 1), (0, pad - cin))
+    return t.reshape(cout, kh * kw * pad).contiguous()
+
+
+def normalize_inception_fid_keys(sd) -> Dict[str, torch.Tensor]:
+    """torch-fidelity's / pytorch-fid's state dict -> the five tensors of every BasicConv2d of the table under
+    ``<name>.conv.weight`` / ``<name>.bn.{weight,bias,running_mean,running_var}``; ``fc.*``, ``num_batches_tracked`` and anything
+    else is ignored, a ``module.`` / ``model.`` / ``inception.`` prefix dropped.  A missing key or a wrong shape raises ``MvdError``."""
+    from ._lib import MvdError
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"Inception-v3 (FID) weights: expected a state dict, got {type(sd).__name__}")
+    found = {}
+    for key in sd.keys():
+        k = key
+        for prefix in ("module.", "model.", "inception.", "base."):
+            if k.startswith(prefix):
+                k = k[len(prefix):]
+        found[k] = sd[key]
+    out = {}
+    for e in INCEPTION_FID_CONVS:
+        name, cin, cout, kh, kw = e[1], e[5], e[6], e[7], e[8]
+        for leaf, shape in (("conv.weight", (cout, cin, kh, kw)), ("bn.weight", (cout,)), ("bn.bias", (cout,)), ("bn.running_mean", (cout,)),
+                            ("bn.running_var", (cout,))):
+            t = found.get(f"{name}.{leaf}")
+            if t is None:
+                raise MvdError(f"Inception-v3 (FID) weights: key '{name}.{leaf}' is missing")
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise MvdError(f"Inception-v3 (FID) weights: '{name}.{leaf}' has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+            out[f"{name}.{leaf}"] = t
+    return out
+
+
+def fold_inception_fid(sd) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """name -> (folded weight rounded to bf16 [cout][cin][kh][kw], folded bias fp32) of every BasicConv2d: what both the kernels
+    and the tests' restatement compute with"""
+    sd = normalize_inception_fid_keys(sd)
+    out = {}
+    for e in INCEPTION_FID_CONVS:
+        n = e[1]
+        w, b = fold_batchnorm(sd[f"{n}.conv.weight"], sd[f"{n}.bn.weight"], sd[f"{n}.bn.bias"], sd[f"{n}.bn.running_mean"], sd[f"{n}.bn.running_var"])
+        out[n] = (w.to(torch.bfloat16), b)
+    return out
+
+
+def pack_inception_fid(sd, device) -> Dict[str, torch.Tensor]:
+    """``mvd_fid_set_weight`` slots: ``<name>.weight`` bf16 (``pack_slice_conv`` of the folded weight; the first layer's three input
+    channels sit in the front end's ``FID_INPUT_CHANNELS``), ``<name>.bias`` fp32."""
+    out = {}
+    folded = fold_inception_fid(sd)
+    for e in INCEPTION_FID_CONVS:
+        name, src = e[1], e[2]
+        w, b = folded[name]
+        out[f"{name}.weight"] = pack_slice_conv(w, FID_INPUT_CHANNELS if src == "img" else 0).to(device).contiguous()
+        out[f"{name}.bias"] = _f32(b, device)
     return out

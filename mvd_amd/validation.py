@@ -16,11 +16,12 @@ no fallback.  Two behaviours of the reference are kept on purpose (DESIGN.md sec
     latents from ``scheduler``'s.
 
 One behaviour is NOT kept: the reference wraps its auxiliary block in ``try / except`` and reports zeros when anything in it
-raises; here the exception reaches the caller.  LPIPS and FID need pretrained networks this project does not run: they are
-accepted as callables / metric objects and called the way the reference calls them.  So are the perceptual loss --
-``mvd_amd.perceptual.PerceptualLoss`` (row N8) is the reference's class on this project's kernels, any other callable works the
-same way -- and a CLIP score object of another library; ``mvd_amd.clip_score.CLIPScore`` (row N7) takes the fused route
-``image_similarity``.
+raises; here the exception reaches the caller.  The perceptual loss, the CLIP score and FID are accepted as callables / metric
+objects and called the way the reference calls them; this project runs all three networks itself --
+``mvd_amd.perceptual.PerceptualLoss`` (row N8) is the reference's class on this project's kernels,
+``mvd_amd.clip_score.CLIPScore`` (row N7) takes the fused route ``image_similarity``, and
+``mvd_amd.fid.FrechetInceptionDistance`` (row N10) is torchmetrics' ``update(imgs, real=)`` / ``compute()`` protocol that
+``_fid_score`` drives -- and any other object with the same interface works the same way.
 """
 from __future__ import annotations
 
