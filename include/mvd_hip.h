@@ -609,6 +609,35 @@ int mvd_op_global_mean(const float* x, int batch, int pixels, int c, float* out,
  * v_mfma_f64_16x16x4_f64 with the images as K (zero padded to a multiple of 4), in image order; no atomics. */
 int mvd_op_feature_stats(const float* f, int n, int d, double* sum, double* cov_sum, void* stream);
 
+/* ---- KID and the Inception score on the same pool3 features ------------------------------------- */
+/* Replaces: everything behind the network in torchmetrics' KernelInceptionDistance and InceptionScore(feature=
+ * "logits_unbiased").  All five: int status with mvd_last_error, every argument checked on the host before anything is launched,
+ * no allocation, no host synchronisation, everything on `stream`; no floating-point atomics, so two calls give the same bits.
+ *
+ * kid_mmd: f_real [n_real][d], f_fake [n_fake][d] fp32 (16-byte aligned, d a multiple of 64); idx int32 [subsets][2][m], slot 0
+ * rows of f_real, slot 1 rows of f_fake (an index outside [0, n) is clamped, never dereferenced: validate on the host), 2 <= m <=
+ * min(n_real, n_fake).  Per subset, with x / y the gathered rows in fp64 and k(a, b) = (a.b gamma + coef)^degree (the dot product
+ * on v_mfma_f64_16x16x4_f64 over d in order, never split; the power by repeated multiplication, degree >= 1):
+ *   S_xx = sum_{i != j} k(x_i, x_j), S_yy likewise, S_xy = sum_{i, j} k(x_i, y_j)   (i, j positions in the subset)
+ *   out[s] = (S_xx + S_yy) / (m (m - 1)) - 2 S_xy / m^2     evaluated as written, IEEE division, no contraction
+ * and sums[s] = {S_xx, S_yy, S_xy} when sums is not NULL.  64 x 64 tiles, one partial each in ws (xx and yy: the tiles on and above
+ * the diagonal, those above counted twice), added in tile order.  No m x m matrix is written anywhere. */
+int64_t mvd_op_kid_workspace_bytes(int subsets, int m);
+int mvd_op_kid_mmd(const float* f_real, int n_real, const float* f_fake, int n_fake, int d, const int* idx, int subsets, int m, int degree, double gamma,
+                   double coef, void* ws, int64_t ws_bytes, double* sums /* [subsets][3], may be NULL */, double* out /* [subsets] */, void* stream);
+/* out[n][classes] = f[n][d] . w[classes][d]^T, all fp32, no bias (torch-fidelity's logits_unbiased: 1008 x 2048); d a multiple of
+ * 4, f and w 16-byte aligned.  fp32 fma accumulation in an order that depends on d alone: a row's logits are the same bits alone
+ * and inside any batch. */
+int mvd_op_fc_logits(const float* f, int n, int d, const float* w, int classes, float* out, void* stream);
+/* The Inception-score head in fp64 from fp32 logits [n][classes]; row j of the shuffled order is row perm[j] (int32 [n]).  Chunks
+ * as torch.chunk(splits): ceil(n / splits) rows each, the last one shorter, possibly fewer than `splits` of them; their number
+ * goes to *n_chunks_out (host, may be NULL).  Per row lse = max + log sum exp(x - max); per (chunk, class) mean_p = (sum over the
+ * chunk's rows in row order of exp(x - lse)) / rows; per row kl = sum_c p ((x - lse) - log mean_p) in class order; out[chunk] =
+ * exp(mean of kl over its rows in row order).  out holds at least min(splits, n) doubles. */
+int64_t mvd_op_inception_score_workspace_bytes(int n, int classes, int splits);
+int mvd_op_inception_score(const float* logits, int n, int classes, const int* perm, int splits, void* ws, int64_t ws_bytes, double* out,
+                           int* n_chunks_out /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

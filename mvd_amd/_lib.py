@@ -248,6 +248,13 @@ _SIGS = {
     "mvd_op_resize_tf1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_global_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_feature_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_kid_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "mvd_op_kid_mmd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_fc_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_op_inception_score_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mvd_op_inception_score": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int),
+                                         C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -12,7 +12,9 @@ reference's val.py without torchmetrics or torch-fidelity, on the HIP kernels of
 The state tensors are plain sums, so a caller may all-reduce them across ranks before ``compute()``; that reduction is not
 built here.  Nothing is ever fetched: the weights come from a state dict, a ``.pth`` / ``.safetensors`` path, or
 ``weights-inception-2015-12-05-6726825d.pth`` / ``pt_inception-2015-12-05-6726825d.pth`` in the local hub cache.  CPU tensors raise
-``MvdError``: there is no fallback.  What is not here: ``feature=64 / 192 / 768``, KID, the Inception score, a backward pass.
+``MvdError``: there is no fallback.  KID and the Inception score run on the same pool3 features: ``mvd_amd.kid`` (row N11); one
+``InceptionV3FeaturesHIP`` can feed all three metrics (``inception=``, ``update_features``).  What is not here:
+``feature=64 / 192 / 768``, a backward pass.
 """
 from __future__ import annotations
 
@@ -23,7 +25,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib as L
-from .packing import fid_program, normalize_inception_fid_keys, pack_inception_fid
+from .packing import fid_program, inception_fc_weight, normalize_inception_fid_keys, pack_inception_fid
 from .perceptual import hub_checkpoint_dirs
 
 INCEPTION_FID_FILES = ("weights-inception-2015-12-05-6726825d.pth", "pt_inception-2015-12-05-6726825d.pth")
@@ -99,13 +101,17 @@ class InceptionV3FeaturesHIP:
     """pool3 features of the FID Inception-v3: ``net(images)`` -> (B, 2048) fp32 on the device.  ``images``: (B, 3, H, W) uint8, or
     floating point in [0, 1] (quantised as torchmetrics' ``normalize=True`` does: ``x * 255`` in fp32, truncated; values outside
     [0, 1] are clamped).  ``max_images_per_pass`` is the pass size: larger batches run as several passes within one call; an
-    image's features do not depend on the batch or the pass it is in."""
+    image's features do not depend on the batch or the pass it is in.  ``fc_weight``: the classifier's (1008, 2048) fp32 weight when
+    the state dict has one (``None`` otherwise); ``logits(pool3)`` applies it without the bias (``mvd_op_fc_logits``)."""
 
     def __init__(self, weights=None, max_images_per_pass: int = 8):
         if int(max_images_per_pass) < 1:
             raise L.MvdError(f"InceptionV3FeaturesHIP: max_images_per_pass={max_images_per_pass!r} must be at least 1")
         self.max_images_per_pass = int(max_images_per_pass)
-        self.state = normalize_inception_fid_keys(load_inception_fid_weights(weights))
+        sd = load_inception_fid_weights(weights)
+        self.state = normalize_inception_fid_keys(sd)
+        self.fc_weight: Optional[torch.Tensor] = inception_fc_weight(sd, required=False)
+        self._fc_dev: Optional[torch.Tensor] = None
         self._handle: Optional[_FidHandle] = None
         self._packed: Dict[str, torch.Tensor] = {}
         self._dev = None
@@ -151,6 +157,25 @@ class InceptionV3FeaturesHIP:
         return out
 
     __call__ = forward
+
+    @torch.no_grad()
+    def logits(self, pool3: torch.Tensor) -> torch.Tensor:
+        """(b, 2048) fp32 pool3 features -> (b, 1008) fp32 ``logits_unbiased``: pool3 . fc.weight^T in fp32, no bias; a row's logits do
+        not depend on the batch"""
+        who = "InceptionV3FeaturesHIP.logits"
+        if self.fc_weight is None:
+            raise L.MvdError(f"{who}: the state dict has no 'fc.weight'")
+        if not isinstance(pool3, torch.Tensor) or not pool3.is_cuda:
+            raise L.MvdError(f"{who} runs on the GPU only (libmvd_hip.so): got a tensor on {getattr(pool3, 'device', None)}; there is no CPU fallback")
+        if pool3.dim() != 2 or pool3.shape[1] != FEATURE_DIM or pool3.shape[0] < 1 or pool3.dtype != torch.float32:
+            raise L.MvdError(f"{who}: features must be (b, {FEATURE_DIM}) fp32, got {tuple(pool3.shape)} {pool3.dtype}")
+        f = pool3.detach().contiguous()
+        if self._fc_dev is None or self._fc_dev.device != f.device:
+            self._fc_dev = self.fc_weight.to(f.device)
+        out = torch.empty(f.shape[0], self._fc_dev.shape[0], device=f.device, dtype=torch.float32)
+        L.call("mvd_op_fc_logits", C.c_void_p(f.data_ptr()), f.shape[0], FEATURE_DIM, C.c_void_p(self._fc_dev.data_ptr()), self._fc_dev.shape[0],
+               C.c_void_p(out.data_ptr()), _stream())
+        return out
 
     @torch.no_grad()
     def update_statistics(self, images: torch.Tensor, total: torch.Tensor, cov_sum: torch.Tensor) -> int:
@@ -205,19 +230,23 @@ class FrechetInceptionDistance:
     """``torchmetrics.image.fid.FrechetInceptionDistance(feature=2048)`` on this project's kernels.  ``update(imgs, real)``: uint8
     images, or (``normalize=True``) floating point in [0, 1]; ``compute()`` -> the FID as a 0-d fp64 device tensor -- the one place
     that synchronises: the six state tensors go to the host and the distance is evaluated in fp64 there (``fid_from_statistics``).
-    ``reset()`` keeps the real statistics when ``reset_real_features=False``.  ``weights``: see ``load_inception_fid_weights``."""
+    ``reset()`` keeps the real statistics when ``reset_real_features=False``.  ``weights``: see ``load_inception_fid_weights``.
+    ``inception``: an ``InceptionV3FeaturesHIP`` shared with other metrics (then ``weights`` and ``max_images_per_pass`` are not used);
+    ``update_features(pool3, real)`` adds the statistics of features from a tower call made elsewhere."""
 
     STATE = ("real_features_sum", "real_features_cov_sum", "real_features_num_samples", "fake_features_sum", "fake_features_cov_sum",
              "fake_features_num_samples")
 
     def __init__(self, feature=2048, reset_real_features: bool = True, normalize: bool = False, weights=None, max_images_per_pass: int = 8,
-                 device="cuda"):
+                 device="cuda", inception=None):
         if isinstance(feature, bool) or not isinstance(feature, int) or feature != FEATURE_DIM:
             raise ValueError(f"FrechetInceptionDistance: feature={feature!r}: only the 2048 pool3 features are built here "
                              "(not 64 / 192 / 768, not a custom module)")
         if not isinstance(reset_real_features, bool) or not isinstance(normalize, bool):
             raise ValueError("FrechetInceptionDistance: reset_real_features and normalize must be bool")
-        self.inception = InceptionV3FeaturesHIP(weights, max_images_per_pass=max_images_per_pass)
+        if inception is not None and not isinstance(inception, InceptionV3FeaturesHIP):
+            raise ValueError(f"FrechetInceptionDistance: inception must be an InceptionV3FeaturesHIP, got {type(inception).__name__}")
+        self.inception = inception if inception is not None else InceptionV3FeaturesHIP(weights, max_images_per_pass=max_images_per_pass)
         self.reset_real_features, self.normalize = reset_real_features, normalize
         self.device = torch.device(device)
         self._allocate(("real", "fake"))
@@ -261,6 +290,22 @@ class FrechetInceptionDistance:
         side = "real" if real else "fake"
         n = self.inception.update_statistics(imgs, getattr(self, f"{side}_features_sum"), getattr(self, f"{side}_features_cov_sum"))
         getattr(self, f"{side}_features_num_samples").add_(n)
+
+    @torch.no_grad()
+    def update_features(self, pool3: torch.Tensor, real: bool) -> None:
+        """the statistics of given (b, 2048) fp32 pool3 features (``mvd_op_feature_stats``): what ``update`` adds behind the tower"""
+        who = "FrechetInceptionDistance.update_features"
+        if not isinstance(pool3, torch.Tensor) or not pool3.is_cuda:
+            raise L.MvdError(f"{who} runs on the GPU only (libmvd_hip.so): pass CUDA tensors; there is no CPU fallback")
+        if pool3.dim() != 2 or pool3.shape[1] != FEATURE_DIM or pool3.shape[0] < 1 or pool3.dtype != torch.float32:
+            raise L.MvdError(f"{who}: features must be (b, {FEATURE_DIM}) fp32, got {tuple(pool3.shape)} {pool3.dtype}")
+        if self.real_features_sum.device != pool3.device:
+            self.to(pool3.device)
+        f = pool3.detach().contiguous()
+        side = "real" if real else "fake"
+        L.call("mvd_op_feature_stats", C.c_void_p(f.data_ptr()), f.shape[0], FEATURE_DIM, C.c_void_p(getattr(self, f"{side}_features_sum").data_ptr()),
+               C.c_void_p(getattr(self, f"{side}_features_cov_sum").data_ptr()), _stream())
+        getattr(self, f"{side}_features_num_samples").add_(f.shape[0])
 
     def compute(self) -> torch.Tensor:
         host = {name: getattr(self, name).detach().cpu() for name in self.STATE}      # the synchronisation of this protocol

@@ -293,6 +293,50 @@ def feature_stats(f, total, cov_sum):
     L.call("mvd_op_feature_stats", _p(f), n, d, _p(total), _p(cov_sum), _s())
 
 
+def kid_mmd(f_real, f_fake, idx, degree=3, gamma=None, coef=1.0, want_sums=False, ws=None):
+    """``mvd_op_kid_mmd``: f_real (n_real, d), f_fake (n_fake, d) fp32, d % 64 == 0; idx (subsets, 2, m) int32, slot 0 rows of
+    f_real, slot 1 rows of f_fake (validate them on the host: the kernel only clamps) -> the polynomial-kernel MMD of every
+    subset, (subsets,) fp64; with ``want_sums`` also (subsets, 3) fp64 = S_xx, S_yy, S_xy.  ``gamma=None``: 1 / d."""
+    assert f_real.dtype == torch.float32 and f_fake.dtype == torch.float32 and f_real.dim() == 2 and f_fake.dim() == 2
+    assert idx.dtype == torch.int32 and idx.dim() == 3 and idx.shape[1] == 2
+    d = f_real.shape[1]
+    assert f_fake.shape[1] == d
+    subsets, _, m = idx.shape
+    need = L.lib().mvd_op_kid_workspace_bytes(subsets, m)
+    if need < 0:
+        raise L.MvdError(f"mvd_op_kid_workspace_bytes: {L.last_error()}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=f_real.device)
+    out = torch.empty(subsets, dtype=torch.float64, device=f_real.device)
+    sums = torch.empty(subsets, 3, dtype=torch.float64, device=f_real.device) if want_sums else None
+    L.call("mvd_op_kid_mmd", _p(f_real), f_real.shape[0], _p(f_fake), f_fake.shape[0], d, _p(idx), subsets, m, int(degree),
+           float(1.0 / d if gamma is None else gamma), float(coef), _p(ws), need, _p(sums), _p(out), _s())
+    return (out, sums) if want_sums else out
+
+
+def fc_logits(f, w):
+    """``mvd_op_fc_logits``: f (n, d) fp32 . w (classes, d)^T fp32 -> (n, classes) fp32, no bias; a row's logits do not depend on n"""
+    assert f.dtype == torch.float32 and w.dtype == torch.float32 and f.dim() == 2 and w.dim() == 2 and f.shape[1] == w.shape[1]
+    out = torch.empty(f.shape[0], w.shape[0], dtype=torch.float32, device=f.device)
+    L.call("mvd_op_fc_logits", _p(f), f.shape[0], f.shape[1], _p(w), w.shape[0], _p(out), _s())
+    return out
+
+
+def inception_score_chunks(logits, perm, splits):
+    """``mvd_op_inception_score``: logits (n, classes) fp32, perm (n,) int32 (row j of the shuffled order is row perm[j]) ->
+    exp(mean KL) of every chunk of ``torch.chunk(splits)``, (chunks,) fp64"""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and perm.dtype == torch.int32 and perm.shape == (logits.shape[0],)
+    n, classes = logits.shape
+    need = L.lib().mvd_op_inception_score_workspace_bytes(n, classes, int(splits))
+    if need < 0:
+        raise L.MvdError(f"mvd_op_inception_score_workspace_bytes: {L.last_error()}")
+    ws = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    out = torch.empty(min(int(splits), n), dtype=torch.float64, device=logits.device)
+    chunks = C.c_int(0)
+    L.call("mvd_op_inception_score", _p(logits), n, classes, _p(perm), int(splits), _p(ws), need, _p(out), C.byref(chunks), _s())
+    return out[:chunks.value]
+
+
 def up4_launches() -> int:
     """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
     return int(L.lib().mvd_debug_up4_launches())

@@ -16,7 +16,7 @@ One-time host work (torch is used as plumbing for the permutes / casts).  Slot l
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 
 import torch
@@ -647,6 +647,34 @@ def normalize_inception_fid_keys(sd) -> Dict[str, torch.Tensor]:
                 raise MvdError(f"Inception-v3 (FID) weights: '{name}.{leaf}' has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
             out[f"{name}.{leaf}"] = t
     return out
+
+
+INCEPTION_FC_SHAPE = (1008, 2048)      # torch-fidelity's fc of the FID Inception-v3: 1008 classes over pool3
+
+
+def inception_fc_weight(sd, required: bool = True) -> Optional[torch.Tensor]:
+    """``fc.weight`` (1008, 2048) of a torch-fidelity / pytorch-fid state dict as contiguous fp32, under the prefixes
+    ``normalize_inception_fid_keys`` strips; ``fc.bias`` is not used (``logits_unbiased``).  Without the key: ``MvdError``, or
+    ``None`` when not ``required``; a wrong shape always raises."""
+    from ._lib import MvdError
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"Inception-v3 (FID) weights: expected a state dict, got {type(sd).__name__}")
+    t = None
+    for key in sd.keys():
+        k = key
+        for prefix in ("module.", "model.", "inception.", "base."):
+            if k.startswith(prefix):
+                k = k[len(prefix):]
+        if k == "fc.weight":
+            t = sd[key]
+            break
+    if t is None:
+        if required:
+            raise MvdError("Inception-v3 (FID) weights: key 'fc.weight' is missing (the Inception score needs the classifier)")
+        return None
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != INCEPTION_FC_SHAPE:
+        raise MvdError(f"Inception-v3 (FID) weights: 'fc.weight' has shape {tuple(getattr(t, 'shape', ()))}, expected {INCEPTION_FC_SHAPE}")
+    return t.detach().to(torch.float32).contiguous()
 
 
 def fold_inception_fid(sd) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
