@@ -638,6 +638,32 @@ int64_t mvd_op_inception_score_workspace_bytes(int n, int classes, int splits);
 int mvd_op_inception_score(const float* logits, int n, int classes, const int* perm, int splits, void* ws, int64_t ws_bytes, double* out,
                            int* n_chunks_out /* host */, void* stream);
 
+/* ---- precision / recall and density / coverage on the same pool3 features ------------------------ */
+/* Replaces: everything behind the network in torch-fidelity's `prc` metric (Kynkaanniemi et al. 2019) and in the `prdc`
+ * package (Naeem et al. 2020).  All three: int status with mvd_last_error, every argument checked on the host before anything is
+ * launched, no allocation, no host synchronisation, everything on `stream`; no floating-point atomics.
+ *
+ * Every comparison is on SQUARED distances, D2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b) in fp64 from fp32 rows of d floats (d a
+ * multiple of 64, 16-byte aligned): the dot product on v_mfma_f64_16x16x4_f64 over d in order, never split; the norms fp64 fma
+ * chains in a fixed order.  No n x n matrix is written anywhere.
+ *
+ * knn_radii: radii_sq[i] = the (k + 1)-th smallest value of row i of D2(f, f), the row's own diagonal entry counted
+ * (kthvalue(k + 1)); knn_sq, when not NULL, receives the row's k + 1 smallest values in ascending order, [n][k + 1] (so one pass
+ * at k = 5 also serves k = 3).  1 <= k <= 15, n >= k + 1.  The columns are split into parts over a 2-D grid and a merge kernel
+ * takes the k + 1 smallest of the parts' lists; force_parts 0 = automatic, otherwise the number of parts (at most one per 64
+ * columns).  The k + 1 smallest values of a multiset do not depend on order: any force_parts and any two calls give the same bits.
+ * ws holds the parts' lists. */
+int64_t mvd_op_knn_radii_workspace_bytes(int n, int k, int force_parts);
+int mvd_op_knn_radii(const float* f, int n, int d, int k, int force_parts, double* radii_sq /* [n] */, double* knn_sq_or_null /* [n][k + 1] */, void* ws,
+                     int64_t ws_bytes, void* stream);
+/* The predicate P[j][i] = D2(q_j, r_i) <= r_radii_sq[i] (closed = 1) or < (closed = 0), never stored: hits_per_query[j] = sum_i
+ * P[j][i] and hits_per_ref[i] = sum_j P[j][i], int32, zeroed by the call, added with integer atomics (exact in any order).
+ * Either output may be NULL.  With radii = knn_radii(r, k):
+ *   precision = #{j : hits_per_query[j] > 0} / nq (q = fake, r = real, closed), recall the same with the sides exchanged;
+ *   density = sum_j hits_per_query[j] / (k nq), coverage = #{i : hits_per_ref[i] > 0} / nr (q = fake, r = real, open). */
+int mvd_op_manifold_counts(const float* q, int nq, const float* r, int nr, int d, const double* r_radii_sq, int closed, int32_t* hits_per_query,
+                           int32_t* hits_per_ref, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,9 @@ _SIGS = {
     "mvd_op_inception_score_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mvd_op_inception_score": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int),
                                          C.c_void_p]),
+    "mvd_op_knn_radii_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mvd_op_knn_radii": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvd_op_manifold_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -337,6 +337,35 @@ def inception_score_chunks(logits, perm, splits):
     return out[:chunks.value]
 
 
+def knn_radii(f, k, force_parts=0, want_list=False, ws=None):
+    """``mvd_op_knn_radii``: f (n, d) fp32, d % 64 == 0, 1 <= k <= 15, n >= k + 1 -> radii_sq (n,) fp64, the (k + 1)-th smallest
+    squared distance of every row to the rows of f (itself included: ``kthvalue(k + 1)``); with ``want_list`` also the k + 1 smallest
+    in ascending order, (n, k + 1).  ``force_parts``: the number of column parts (0: automatic); the bits do not depend on it."""
+    assert f.dtype == torch.float32 and f.dim() == 2
+    n, d = f.shape
+    need = L.lib().mvd_op_knn_radii_workspace_bytes(n, int(k), int(force_parts))
+    if need < 0:
+        raise L.MvdError(f"mvd_op_knn_radii_workspace_bytes: {L.last_error()}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=f.device)
+    radii = torch.empty(n, dtype=torch.float64, device=f.device)
+    knn = torch.empty(n, int(k) + 1, dtype=torch.float64, device=f.device) if want_list else None
+    L.call("mvd_op_knn_radii", _p(f), n, d, int(k), int(force_parts), _p(radii), _p(knn), _p(ws), need, _s())
+    return (radii, knn) if want_list else radii
+
+
+def manifold_counts(q, r, radii_sq, closed, want_query=True, want_ref=True):
+    """``mvd_op_manifold_counts``: q (nq, d), r (nr, d) fp32, radii_sq (nr,) fp64 -> (hits_per_query (nq,), hits_per_ref (nr,))
+    int32: the row and column sums of P[j][i] = D2(q_j, r_i) <= radii_sq[i] (``closed``) or < (not ``closed``); an output that is
+    not wanted is None"""
+    assert q.dtype == torch.float32 and r.dtype == torch.float32 and q.dim() == 2 and r.dim() == 2 and q.shape[1] == r.shape[1]
+    assert radii_sq.dtype == torch.float64 and radii_sq.shape == (r.shape[0],)
+    hq = torch.empty(q.shape[0], dtype=torch.int32, device=q.device) if want_query else None
+    hr = torch.empty(r.shape[0], dtype=torch.int32, device=q.device) if want_ref else None
+    L.call("mvd_op_manifold_counts", _p(q), q.shape[0], _p(r), r.shape[0], q.shape[1], _p(radii_sq), int(bool(closed)), _p(hq), _p(hr), _s())
+    return hq, hr
+
+
 def up4_launches() -> int:
     """Launches of the 2x2 sub-pixel upsampling convolution by this process so far."""
     return int(L.lib().mvd_debug_up4_launches())
