@@ -301,3 +301,55 @@ def call(name: str, *args):
     if rc != 0:
         raise MvdError(f"{name} failed (rc={rc}): {last_error()}")
     return rc
+
+
+def stream() -> C.c_void_p:
+    """the current torch stream, as the ``void* stream`` argument of the entry points"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def dtype_code(t) -> int:
+    """the ``dtype`` argument of the ``*_set_weight`` entry points: 0 fp32, 1 bf16"""
+    import torch
+    return {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
+
+
+class Handle:
+    """One ``mvd_<family>_t`` (vae, text, vision, vgg, lpips, fid) with its workspace: ``.h`` from ``mvd_<family>_create(*create_args,
+    &h)``, destroyed with the object; ``.ws`` grown on demand and bound when it moves (``rebind_always``: on every ``workspace``
+    call -- the text tower and the VAE, whose callers may have bound another buffer in between)."""
+
+    def __init__(self, family: str, *create_args, rebind_always: bool = False):
+        self.family, self.rebind_always = family, rebind_always
+        self.h = C.c_void_p()
+        self.ws = None
+        call(f"mvd_{family}_create", *create_args, C.byref(self.h))
+
+    def __del__(self):
+        try:
+            if self.h:
+                getattr(lib(), f"mvd_{self.family}_destroy")(self.h)
+        except Exception:
+            pass
+
+    def set_weights(self, packed) -> None:
+        """registers every tensor of ``packed`` ({slot: fp32 / bf16 device tensor}); the caller keeps them alive"""
+        for slot, t in packed.items():
+            call(f"mvd_{self.family}_set_weight", self.h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dtype_code(t))
+
+    def workspace_bytes(self, *size_args, sizer: str = "workspace_bytes") -> int:
+        need = getattr(lib(), f"mvd_{self.family}_{sizer}")(self.h, *size_args)
+        if need < 0:
+            raise MvdError(f"{self.family} {sizer}: {last_error()}")
+        return need
+
+    def workspace(self, device, *size_args, sizer: str = "workspace_bytes") -> None:
+        import torch
+        need = self.workspace_bytes(*size_args, sizer=sizer)
+        moved = self.ws is None or self.ws.numel() < need or self.ws.device != device
+        if moved:
+            self.ws = None
+            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
+        if moved or self.rebind_always:
+            call(f"mvd_{self.family}_bind_workspace", self.h, C.c_void_p(self.ws.data_ptr()), self.ws.numel())

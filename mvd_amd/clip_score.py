@@ -31,7 +31,7 @@ from . import _lib as L
 from .clip_tokenizer import CLIPTokenizerLite
 from .hub import resolve_snapshot
 from .text_encoder import CLIPTextConfigLite, CLIPTextModelHIP
-from .vision_encoder import CLIPImageProcessorLite, CLIPVisionConfigLite, CLIPVisionModelHIP, _stream, split_clip_state_dict
+from .vision_encoder import CLIPImageProcessorLite, CLIPVisionConfigLite, CLIPVisionModelHIP, split_clip_state_dict
 
 FILES = ("config.json", "model.safetensors", "preprocessor_config.json", "vocab.json", "merges.txt")
 _TEXT_KEYS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings",
@@ -51,7 +51,7 @@ def clip_cosine(a: torch.Tensor, b: torch.Tensor):
     a, b = a.float().contiguous(), b.float().contiguous()
     rows = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
     mean = torch.empty((), device=a.device, dtype=torch.float32)
-    L.call("mvd_op_clip_cosine", _p(a), _p(b), a.shape[0], a.shape[1], _p(rows), _p(mean), _stream())
+    L.call("mvd_op_clip_cosine", _p(a), _p(b), a.shape[0], a.shape[1], _p(rows), _p(mean), L.stream())
     return rows, mean
 
 
@@ -66,7 +66,7 @@ def pool_project(hidden: torch.Tensor, proj_w: torch.Tensor, ids=None, eos_token
     raw = torch.empty(B, proj_w.shape[0], device=hidden.device, dtype=torch.float32)
     nrm = torch.empty_like(raw)
     L.call("mvd_op_clip_pool_project", _p(hidden), _p(delta), _p(ids32), B, T, H, int(eos_token_id), _p(g), _p(b), float(eps), _p(proj_w),
-           proj_w.shape[0], _p(raw), _p(nrm), _stream())
+           proj_w.shape[0], _p(raw), _p(nrm), L.stream())
     return raw, nrm
 
 

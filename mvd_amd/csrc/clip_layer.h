@@ -17,12 +17,6 @@
 
 namespace {
 
-int tcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-
 // ---------------------------------------------------------------- residual add + LayerNorm
 // x[row] += delta[row] (fp32, in place; delta may be null), then y = LN(x) as bf16 (y_bf) or fp32 (y_f32).  One wave per
 // row, the row in registers (H <= 2048), two-pass variance.
@@ -132,11 +126,11 @@ struct ClipCtx {
     if (err) return err;
     if (dry) return 0;
     hipLaunchKernelGGL(text_add_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, delta, g, b, rows, H, eps, y_bf, y_f32);
-    return tcheck("add+layernorm");
+    return launch_check("add+layernorm");
   }
 };
 
-size_t cnt_bytes(int cnt) { return ((size_t)cnt * 4 + 255) & ~size_t(255); }
+size_t cnt_bytes(int cnt) { return align256((size_t)cnt * 4); }
 
 // the activations of the layer schedule, allocated in this order
 struct ClipBufs {
@@ -177,7 +171,7 @@ int clip_layers(ClipCtx& x, const ClipBufs& b, int layers, int H, int I, int M, 
     if (!x.dry) {
       const long n8 = (long)M * I / 8;
       hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, x.s, b.f1, n8, act, b.g1);
-      CHECK(tcheck("activation"));
+      CHECK(launch_check("activation"));
     }
     CHECK(x.linear(b.g1, I, M, w2, bf2, H, b.dl, true));
   }

@@ -81,6 +81,23 @@ MVD_DEVINL float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+MVD_DEVINL double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+MVD_DEVINL double block_sum_f64(double v, double* red) {   // 256 threads, red[4] in LDS; every thread gets the sum (waves added in order)
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+// the elementwise maximum of two bf16 pairs: one of the inputs, so nothing is rounded
+MVD_DEVINL unsigned int max2bf(unsigned int a, unsigned int b) {
+  const float lo = fmaxf(bflo(a), bflo(b)), hi = fmaxf(bfhi(a), bfhi(b));
+  return pack2bf(lo, hi);
+}
 
 // XCD-aware bijective block remap (blocks b, b+8, ... share an XCD): gives each XCD a
 // contiguous chunk of the logical tile order so neighbouring tiles hit the same L2.

@@ -27,14 +27,6 @@ typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 namespace {
 
-int fcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-long blocks_of(long n) { return (n + 255) / 256; }
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 constexpr int FID_SIZE = 299;      // the tower's input
 constexpr int FID_IN_C = 16;       // channels of the resized map: r, g, b and 13 zeros (the convolution reads multiples of 16)
 
@@ -133,7 +125,7 @@ int launch_conv(const bf16_t* x, int batch, int h, int w, int ld_in, int cin_off
   if ((cout + 63) / 64 > 65535) { mvd_set_error("conv_relu_slice: too many output channels"); return -1; }
   ConvArgs a{x, wt, bias, out, h, w, ld_in, cin_off, cin, cin_pad_of(cin), oh, ow, kh, kw, stride, ph, pw, cout, c_off, ld_out, out_f32, M};
   hipLaunchKernelGGL(conv_relu_slice_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)((cout + 63) / 64)), dim3(256), 0, s, a);
-  return fcheck("conv_relu_slice");
+  return launch_check("conv_relu_slice");
 }
 
 // ---------------------------------------------------------------- 3x3 pools into a channel slice
@@ -190,7 +182,7 @@ int launch_pool(const bf16_t* x, int batch, int h, int w, int ld_in, int cin_off
   const long total = (long)batch * oh * ow * (c / 8);
   if (blocks_of(total) >= (1L << 31) || (long)batch * h * w >= (1L << 31)) { mvd_set_error("pool3x3_slice: too many elements for one launch"); return -1; }
   hipLaunchKernelGGL(pool3x3_slice_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, h, w, ld_in, cin_off, oh, ow, c / 8, mode, ld_out, c_off, total, y);
-  return fcheck("pool3x3_slice");
+  return launch_check("pool3x3_slice");
 }
 
 // ---------------------------------------------------------------- front end: quantise, TF1-legacy bilinear resize, (v - 128) / 128
@@ -249,7 +241,7 @@ int launch_resize(const void* src, int dtype, int batch, int h, int w, bf16_t* o
   const float sh = (float)((double)h / (double)FID_SIZE), sw = (float)((double)w / (double)FID_SIZE);
   if (dtype == 1) hipLaunchKernelGGL(resize_tf1_kernel<true>, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, src, h, w, sh, sw, total, out);
   else hipLaunchKernelGGL(resize_tf1_kernel<false>, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, src, h, w, sh, sw, total, out);
-  return fcheck("resize_tf1");
+  return launch_check("resize_tf1");
 }
 
 // ---------------------------------------------------------------- the mean over the pixels of an fp32 NHWC map, in pixel order
@@ -269,7 +261,7 @@ int launch_global_mean(const float* x, int batch, int pixels, int c, float* out,
   const long total = (long)batch * c;
   if (blocks_of(total) >= (1L << 31)) { mvd_set_error("global_mean: too many elements for one launch"); return -1; }
   hipLaunchKernelGGL(global_mean_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, pixels, c, total, out);
-  return fcheck("global_mean");
+  return launch_check("global_mean");
 }
 
 // ---------------------------------------------------------------- feature statistics in fp64
@@ -324,9 +316,9 @@ int launch_feature_stats(const float* f, int n, int d, double* sum, double* cov,
   if (!f || !sum || !cov || n <= 0 || d <= 0 || d % 64 || d > 64 * 65535) { mvd_set_error("feature_stats: bad argument (n >= 1, d a multiple of 64)"); return -1; }
   if (((uintptr_t)f & 3) || (((uintptr_t)sum | (uintptr_t)cov) & 7)) { mvd_set_error("feature_stats: misaligned buffer"); return -1; }
   hipLaunchKernelGGL(feature_sum_kernel, dim3((unsigned)blocks_of(d)), dim3(256), 0, s, f, n, d, sum);
-  CHECK(fcheck("feature_stats (sum)"));
+  CHECK(launch_check("feature_stats (sum)"));
   hipLaunchKernelGGL(feature_cov_kernel, dim3(d / 64, d / 64), dim3(256), 0, s, f, n, d, cov);
-  return fcheck("feature_stats (cov_sum)");
+  return launch_check("feature_stats (cov_sum)");
 }
 
 // ---------------------------------------------------------------- the program of mvd_fid_create
@@ -337,14 +329,11 @@ struct Buf { int channels, f32; };
 
 }  // namespace
 
-struct mvd_fid {
+struct mvd_fid : ModuleBase {
   std::vector<Op> ops;
   std::vector<Buf> bufs;
   std::vector<std::string> names;      // of the convolutions: weight slots "<name>.weight" / "<name>.bias"
   int final_buf = 0, max_pass = 8;
-  WeightTable w;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
-  Arena ar;
 };
 
 namespace {
@@ -442,9 +431,7 @@ int run_features(const char* who, mvd_fid* v, size_t head, const void* images, i
   const int D = feature_dim(v);
   for (int p0 = 0; p0 < n; p0 += P) {
     const int np = n - p0 < P ? n - p0 : P;
-    v->ar.reset(false);
-    v->ar.base = reinterpret_cast<char*>(v->ws_ptr) + head;
-    v->ar.cap = (size_t)v->ws_bytes - head;
+    module_bind_arena(*v, head);
     CHECK(run_pass(v, false, reinterpret_cast<const char*>(images) + p0 * img, dtype, np, h, w, feat_out + (size_t)p0 * D, s));
   }
   return 0;
@@ -490,10 +477,7 @@ int mvd_fid_create(const int* program, int n_ops, const int* buffers, int n_buff
 int mvd_fid_destroy(mvd_fid_t* v) { delete v; return 0; }
 
 int mvd_fid_set_weight(mvd_fid_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("fid_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("fid_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(v, "fid", slot, ptr, numel, dtype);
 }
 
 int mvd_fid_feature_dim(mvd_fid_t* v) {
@@ -509,9 +493,7 @@ int64_t mvd_fid_workspace_bytes(mvd_fid_t* v, int images) {
 }
 
 int mvd_fid_bind_workspace(mvd_fid_t* v, void* ws, int64_t bytes) {
-  if (!v || !ws || bytes <= 0 || ((uintptr_t)ws & 255)) { mvd_set_error("fid_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  v->ws_ptr = ws; v->ws_bytes = bytes;
-  return 0;
+  return module_bind_workspace(v, "fid", ws, bytes, 0);
 }
 
 int mvd_fid_features(mvd_fid_t* v, const void* images, int dtype, int n, int h, int w, float* feat_out, void* stream) {

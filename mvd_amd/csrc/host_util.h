@@ -1,5 +1,6 @@
-// Host-side plumbing shared by the schedules (engine.hip, vae.hip, text.hip / vision.hip) and the operator-level entry points:
-// weight slots, the bump arena, activations, the two shapes of MvdGemmArgs and the tiled launch with its reduce pass.
+// Host-side plumbing shared by the schedules (engine.hip, vae.hip, text.hip / vision.hip, the metric towers) and the operator-level
+// entry points: the launch check, weight slots, the bump arena, activations, the two shapes of MvdGemmArgs, the tiled launch with its
+// reduce pass, and the scaffold of a handle module (ModuleBase, TowerCtx, pairs_per_pass).
 // What is NOT here is routing: which kernel family a problem goes to differs per schedule on purpose (the VAE never takes
 // the small-M kernels, the CLIP towers (clip_layer.h) ask mvd_gemm_sm_plan first, the engine adds the xs / ws / up4 / two-stream policy).
 #pragma once
@@ -12,6 +13,15 @@
 #include "kernels.h"
 
 #define CHECK(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+// after a kernel launch: -3 and "<what> launch: <error>" when it did not go out
+inline int launch_check(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
+  return 0;
+}
+inline long blocks_of(long n) { return (n + 255) / 256; }      // workgroups of 256 threads over n items
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 struct Weight { const void* p; int64_t numel; int dtype; };   // dtype: 0 fp32, 1 bf16
 
@@ -41,7 +51,7 @@ struct Arena {
   size_t cap = 0, off = 0, high = 0;
   bool dry = false;
   void* alloc(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
+    off = align256(off);
     void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
     off += bytes;
     if (off > high) high = off;
@@ -103,4 +113,70 @@ template <class Wrap> int launch_tiled(const MvdGemmArgs& g, hipStream_t s, int 
 }
 inline int launch_tiled(const MvdGemmArgs& g, hipStream_t s, int force_cfg = -1) {
   return launch_tiled(g, s, force_cfg, [](auto&& launch) { return launch(); });
+}
+
+// the tiled kernels with the split-K the tile heuristic asks for; the partials live in the arena for the launch alone
+inline int arena_gemm(Arena& ar, MvdGemmArgs& g, hipStream_t s, bool dry) {
+  const int S = mvd_gemm_pick_splitk(g);
+  const size_t mark = ar.off;
+  if (S > 1) { g.splitk = S; g.part = ar.alloc_n<float>((size_t)S * g.M * g.N); }
+  const int r = dry ? 0 : launch_tiled(g, s);
+  ar.off = mark;
+  return r;
+}
+
+// ---------------------------------------------------------------- the scaffold of a handle module (mvd_vae, mvd_text, mvd_vision, mvd_vgg, ...)
+// What every handle owns: its weight slots, the bound workspace and the arena over it.  `who` is the module's name in its
+// messages ("vgg" -> "vgg_set_weight: ...").
+struct ModuleBase {
+  WeightTable w;
+  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
+  Arena ar;
+};
+inline int module_set_weight(ModuleBase* m, const char* who, const char* slot, const void* ptr, int64_t numel, int dtype) {
+  if (!m || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("%s_set_weight: bad argument", who); return -1; }
+  if ((uintptr_t)ptr & 15) { mvd_set_error("%s_set_weight: '%s' must be 16-byte aligned", who, slot); return -1; }
+  m->w.m[slot] = Weight{ptr, numel, dtype};
+  return 0;
+}
+// min_bytes: what the module keeps at the head of its workspace (a buffer of that size or less holds nothing)
+inline int module_bind_workspace(ModuleBase* m, const char* who, void* ws, int64_t bytes, int64_t min_bytes) {
+  if (!m || !ws || bytes <= min_bytes || ((uintptr_t)ws & 255)) { mvd_set_error("%s_bind_workspace: bad argument (256-byte aligned buffer)", who); return -1; }
+  m->ws_ptr = ws; m->ws_bytes = bytes;
+  return 0;
+}
+// a real run's arena: the bound workspace behind its first `head` bytes
+inline void module_bind_arena(ModuleBase& m, size_t head) {
+  m.ar.reset(false);
+  m.ar.base = reinterpret_cast<char*>(m.ws_ptr) + head;
+  m.ar.cap = (size_t)m.ws_bytes - head;
+}
+
+// One run of a tower's schedule over m->ar.  dry: sizes only; check_w false (sizing): weight slots are not looked at.  The first
+// failed lookup stays in err, and W() answers null from then on.
+struct TowerCtx {
+  ModuleBase* m; hipStream_t s; bool dry, check_w;
+  const char* prefix;      // of the weight-slot messages ("vgg: ", "lpips: ")
+  int err = 0;
+  const void* W(const std::string& n, int dtype, int64_t numel) {
+    if (!check_w) return (const void*)(uintptr_t)0x1000;
+    if (err) return nullptr;
+    return m->w.find(n, dtype, numel, &err, prefix);
+  }
+  // the partials are exactly what this launch needs (a tower whose pass sizes must be monotone in the batch reserves its own bound)
+  int gemm(MvdGemmArgs& g) { return err ? err : arena_gemm(m->ar, g, s, dry); }
+};
+
+// Pairs per pass of a loss that runs in several passes: *pp shrinks (by the ratio of bound to need) until its passes fit `bound` bytes.
+// need_of(pp, &need) sizes them: an error, or 0 with need = the bytes, ~size_t(0) when a pass of pp pairs has 2^31 rows or more.
+// -4 and "<who>: workspace too small for one pair ..." when not even one pair fits.
+template <class NeedOf> int pairs_per_pass(const char* who, int h, int w, int64_t bound, NeedOf&& need_of, int* pp) {
+  for (;;) {
+    size_t need = 0;
+    CHECK(need_of(*pp, &need));
+    if (need <= (size_t)bound) return 0;
+    if (*pp == 1) { mvd_set_error("%s: workspace too small for one pair of %d x %d: need %zu bytes, bound %lld", who, h, w, need, (long long)bound); return -4; }
+    const int guess = need == ~size_t(0) ? *pp / 2 : (int)((double)*pp * (double)bound / (double)need);
+    *pp = guess < 1 ? 1 : (guess >= *pp ? *pp - 1 : guess);
+  }
 }

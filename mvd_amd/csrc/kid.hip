@@ -20,13 +20,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 namespace {
 
-int kcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // ---------------------------------------------------------------- polynomial-kernel MMD
 // Tiles of one subset, T = ceil(m / 64): xx and yy keep the T (T + 1) / 2 tiles with tj >= ti, row-major over (ti, tj), and count a
 // tile off the diagonal twice (a multiplication by 2: exact); xy keeps all T T.  Tile order: xx, yy, xy.
@@ -317,9 +310,9 @@ int mvd_op_kid_mmd(const float* f_real, int n_real, const float* f_fake, int n_f
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(kid_mmd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f_real, n_real, f_fake, n_fake, d, idx, m, degree, gamma, coef, tiles,
                      (double*)ws);
-  CHECK(kcheck("kid_mmd"));
+  CHECK(launch_check("kid_mmd"));
   hipLaunchKernelGGL(kid_finish_kernel, dim3((unsigned)((subsets + 255) / 256)), dim3(256), 0, s, (const double*)ws, subsets, m, tiles, sums, out);
-  return kcheck("kid_mmd (finish)");
+  return launch_check("kid_mmd (finish)");
 }
 
 int mvd_op_fc_logits(const float* f, int n, int d, const float* w, int classes, float* out, void* stream) {
@@ -328,7 +321,7 @@ int mvd_op_fc_logits(const float* f, int n, int d, const float* w, int classes, 
   const long by = ((long)n + FC_ROWS - 1) / FC_ROWS;
   if (by > 65535) { mvd_set_error("fc_logits: n = %d is too many rows for one launch (at most %d)", n, 65535 * FC_ROWS); return -1; }
   hipLaunchKernelGGL(fc_logits_kernel, dim3((unsigned)((classes + 3) / 4), (unsigned)by), dim3(256), 0, (hipStream_t)stream, f, n, d, w, classes, out);
-  return kcheck("fc_logits");
+  return launch_check("fc_logits");
 }
 
 int64_t mvd_op_inception_score_workspace_bytes(int n, int classes, int splits) {
@@ -354,12 +347,12 @@ int mvd_op_inception_score(const float* logits, int n, int classes, const int* p
   double* log_mean = (double*)((char*)ws + L.log_mean);
   double* kl = (double*)((char*)ws + L.kl);
   hipLaunchKernelGGL(is_lse_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, logits, n, classes, lse);
-  CHECK(kcheck("inception_score (lse)"));
+  CHECK(launch_check("inception_score (lse)"));
   hipLaunchKernelGGL(is_mean_kernel, dim3((unsigned)mean_blocks), dim3(256), 0, s, logits, n, classes, perm, L.chunk, L.n_chunks, (const double*)lse, log_mean);
-  CHECK(kcheck("inception_score (mean)"));
+  CHECK(launch_check("inception_score (mean)"));
   hipLaunchKernelGGL(is_kl_kernel, dim3((unsigned)L.n_chunks), dim3(256), 0, s, logits, n, classes, perm, L.chunk, (const double*)lse,
                      (const double*)log_mean, kl, out);
-  return kcheck("inception_score (kl)");
+  return launch_check("inception_score (kl)");
 }
 
 }  // extern "C"

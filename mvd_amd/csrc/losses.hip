@@ -17,12 +17,6 @@ constexpr int NT = 256;                 // threads of every kernel here (4 waves
 
 MVD_DEVINL int clamp_t(int t, int T) { return t < 0 ? 0 : (t >= T ? T - 1 : t); }      // address safety only
 
-MVD_DEVINL double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // block-wide sums of (a, b), the same value in every thread: shuffle tree per wave, then the four wave sums in wave order
 MVD_DEVINL void block_sum2(float& a, float& b, float* sm /* [8] */) {
   a = wave_sum(a);
@@ -298,8 +292,8 @@ __global__ __launch_bounds__(NT) void image_metrics_finalize_kernel(const float*
     double a = 0.0, b = 0.0;
 #pragma unroll 8                          // eight loads in flight; the adds stay in index order
     for (long i = lane; i < ppi; i += 64) { const float2 v = p[i]; a += (double)v.x; b += (double)v.y; }
-    a = wave_sum_d(a) * inv_px;
-    b = want_ssim ? wave_sum_d(b) * inv_map : 0.0;
+    a = wave_sum_f64(a) * inv_px;
+    b = want_ssim ? wave_sum_f64(b) * inv_map : 0.0;
     if (lane == 0) {
       img_acc[2 * img] = a;
       img_acc[2 * img + 1] = b;
@@ -312,8 +306,8 @@ __global__ __launch_bounds__(NT) void image_metrics_finalize_kernel(const float*
     const volatile double* acc = img_acc;
     double a = 0.0, b = 0.0;
     for (int i = lane; i < n_img; i += 64) { a += acc[2 * i]; b += acc[2 * i + 1]; }
-    a = wave_sum_d(a) / n_img;
-    b = wave_sum_d(b) / n_img;
+    a = wave_sum_f64(a) / n_img;
+    b = wave_sum_f64(b) / n_img;
     if (lane == 0) {
       result[0] = (float)a;
       result[1] = (float)b;

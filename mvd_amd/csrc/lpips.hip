@@ -23,14 +23,6 @@
 
 namespace {
 
-int lcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-long blocks_of(long n) { return (n + 255) / 256; }
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // ---------------------------------------------------------------- im2col, from the fp32 NCHW image: 11x11, stride 4, pad 2, 3 channels
 // One thread per 16-byte chunk (8 columns) of a row; column (ky * 11 + kx) * 3 + c, zero padded 363 -> 384.  Images b < nx come
 // from x, the others from y: both halves of a pair in one launch.  The affine map touches in-image taps only.
@@ -86,10 +78,6 @@ __global__ __launch_bounds__(256) void im2col_patch_map_kernel(const bf16_t* __r
 // ---------------------------------------------------------------- 3x3 max-pool, stride 2, no padding, floor
 // One thread per 16-byte chunk (8 channels) of the output: nine 16-byte loads, one store.  The maximum of bf16 values is one of
 // them, so nothing is rounded.  The last window ends at row 2 (oh - 1) + 2 <= h - 1.
-MVD_DEVINL unsigned int max2bf(unsigned int a, unsigned int b) {
-  const float lo = fmaxf(bflo(a), bflo(b)), hi = fmaxf(bfhi(a), bfhi(b));
-  return pack2bf(lo, hi);
-}
 __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const bf16_t* __restrict__ x, int h, int w, int oh, int ow, int c8, long total,
                                                            bf16_t* __restrict__ y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -124,18 +112,6 @@ constexpr int HEAD_MAX_LAYERS = 8;
 struct HeadLayer { const void* x; const void* y; const float* w; int pixels, c, bf16, relu, chunk0, nchunks; };
 struct HeadTable { HeadLayer L[HEAD_MAX_LAYERS]; int n, chunks; };
 
-MVD_DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-MVD_DEVINL double block_sum_f64(double v, double* red) {   // 256 threads; every thread gets the sum
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 MVD_DEVINL float sum8(float v) {      // over the eight lanes of a pixel
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -263,9 +239,9 @@ int finish_table(HeadTable& T, const char* who) {
 int launch_head(const HeadTable& T, int pairs, double* part, double* total, int first, int last, long all_pairs, float* per_pair, float* per_layer,
                 float* mean, hipStream_t s) {
   hipLaunchKernelGGL(lpips_head_kernel, dim3(T.chunks, pairs), dim3(256), 0, s, T, part);
-  CHECK(lcheck("lpips head"));
+  CHECK(launch_check("lpips head"));
   hipLaunchKernelGGL(lpips_finish_kernel, dim3(1), dim3(256), 0, s, T, part, pairs, total, first, last, all_pairs, per_pair, per_layer, mean);
-  return lcheck("lpips finish");
+  return launch_check("lpips finish");
 }
 
 int launch_im2col_image(const float* x, int nx, const float* y, int ny, int h, int w, const float* scale, const float* shift, bf16_t* out, hipStream_t s) {
@@ -274,13 +250,13 @@ int launch_im2col_image(const float* x, int nx, const float* y, int ny, int h, i
   if (blocks_of(total) >= (1L << 31)) { mvd_set_error("im2col_patch: too many rows for one launch"); return -1; }
   hipLaunchKernelGGL(im2col_patch_image_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, nx, y ? y : x, h, w, oh, ow, scale[0], scale[1], scale[2],
                      shift[0], shift[1], shift[2], total, out);
-  return lcheck("im2col_patch (image)");
+  return launch_check("im2col_patch (image)");
 }
 int launch_im2col_map(const bf16_t* x, int batch, int h, int w, bf16_t* out, hipStream_t s) {
   const long total = (long)batch * h * w * (P2_COLS / 8);
   if (blocks_of(total) >= (1L << 31)) { mvd_set_error("im2col_patch: too many rows for one launch"); return -1; }
   hipLaunchKernelGGL(im2col_patch_map_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, h, w, total, out);
-  return lcheck("im2col_patch (map)");
+  return launch_check("im2col_patch (map)");
 }
 int launch_maxpool3(const bf16_t* x, int batch, int h, int w, int c, bf16_t* y, hipStream_t s) {
   if (!x || !y || batch <= 0 || h < 3 || w < 3 || c <= 0 || c % 8) { mvd_set_error("maxpool3x3s2: bad arguments (batch %d, %d x %d, c=%d: c %% 8 == 0, h, w >= 3)", batch, h, w, c); return -1; }
@@ -289,7 +265,7 @@ int launch_maxpool3(const bf16_t* x, int batch, int h, int w, int c, bf16_t* y, 
   const long total = (long)batch * oh * ow * (c / 8);
   if (blocks_of(total) >= (1L << 31)) { mvd_set_error("maxpool3x3s2: too many elements for one launch"); return -1; }
   hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, h, w, oh, ow, c / 8, total, y);
-  return lcheck("maxpool3x3s2");
+  return launch_check("maxpool3x3s2");
 }
 
 // ---------------------------------------------------------------- the layer table of torchvision's alexnet().features[:12]
@@ -312,46 +288,35 @@ Geo geo_of(int h, int w) {
 
 }  // namespace
 
-struct mvd_lpips {
-  WeightTable w;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
-  Arena ar;
-};
+struct mvd_lpips : ModuleBase {};
 
 namespace {
 
-constexpr size_t kSplitReserve = (size_t)512 * 128 * 128;      // floats: see LCtx::gemm
+constexpr size_t kSplitReserve = (size_t)512 * 128 * 128;      // floats: see tower_gemm
 
-struct LCtx {
-  mvd_lpips* v; hipStream_t s; bool dry, check_w;
-  int err = 0;
-  const void* W(const std::string& n, int dtype, int64_t numel) {
-    if (!check_w) return (const void*)(uintptr_t)0x1000;
-    if (err) return nullptr;
-    return v->w.find(n, dtype, numel, &err, "lpips: ");
+// The lock-step tiles with the split-K the tile heuristic asks for, as the VGG tower does -- but NOT TowerCtx::gemm: the split
+// factor is not monotone in M (a smaller batch can ask for a split that a larger one does not), so the sizing run reserves a bound
+// on the partials that is: S <= 16, and S <= 512 / tiles with tiles >= M N / (128 x 128) on the ReLU tiles, so
+// S M N <= min(16 M N, 512 x 128 x 128).  Then the bytes of a pass never shrink when images are added, and a workspace sized for a
+// full pass holds every shorter one.
+int tower_gemm(TowerCtx& c, MvdGemmArgs& g) {
+  if (c.err) return c.err;
+  Arena& ar = c.m->ar;
+  const int S = mvd_gemm_pick_splitk(g);
+  const size_t mark = ar.off;
+  const size_t mn = (size_t)g.M * g.N, reserve = 16 * mn < kSplitReserve ? 16 * mn : kSplitReserve;
+  if (S > 1) {
+    g.splitk = S;
+    if (!c.dry && S * mn > reserve) { mvd_set_error("lpips: split-K %d of a %d x %d GEMM exceeds the partials the workspace was sized for", S, g.M, g.N); return c.err = -4; }
+    g.part = ar.alloc_n<float>(c.dry ? reserve : S * mn);
+  } else if (c.dry) {
+    ar.alloc_n<float>(reserve);
   }
-  // the lock-step tiles with the split-K the tile heuristic asks for, as the VGG tower does.  The split factor is NOT monotone
-  // in M (a smaller batch can ask for a split that a larger one does not), so the sizing run reserves a bound on the partials that
-  // is: S <= 16, and S <= 512 / tiles with tiles >= M N / (128 x 128) on the ReLU tiles, so S M N <= min(16 M N, 512 x 128 x 128).
-  // Then the bytes of a pass never shrink when images are added, and a workspace sized for a full pass holds every shorter one.
-  int gemm(MvdGemmArgs& g) {
-    if (err) return err;
-    const int S = mvd_gemm_pick_splitk(g);
-    const size_t mark = v->ar.off;
-    const size_t mn = (size_t)g.M * g.N, reserve = 16 * mn < kSplitReserve ? 16 * mn : kSplitReserve;
-    if (S > 1) {
-      g.splitk = S;
-      if (!dry && S * mn > reserve) { mvd_set_error("lpips: split-K %d of a %d x %d GEMM exceeds the partials the workspace was sized for", S, g.M, g.N); return err = -4; }
-      g.part = v->ar.alloc_n<float>(dry ? reserve : S * mn);
-    } else if (dry) {
-      v->ar.alloc_n<float>(reserve);
-    }
-    if (v->ar.overflow()) { mvd_set_error("lpips: workspace too small for this pass"); return err = -4; }
-    const int r = dry ? 0 : launch_tiled(g, s);
-    v->ar.off = mark;
-    return r;
-  }
-};
+  if (ar.overflow()) { mvd_set_error("lpips: workspace too small for this pass"); return c.err = -4; }
+  const int r = c.dry ? 0 : launch_tiled(g, c.s);
+  ar.off = mark;
+  return r;
+}
 
 int check_geometry(const char* who, int images, int h, int w) {
   // below 31 the second pool has no output: (h - 7) / 4 + 1 = 6 -> 2 -> nothing
@@ -363,8 +328,8 @@ int check_geometry(const char* who, int images, int h, int w) {
 
 // x / y: two fp32 NCHW arrays of nx / ny images that form ONE batch of nx + ny (y may be null).  taps: null, or five nullable
 // buffers; tap_out receives where the five maps are (the caller's buffers, or the arena's).
-int tower(LCtx& c, const float* x, int nx, const float* y, int ny, int h, int w, void* const* taps, bf16_t** tap_out) {
-  Arena& ar = c.v->ar;
+int tower(TowerCtx& c, const float* x, int nx, const float* y, int ny, int h, int w, void* const* taps, bf16_t** tap_out) {
+  Arena& ar = c.m->ar;
   const int B = nx + ny;
   const Geo G = geo_of(h, w);
   bf16_t* tap[5];
@@ -392,7 +357,7 @@ int tower(LCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
     }
     MvdGemmArgs g = gemm_dense(cols, nullptr, P1_COLS, 0, M, wt[0], 0, bias[0], 64, tap[0], 64);
     g.relu = 1;
-    CHECK(c.gemm(g));
+    CHECK(tower_gemm(c, g));
     ar.off = mark;
   }
   // pool, conv2: im2col rows, then a dense GEMM (the buffers below reuse the rows of conv1: everything is in stream order)
@@ -407,7 +372,7 @@ int tower(LCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
     }
     MvdGemmArgs g = gemm_dense(cols, nullptr, P2_COLS, 0, M, wt[1], 0, bias[1], 192, tap[1], 192);
     g.relu = 1;
-    CHECK(c.gemm(g));
+    CHECK(tower_gemm(c, g));
     ar.off = mark;
   }
   // pool, conv3 - conv5 on the implicit-GEMM tiles
@@ -418,7 +383,7 @@ int tower(LCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
   for (int k = 2; k < 5; ++k) {
     MvdGemmArgs g = gemm_conv3(in, G.ph2, G.pw2, kConvs[k].cin, 1, 0, 0, nullptr, nullptr, 0, 0, wt[k], bias[k], B, G.ph2, G.pw2, kConvs[k].cout, tap[k]);
     g.relu = 1;
-    CHECK(c.gemm(g));
+    CHECK(tower_gemm(c, g));
     in = tap[k];
   }
   ar.off = mark;
@@ -426,7 +391,7 @@ int tower(LCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
 }
 
 // the head's table over the taps of `np` pairs stacked as [x of the pass; y of the pass]
-int pair_table(LCtx& c, bf16_t* const* tap, int np, const Geo& G, HeadTable& T) {
+int pair_table(TowerCtx& c, bf16_t* const* tap, int np, const Geo& G, HeadTable& T) {
   memset(&T, 0, sizeof(T));
   T.n = 5;
   for (int k = 0; k < 5; ++k) {
@@ -441,7 +406,7 @@ int pair_table(LCtx& c, bf16_t* const* tap, int np, const Geo& G, HeadTable& T) 
 // arena bytes of one pass over `images` images, the head's partial sums of images / 2 pairs included
 int pass_bytes(mvd_lpips* v, int images, int h, int w, size_t* out) {
   v->ar.reset(true);
-  LCtx c{v, nullptr, true, false};
+  TowerCtx c{v, nullptr, true, false, "lpips: "};
   bf16_t* tap[5];
   CHECK(tower(c, nullptr, images, nullptr, 0, h, w, nullptr, tap));
   HeadTable T;
@@ -452,7 +417,7 @@ int pass_bytes(mvd_lpips* v, int images, int h, int w, size_t* out) {
 }
 
 int check_weights(mvd_lpips* v, bool head) {
-  LCtx c{v, nullptr, true, true};
+  TowerCtx c{v, nullptr, true, true, "lpips: "};
   for (int k = 0; k < 5; ++k) {
     const std::string name = "features." + std::to_string(kConvs[k].idx);
     c.W(name + ".weight", 1, kConvs[k].cout * packed_k(kConvs[k]));
@@ -461,12 +426,6 @@ int check_weights(mvd_lpips* v, bool head) {
     if (c.err) return c.err;
   }
   return 0;
-}
-
-void bind_arena(mvd_lpips* v) {
-  v->ar.reset(false);
-  v->ar.base = reinterpret_cast<char*>(v->ws_ptr) + HEAD_BYTES;
-  v->ar.cap = (size_t)v->ws_bytes - HEAD_BYTES;
 }
 
 }  // namespace
@@ -481,10 +440,7 @@ int mvd_lpips_create(mvd_lpips_t** out) {
 int mvd_lpips_destroy(mvd_lpips_t* v) { delete v; return 0; }
 
 int mvd_lpips_set_weight(mvd_lpips_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("lpips_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("lpips_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(v, "lpips", slot, ptr, numel, dtype);
 }
 
 int64_t mvd_lpips_workspace_bytes(mvd_lpips_t* v, int images, int h, int w) {
@@ -496,9 +452,7 @@ int64_t mvd_lpips_workspace_bytes(mvd_lpips_t* v, int images, int h, int w) {
 }
 
 int mvd_lpips_bind_workspace(mvd_lpips_t* v, void* ws, int64_t bytes) {
-  if (!v || !ws || bytes <= HEAD_BYTES || ((uintptr_t)ws & 255)) { mvd_set_error("lpips_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  v->ws_ptr = ws; v->ws_bytes = bytes;
-  return 0;
+  return module_bind_workspace(v, "lpips", ws, bytes, HEAD_BYTES);
 }
 
 int mvd_lpips_features(mvd_lpips_t* v, const float* images_nchw, int images, int h, int w, void* const* taps, void* stream) {
@@ -511,8 +465,8 @@ int mvd_lpips_features(mvd_lpips_t* v, const float* images_nchw, int images, int
   if (int r = pass_bytes(v, images, h, w, &need)) return r;
   if (!v->ws_ptr) { mvd_set_error("lpips_features: workspace not bound"); return -1; }
   if (need > (size_t)v->ws_bytes) { mvd_set_error("lpips_features: workspace too small: need %zu bytes, bound %lld", need, (long long)v->ws_bytes); return -4; }
-  bind_arena(v);
-  LCtx c{v, (hipStream_t)stream, false, true};
+  module_bind_arena(*v, HEAD_BYTES);
+  TowerCtx c{v, (hipStream_t)stream, false, true, "lpips: "};
   bf16_t* tap[5];
   return tower(c, images_nchw, images, nullptr, 0, h, w, taps, tap);
 }
@@ -528,28 +482,21 @@ int mvd_lpips_distance(mvd_lpips_t* v, const float* x, const float* y, int pairs
   // pairs per pass: as many as the bound workspace holds
   int pp = pairs > 32768 ? 32768 : pairs;      // (the head's grid: one row of workgroups per pair)
   if (max_pairs_per_pass > 0 && pp > max_pairs_per_pass) pp = max_pairs_per_pass;
-  size_t need = 0;
-  for (;;) {
-    if ((long)2 * pp * G.h[0] * G.w[0] < (1L << 31) - 256) {
-      if (int r = pass_bytes(v, 2 * pp, h, w, &need)) return r;
-      // the shorter last pass is sized too: nothing is launched unless every pass that will run fits
-      size_t tail = 0;
-      if (pairs % pp) { if (int r = pass_bytes(v, 2 * (pairs % pp), h, w, &tail)) return r; }
-      if (tail > need) need = tail;
-      if (need <= (size_t)v->ws_bytes) break;
-    } else {
-      need = ~size_t(0);
-    }
-    if (pp == 1) { mvd_set_error("lpips_distance: workspace too small for one pair of %d x %d: need %zu bytes, bound %lld", h, w, need, (long long)v->ws_bytes); return -4; }
-    int guess = need == ~size_t(0) ? pp / 2 : (int)((double)pp * (double)v->ws_bytes / (double)need);
-    pp = guess < 1 ? 1 : (guess >= pp ? pp - 1 : guess);
-  }
+  CHECK(pairs_per_pass("lpips_distance", h, w, v->ws_bytes, [&](int n, size_t* need) {
+    if ((long)2 * n * G.h[0] * G.w[0] >= (1L << 31) - 256) { *need = ~size_t(0); return 0; }
+    CHECK(pass_bytes(v, 2 * n, h, w, need));
+    // the shorter last pass is sized too: nothing is launched unless every pass that will run fits
+    size_t tail = 0;
+    if (pairs % n) CHECK(pass_bytes(v, 2 * (pairs % n), h, w, &tail));
+    if (tail > *need) *need = tail;
+    return 0;
+  }, &pp));
   const size_t img = (size_t)3 * h * w;
   double* total = reinterpret_cast<double*>(v->ws_ptr);
   for (int p0 = 0; p0 < pairs; p0 += pp) {
     const int np = pairs - p0 < pp ? pairs - p0 : pp;
-    bind_arena(v);
-    LCtx c{v, (hipStream_t)stream, false, true};
+    module_bind_arena(*v, HEAD_BYTES);
+    TowerCtx c{v, (hipStream_t)stream, false, true, "lpips: "};
     bf16_t* tap[5];
     CHECK(tower(c, x + p0 * img, np, y + p0 * img, np, h, w, nullptr, tap));
     HeadTable T;

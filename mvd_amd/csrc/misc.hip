@@ -3,7 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "kernels.h"
+#include "host_util.h"
 
 static thread_local char g_err[512] = "";
 void mvd_set_error(const char* fmt, ...) {
@@ -435,11 +435,6 @@ __global__ void film_nchw_f32_kernel(const float* __restrict__ x, int c, int hw,
   y[i] = fmaf(x[i], scale[bc], shift[bc]);
 }
 
-int check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
 inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
@@ -449,14 +444,14 @@ int mvd_launch_nchw_to_nhwc(const float* x, int batch, int c, int hw, const floa
   if (!x || !y || batch <= 0 || c <= 0 || hw <= 0 || ((scale == nullptr) != (shift == nullptr))) { mvd_set_error("nchw_to_nhwc: bad arguments"); return -1; }
   const long total = (long)batch * c * hw;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, x, c, hw, scale, shift, ld_ss, y, total);
-  return check("nchw_to_nhwc");
+  return launch_check("nchw_to_nhwc");
 }
 
 int mvd_launch_nhwc_to_nchw_f32(const bf16_t* x, int batch, int hw, int c, float* y, hipStream_t s) {
   if (!x || !y || batch <= 0 || c <= 0 || hw <= 0) { mvd_set_error("nhwc_to_nchw: bad arguments"); return -1; }
   const long total = (long)batch * c * hw;
   hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, x, hw, c, y, total);
-  return check("nhwc_to_nchw");
+  return launch_check("nhwc_to_nchw");
 }
 
 int mvd_launch_film(const bf16_t* x, int batch, int hw, int c, const float* scale, const float* shift, int ld_ss,
@@ -466,7 +461,7 @@ int mvd_launch_film(const bf16_t* x, int batch, int hw, int c, const float* scal
   int grid = nblk(nvec, 256);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(film_kernel, dim3(grid), dim3(256), 0, s, x, hw, c, scale, shift, ld_ss, y, nvec);
-  return check("film");
+  return launch_check("film");
 }
 
 int mvd_launch_conv_in(const bf16_t* x, int batch, int h, int w, int cin, const float* wt, const float* bias, int cout,
@@ -474,7 +469,7 @@ int mvd_launch_conv_in(const bf16_t* x, int batch, int h, int w, int cin, const 
   if (!x || !y || !wt || !bias || batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cin > 16 || (cout % 8)) { mvd_set_error("conv_in: bad arguments"); return -1; }
   const long total = (long)batch * h * w * (cout / 8);
   hipLaunchKernelGGL(conv_in_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, x, h, w, cin, wt, bias, cout, y, total);
-  return check("conv_in");
+  return launch_check("conv_in");
 }
 
 #ifdef MVD_PROBE
@@ -543,12 +538,12 @@ int mvd_launch_conv_out(const bf16_t* x, int batch, int h, int w, int c, const b
                 (int)getpid(), calls - 1, c0, c1, c2, (unsigned long long)vc[3], (unsigned long long)vc[3] % 4);
       }
     }
-    return check("conv_out4");
+    return launch_check("conv_out4");
   }
 #endif
   const long pix = (long)batch * h * w;
   hipLaunchKernelGGL(conv_out_kernel, dim3(nblk(pix, 4)), dim3(256), 0, s, x, batch, h, w, c, wt, bias, cout, y);
-  return check("conv_out");
+  return launch_check("conv_out");
 }
 
 int mvd_launch_f32_to_bf16(const float* x, int64_t n, bf16_t* y, hipStream_t s) {
@@ -556,7 +551,7 @@ int mvd_launch_f32_to_bf16(const float* x, int64_t n, bf16_t* y, hipStream_t s) 
   int grid = nblk(n, 256);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid), dim3(256), 0, s, x, (long)n, y);
-  return check("f32_to_bf16");
+  return launch_check("f32_to_bf16");
 }
 
 int mvd_launch_skinny_linear(const float* x, int ldx, int batch, int k, const void* w, int wbf16, const float* bias, int n,
@@ -575,18 +570,18 @@ int mvd_launch_skinny_linear(const float* x, int ldx, int batch, int k, const vo
     const MvdSegTable none{};
     if (wbf16) hipLaunchKernelGGL((skinny_mfma_kernel<true, false>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy, none, 0);
     else hipLaunchKernelGGL((skinny_mfma_kernel<false, false>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy, none, 0);
-    return check("skinny_mfma");
+    return launch_check("skinny_mfma");
   }
   if (vec && use_vec) {
     constexpr int F = 2;
     const dim3 g(nblk(n, 4 * F));
     if (wbf16) hipLaunchKernelGGL((skinny_linear_vec_kernel<true, F>), g, dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy);
     else hipLaunchKernelGGL((skinny_linear_vec_kernel<false, F>), g, dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy);
-    return check("skinny_linear");
+    return launch_check("skinny_linear");
   }
   if (wbf16) hipLaunchKernelGGL(skinny_linear_kernel<true>, dim3(nblk(n, 4)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy);
   else hipLaunchKernelGGL(skinny_linear_kernel<false>, dim3(nblk(n, 4)), dim3(256), 0, s, x, ldx, batch, k, w, bias, n, act_in, y, ldy);
-  return check("skinny_linear");
+  return launch_check("skinny_linear");
 }
 
 int mvd_launch_skinny_linear_grouped(const float* x, int ldx, int xseg, int batch, int k, const float* w, const float* bias, int n,
@@ -598,10 +593,10 @@ int mvd_launch_skinny_linear_grouped(const float* x, int ldx, int xseg, int batc
   for (int g = 0; g + 1 < seg.n; ++g) tiles_ok = tiles_ok && seg.end[g] % 32 == 0;
   if (tiles_ok) {
     hipLaunchKernelGGL((skinny_mfma_kernel<false, true>), dim3(nblk(n, 32)), dim3(256), 0, s, x, ldx, batch, k, (const void*)w, bias, n, 0, y, ldy, seg, xseg);
-    return check("skinny_mfma_grouped");
+    return launch_check("skinny_mfma_grouped");
   }
   hipLaunchKernelGGL((skinny_linear_vec_kernel<false, 2, true>), dim3(nblk(n, 8)), dim3(256), 0, s, x, ldx, batch, k, (const void*)w, bias, n, 0, y, ldy, seg, xseg);
-  return check("skinny_linear_grouped");
+  return launch_check("skinny_linear_grouped");
 }
 
 __global__ void film_params_grouped_kernel(const float* __restrict__ raw, int batch, int ldraw, const MvdSegTable seg, float strength,
@@ -628,20 +623,20 @@ int mvd_launch_film_params_grouped(const float* raw, int batch, const MvdSegTabl
   if (!raw || !out || batch <= 0 || out_rows < batch || seg.n < 1 || seg.n > 16) { mvd_set_error("film_params_grouped: bad arguments"); return -1; }
   const int total = out_rows * (seg.end[seg.n - 1] / 2);
   hipLaunchKernelGGL(film_params_grouped_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, raw, batch, seg.end[seg.n - 1], seg, strength, out, out_rows, total);
-  return check("film_params_grouped");
+  return launch_check("film_params_grouped");
 }
 
 int mvd_launch_timestep_embedding(const float* t, int batch, int dim, float* y, hipStream_t s) {
   if (!t || !y || batch <= 0 || dim <= 0 || (dim & 1)) { mvd_set_error("timestep_embedding: bad arguments"); return -1; }
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3(batch), dim3(128), 0, s, t, dim, y);
-  return check("timestep_embedding");
+  return launch_check("timestep_embedding");
 }
 
 int mvd_launch_camera_features(const float* src, const float* tgt, int batch, int cam_rows, int nfreq, float max_freq,
                                float* rflat, float* enc, hipStream_t s) {
   if (!src || !tgt || !rflat || !enc || batch <= 0 || (cam_rows != 3 && cam_rows != 4) || nfreq < 2) { mvd_set_error("camera_features: bad arguments"); return -1; }
   hipLaunchKernelGGL(camera_features_kernel, dim3(batch), dim3(256), 0, s, src, tgt, cam_rows, nfreq, logf(max_freq), rflat, enc);
-  return check("camera_features");
+  return launch_check("camera_features");
 }
 
 int mvd_launch_film_params(const float* raw, int batch, int dim, float strength, float* scale, float* shift, int out_rows,
@@ -649,7 +644,7 @@ int mvd_launch_film_params(const float* raw, int batch, int dim, float strength,
   if (!raw || !scale || !shift || batch <= 0 || dim <= 0 || out_rows < batch) { mvd_set_error("film_params: bad arguments"); return -1; }
   const int total = out_rows * dim;
   hipLaunchKernelGGL(film_params_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, raw, batch, dim, strength, scale, shift, total);
-  return check("film_params");
+  return launch_check("film_params");
 }
 
 int mvd_launch_film_nchw_f32(const float* x, int batch, int c, int hw, const float* scale, const float* shift, float* y,
@@ -657,7 +652,7 @@ int mvd_launch_film_nchw_f32(const float* x, int batch, int c, int hw, const flo
   if (!x || !y || !scale || !shift || batch <= 0 || c <= 0 || hw <= 0) { mvd_set_error("film_nchw: bad arguments"); return -1; }
   const long total = (long)batch * c * hw;
   hipLaunchKernelGGL(film_nchw_f32_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, x, c, hw, scale, shift, y, total);
-  return check("film_nchw");
+  return launch_check("film_nchw");
 }
 
 int mvd_launch_im2col_in(const float* x, int batch, int c, int h, int w, const float* scale, const float* shift, int ld_ss,
@@ -674,5 +669,5 @@ int mvd_launch_im2col_in(const float* x, int batch, int c, int h, int w, const f
     case 6: hipLaunchKernelGGL(im2col_in_kernel<6>, g, t, 0, s, x, h, w, scale, shift, ld_ss, y, total); break;
     default: hipLaunchKernelGGL(im2col_in_kernel<7>, g, t, 0, s, x, h, w, scale, shift, ld_ss, y, total); break;
   }
-  return check("im2col_in");
+  return launch_check("im2col_in");
 }

@@ -26,13 +26,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 namespace {
 
-int pcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 constexpr int PR_KC = 32;             // K elements staged per step
 constexpr int PR_LD = PR_KC + 4;      // LDS row stride in floats: 16-byte rows, lane (q, r) reads bank 4 r + q of 64 (kid_mmd_kernel's stage)
 constexpr int PR_STAGE_BYTES = 128 * PR_LD * 4;
@@ -311,9 +304,9 @@ int mvd_op_knn_radii(const float* f, int n, int d, int k, int force_parts, doubl
   const int tiles = (n + 63) / 64, parts = knn_parts(n, force_parts);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(knn_radii_kernel, dim3((unsigned)tiles, (unsigned)parts), dim3(256), 0, s, f, n, d, k, tiles, parts, (double*)ws);
-  CHECK(pcheck("knn_radii"));
+  CHECK(launch_check("knn_radii"));
   hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)tiles), dim3(64), 0, s, (const double*)ws, n, k, parts, radii_sq, knn_sq);
-  return pcheck("knn_radii (merge)");
+  return launch_check("knn_radii (merge)");
 }
 
 int mvd_op_manifold_counts(const float* q, int nq, const float* r, int nr, int d, const double* r_radii_sq, int closed, int32_t* hits_per_query,
@@ -337,7 +330,7 @@ int mvd_op_manifold_counts(const float* q, int nq, const float* r, int nr, int d
   if (!hits_per_query && !hits_per_ref) return 0;
   hipLaunchKernelGGL(manifold_counts_kernel, dim3((unsigned)rt, (unsigned)qt), dim3(256), 0, s, q, nq, r, nr, d, r_radii_sq, closed, (int*)hits_per_query,
                      (int*)hits_per_ref);
-  return pcheck("manifold_counts");
+  return launch_check("manifold_counts");
 }
 
 }  // extern "C"

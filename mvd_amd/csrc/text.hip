@@ -181,15 +181,13 @@ int launch_attn_causal(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t
   // scale == 0: q already carries softmax_scale * log2(e) (the packed q rows, as for mvd_op_attention)
   const float sl = scale == 0.f ? 1.0f : scale * 1.4426950408889634f;
   hipLaunchKernelGGL(text_attn_causal_kernel, dim3(batch * heads), dim3(256), 0, s, q, k, v, o, heads, n, ldq, ldk, ldv, ldo, sl);
-  return tcheck("attention_causal");
+  return launch_check("attention_causal");
 }
 
 }  // namespace
 
-struct mvd_text {
+struct mvd_text : ModuleBase {      // (ar unused: the arena of a run lives in its ClipCtx, behind the split-K tile counters)
   mvd_text_config_t cfg;
-  WeightTable w;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
 };
 
 namespace {
@@ -213,7 +211,7 @@ int encode_impl(mvd_text* t, const int* ids, int B, int T, float* out, hipStream
   if (x.err) return x.err;
   if (!dry) {
     hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, tok, pos, M, T, H, c.vocab_size, b.xs);
-    CHECK(tcheck("text embedding"));
+    CHECK(launch_check("text embedding"));
   }
   CHECK(clip_layers(x, b, c.num_layers, H, I, M, c.act, [&](const bf16_t* qkv, bf16_t* at) {
     return launch_attn_causal(qkv, qkv + H, qkv + 2 * H, at, B, c.num_heads, T, 3 * H, 3 * H, 3 * H, H, 0.f, s);   // q rows prescaled at pack time
@@ -253,10 +251,7 @@ int mvd_text_create(const mvd_text_config_t* cfg, mvd_text_t** out) {
 int mvd_text_destroy(mvd_text_t* t) { delete t; return 0; }
 
 int mvd_text_set_weight(mvd_text_t* t, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!t || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("text_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("text_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  t->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(t, "text", slot, ptr, numel, dtype);
 }
 
 int64_t mvd_text_workspace_bytes(mvd_text_t* t, int batch, int seq_len) {
@@ -268,9 +263,7 @@ int64_t mvd_text_workspace_bytes(mvd_text_t* t, int batch, int seq_len) {
 }
 
 int mvd_text_bind_workspace(mvd_text_t* t, void* ws, int64_t bytes) {
-  if (!t || !ws || bytes <= 0 || ((uintptr_t)ws & 255)) { mvd_set_error("text_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  t->ws_ptr = ws; t->ws_bytes = bytes;
-  return 0;
+  return module_bind_workspace(t, "text", ws, bytes, 0);
 }
 
 int mvd_text_encode(mvd_text_t* t, const int32_t* ids, int batch, int seq_len, float* out, void* stream) {

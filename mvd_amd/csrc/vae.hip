@@ -76,19 +76,10 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, const floa
   out[i] = (mean + __expf(0.5f * lv) * noise[i]) * scale;
 }
 
-int vcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-
 }  // namespace
 
-struct mvd_vae {
+struct mvd_vae : ModuleBase {
   mvd_vae_config_t cfg;
-  WeightTable w;
-  Arena ar;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
 };
 
 namespace {
@@ -106,15 +97,7 @@ struct VCtx {
   Act act(int B, int H, int W_, int C) { return arena_act(v->ar, B, H, W_, C); }
 
   // the tiled kernels only (never the small-M kernels); an unsplit launch leaves splitk = 0, "undecided"
-  int gemm(MvdGemmArgs& g) {
-    if (err) return err;
-    const int S = mvd_gemm_pick_splitk(g);
-    const size_t mark = v->ar.off;
-    if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * g.M * g.N); }
-    const int r = dry ? 0 : launch_tiled(g, s);
-    v->ar.off = mark;
-    return r;
-  }
+  int gemm(MvdGemmArgs& g) { return err ? err : arena_gemm(v->ar, g, s, dry); }
   int linear(const bf16_t* a, int k, int M, const bf16_t* w, const float* bias, int N, const bf16_t* res, void* out, float alpha = 1.f,
              bool out_f32 = false) {
     MvdGemmArgs g = gemm_dense(a, nullptr, k, 0, M, w, 0, bias, N, out, N);
@@ -176,7 +159,7 @@ struct VCtx {
       const size_t o0 = (size_t)b * hw * C;
       CHECK(linear(wv, C, C, xn + o0, nullptr, hw, nullptr, vt));                          // V^T = W_v . x^T   [C][hw]
       CHECK(linear(q + o0, C, hw, k + o0, nullptr, hw, nullptr, sc, scale, true));          // S = q.k^T / sqrt(C)  fp32
-      if (!dry) { hipLaunchKernelGGL(softmax_rows_kernel, dim3(hw), dim3(256), 0, s, sc, hw, pr); CHECK(vcheck("vae softmax")); }
+      if (!dry) { hipLaunchKernelGGL(softmax_rows_kernel, dim3(hw), dim3(256), 0, s, sc, hw, pr); CHECK(launch_check("vae softmax")); }
       CHECK(linear(pr, hw, hw, vt, bv, C, nullptr, o + o0));                                // P.V + b_v
     }
     CHECK(linear(o, C, M, WB(key + ".out.w", (int64_t)C * C), WF(key + ".out.b", C), C, x.p, out.p));   // to_out + residual
@@ -212,7 +195,7 @@ struct VCtx {
     if (dry || err) return err;
     const long total = (long)B * hw;
     hipLaunchKernelGGL(pointwise_small_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, cin, cout, hw, w, b, y, total);
-    return vcheck("vae pointwise");
+    return launch_check("vae pointwise");
   }
 };
 
@@ -315,10 +298,7 @@ int mvd_vae_create(const mvd_vae_config_t* cfg, mvd_vae_t** out) {
 int mvd_vae_destroy(mvd_vae_t* v) { delete v; return 0; }
 
 int mvd_vae_set_weight(mvd_vae_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("vae_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("vae_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(v, "vae", slot, ptr, numel, dtype);
 }
 
 int64_t mvd_vae_workspace_bytes(mvd_vae_t* v, int batch, int height, int width, int decode) {
@@ -330,8 +310,7 @@ int64_t mvd_vae_workspace_bytes(mvd_vae_t* v, int batch, int height, int width, 
 }
 
 int mvd_vae_bind_workspace(mvd_vae_t* v, void* ws, int64_t ws_bytes) {
-  if (!v || !ws || ws_bytes <= 0 || ((uintptr_t)ws & 255)) { mvd_set_error("vae_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  v->ws_ptr = ws; v->ws_bytes = ws_bytes;
+  CHECK(module_bind_workspace(v, "vae", ws, ws_bytes, 0));
   v->ar.base = (char*)ws; v->ar.cap = (size_t)ws_bytes;
   return 0;
 }
@@ -369,7 +348,7 @@ int mvd_vae_mid_attention(mvd_vae_t* v, int decoder, const void* x_nhwc, int bat
 int mvd_op_softmax_rows(const float* s, int rows, int n, void* p_bf16, void* stream) {
   if (!s || !p_bf16 || rows <= 0 || n <= 0) { mvd_set_error("softmax_rows: bad argument"); return -1; }
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, s, n, (bf16_t*)p_bf16);
-  return vcheck("softmax_rows");
+  return launch_check("softmax_rows");
 }
 
 int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, int channels, int hw, float scale, float* out, void* stream) {
@@ -377,7 +356,7 @@ int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, 
   const long total = (long)batch * channels * hw;
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, moments, noise, channels, hw,
                      scale, out, total);
-  return vcheck("gaussian_sample");
+  return launch_check("gaussian_sample");
 }
 
 }  // extern "C"

@@ -21,20 +21,10 @@
 
 namespace {
 
-int vcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { mvd_set_error("%s launch: %s", what, hipGetErrorString(e)); return -3; }
-  return 0;
-}
-
 // ---------------------------------------------------------------- 2x2 max-pool, stride 2 (floor: an odd trailing row / column is dropped)
 // One thread per 16-byte chunk (8 channels) of the output: four 16-byte loads, one store; consecutive threads take consecutive
 // chunks of a pixel, so a wave reads and writes whole 128-byte lines.  The values are post-ReLU bf16 (no NaN handling needed
 // beyond what v_max gives); the maximum of bf16 values is one of them, so nothing is rounded.
-MVD_DEVINL unsigned int max2bf(unsigned int a, unsigned int b) {
-  const float lo = fmaxf(bflo(a), bflo(b)), hi = fmaxf(bfhi(a), bfhi(b));
-  return pack2bf(lo, hi);
-}
 __global__ __launch_bounds__(256) void maxpool2x2_kernel(const bf16_t* __restrict__ x, int h, int w, int c8, long total, bf16_t* __restrict__ y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -61,18 +51,6 @@ __global__ __launch_bounds__(256) void maxpool2x2_kernel(const bf16_t* __restric
 // launches give the same bits.  Against an fp64 evaluation of the same fp32 features the error is the fp64 round-off of
 // ~n additions plus ONE rounding of the result to fp32: below 1e-7 relative.
 constexpr int SQ_CHUNK = 4096;      // elements per workgroup: 256 lanes x 4 float4
-MVD_DEVINL double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-MVD_DEVINL double block_sum_f64(double v, double* red) {   // 256 threads; every thread gets the sum
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 __global__ __launch_bounds__(256) void sqdiff_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, int nchunks, double* __restrict__ part) {
   __shared__ double red[4];
   const int chunk = blockIdx.x, pair = blockIdx.y;
@@ -115,18 +93,16 @@ __global__ void vgg_affine_kernel(Affine a, float* __restrict__ out) {
   if (threadIdx.x < 8) out[threadIdx.x] = a.v[threadIdx.x];
 }
 
-long blocks_of(long n) { return (n + 255) / 256; }
 int sq_chunks(long n) { return (int)((n + SQ_CHUNK - 1) / SQ_CHUNK); }
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // part: pairs * sq_chunks(n) doubles; total: one double
 int launch_sqdiff(const float* a, const float* b, int pairs, long n, double* part, double* total, int first, int last, long all_pairs, float* per_pair,
                   float* mean, hipStream_t s) {
   const int nc = sq_chunks(n);
   hipLaunchKernelGGL(sqdiff_kernel, dim3(nc, pairs), dim3(256), 0, s, a, b, n, nc, part);
-  CHECK(vcheck("sqdiff"));
+  CHECK(launch_check("sqdiff"));
   hipLaunchKernelGGL(sqdiff_finish_kernel, dim3(1), dim3(256), 0, s, part, pairs, nc, n, total, first, last, all_pairs, per_pair, mean);
-  return vcheck("sqdiff finish");
+  return launch_check("sqdiff finish");
 }
 
 // ---------------------------------------------------------------- the layer table of torchvision's vgg16().features[:29]
@@ -145,36 +121,14 @@ int mvd_launch_maxpool2x2(const bf16_t* x, int batch, int h, int w, int c, bf16_
   const long total = (long)batch * (h / 2) * (w / 2) * (c / 8);
   if (blocks_of(total) >= (1L << 31)) { mvd_set_error("maxpool2x2: too many elements for one launch"); return -1; }
   hipLaunchKernelGGL(maxpool2x2_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, x, h, w, c / 8, total, y);
-  return vcheck("maxpool2x2");
+  return launch_check("maxpool2x2");
 }
 
-struct mvd_vgg {
-  WeightTable w;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
-  Arena ar;
-};
+struct mvd_vgg : ModuleBase {};
 
 namespace {
 
-struct VCtx {
-  mvd_vgg* v; hipStream_t s; bool dry, check_w;
-  int err = 0;
-  const void* W(const std::string& n, int dtype, int64_t numel) {
-    if (!check_w) return (const void*)(uintptr_t)0x1000;
-    if (err) return nullptr;
-    return v->w.find(n, dtype, numel, &err, "vgg: ");
-  }
-  // the lock-step tiles with the split-K the tile heuristic asks for (deep layers of small images: M = images * h * w / 256)
-  int gemm(MvdGemmArgs& g) {
-    if (err) return err;
-    const int S = mvd_gemm_pick_splitk(g);
-    const size_t mark = v->ar.off;
-    if (S > 1) { g.splitk = S; g.part = v->ar.alloc_n<float>((size_t)S * g.M * g.N); }
-    const int r = dry ? 0 : launch_tiled(g, s);
-    v->ar.off = mark;
-    return r;
-  }
-};
+// (the tower runs on a TowerCtx; its gemm() splits K where the tile heuristic asks for it: deep layers of small images, M = images * h * w / 256)
 
 int check_geometry(const char* who, int images, int h, int w) {
   if (images <= 0 || h < 16 || w < 16 || h > 32768 || w > 32768) { mvd_set_error("%s: bad shape (%d images of %d x %d: h, w in [16, 32768])", who, images, h, w); return -1; }
@@ -184,8 +138,8 @@ int check_geometry(const char* who, int images, int h, int w) {
 }
 
 // x / y: two fp32 NCHW arrays of nx / ny images that form ONE batch of nx + ny (y may be null).  feat [nx + ny][h/16][w/16][512] fp32.
-int tower(VCtx& c, const float* x, int nx, const float* y, int ny, int h, int w, float* feat, void* const* taps) {
-  Arena& ar = c.v->ar;
+int tower(TowerCtx& c, const float* x, int nx, const float* y, int ny, int h, int w, float* feat, void* const* taps) {
+  Arena& ar = c.m->ar;
   const int B = nx + ny;
   const size_t rows = (size_t)B * h * w;
   bf16_t* buf[2] = {ar.alloc_n<bf16_t>(rows * 64), ar.alloc_n<bf16_t>(rows * 64)};
@@ -196,7 +150,7 @@ int tower(VCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
     Affine af; memset(&af, 0, sizeof(af));
     for (int k = 0; k < 3; ++k) { af.v[k] = 0.5f / stdv[k]; af.v[4 + k] = (0.5f - mean[k]) / stdv[k]; }
     hipLaunchKernelGGL(vgg_affine_kernel, dim3(1), dim3(64), 0, c.s, af, ss);
-    CHECK(vcheck("vgg front-end constants"));
+    CHECK(launch_check("vgg front-end constants"));
     CHECK(mvd_launch_im2col_in(x, nx, 3, h, w, ss, ss + 4, 0, buf[0], c.s));
     if (ny) CHECK(mvd_launch_im2col_in(y, ny, 3, h, w, ss, ss + 4, 0, buf[0] + (size_t)nx * h * w * 64, c.s));
   }
@@ -231,7 +185,7 @@ int tower(VCtx& c, const float* x, int nx, const float* y, int ny, int h, int w,
 // arena bytes of one pass over `images` images, the internal fp32 feature buffer and the loss partials included
 int pass_bytes(mvd_vgg* v, int images, int h, int w, size_t* out) {
   v->ar.reset(true);
-  VCtx c{v, nullptr, true, false};
+  TowerCtx c{v, nullptr, true, false, "vgg: "};
   const long n = (long)(h / 16) * (w / 16) * 512;
   float* feat = v->ar.alloc_n<float>((size_t)images * n);
   v->ar.alloc_n<double>((size_t)((images + 1) / 2) * sq_chunks(n));
@@ -241,7 +195,7 @@ int pass_bytes(mvd_vgg* v, int images, int h, int w, size_t* out) {
 }
 
 int check_weights(mvd_vgg* v) {
-  VCtx c{v, nullptr, true, true};
+  TowerCtx c{v, nullptr, true, true, "vgg: "};
   for (const VggConv& L : kConvs) {
     const std::string name = "features." + std::to_string(L.idx);
     c.W(name + ".weight", 1, (int64_t)L.cout * (L.idx == 0 ? 64 : 9 * L.cin));
@@ -249,12 +203,6 @@ int check_weights(mvd_vgg* v) {
     if (c.err) return c.err;
   }
   return 0;
-}
-
-void bind_arena(mvd_vgg* v) {
-  v->ar.reset(false);
-  v->ar.base = reinterpret_cast<char*>(v->ws_ptr) + HEAD_BYTES;
-  v->ar.cap = (size_t)v->ws_bytes - HEAD_BYTES;
 }
 
 }  // namespace
@@ -269,10 +217,7 @@ int mvd_vgg_create(mvd_vgg_t** out) {
 int mvd_vgg_destroy(mvd_vgg_t* v) { delete v; return 0; }
 
 int mvd_vgg_set_weight(mvd_vgg_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("vgg_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("vgg_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(v, "vgg", slot, ptr, numel, dtype);
 }
 
 int64_t mvd_vgg_workspace_bytes(mvd_vgg_t* v, int images, int h, int w) {
@@ -284,9 +229,7 @@ int64_t mvd_vgg_workspace_bytes(mvd_vgg_t* v, int images, int h, int w) {
 }
 
 int mvd_vgg_bind_workspace(mvd_vgg_t* v, void* ws, int64_t bytes) {
-  if (!v || !ws || bytes <= HEAD_BYTES || ((uintptr_t)ws & 255)) { mvd_set_error("vgg_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  v->ws_ptr = ws; v->ws_bytes = bytes;
-  return 0;
+  return module_bind_workspace(v, "vgg", ws, bytes, HEAD_BYTES);
 }
 
 int mvd_vgg_features(mvd_vgg_t* v, const float* images_nchw, int images, int h, int w, float* feat_out, void* const* taps, void* stream) {
@@ -297,8 +240,8 @@ int mvd_vgg_features(mvd_vgg_t* v, const float* images_nchw, int images, int h, 
   if (int r = pass_bytes(v, images, h, w, &need)) return r;
   if (!v->ws_ptr) { mvd_set_error("vgg_features: workspace not bound"); return -1; }
   if (need > (size_t)v->ws_bytes) { mvd_set_error("vgg_features: workspace too small: need %zu bytes, bound %lld", need, (long long)v->ws_bytes); return -4; }
-  bind_arena(v);
-  VCtx c{v, (hipStream_t)stream, false, true};
+  module_bind_arena(*v, HEAD_BYTES);
+  TowerCtx c{v, (hipStream_t)stream, false, true, "vgg: "};
   return tower(c, images_nchw, images, nullptr, 0, h, w, feat_out, taps);
 }
 
@@ -310,25 +253,17 @@ int mvd_vgg_perceptual(mvd_vgg_t* v, const float* x, const float* y, int pairs, 
   if (!v->ws_ptr) { mvd_set_error("vgg_perceptual: workspace not bound"); return -1; }
   // pairs per pass: as many as the bound workspace holds
   int pp = pairs > 32768 ? 32768 : pairs;      // (the loss kernel's grid: one row of workgroups per pair)
-  size_t need = 0;
-  for (;;) {
-    if ((long)2 * pp * h * w < (1L << 31) - 256) {
-      if (int r = pass_bytes(v, 2 * pp, h, w, &need)) return r;
-      if (need <= (size_t)v->ws_bytes) break;
-    } else {
-      need = ~size_t(0);
-    }
-    if (pp == 1) { mvd_set_error("vgg_perceptual: workspace too small for one pair of %d x %d: need %zu bytes, bound %lld", h, w, need, (long long)v->ws_bytes); return -4; }
-    int guess = need == ~size_t(0) ? pp / 2 : (int)((double)pp * (double)v->ws_bytes / (double)need);
-    pp = guess < 1 ? 1 : (guess >= pp ? pp - 1 : guess);
-  }
+  CHECK(pairs_per_pass("vgg_perceptual", h, w, v->ws_bytes, [&](int n, size_t* need) {
+    if ((long)2 * n * h * w >= (1L << 31) - 256) { *need = ~size_t(0); return 0; }
+    return pass_bytes(v, 2 * n, h, w, need);
+  }, &pp));
   const long n = (long)(h / 16) * (w / 16) * 512;
   const size_t img = (size_t)3 * h * w;
   double* total = reinterpret_cast<double*>(v->ws_ptr);
   for (int p0 = 0; p0 < pairs; p0 += pp) {
     const int np = pairs - p0 < pp ? pairs - p0 : pp;
-    bind_arena(v);
-    VCtx c{v, (hipStream_t)stream, false, true};
+    module_bind_arena(*v, HEAD_BYTES);
+    TowerCtx c{v, (hipStream_t)stream, false, true, "vgg: "};
     float* feat = v->ar.alloc_n<float>((size_t)2 * np * n);
     double* part = v->ar.alloc_n<double>((size_t)np * sq_chunks(n));
     CHECK(tower(c, x + p0 * img, np, y + p0 * img, np, h, w, feat, nullptr));

@@ -91,7 +91,6 @@ size_t pass_ints(int in, int out) {
   const int ksize = (int)ceil(2.0 * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
   return (size_t)out * (ksize + 2);
 }
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 size_t table_bytes(int h, int w, int resize_to) {
   if (h <= 0 || w <= 0 || resize_to <= 0) return 0;
   int oh, ow;
@@ -327,10 +326,10 @@ int launch_pool_project(const float* hidden, const float* delta, const int* ids,
                         float eps, const float* wp, int proj, float* raw, float* nrm, hipStream_t s) {
   hipLaunchKernelGGL(clip_pool_project_kernel, dim3(batch, (proj + PP_SLICE - 1) / PP_SLICE), dim3(256), 0, s, hidden, delta, ids, T, H, eos_id, gamma, beta, eps,
                      wp, proj, raw, nrm);
-  CHECK(tcheck("clip pool + projection"));
+  CHECK(launch_check("clip pool + projection"));
   if (nrm) {
     hipLaunchKernelGGL(clip_l2norm_kernel, dim3(batch), dim3(256), 0, s, nrm, proj);
-    CHECK(tcheck("clip L2 normalisation"));
+    CHECK(launch_check("clip L2 normalisation"));
   }
   return 0;
 }
@@ -356,14 +355,10 @@ __global__ __launch_bounds__(256) void clip_cosine_kernel(const float* __restric
   if (threadIdx.x == 0 && mean) *mean = (float)((((part[0] + part[1]) + part[2]) + part[3]) / (double)batch);
 }
 
-long blocks_of(long n) { return (n + 255) / 256; }
-
 }  // namespace
 
-struct mvd_vision {
+struct mvd_vision : ModuleBase {      // (ar unused: the arena of a run lives in its ClipCtx, behind the split-K tile counters)
   mvd_vision_config_t cfg;
-  WeightTable w;
-  void* ws_ptr = nullptr; int64_t ws_bytes = 0;
   std::map<std::tuple<int, int, int>, Geometry> geo;        // (h, w, resize_to) -> host tables, built once
   std::tuple<int, int, int> resident{0, 0, 0};              // the geometry whose tables sit at the head of the workspace
   size_t head_bytes = 0;                                    // bytes of that table region (the patch rows start behind it)
@@ -402,12 +397,12 @@ int vencode_impl(mvd_vision* v, const float* pixel_values, int B, float* last_hi
   if (!dry && pixel_values) {
     const long total = (long)B * np * Kp;
     hipLaunchKernelGGL(vit_patchify_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, s, pixel_values, total, c.image_size, c.patch_size, Kp, patches);
-    CHECK(tcheck("vision patchify"));
+    CHECK(launch_check("vision patchify"));
   }
   CHECK(x.linear(patches, Kp, B * np, wpatch, nullptr, H, po, true));
   if (!dry) {
     hipLaunchKernelGGL(vit_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, po, cls, pos, gp, bp, M, T, H, c.layer_norm_eps, b.xs);
-    CHECK(tcheck("vision embedding"));
+    CHECK(launch_check("vision embedding"));
   }
   CHECK(clip_layers(x, b, c.num_layers, H, I, M, c.act, [&](const bf16_t* qkv, bf16_t* at) {
     MvdAttnArgs a; memset(&a, 0, sizeof(a));
@@ -421,7 +416,7 @@ int vencode_impl(mvd_vision* v, const float* pixel_values, int B, float* last_hi
       if (dl) {
         const long n4 = (long)M * H / 4;
         hipLaunchKernelGGL(vit_fold_kernel, dim3((unsigned)blocks_of(n4)), dim3(256), 0, s, b.xs, dl, n4, last_hidden);
-        CHECK(tcheck("vision last hidden state"));
+        CHECK(launch_check("vision last hidden state"));
       } else if (hipMemcpyAsync(last_hidden, b.xs, (size_t)M * H * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { mvd_set_error("vision_encode: hipMemcpyAsync failed"); return -3; }
     }
     CHECK(launch_pool_project(b.xs, dl, nullptr, B, T, H, 0, go, bo, c.layer_norm_eps, wproj, c.projection_dim, embeds, embeds_norm, s));
@@ -464,10 +459,7 @@ int mvd_vision_create(const mvd_vision_config_t* cfg, mvd_vision_t** out) {
 int mvd_vision_destroy(mvd_vision_t* v) { delete v; return 0; }
 
 int mvd_vision_set_weight(mvd_vision_t* v, const char* slot, const void* ptr, int64_t numel, int dtype) {
-  if (!v || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("vision_set_weight: bad argument"); return -1; }
-  if ((uintptr_t)ptr & 15) { mvd_set_error("vision_set_weight: '%s' must be 16-byte aligned", slot); return -1; }
-  v->w.m[slot] = Weight{ptr, numel, dtype};
-  return 0;
+  return module_set_weight(v, "vision", slot, ptr, numel, dtype);
 }
 
 int64_t mvd_vision_workspace_bytes(mvd_vision_t* v, int batch, int h, int w, int resize_to) {
@@ -482,8 +474,7 @@ int64_t mvd_vision_workspace_bytes(mvd_vision_t* v, int batch, int h, int w, int
 }
 
 int mvd_vision_bind_workspace(mvd_vision_t* v, void* ws, int64_t bytes) {
-  if (!v || !ws || bytes <= 0 || ((uintptr_t)ws & 255)) { mvd_set_error("vision_bind_workspace: bad argument (256-byte aligned buffer)"); return -1; }
-  v->ws_ptr = ws; v->ws_bytes = bytes;
+  CHECK(module_bind_workspace(v, "vision", ws, bytes, 0));
   v->resident = std::make_tuple(0, 0, 0); v->head_bytes = 0; v->pre_batch = 0;
   return 0;
 }
@@ -534,7 +525,7 @@ int mvd_vision_preprocess(mvd_vision_t* v, const float* images, int batch, int h
   if (!g.vp.skipped()) { kv = tab + g.off_v; xv = kv + (size_t)oh * g.vp.ksize; cv = xv + oh; }
   const long th = (long)batch * 3 * h * ow;
   hipLaunchKernelGGL(clip_resize_h_kernel, dim3((unsigned)blocks_of(th)), dim3(256), 0, s, images, th, w, ow, quantize, kh, xh, ch, g.hp.ksize, inter);
-  CHECK(tcheck("vision resize (horizontal)"));
+  CHECK(launch_check("vision resize (horizontal)"));
   NormArgs na;
   for (int c = 0; c < 3; ++c) { na.mean[c] = mean[c]; na.std[c] = std_[c]; }
   const int top = (oh - crop) / 2, left = (ow - crop) / 2;
@@ -542,7 +533,7 @@ int mvd_vision_preprocess(mvd_vision_t* v, const float* images, int batch, int h
   const long tv = want_patches ? (long)batch * (v->tokens() - 1) * Kp : (long)batch * 3 * crop * crop;
   hipLaunchKernelGGL(clip_resize_v_kernel, dim3((unsigned)blocks_of(tv)), dim3(256), 0, s, inter, tv, h, ow, crop, top, left, kv, xv, cv, g.vp.ksize, na, P, Kp,
                      want_patches ? patches : nullptr, pixel_values);
-  CHECK(tcheck("vision resize (vertical)"));
+  CHECK(launch_check("vision resize (vertical)"));
   if (want_patches) v->pre_batch = batch;
   return 0;
 }
@@ -581,7 +572,7 @@ int mvd_op_clip_pool_project(const float* hidden, const float* delta, const int3
 int mvd_op_clip_cosine(const float* a, const float* b, int batch, int dim, float* per_row_out, float* mean_out, void* stream) {
   if (!a || !b || (!per_row_out && !mean_out) || batch <= 0 || dim <= 0) { mvd_set_error("clip_cosine: bad argument"); return -1; }
   hipLaunchKernelGGL(clip_cosine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, b, batch, dim, per_row_out, mean_out);
-  return tcheck("clip_cosine");
+  return launch_check("clip_cosine");
 }
 
 }  // extern "C"

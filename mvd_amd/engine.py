@@ -18,10 +18,6 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class MVDEngine:
     def __init__(self, cfg: UNetConfig, cam_output_dim: int = 1024, cam_hidden_dim: int = 512,
                  simple_cam_encoder: bool = False, cam_modulation_strength: float = 0.2, device="cuda:0",
@@ -65,8 +61,7 @@ class MVDEngine:
     def _register(self, set_id: int, packed: Dict[str, torch.Tensor]):
         for slot, t in packed.items():
             assert t.is_cuda and t.is_contiguous()
-            dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-            L.call("mvd_engine_set_weight", self._h, set_id, slot.encode(), _ptr(t), t.numel(), dt)
+            L.call("mvd_engine_set_weight", self._h, set_id, slot.encode(), _ptr(t), t.numel(), L.dtype_code(t))
         self._weights[set_id].update(packed)
         self._arenas_stale = True
 
@@ -109,8 +104,7 @@ class MVDEngine:
             self._weights[int(i)][k] = v
         for i, d in enumerate(self._weights):
             for slot, t in d.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_engine_set_weight", self._h, i, slot.encode(), _ptr(t), t.numel(), dt)
+                L.call("mvd_engine_set_weight", self._h, i, slot.encode(), _ptr(t), t.numel(), L.dtype_code(t))
         self._arenas_stale = False
 
     def weight_bytes(self) -> int:
@@ -208,11 +202,11 @@ class MVDEngine:
             cur = torch.cuda.current_stream(self.device)
             self._gstream.wait_stream(cur)
             with torch.cuda.stream(self._gstream):
-                L.call("mvd_unet_forward", self._h, C.byref(a), _stream())
+                L.call("mvd_unet_forward", self._h, C.byref(a), L.stream())
             cur.wait_stream(self._gstream)
             out = out.clone() if user_out is None else user_out.copy_(out)
         else:
-            L.call("mvd_unet_forward", self._h, C.byref(a), _stream())
+            L.call("mvd_unet_forward", self._h, C.byref(a), L.stream())
         if use_img and not reuse_ref:
             self._ref_valid = (B, H, W, Lt, ref_batch)
         return out
@@ -238,7 +232,7 @@ class MVDEngine:
         a.batch, a.height, a.width, a.text_len = main_batch, H, W, Lt
         a.source_latents, a.encoder_text = source_latents.data_ptr(), encoder_text.data_ptr()
         a.ref_batch, a.flags = Br, L.MVD_USE_IMAGE
-        L.call("mvd_engine_reference_encode", self._h, C.byref(a), _ptr(stats), _stream())
+        L.call("mvd_engine_reference_encode", self._h, C.byref(a), _ptr(stats), L.stream())
         self._ref_valid = None
         self._ref_pending = (main_batch, H, W, Lt, Br)
         n = torch.empty(npix, dtype=torch.float32, device=self.device)
@@ -259,7 +253,7 @@ class MVDEngine:
         npix = L.lib().mvd_engine_reference_pixels(self._h, pend[1], pend[2])
         if not (mean_k.is_cuda and mean_k.dtype == torch.float32 and mean_k.is_contiguous() and tuple(mean_k.shape) == (npix, 2)):
             raise L.MvdError(f"reference_finish expects a contiguous fp32 CUDA tensor [{npix}, 2]")
-        L.call("mvd_engine_reference_finish", self._h, _ptr(mean_k), _stream())
+        L.call("mvd_engine_reference_finish", self._h, _ptr(mean_k), L.stream())
         self._ref_pending = None
         self._ref_valid = pend
 
@@ -329,11 +323,11 @@ class MVDEngine:
             c, h, w = C.c_int(), C.c_int(), C.c_int()
             L.call("mvd_engine_feature_shape", self._h, i, C.byref(c), C.byref(h), C.byref(w))
             t = torch.empty(self._last_ref_batch, c.value, h.value, w.value, dtype=torch.float32, device=self.device)
-            L.call("mvd_engine_get_feature", self._h, i, _ptr(t), _stream())
+            L.call("mvd_engine_get_feature", self._h, i, _ptr(t), L.stream())
             res[n] = t
         return res
 
     def camera_embedding(self, batch: int) -> torch.Tensor:
         t = torch.empty(batch, self.cam_output_dim, dtype=torch.float32, device=self.device)
-        L.call("mvd_engine_get_camera_embedding", self._h, _ptr(t), _stream())
+        L.call("mvd_engine_get_camera_embedding", self._h, _ptr(t), L.stream())
         return t

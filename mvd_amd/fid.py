@@ -26,14 +26,10 @@ import torch
 
 from . import _lib as L
 from .packing import fid_program, inception_fc_weight, normalize_inception_fid_keys, pack_inception_fid
-from .perceptual import hub_checkpoint_dirs
+from .hub import hub_checkpoint_dirs, resolve_state_dict
 
 INCEPTION_FID_FILES = ("weights-inception-2015-12-05-6726825d.pth", "pt_inception-2015-12-05-6726825d.pth")
 FEATURE_DIM = 2048
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def inception_weight_candidates():
@@ -43,58 +39,17 @@ def inception_weight_candidates():
 def load_inception_fid_weights(weights=None) -> Dict[str, torch.Tensor]:
     """A state dict from ``weights``: a dict as it is, a ``.pth`` / ``.safetensors`` path, or ``None`` = the first of
     ``INCEPTION_FID_FILES`` in the local hub cache.  Never downloads: a file that is not there raises ``MvdError``."""
-    who = "InceptionV3FeaturesHIP"
-    if weights is not None and hasattr(weights, "keys"):
-        return weights
-    if weights is not None:
-        path = os.fspath(weights)
-        if not os.path.isfile(path):
-            raise L.MvdError(f"{who}: weight file {path!r} does not exist (nothing is downloaded)")
-    else:
-        cands = inception_weight_candidates()
-        path = next((p for p in cands if os.path.isfile(p)), None)
-        if path is None:
-            raise L.MvdError(f"{who}: no Inception-v3 (FID) weight file found; tried {cands}.  Nothing is downloaded: put the file there, "
-                             "or pass a path or a state dict")
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        return load_file(path)
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not hasattr(sd, "keys"):
-        raise L.MvdError(f"{who}: {path!r} holds a {type(sd).__name__}, not a state dict")
-    return sd
+    return resolve_state_dict(weights, inception_weight_candidates(), "InceptionV3FeaturesHIP", "Inception-v3 (FID) weight")
 
 
-class _FidHandle:
-    """One ``mvd_fid_t`` (the program of ``packing.fid_program``) with its workspace (grown on demand, rebound when it moves)."""
+class _FidHandle(L.Handle):
+    """One ``mvd_fid_t`` (the program of ``packing.fid_program``); ``workspace_bytes(images)``, ``workspace(device, images)``."""
 
     def __init__(self, max_images_per_pass: int):
         prog, bufs, names, final = fid_program()
-        self.h = C.c_void_p()
         n_ops, n_bufs = len(prog) // 13, len(bufs) // 2
-        L.call("mvd_fid_create", (C.c_int * len(prog))(*prog), n_ops, (C.c_int * len(bufs))(*bufs), n_bufs,
-               (C.c_char_p * len(names))(*[n.encode() for n in names]), len(names), final, int(max_images_per_pass), C.byref(self.h))
-        self.ws = None
-
-    def __del__(self):
-        try:
-            if self.h:
-                L.lib().mvd_fid_destroy(self.h)
-        except Exception:
-            pass
-
-    def workspace_bytes(self, images: int) -> int:
-        need = L.lib().mvd_fid_workspace_bytes(self.h, images)
-        if need < 0:
-            raise L.MvdError(f"fid workspace_bytes: {L.last_error()}")
-        return need
-
-    def workspace(self, device, images: int):
-        need = self.workspace_bytes(images)
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = None
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-            L.call("mvd_fid_bind_workspace", self.h, C.c_void_p(self.ws.data_ptr()), self.ws.numel())
+        super().__init__("fid", (C.c_int * len(prog))(*prog), n_ops, (C.c_int * len(bufs))(*bufs), n_bufs,
+                         (C.c_char_p * len(names))(*[n.encode() for n in names]), len(names), final, int(max_images_per_pass))
 
 
 class InceptionV3FeaturesHIP:
@@ -128,9 +83,7 @@ class InceptionV3FeaturesHIP:
         if self._handle is None:
             self._handle = _FidHandle(self.max_images_per_pass)
         self._packed = pack_inception_fid(self.state, dev)
-        for slot, t in self._packed.items():
-            dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-            L.call("mvd_fid_set_weight", self._handle.h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+        self._handle.set_weights(self._packed)
         self._dev = dev
 
     def _images(self, t) -> torch.Tensor:
@@ -153,7 +106,7 @@ class InceptionV3FeaturesHIP:
         b, _, h, w = x.shape
         self._handle.workspace(x.device, b)
         out = torch.empty(b, FEATURE_DIM, device=x.device, dtype=torch.float32)
-        L.call("mvd_fid_features", self._handle.h, C.c_void_p(x.data_ptr()), int(x.dtype == torch.float32), b, h, w, C.c_void_p(out.data_ptr()), _stream())
+        L.call("mvd_fid_features", self._handle.h, C.c_void_p(x.data_ptr()), int(x.dtype == torch.float32), b, h, w, C.c_void_p(out.data_ptr()), L.stream())
         return out
 
     __call__ = forward
@@ -174,7 +127,7 @@ class InceptionV3FeaturesHIP:
             self._fc_dev = self.fc_weight.to(f.device)
         out = torch.empty(f.shape[0], self._fc_dev.shape[0], device=f.device, dtype=torch.float32)
         L.call("mvd_op_fc_logits", C.c_void_p(f.data_ptr()), f.shape[0], FEATURE_DIM, C.c_void_p(self._fc_dev.data_ptr()), self._fc_dev.shape[0],
-               C.c_void_p(out.data_ptr()), _stream())
+               C.c_void_p(out.data_ptr()), L.stream())
         return out
 
     @torch.no_grad()
@@ -188,7 +141,7 @@ class InceptionV3FeaturesHIP:
         b, _, h, w = x.shape
         self._handle.workspace(x.device, b)
         L.call("mvd_fid_update", self._handle.h, C.c_void_p(x.data_ptr()), int(x.dtype == torch.float32), b, h, w, C.c_void_p(total.data_ptr()),
-               C.c_void_p(cov_sum.data_ptr()), _stream())
+               C.c_void_p(cov_sum.data_ptr()), L.stream())
         return b
 
 
@@ -304,7 +257,7 @@ class FrechetInceptionDistance:
         f = pool3.detach().contiguous()
         side = "real" if real else "fake"
         L.call("mvd_op_feature_stats", C.c_void_p(f.data_ptr()), f.shape[0], FEATURE_DIM, C.c_void_p(getattr(self, f"{side}_features_sum").data_ptr()),
-               C.c_void_p(getattr(self, f"{side}_features_cov_sum").data_ptr()), _stream())
+               C.c_void_p(getattr(self, f"{side}_features_cov_sum").data_ptr()), L.stream())
         getattr(self, f"{side}_features_num_samples").add_(f.shape[0])
 
     def compute(self) -> torch.Tensor:

@@ -1,4 +1,5 @@
-"""Offline resolution of a ``pretrained_model_name_or_path`` the way the reference's loaders see it.
+"""Offline resolution of a ``pretrained_model_name_or_path`` the way the reference's loaders see it, and of the single weight
+files of the metric towers (``resolve_state_dict``: a state dict, a path, or a file of the local torch hub cache).
 
 The reference builds everything with ``from_pretrained(name, cache_dir=...)`` (mvd_unet.py:46-52, 411-415;
 image_encoder.py:18-22; infer.py:33-44 passes ``--base-model stabilityai/stable-diffusion-2-1`` and the cache directory it
@@ -74,3 +75,41 @@ def resolve_snapshot(name_or_path, cache_dir=None, revision: Optional[str] = Non
         f"pretrained model {p!r}: not a directory and no cached snapshot found (looked for {', '.join(tried) or 'a local path'}). "
         "This build has no network access and never random-initialises a named model: pass a snapshot directory, populate the "
         "huggingface cache (cache_dir / HF_HOME), or pass None with unet_config= for checkpoint-free construction.")
+
+
+def hub_checkpoint_dirs() -> List[str]:
+    """Where ``torch.hub`` keeps downloaded checkpoints: ``$TORCH_HOME/hub/checkpoints``, then ``~/.cache/torch/hub/checkpoints``."""
+    dirs = []
+    if os.environ.get("TORCH_HOME"):
+        dirs.append(os.path.join(os.environ["TORCH_HOME"], "hub", "checkpoints"))
+    dirs.append(os.path.join(os.path.expanduser("~"), ".cache", "torch", "hub", "checkpoints"))
+    return dirs
+
+
+def load_state_file(path: str, who: str):
+    """the state dict a ``.pth`` / ``.safetensors`` file holds"""
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path)
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not hasattr(sd, "keys"):
+        raise MvdError(f"{who}: {path!r} holds a {type(sd).__name__}, not a state dict")
+    return sd
+
+
+def resolve_state_dict(given, candidates: List[str], who: str, what: str):
+    """A state dict from ``given`` (a dict as it is, a path) or, for ``None``, the first existing file of ``candidates``.  Never
+    downloads: a file that is not there raises ``MvdError``."""
+    if given is not None and hasattr(given, "keys"):
+        return given
+    if given is not None:
+        path = os.fspath(given)
+        if not os.path.isfile(path):
+            raise MvdError(f"{who}: {what} file {path!r} does not exist (nothing is downloaded)")
+        return load_state_file(path, who)
+    path = next((p for p in candidates if os.path.isfile(p)), None)
+    if path is None:
+        raise MvdError(f"{who}: no {what} file found; tried {candidates}.  Nothing is downloaded: put the file there, or pass a path "
+                       "or a state dict")
+    return load_state_file(path, who)

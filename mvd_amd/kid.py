@@ -17,7 +17,6 @@ lists across ranks, a backward pass.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Tuple
 
 import torch
@@ -26,10 +25,6 @@ from . import _lib as L
 from .fid import FEATURE_DIM, InceptionV3FeaturesHIP
 
 NUM_CLASSES = 1008
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _is_pos_int(v) -> bool:

@@ -26,9 +26,10 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
+from .hub import hub_checkpoint_dirs, resolve_state_dict
 from .packing import (ALEX_CONVS, ALEX_TAP_CHANNELS, LPIPS_SCALE, LPIPS_SHIFT, VGG16_CONVS, VGG_LPIPS_TAP_CHANNELS, normalize_backbone_keys,
                       normalize_lpips_lin_keys, pack_alex)
-from .perceptual import VGG16_FILE, TAP_NAMES, VGG16FeaturesHIP, hub_checkpoint_dirs
+from .perceptual import VGG16_FILE, TAP_NAMES, VGG16FeaturesHIP
 
 ALEX_FILE = "alexnet-owt-7be5be79.pth"      # torchvision's AlexNet_Weights.IMAGENET1K_V1
 # torchvision's alexnet().features[:12]
@@ -44,42 +45,12 @@ _BACKBONE_FILE = {"alex": ALEX_FILE, "vgg": VGG16_FILE}
 _LPIPS_DEFAULTS = dict(pretrained=True, lpips=True, use_dropout=True, eval_mode=True, verbose=True, pnet_rand=False, pnet_tune=False)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def alex_tap_sizes(h: int, w: int) -> List[Tuple[int, int]]:
     """(h, w) of the five AlexNet taps of an h x w image"""
     c1 = ((h - 7) // 4 + 1, (w - 7) // 4 + 1)
     p1 = ((c1[0] - 3) // 2 + 1, (c1[1] - 3) // 2 + 1)
     p2 = ((p1[0] - 3) // 2 + 1, (p1[1] - 3) // 2 + 1)
     return [c1, p1, p2, p2, p2]
-
-
-def _load_file(path: str, who: str):
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        return load_file(path)
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not hasattr(sd, "keys"):
-        raise L.MvdError(f"{who}: {path!r} holds a {type(sd).__name__}, not a state dict")
-    return sd
-
-
-def _resolve(given, candidates: List[str], who: str, what: str):
-    """a state dict from ``given`` (a dict as it is, a path) or the first existing file of ``candidates``; never downloads"""
-    if given is not None and hasattr(given, "keys"):
-        return given
-    if given is not None:
-        path = os.fspath(given)
-        if not os.path.isfile(path):
-            raise L.MvdError(f"{who}: {what} file {path!r} does not exist (nothing is downloaded)")
-        return _load_file(path, who)
-    path = next((p for p in candidates if os.path.isfile(p)), None)
-    if path is None:
-        raise L.MvdError(f"{who}: no {what} file found; tried {candidates}.  Nothing is downloaded: put the file there, or pass a path "
-                         "or a state dict")
-    return _load_file(path, who)
 
 
 def _lpips_package_dirs() -> List[str]:
@@ -98,29 +69,11 @@ def lin_weight_candidates(net: str) -> List[str]:
             + [os.path.join(d, f"lpips-v0.1-{net}.pth") for d in hub_checkpoint_dirs()])
 
 
-class _LpipsHandle:
-    """One ``mvd_lpips_t`` with its workspace (grown on demand, rebound when it moves)."""
+class _LpipsHandle(L.Handle):
+    """One ``mvd_lpips_t``; ``workspace(device, images, h, w)``."""
 
     def __init__(self):
-        self.h = C.c_void_p()
-        L.call("mvd_lpips_create", C.byref(self.h))
-        self.ws = None
-
-    def __del__(self):
-        try:
-            if self.h:
-                L.lib().mvd_lpips_destroy(self.h)
-        except Exception:
-            pass
-
-    def workspace(self, device, images: int, h: int, w: int):
-        need = L.lib().mvd_lpips_workspace_bytes(self.h, images, h, w)
-        if need < 0:
-            raise L.MvdError(f"lpips workspace_bytes: {L.last_error()}")
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = None
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-            L.call("mvd_lpips_bind_workspace", self.h, C.c_void_p(self.ws.data_ptr()), self.ws.numel())
+        super().__init__("lpips")
 
 
 def lpips_head(xs, ys, lin_w, relu_in=None, per_layer: bool = False, ws: Optional[torch.Tensor] = None, mean: bool = False):
@@ -145,7 +98,7 @@ def lpips_head(xs, ys, lin_w, relu_in=None, per_layer: bool = False, ws: Optiona
     L.call("mvd_op_lpips_head", n, ptrs(xs), ptrs(ys), (C.c_int * n)(*[int(a.dtype == torch.bfloat16) for a in xs]),
            (C.c_int * n)(*[int(bool(r)) for r in relu_in]), pixels, chans, ptrs(lin_w), pairs,
            None if mean else C.c_void_p(out.data_ptr()), C.c_void_p(layers.data_ptr()) if per_layer else None,
-           C.c_void_p(out.data_ptr()) if mean else None, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+           C.c_void_p(out.data_ptr()) if mean else None, C.c_void_p(ws.data_ptr()), ws.numel(), L.stream())
     return out, layers, ws
 
 
@@ -182,9 +135,9 @@ class LPIPS:
             if given is not None and hasattr(given, "keys") and any(k.startswith("net.slice") for k in given.keys()) \
                     and any(k.startswith("lin") for k in given.keys()):
                 both = given
-        bb = _resolve(backbone if backbone is not None else both, [os.path.join(d, _BACKBONE_FILE[net]) for d in hub_checkpoint_dirs()],
-                      who, f"{net} backbone ({_BACKBONE_FILE[net]})")
-        lin = _resolve(model_path if model_path is not None else both, lin_weight_candidates(net), who, f"linear-head ({net}.pth)")
+        bb = resolve_state_dict(backbone if backbone is not None else both, [os.path.join(d, _BACKBONE_FILE[net]) for d in hub_checkpoint_dirs()],
+                                who, f"{net} backbone ({_BACKBONE_FILE[net]})")
+        lin = resolve_state_dict(model_path if model_path is not None else both, lin_weight_candidates(net), who, f"linear-head ({net}.pth)")
         convs = ALEX_CONVS if net == "alex" else VGG16_CONVS
         self.backbone = normalize_backbone_keys(bb, convs, "AlexNet" if net == "alex" else "VGG-16")
         self.lins = normalize_lpips_lin_keys(lin, self.chns)
@@ -214,9 +167,7 @@ class LPIPS:
             if self._handle is None:
                 self._handle = _LpipsHandle()
             self._packed = pack_alex(self.backbone, self.lins, dev)
-            for slot, t in self._packed.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_lpips_set_weight", self._handle.h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+            self._handle.set_weights(self._packed)
         else:
             self._packed = {k: v.to(device=dev, dtype=torch.float32).contiguous() for k, v in self.lins.items()}
         self._dev = dev
@@ -244,7 +195,7 @@ class LPIPS:
             return [taps[n] for n in TAP_NAMES] + [feat.clamp_min(0.0)]
         self._handle.workspace(x.device, b, h, w)
         taps = [torch.empty(b, th, tw, c, device=x.device, dtype=torch.bfloat16) for (th, tw), c in zip(alex_tap_sizes(h, w), self.chns)]
-        L.call("mvd_lpips_features", self._handle.h, C.c_void_p(x.data_ptr()), b, h, w, (C.c_void_p * 5)(*[t.data_ptr() for t in taps]), _stream())
+        L.call("mvd_lpips_features", self._handle.h, C.c_void_p(x.data_ptr()), b, h, w, (C.c_void_p * 5)(*[t.data_ptr() for t in taps]), L.stream())
         return [t.permute(0, 3, 1, 2) for t in taps]
 
     @torch.no_grad()
@@ -262,7 +213,7 @@ class LPIPS:
             self._handle.workspace(x.device, 2 * min(b, self.max_pairs_per_pass), h, w)
             L.call("mvd_lpips_distance", self._handle.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, h, w, self.max_pairs_per_pass,
                    C.c_void_p(out.data_ptr()),
-                   C.c_void_p(layers.data_ptr()) if retPerLayer else None, None, _stream())
+                   C.c_void_p(layers.data_ptr()) if retPerLayer else None, None, L.stream())
         else:
             pp = self.max_pairs_per_pass
             lin_w = [self._packed[f"lin{k}.weight"] for k in range(5)]
@@ -294,5 +245,5 @@ class LPIPS:
         mean = torch.empty((), device=x.device, dtype=torch.float32)
         self._handle.workspace(x.device, 2 * min(b, self.max_pairs_per_pass), h, w)
         L.call("mvd_lpips_distance", self._handle.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, h, w, self.max_pairs_per_pass,
-               None, None, C.c_void_p(mean.data_ptr()), _stream())
+               None, None, C.c_void_p(mean.data_ptr()), L.stream())
         return mean

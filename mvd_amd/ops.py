@@ -20,8 +20,7 @@ def _p(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr())
 
 
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_s = L.stream
 
 
 def _bf16(*ts):

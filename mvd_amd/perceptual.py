@@ -16,12 +16,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Union
+from typing import Dict, Optional, Union
 
 import torch
 from torch import nn
 
 from . import _lib as L
+from .hub import hub_checkpoint_dirs, resolve_state_dict      # (hub_checkpoint_dirs stays importable from here)
 from .packing import VGG16_CONVS, normalize_vgg_keys, pack_vgg
 
 VGG16_FILE = "vgg16-397923af.pth"          # torchvision's VGG16_Weights.IMAGENET1K_V1
@@ -29,41 +30,14 @@ TAP_NAMES = ("relu1_2", "relu2_2", "relu3_3", "relu4_3")
 TAP_CHANNELS = (64, 128, 256, 512)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def hub_checkpoint_dirs() -> List[str]:
-    """Where ``torch.hub`` keeps downloaded checkpoints: ``$TORCH_HOME/hub/checkpoints``, then ``~/.cache/torch/hub/checkpoints``."""
-    dirs = []
-    if os.environ.get("TORCH_HOME"):
-        dirs.append(os.path.join(os.environ["TORCH_HOME"], "hub", "checkpoints"))
-    dirs.append(os.path.join(os.path.expanduser("~"), ".cache", "torch", "hub", "checkpoints"))
-    return dirs
-
-
 def load_vgg16_weights(weights: Union[None, str, os.PathLike, Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """A state dict from ``weights``: a dict as it is, a ``.pth`` / ``.safetensors`` path, or ``None`` = ``vgg16-397923af.pth`` in the
     local hub cache.  Never downloads: a file that is not there raises ``MvdError``."""
-    if weights is not None and hasattr(weights, "keys"):
-        return weights
-    if weights is None:
-        tried = [os.path.join(d, VGG16_FILE) for d in hub_checkpoint_dirs()]
-        path = next((p for p in tried if os.path.isfile(p)), None)
-        if path is None:
-            raise L.MvdError(f"PerceptualLoss: {VGG16_FILE} not found in {tried} and nothing is downloaded: put torchvision's "
-                             "VGG-16 checkpoint there, or pass weights=<path or state dict>")
-    else:
-        path = os.fspath(weights)
-        if not os.path.isfile(path):
-            raise L.MvdError(f"PerceptualLoss: weights file {path!r} does not exist (nothing is downloaded)")
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        return load_file(path)
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not hasattr(sd, "keys"):
-        raise L.MvdError(f"PerceptualLoss: {path!r} holds a {type(sd).__name__}, not a state dict")
-    return sd
+    tried = [os.path.join(d, VGG16_FILE) for d in hub_checkpoint_dirs()]
+    if weights is None and not any(os.path.isfile(p) for p in tried):      # (this module's own wording of "no file found")
+        raise L.MvdError(f"PerceptualLoss: {VGG16_FILE} not found in {tried} and nothing is downloaded: put torchvision's "
+                         "VGG-16 checkpoint there, or pass weights=<path or state dict>")
+    return resolve_state_dict(weights, tried, "PerceptualLoss", "weights")
 
 
 class _Conv(nn.Module):
@@ -75,29 +49,11 @@ class _Conv(nn.Module):
         self.bias = nn.Parameter(torch.empty(cout), requires_grad=False)
 
 
-class _VggHandle:
-    """One ``mvd_vgg_t`` with its workspace (grown on demand, rebound when it moves)."""
+class _VggHandle(L.Handle):
+    """One ``mvd_vgg_t``; ``workspace(device, images, h, w)``."""
 
     def __init__(self):
-        self.h = C.c_void_p()
-        L.call("mvd_vgg_create", C.byref(self.h))
-        self.ws = None
-
-    def __del__(self):
-        try:
-            if self.h:
-                L.lib().mvd_vgg_destroy(self.h)
-        except Exception:
-            pass
-
-    def workspace(self, device, images: int, h: int, w: int):
-        need = L.lib().mvd_vgg_workspace_bytes(self.h, images, h, w)
-        if need < 0:
-            raise L.MvdError(f"vgg workspace_bytes: {L.last_error()}")
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = None
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-            L.call("mvd_vgg_bind_workspace", self.h, C.c_void_p(self.ws.data_ptr()), self.ws.numel())
+        super().__init__("vgg")
 
 
 def _images(t, who: str) -> torch.Tensor:
@@ -142,9 +98,7 @@ class VGG16FeaturesHIP(nn.Module):
         if self._dirty or self._dev != dev:
             with torch.no_grad():
                 self._packed = pack_vgg(self.state_dict(), dev)
-            for slot, t in self._packed.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_vgg_set_weight", self._handle.h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+            self._handle.set_weights(self._packed)
             self._dirty, self._dev = False, dev
 
     @torch.no_grad()
@@ -160,7 +114,7 @@ class VGG16FeaturesHIP(nn.Module):
         if taps:
             tap_t = [torch.empty(b, h >> i, w >> i, c, device=x.device, dtype=torch.bfloat16) for i, c in enumerate(TAP_CHANNELS)]
             tap_p = (C.c_void_p * 4)(*[t.data_ptr() for t in tap_t])
-        L.call("mvd_vgg_features", self._handle.h, C.c_void_p(x.data_ptr()), b, h, w, C.c_void_p(feat.data_ptr()), tap_p, _stream())
+        L.call("mvd_vgg_features", self._handle.h, C.c_void_p(x.data_ptr()), b, h, w, C.c_void_p(feat.data_ptr()), tap_p, L.stream())
         out = feat.permute(0, 3, 1, 2)
         return (out, {n: t.permute(0, 3, 1, 2) for n, t in zip(TAP_NAMES, tap_t)}) if taps else out
 
@@ -195,7 +149,7 @@ class PerceptualLoss:
         loss = torch.empty((), device=x.device, dtype=torch.float32)
         pp = torch.empty(b, device=x.device, dtype=torch.float32) if per_pair else None
         L.call("mvd_vgg_perceptual", hd.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, h, w, C.c_void_p(loss.data_ptr()),
-               C.c_void_p(pp.data_ptr()) if per_pair else None, _stream())
+               C.c_void_p(pp.data_ptr()) if per_pair else None, L.stream())
         return loss, pp
 
     @torch.no_grad()

@@ -115,11 +115,18 @@ class CLIPTextModelHIP(nn.Module):
         self.encoder = nn.Module()
         self.encoder.layers = nn.ModuleList([_layer(h, cfg.intermediate_size) for _ in range(cfg.num_hidden_layers)])
         self.final_layer_norm = nn.LayerNorm(h)
-        self._h = None
+        self._handle: Optional[L.Handle] = None
         self._dev = None
         self._packed: Dict[str, torch.Tensor] = {}
-        self._ws = None
         self._dirty = True
+
+    @property
+    def _h(self):
+        return self._handle.h if self._handle is not None else None
+
+    @property
+    def _ws(self):
+        return self._handle.ws if self._handle is not None else None
 
     @classmethod
     def from_snapshot(cls, path: str) -> "CLIPTextModelHIP":
@@ -143,13 +150,6 @@ class CLIPTextModelHIP(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("parameter container; the arithmetic runs in libmvd_hip.so")
 
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().mvd_text_destroy(self._h)
-        except Exception:
-            pass
-
     # ------------------------------------------------------------------ engine plumbing
     def _sync(self) -> torch.device:
         if not torch.cuda.is_available():
@@ -157,31 +157,18 @@ class CLIPTextModelHIP(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise L.MvdError(f"CLIPTextModelHIP is on {dev}: move it to a cuda device (there is no CPU fallback)")
-        if self._h is None:
+        if self._handle is None:
             c, cfg = L.mvd_text_config_t(), self.config
             c.vocab_size, c.hidden_size, c.intermediate_size = cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size
             c.num_layers, c.num_heads, c.max_positions = cfg.num_hidden_layers, cfg.num_attention_heads, cfg.max_position_embeddings
             c.layer_norm_eps, c.act = cfg.layer_norm_eps, ACTS[cfg.hidden_act]
-            h = C.c_void_p()
-            L.call("mvd_text_create", C.byref(c), C.byref(h))
-            self._h = h
+            self._handle = L.Handle("text", C.byref(c), rebind_always=True)
         if self._dirty or self._dev != dev:
             with torch.no_grad():
                 self._packed = pack_text(self.state_dict(), self.config, dev)
-            for slot, t in self._packed.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_text_set_weight", self._h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+            self._handle.set_weights(self._packed)
             self._dirty, self._dev = False, dev
         return dev
-
-    def _workspace(self, batch, seq_len):
-        need = L.lib().mvd_text_workspace_bytes(self._h, batch, seq_len)
-        if need < 0:
-            raise L.MvdError(f"text workspace_bytes: {L.last_error()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
-        L.call("mvd_text_bind_workspace", self._h, C.c_void_p(self._ws.data_ptr()), self._ws.numel())
 
     # ------------------------------------------------------------------ the transformers protocol
     @torch.no_grad()
@@ -197,8 +184,7 @@ class CLIPTextModelHIP(nn.Module):
             raise L.MvdError(f"CLIPTextModelHIP: token ids must be in [0, {self.config.vocab_size}), got [{lo}, {hi}]")
         dev = self._sync()
         ids = input_ids.to(dev, torch.int32).contiguous()
-        self._workspace(B, T)
+        self._handle.workspace(dev, B, T)
         out = torch.empty(B, T, self.config.hidden_size, device=dev, dtype=torch.float32)
-        L.call("mvd_text_encode", self._h, C.c_void_p(ids.data_ptr()), B, T, C.c_void_p(out.data_ptr()),
-               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        L.call("mvd_text_encode", self._h, C.c_void_p(ids.data_ptr()), B, T, C.c_void_p(out.data_ptr()), L.stream())
         return TextEncoderOutput((out,))

@@ -182,7 +182,7 @@ class DiagonalGaussianDistribution:
         noise = noise.to(self.parameters.device, torch.float32).contiguous()
         out = torch.empty_like(noise)
         L.call("mvd_op_gaussian_sample", C.c_void_p(self.parameters.data_ptr()), C.c_void_p(noise.data_ptr()), B, c2 // 2, H * W, 1.0,
-               C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+               C.c_void_p(out.data_ptr()), L.stream())
         return out
 
     def mode(self) -> torch.Tensor:
@@ -198,11 +198,18 @@ class AutoencoderKLHIP(nn.Module):
         lc = self.config.latent_channels
         self.quant_conv = nn.Conv2d(2 * lc, 2 * lc, 1)
         self.post_quant_conv = nn.Conv2d(lc, lc, 1)
-        self._h = None
+        self._handle: Optional[L.Handle] = None
         self._dev = None
         self._packed: Dict[str, torch.Tensor] = {}
-        self._ws = None
         self._dirty = True
+
+    @property
+    def _h(self):
+        return self._handle.h if self._handle is not None else None
+
+    @property
+    def _ws(self):
+        return self._handle.ws if self._handle is not None else None
 
     @classmethod
     def from_snapshot(cls, path: str) -> "AutoencoderKLHIP":
@@ -239,13 +246,6 @@ class AutoencoderKLHIP(nn.Module):
         self._dirty = True
         return super().to(*a, **k)
 
-    def __del__(self):
-        try:
-            if self._h:
-                L.lib().mvd_vae_destroy(self._h)
-        except Exception:
-            pass
-
     # ------------------------------------------------------------------ engine plumbing
     def _sync(self) -> torch.device:
         if not torch.cuda.is_available():
@@ -253,33 +253,20 @@ class AutoencoderKLHIP(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise L.MvdError(f"AutoencoderKLHIP is on {dev}: move it to a cuda device (there is no CPU fallback)")
-        if self._h is None:
+        if self._handle is None:
             c = L.mvd_vae_config_t()
             cfg = self.config
             c.in_channels, c.latent_channels, c.num_levels = cfg.in_channels, cfg.latent_channels, len(cfg.block_out_channels)
             for i, ch in enumerate(cfg.block_out_channels):
                 c.block_out_channels[i] = ch
             c.layers_per_block, c.norm_num_groups, c.norm_eps = cfg.layers_per_block, cfg.norm_num_groups, cfg.norm_eps
-            h = C.c_void_p()
-            L.call("mvd_vae_create", C.byref(c), C.byref(h))
-            self._h = h
+            self._handle = L.Handle("vae", C.byref(c), rebind_always=True)
         if self._dirty or self._dev != dev:
             with torch.no_grad():
                 self._packed = pack_vae(self.state_dict(), self.config, dev)
-            for slot, t in self._packed.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_vae_set_weight", self._h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+            self._handle.set_weights(self._packed)
             self._dirty, self._dev = False, dev
         return dev
-
-    def _workspace(self, batch, h, w, decode):
-        need = L.lib().mvd_vae_workspace_bytes(self._h, batch, h, w, int(decode))
-        if need < 0:
-            raise L.MvdError(f"vae workspace_bytes: {L.last_error()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
-        L.call("mvd_vae_bind_workspace", self._h, C.c_void_p(self._ws.data_ptr()), self._ws.numel())
 
     @torch.no_grad()
     def mid_attention(self, x: torch.Tensor, decoder: bool) -> torch.Tensor:
@@ -289,16 +276,9 @@ class AutoencoderKLHIP(nn.Module):
         assert x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous() and x.device == dev
         assert x.shape[3] == self.config.block_out_channels[-1], "the mid block runs at the deepest level's channel count"
         B, H, W, _ = x.shape
-        need = L.lib().mvd_vae_mid_attention_workspace_bytes(self._h, int(decoder), B, H, W)
-        if need < 0:
-            raise L.MvdError(f"vae mid_attention_workspace_bytes: {L.last_error()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
-        L.call("mvd_vae_bind_workspace", self._h, C.c_void_p(self._ws.data_ptr()), self._ws.numel())
+        self._handle.workspace(dev, int(decoder), B, H, W, sizer="mid_attention_workspace_bytes")
         out = torch.empty_like(x)
-        L.call("mvd_vae_mid_attention", self._h, int(decoder), C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
-               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        L.call("mvd_vae_mid_attention", self._h, int(decoder), C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()), L.stream())
         return out
 
     # ------------------------------------------------------------------ the diffusers protocol
@@ -308,10 +288,9 @@ class AutoencoderKLHIP(nn.Module):
         x = x.to(dev, torch.float32).contiguous()
         B, _, H, W = x.shape
         f = 2 ** (len(self.config.block_out_channels) - 1)
-        self._workspace(B, H, W, False)
+        self._handle.workspace(dev, B, H, W, 0)
         mom = torch.empty(B, 2 * self.config.latent_channels, H // f, W // f, device=dev, dtype=torch.float32)
-        L.call("mvd_vae_encode", self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(mom.data_ptr()),
-               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        L.call("mvd_vae_encode", self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(mom.data_ptr()), L.stream())
         dist = DiagonalGaussianDistribution(mom)
         return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
 
@@ -321,8 +300,7 @@ class AutoencoderKLHIP(nn.Module):
         z = z.to(dev, torch.float32).contiguous()
         B, _, h, w = z.shape
         f = 2 ** (len(self.config.block_out_channels) - 1)
-        self._workspace(B, h, w, True)
+        self._handle.workspace(dev, B, h, w, 1)
         img = torch.empty(B, self.config.in_channels, h * f, w * f, device=dev, dtype=torch.float32)
-        L.call("mvd_vae_decode", self._h, C.c_void_p(z.data_ptr()), B, h, w, C.c_void_p(img.data_ptr()),
-               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        L.call("mvd_vae_decode", self._h, C.c_void_p(z.data_ptr()), B, h, w, C.c_void_p(img.data_ptr()), L.stream())
         return SimpleNamespace(sample=img) if return_dict else (img,)

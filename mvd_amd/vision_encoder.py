@@ -107,45 +107,26 @@ def pack_vision(sd: Dict[str, torch.Tensor], cfg: CLIPVisionConfigLite, device) 
     return out
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _f3(values):
     return (C.c_float * 3)(*[float(x) for x in values])
 
 
-class _VisionHandle:
-    """One ``mvd_vision_t`` with its workspace (grown on demand, rebound when it moves)."""
+class _VisionHandle(L.Handle):
+    """One ``mvd_vision_t`` with its workspace and the resize geometry the resampling tables at its head belong to."""
 
     def __init__(self, cfg: CLIPVisionConfigLite):
         c = L.mvd_vision_config_t()
         c.image_size, c.patch_size, c.hidden_size, c.intermediate_size = cfg.image_size, cfg.patch_size, cfg.hidden_size, cfg.intermediate_size
         c.num_layers, c.num_heads, c.projection_dim = cfg.num_hidden_layers, cfg.num_attention_heads, cfg.projection_dim
         c.layer_norm_eps, c.act = cfg.layer_norm_eps, ACTS[cfg.hidden_act]
-        self.h = C.c_void_p()
-        L.call("mvd_vision_create", C.byref(c), C.byref(self.h))
-        self.ws = None
+        super().__init__("vision", C.byref(c))
         self.geometry = (0, 0, 0)
-
-    def __del__(self):
-        try:
-            if self.h:
-                L.lib().mvd_vision_destroy(self.h)
-        except Exception:
-            pass
 
     def workspace(self, device, batch, h=0, w=0, resize_to=0):
         if h == 0:                     # encode only: the resampling tables of the last geometry stay where they are
             h, w, resize_to = self.geometry
         self.geometry = (h, w, resize_to)
-        need = L.lib().mvd_vision_workspace_bytes(self.h, batch, h, w, resize_to)
-        if need < 0:
-            raise L.MvdError(f"vision workspace_bytes: {L.last_error()}")
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = None
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-            L.call("mvd_vision_bind_workspace", self.h, C.c_void_p(self.ws.data_ptr()), self.ws.numel())
+        super().workspace(device, batch, h, w, resize_to)
 
     def preprocess(self, images, quantize, resize_to, crop, mean, std, want_patches, want_pixel_values):
         B, ch, h, w = images.shape
@@ -154,7 +135,7 @@ class _VisionHandle:
         self.workspace(images.device, B, h, w, resize_to)
         pv = torch.empty(B, 3, crop, crop, device=images.device, dtype=torch.float32) if want_pixel_values else None
         L.call("mvd_vision_preprocess", self.h, C.c_void_p(images.data_ptr()), B, h, w, int(quantize), int(resize_to), int(crop),
-               _f3(mean), _f3(std), int(want_patches), C.c_void_p(pv.data_ptr()) if pv is not None else None, _stream())
+               _f3(mean), _f3(std), int(want_patches), C.c_void_p(pv.data_ptr()) if pv is not None else None, L.stream())
         return pv
 
 
@@ -306,9 +287,7 @@ class CLIPVisionModelHIP(nn.Module):
         if self._dirty or self._dev != dev:
             with torch.no_grad():
                 self._packed = pack_vision(self.state_dict(), self.config, dev)
-            for slot, t in self._packed.items():
-                dt = {torch.float32: 0, torch.bfloat16: 1}[t.dtype]
-                L.call("mvd_vision_set_weight", self._handle.h, slot.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt)
+            self._handle.set_weights(self._packed)
             self._dirty, self._dev = False, dev
         return dev
 
@@ -318,7 +297,7 @@ class CLIPVisionModelHIP(nn.Module):
         raw = torch.empty(batch, cfg.projection_dim, device=dev, dtype=torch.float32)
         nrm = torch.empty_like(raw)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-        L.call("mvd_vision_encode", self._handle.h, p(pixel_values), batch, p(hid), p(raw), p(nrm), _stream())
+        L.call("mvd_vision_encode", self._handle.h, p(pixel_values), batch, p(hid), p(raw), p(nrm), L.stream())
         return hid, raw, nrm
 
     def _check_pixel_values(self, pixel_values):
