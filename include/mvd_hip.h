@@ -664,6 +664,25 @@ int mvd_op_knn_radii(const float* f, int n, int d, int k, int force_parts, doubl
 int mvd_op_manifold_counts(const float* q, int nq, const float* r, int nr, int d, const double* r_radii_sq, int closed, int32_t* hits_per_query,
                            int32_t* hits_per_ref, void* stream);
 
+/* ---- image front end of the data loader (N13): composite on white, LANCZOS resize, normalisation ----------------------
+ * What the reference's dataset does to every decoded render with PIL on the host (objaverse_dataset.py:279-294, :259-266):
+ * Image.alpha_composite(white, img).convert("RGB") (channels == 4 only), resize((out_w, out_h), LANCZOS) -- Pillow's 8-bit
+ * two-pass resample in integers, byte for byte -- and float(byte) / 127.5f - 1.0f (an fp32 division and an fp32 subtraction).
+ * src [batch][h][w][channels] uint8 on the device (channels 3 or 4: the layout of np.array(Image.open(...))), any alignment;
+ * when src is a multiple of 4 but not of 16, the 16-byte loads start at src rounded down to 16 bytes, i.e. up to 12 bytes in front
+ * of the buffer are read (same 16-byte line, so never another page; the values are not used);
+ * out_u8 [batch][out_h][out_w][3] uint8 and / or out_f32 [batch][3][out_h][out_w] fp32, at least one not NULL.  A pass whose
+ * sizes are equal is skipped.  The workspace (256-byte aligned, workspace_bytes(...) bytes) holds the coefficient tables and the
+ * uint8 intermediate; the tables are built once per geometry on the host and kept for the life of the process (tens of KB each; the
+ * first 64 geometries also keep a page-locked copy for the upload, later ones upload from pageable memory).  Nothing synchronises.  Refused: a geometry whose
+ * weights could overflow the 32-bit accumulator, and a horizontal scale above ~9 (the source span of one workgroup).
+ * image_frontend_spans: {columns, rows} of a workgroup of the horizontal kernel, then of the vertical kernel (for tests that
+ * plant values on both sides of every boundary). */
+int mvd_op_image_frontend_spans(int* out4);
+int64_t mvd_op_image_frontend_workspace_bytes(int batch, int h, int w, int channels, int out_h, int out_w);
+int mvd_op_image_frontend(const uint8_t* src, int batch, int h, int w, int channels, int out_h, int out_w, uint8_t* out_u8, float* out_f32,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,10 @@ _SIGS = {
     "mvd_op_knn_radii_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mvd_op_knn_radii": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mvd_op_manifold_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_image_frontend_spans": (C.c_int, [C.POINTER(C.c_int)]),
+    "mvd_op_image_frontend_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvd_op_image_frontend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

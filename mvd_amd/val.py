@@ -1,0 +1,415 @@
+"""The reference's validation script (val.py) on this project's classes: the same metrics, the same two CSV
+files with the same columns in the same order and the same aggregation rules, without Lightning, torchmetrics, lpips,
+pytorch_msssim, icecream or lovely_tensors.
+
+    python -m mvd_amd.val --ckpt last.ckpt --dataset-path /data/objaverse --config infer_config.yaml --output-dir outputs/val
+
+writes ``<output-dir>/<timestamp>/validation_results.csv`` (one row per sample), ``overall_metrics.csv`` and ``samples/*.png``.
+
+Configuration keys read (the reference ships no ``config/infer_config.yaml``; this is the whole list): ``architecture``,
+``torch_dtype``, ``use_camera_conditioning``, ``use_image_conditioning``, ``img_ref_scale``, ``cam_modulation_strength``,
+``cam_output_dim``, ``cam_hidden_dim``, ``simple_encoder``, ``scheduler_config`` (optional, ignored as in the reference),
+``use_memory_efficient_attention`` / ``enable_gradient_checkpointing`` (optional here, no meaning on this engine), ``image_size``
+([width, height]), ``max_views_per_object``, ``batch_size``, ``num_workers``, ``num_inference_steps``, ``guidance_scale``,
+``ref_scale``, ``clip_model_name`` (optional); and this project's own optional keys ``cache_dir`` (local huggingface cache of the
+architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics`` and ``metric_weights`` (a
+mapping of the ``ValidationMetrics`` weight keywords to paths).
+
+What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
+of the per-metric aggregates; ``clip_score`` is a per-batch value copied to each of the batch's samples and aggregated apart;
+PSNR / SSIM / LPIPS / perceptual loss are evaluated again per sample; the comparison image is saved for the LAST sample of each
+batch only; a batch that raises is logged and skipped.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import datetime
+import logging
+import os
+import time
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from ._lib import MvdError
+
+logger = logging.getLogger(__name__)
+
+EXTRA_METRICS = ("kid", "is", "prc", "dc")
+NOT_AVERAGED = ("clip_score", "batch_inference_time_seconds", "num_samples_in_batch")
+DEFAULT_CLIP = "openai/clip-vit-large-patch14"
+
+
+def _build(what: str, make, level=logging.ERROR):
+    try:
+        return make()
+    except Exception as e:  # noqa: BLE001  (the reference's rule: the run goes on and the metric scores 0.0)
+        logger.log(level, "Failed to initialize %s: %s", what, e)
+        return None
+
+
+class ValidationMetrics:
+    """The reference's metric set on the N6-N12 classes.  ``*_weights`` / ``*_path`` keywords go to those classes (``None``: their
+    own search of the local caches).  ``extra_metrics``: any of "kid", "is", "prc", "dc"; with at least one of them a single
+    ``InceptionV3FeaturesHIP`` serves FID and the extras, and every batch costs one tower call per side."""
+
+    def __init__(self, device, clip_model_name: str = DEFAULT_CLIP, *, clip_cache_dir=None, perceptual_weights=None, lpips_backbone=None,
+                 lpips_model_path=None, inception_weights=None, extra_metrics: Sequence[str] = (), kid_subsets: int = 100,
+                 kid_subset_size: int = 1000, is_splits: int = 10, prc_neighborhood: int = 3, dc_nearest_k: int = 5, max_images_per_pass: int = 8):
+        from .clip_score import CLIPScore
+        from .fid import FrechetInceptionDistance, InceptionV3FeaturesHIP
+        from .lpips import LPIPS
+        from .perceptual import PerceptualLoss
+        from .validation import SSIM, PeakSignalNoiseRatio
+        unknown = [m for m in extra_metrics if m not in EXTRA_METRICS]
+        if unknown:
+            raise MvdError(f"ValidationMetrics: extra_metrics {unknown}: expected some of {EXTRA_METRICS}")
+        self.device = device
+        self.extra_metrics = tuple(m for m in EXTRA_METRICS if m in extra_metrics)
+        self.ssim = _build("SSIM", lambda: SSIM(data_range=2.0, size_average=True).to(device))
+        self.psnr = _build("PSNR", lambda: PeakSignalNoiseRatio(data_range=2.0).to(device))
+        self.perceptual_loss = _build("Perceptual loss", lambda: PerceptualLoss(device=device, weights=perceptual_weights))
+        self.lpips_metric = _build("LPIPS", lambda: LPIPS(net="alex", backbone=lpips_backbone, model_path=lpips_model_path).to(device))
+        self.clip_score_metric = _build("CLIPScore", lambda: CLIPScore(model_name_or_path=clip_model_name, cache_dir=clip_cache_dir).to(device),
+                                        logging.WARNING)
+        self.inception = None
+        if self.extra_metrics:
+            self.inception = _build("Inception-v3", lambda: InceptionV3FeaturesHIP(inception_weights, max_images_per_pass=max_images_per_pass),
+                                    logging.WARNING)
+        shared = dict(inception=self.inception) if self.inception is not None else dict(weights=inception_weights,
+                                                                                          max_images_per_pass=max_images_per_pass)
+        self.fid_metric = _build("FID", lambda: FrechetInceptionDistance(normalize=True, **shared).to(device), logging.WARNING)
+        self.kid_metric = self.is_metric = self.prc_metric = self.dc_metric = None
+        if self.inception is not None:
+            from .kid import InceptionScore, KernelInceptionDistance
+            from .prdc import DensityCoverage, PrecisionRecall
+            tower = dict(inception=self.inception, normalize=True)
+            if "kid" in self.extra_metrics:
+                self.kid_metric = _build("KID", lambda: KernelInceptionDistance(subsets=kid_subsets, subset_size=kid_subset_size, **tower), logging.WARNING)
+            if "is" in self.extra_metrics:
+                self.is_metric = _build("Inception score", lambda: InceptionScore(splits=is_splits, **tower), logging.WARNING)
+            if "prc" in self.extra_metrics:
+                self.prc_metric = _build("precision/recall", lambda: PrecisionRecall(neighborhood=prc_neighborhood, **tower), logging.WARNING)
+            if "dc" in self.extra_metrics:
+                self.dc_metric = _build("density/coverage", lambda: DensityCoverage(nearest_k=dc_nearest_k, **tower), logging.WARNING)
+
+    def _scalar(self, name: str, metric, fn) -> float:
+        if metric is None:
+            return 0.0
+        try:
+            return fn()
+        except Exception as e:  # noqa: BLE001
+            logger.warning("%s calculation failed: %s", name, e)
+            return 0.0
+
+    def calculate_metrics(self, generated_images: torch.Tensor, target_images: torch.Tensor, prompts: Optional[List[str]] = None) -> Dict[str, float]:
+        """images in [-1, 1]; -> {"psnr", "ssim", "perceptual_loss", "lpips", "clip_score"} of the batch, and the batch is added to
+        the FID statistics (and to the extras')"""
+        metrics: Dict[str, float] = {}
+        with torch.no_grad():
+            gen, tgt = generated_images.float(), target_images.float()
+            metrics["psnr"] = self._scalar("PSNR", self.psnr, lambda: self.psnr(gen, tgt).item())
+            metrics["ssim"] = self._scalar("SSIM", self.ssim, lambda: self.ssim(gen, tgt).item())
+            metrics["perceptual_loss"] = self._scalar("Perceptual loss", self.perceptual_loss, lambda: self.perceptual_loss(gen, tgt).item())
+            metrics["lpips"] = self._scalar("LPIPS", self.lpips_metric, lambda: self.lpips_metric(gen, tgt).mean().item())
+
+            def clip():
+                gen_uint8 = ((gen.clamp(-1, 1) + 1) / 2.0 * 255).to(torch.uint8)
+                return self.clip_score_metric(gen_uint8, prompts).item()
+            metrics["clip_score"] = self._scalar("CLIP score", self.clip_score_metric if prompts is not None else None, clip)
+            if self.fid_metric is not None or self.inception is not None:
+                try:
+                    gen_fid, tgt_fid = (gen.clamp(-1, 1) + 1) / 2.0, (tgt.clamp(-1, 1) + 1) / 2.0
+                    if self.inception is not None:      # the shared tower feeds whichever of FID and the extras were built
+                        self._update_shared(self.inception.forward(gen_fid), self.inception.forward(tgt_fid))
+                    else:
+                        self.fid_metric.update(gen_fid, real=False)
+                        self.fid_metric.update(tgt_fid, real=True)
+                except Exception as e:  # noqa: BLE001
+                    logger.warning("FID update failed: %s", e)
+        return metrics
+
+    def _update_shared(self, fake: torch.Tensor, real: torch.Tensor) -> None:
+        """one tower call per side feeds every feature metric"""
+        for m in (self.fid_metric, self.kid_metric, self.prc_metric, self.dc_metric):
+            if m is not None:
+                m.update_features(fake, real=False)
+                m.update_features(real, real=True)
+        if self.is_metric is not None:
+            self.is_metric.update_features(fake)
+
+    def compute_fid(self) -> float:
+        return self._scalar("FID", self.fid_metric, lambda: self.fid_metric.compute().item())
+
+    def reset_fid(self):
+        if self.fid_metric is not None:
+            self.fid_metric.reset()
+
+    def compute_extras(self) -> Dict[str, float]:
+        """the rows appended to overall_metrics.csv behind the reference's (only for the metrics asked for)"""
+        out: Dict[str, float] = {}
+
+        def put(names, metric, what):
+            if metric is None:
+                vals = [0.0] * len(names)
+            else:
+                try:
+                    vals = [float(v) for v in metric.compute()][:len(names)]
+                except Exception as e:  # noqa: BLE001
+                    logger.warning("%s computation failed: %s", what, e)
+                    vals = [0.0] * len(names)
+            out.update(zip(names, vals))
+        if "kid" in self.extra_metrics:
+            put(("kid_mean", "kid_std"), self.kid_metric, "KID")
+        if "is" in self.extra_metrics:
+            put(("inception_score_mean", "inception_score_std"), self.is_metric, "Inception score")
+        if "prc" in self.extra_metrics:
+            put(("precision", "recall", "f_score"), self.prc_metric, "precision/recall")
+        if "dc" in self.extra_metrics:
+            put(("density", "coverage"), self.dc_metric, "density/coverage")
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- configuration
+def load_config(config_path: str) -> Dict:
+    if not os.path.exists(config_path):
+        raise FileNotFoundError(f"Configuration file not found: {config_path}")
+    try:
+        import yaml
+    except ImportError as e:
+        raise MvdError("reading the configuration needs the 'PyYAML' package (yaml), which is not installed") from e
+    with open(config_path, "r") as f:
+        return yaml.safe_load(f)
+
+
+def setup_pipeline(config: Dict, checkpoint_path: str, device):
+    """``create_mvd_pipeline(config["architecture"], ..., text_encoder="hip")`` with the checkpoint's UNet weights, in eval mode on
+    ``device``; nothing is fetched (``config["cache_dir"]`` or ``HF_HOME`` names the local cache)"""
+    if not os.path.exists(checkpoint_path):
+        raise FileNotFoundError(f"Checkpoint file not found: {checkpoint_path}")
+    from .checkpoint import load_lightning_checkpoint
+    from .mvd_unet import create_mvd_pipeline
+    pipeline = create_mvd_pipeline(
+        pretrained_model_name_or_path=config["architecture"],
+        use_memory_efficient_attention=config.get("use_memory_efficient_attention", True),
+        enable_gradient_checkpointing=config.get("enable_gradient_checkpointing", False),
+        dtype=getattr(torch, config["torch_dtype"]),
+        use_camera_conditioning=config["use_camera_conditioning"], use_image_conditioning=config["use_image_conditioning"],
+        img_ref_scale=config["img_ref_scale"], cam_modulation_strength=config["cam_modulation_strength"],
+        cam_output_dim=config["cam_output_dim"], cam_hidden_dim=config["cam_hidden_dim"], simple_cam_encoder=config["simple_encoder"],
+        cache_dir=config.get("cache_dir"), scheduler_config=config.get("scheduler_config", {}), sampler=config.get("sampler", "ddpm"),
+        text_encoder="hip")
+    missing, unexpected = load_lightning_checkpoint(pipeline.unet, checkpoint_path)
+    if missing:
+        logger.warning("Missing keys in checkpoint: %s...", missing[:5])
+    if unexpected:
+        logger.warning("Unexpected keys in checkpoint: %s...", unexpected[:5])
+    pipeline = pipeline.to(device)
+    for m in (pipeline.unet, pipeline.vae, pipeline.text_encoder):
+        if m is not None and hasattr(m, "eval"):
+            m.eval()
+    return pipeline
+
+
+# ---------------------------------------------------------------------------------------------------------------- the run
+def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *, metrics: Optional[ValidationMetrics] = None,
+                   extra_metrics: Sequence[str] = (), metric_kwargs: Optional[Dict] = None, on_batch=None):
+    """-> (all_results, overall_metrics) and the two CSV files under ``output_dir``.  ``metrics``: a ready ``ValidationMetrics``
+    (otherwise one is built from ``config`` / ``extra_metrics`` / ``metric_kwargs``).  ``on_batch(batch_idx, generated, target,
+    prompts)`` (optional) sees every batch's tensors before they are scored.  For a dataset in device mode the loader's workers
+    return the raw samples and ``DeviceCollate`` runs here, in the main process (any ``num_workers``)."""
+    from torch.utils.data import DataLoader
+    output_dir = Path(output_dir)
+    output_dir.mkdir(exist_ok=True, parents=True)
+    calc = metrics if metrics is not None else ValidationMetrics(device, config.get("clip_model_name", DEFAULT_CLIP), extra_metrics=extra_metrics,
+                                                                 **(metric_kwargs or {}))
+    loader_kw = dict(batch_size=config["batch_size"], shuffle=False, num_workers=config["num_workers"])
+    device_collate = None
+    if getattr(dataset, "frontend", "host") == "device":
+        # the workers only inflate and hand the raw arrays back; the copy and the kernels run here, in the process that owns the GPU
+        from .dataset import DeviceCollate, raw_collate
+        loader_kw["collate_fn"] = raw_collate
+        device_collate = DeviceCollate(device, dataset.target_size)
+    else:
+        loader_kw["pin_memory"] = True
+    dataloader = DataLoader(dataset, **loader_kw)
+    on_gpu = torch.device(device).type == "cuda"
+    all_results, batch_metrics = [], []
+    with torch.no_grad():
+        for batch_idx, batch in enumerate(dataloader):
+            try:
+                if device_collate is not None:
+                    batch = device_collate(batch)
+                source_images, target_images = batch["source_image"].to(device), batch["target_image"].to(device)
+                source_camera, target_camera = batch.get("source_camera"), batch.get("target_camera")
+                prompts, object_uids = batch["prompt"], batch["object_uid"]
+                if source_camera is not None:
+                    source_camera = source_camera.to(device)
+                if target_camera is not None:
+                    target_camera = target_camera.to(device)
+                # a host clock around the pipeline call; the device is drained inside the window so that the figure is the work's
+                start = time.perf_counter()
+                out = pipeline(prompt=prompts, num_inference_steps=config["num_inference_steps"], source_camera=source_camera,
+                               target_camera=target_camera, source_images=source_images, guidance_scale=config["guidance_scale"],
+                               ref_scale=config["ref_scale"], output_type="pt", use_camera_embeddings=config["use_camera_conditioning"],
+                               use_image_conditioning=config["use_image_conditioning"])
+                if on_gpu:
+                    torch.cuda.synchronize()
+                batch_time = time.perf_counter() - start
+                n = len(object_uids)
+                logger.info("Batch %d inference time: %.4f seconds for %d samples.", batch_idx, batch_time, n)
+                generated_images = (out["images"] * 2.0 - 1.0).to(device)
+                if on_batch is not None:
+                    on_batch(batch_idx, generated_images, target_images, prompts)
+                bm = calc.calculate_metrics(generated_images, target_images, prompts)
+                bm["batch_inference_time_seconds"] = batch_time
+                bm["num_samples_in_batch"] = n
+                per_sample_time = batch_time / n if n > 0 else 0
+                again = {"psnr": calc.psnr, "ssim": calc.ssim, "lpips": calc.lpips_metric, "perceptual_loss": calc.perceptual_loss}
+                for i in range(n):
+                    sample = {"inference_time_seconds": per_sample_time}
+                    for name, value in bm.items():
+                        if name in NOT_AVERAGED:
+                            sample[name] = value              # the batch's value, as it is
+                        elif again.get(name) is not None:
+                            sample[name] = again[name](generated_images[i:i + 1], target_images[i:i + 1]).item()
+                        else:
+                            sample[name] = 0.0
+                    all_results.append({"object_uid": object_uids[i], "prompt": prompts[i], **sample})
+                # (the reference's indentation: behind the loop, so the last sample of the batch)
+                save_sample_images(source_images[i], target_images[i], generated_images[i], object_uids[i], sample, output_dir, batch_idx)
+                batch_metrics.append(bm)
+            except Exception as e:  # noqa: BLE001
+                logger.error("Error processing batch %d: %s", batch_idx, e)
+                continue
+    overall = calculate_overall_metrics(batch_metrics, calc.compute_fid())
+    if calc.extra_metrics:
+        overall.update(calc.compute_extras())
+    save_results(all_results, overall, output_dir)
+    return all_results, overall
+
+
+def save_sample_images(source_image_tensor, target_image_tensor, generated_image_tensor, object_uid, metrics: Dict[str, float], output_dir: Path,
+                       batch_idx: int):
+    """source | target | generated side by side under a header line, as ``samples/comparison_batch<NNNN>_uid_<uid>.png``"""
+    try:
+        from PIL import Image, ImageDraw
+    except ImportError:
+        logger.warning("the 'Pillow' package (PIL) is not installed: no comparison image for UID %s, batch %d", object_uid, batch_idx)
+        return
+    samples_dir = Path(output_dir) / "samples"
+    samples_dir.mkdir(exist_ok=True, parents=True)
+
+    def to_pil(t):
+        return Image.fromarray(((t.cpu().permute(1, 2, 0) + 1) / 2 * 255).numpy().astype("uint8"))
+    try:
+        ims = [to_pil(source_image_tensor), to_pil(target_image_tensor), to_pil(generated_image_tensor)]
+        header = 30
+        sheet = Image.new("RGB", (sum(im.width for im in ims), ims[0].height + header), (255, 255, 255))
+        text = (f"UID: {object_uid} | LPIPS: {metrics.get('lpips', 0.0):.3f} | PSNR: {metrics.get('psnr', 0.0):.2f} | "
+                f"SSIM: {metrics.get('ssim', 0.0):.3f}")
+        ImageDraw.Draw(sheet).text((10, 5), text, fill="black")
+        x = 0
+        for im in ims:
+            sheet.paste(im, (x, header))
+            x += im.width
+        sheet.save(samples_dir / f"comparison_batch{batch_idx:04d}_uid_{object_uid}.png")
+    except Exception as e:  # noqa: BLE001
+        logger.warning("Failed to save sample comparison image for UID %s, batch %d: %s", object_uid, batch_idx, e)
+
+
+def calculate_overall_metrics(batch_metrics: List[Dict], final_fid: float) -> Dict[str, float]:
+    """the reference's aggregation: mean / std / min / max over the batches' values that are > 0 (a metric with none has no rows),
+    then ``fid``, then the CLIP score's mean / std over its values > 0, then the timing rows"""
+    if not batch_metrics:
+        return {}
+    agg: Dict[str, float] = {}
+    for name in batch_metrics[0].keys():
+        if name in NOT_AVERAGED:
+            continue
+        values = [b[name] for b in batch_metrics if name in b and b[name] > 0]
+        if values:
+            agg[f"{name}_mean"], agg[f"{name}_std"] = np.mean(values), np.std(values)
+            agg[f"{name}_min"], agg[f"{name}_max"] = np.min(values), np.max(values)
+    agg["fid"] = final_fid
+    clip = [s for s in (b.get("clip_score", 0) for b in batch_metrics) if s > 0]
+    if clip:
+        agg["clip_score_mean"], agg["clip_score_std"] = np.mean(clip), np.std(clip)
+    times = [b["batch_inference_time_seconds"] for b in batch_metrics if "batch_inference_time_seconds" in b]
+    counts = [b["num_samples_in_batch"] for b in batch_metrics if "num_samples_in_batch" in b]
+    if times:
+        agg["mean_batch_inference_time_seconds"], agg["std_batch_inference_time_seconds"] = np.mean(times), np.std(times)
+        agg["min_batch_inference_time_seconds"], agg["max_batch_inference_time_seconds"] = np.min(times), np.max(times)
+        total, samples = np.sum(times), np.sum(counts)
+        agg["total_inference_duration_seconds"] = total
+        agg["total_samples_processed_in_inference"] = samples
+        agg["avg_per_sample_inference_time_seconds"] = total / samples if samples > 0 else 0.0
+    else:
+        agg["mean_batch_inference_time_seconds"] = 0.0
+        agg["total_inference_duration_seconds"] = 0.0
+        agg["total_samples_processed_in_inference"] = 0.0
+        agg["avg_per_sample_inference_time_seconds"] = 0.0
+    return agg
+
+
+def save_results(all_results: List[Dict], overall_metrics: Dict, output_dir: Path):
+    output_dir = Path(output_dir)
+    if all_results:
+        with open(output_dir / "validation_results.csv", "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=all_results[0].keys())
+            w.writeheader()
+            w.writerows(all_results)
+    with open(output_dir / "overall_metrics.csv", "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["Metric", "Value"])
+        for metric, value in overall_metrics.items():
+            w.writerow([metric, value])
+
+
+def main(argv=None) -> int:
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+    ap = argparse.ArgumentParser(description="Validation of a checkpoint on an Objaverse render tree")
+    ap.add_argument("--ckpt", type=str, required=True, help="Path to trained checkpoint")
+    ap.add_argument("--dataset-path", type=str, required=True, help="Path to the dataset root (holds renders_final/*.zip)")
+    ap.add_argument("--config", type=str, default="config/infer_config.yaml", help="Path to inference configuration file")
+    ap.add_argument("--output-dir", type=str, default="outputs/gso_validation", help="Output directory for results")
+    ap.add_argument("--extra-metrics", type=str, default=None, help=f"comma-separated subset of {','.join(EXTRA_METRICS)} (default: the config's, else none)")
+    ap.add_argument("--frontend", choices=("host", "device"), default=None, help="where composite + resize run (default: the config's, else host)")
+    args = ap.parse_args(argv)
+    try:
+        config = load_config(args.config)
+    except Exception as e:  # noqa: BLE001
+        logger.error("Failed to load configuration: %s", e)
+        return 1
+    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+    output_dir.mkdir(exist_ok=True, parents=True)
+    extras = args.extra_metrics.split(",") if args.extra_metrics else list(config.get("extra_metrics", ()))
+    try:
+        pipeline = setup_pipeline(config, args.ckpt, device)
+    except Exception as e:  # noqa: BLE001
+        logger.error("Failed to setup pipeline: %s", e)
+        return 1
+    try:
+        from .dataset import ObjaverseDataset
+        dataset = ObjaverseDataset(data_root=args.dataset_path, split="test", target_size=(config["image_size"][0], config["image_size"][1]),
+                                   max_views_per_object=config["max_views_per_object"], frontend=args.frontend or config.get("frontend", "host"))
+    except Exception as e:  # noqa: BLE001
+        logger.error("Failed to load dataset: %s", e)
+        return 1
+    try:
+        kw = dict(config.get("metric_weights", {}), clip_cache_dir=config.get("cache_dir"))
+        all_results, overall = run_validation(pipeline, dataset, config, device, output_dir, extra_metrics=[m for m in extras if m], metric_kwargs=kw)
+        logger.info("Calculated metrics: %s", overall)
+        logger.info("%d samples scored; results under %s", len(all_results), output_dir)
+        return 0
+    except Exception as e:  # noqa: BLE001
+        logger.error("Validation failed: %s", e)
+        return 1
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
