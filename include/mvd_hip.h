@@ -72,8 +72,22 @@ enum {
   MVD_USE_CAMERA = 1,       /* use_camera_conditioning and target_camera is not None (mvd_unet.py:241) */
   MVD_USE_IMAGE = 2,        /* use_image_conditioning and source_image_latents is not None (:269)      */
   MVD_REUSE_REF = 4,        /* reuse reference K/V computed by a previous call (inputs step-invariant)  */
-  MVD_KEEP_FEATURES = 8     /* keep the 16 encoder feature maps for mvd_engine_get_feature               */
+  MVD_KEEP_FEATURES = 8,    /* keep the 16 encoder feature maps for mvd_engine_get_feature               */
+  MVD_SHARE_REF = 16        /* `views` views of ONE object in one forward, sharing one reference (below)  */
 };
+
+/* MVD_SHARE_REF (with MVD_USE_IMAGE; no counterpart in the reference, whose infer.py:111-122 makes one batch-1 call per
+ * view): the forward computes what `views` independent forwards of batch g = batch / views (1, or 2 under classifier-free
+ * guidance) with a ONE-row reference compute, from one encoder pass and one copy of the reference K/V.  The sample rows come
+ * in the pipeline's order [uncond x views | cond x views]: row r = j * views + v is row j of view v's own call, so it
+ *   - attends reference tokens [j * hw / g, (j + 1) * hw / g) of the single reference in both adapter branches (Q4 at
+ *     batch g), and text row j;
+ *   - takes camera v (cam_batch = views: the existing r % cam_batch rule), timesteps[r];
+ * the encoder pass, the Q2 statistics and the ref_kv projection run once, at ref_batch = 1.  Shapes: batch = g * views with
+ * g in {1, 2}; ref_batch = 1; `text` holds g rows and `encoder_text` 1 row; the cameras hold 0, 1 or `views` rows; hw % g == 0 at
+ * every level.  Anything else is rejected on the host before any launch, as is the flag on mvd_engine_reference_encode
+ * (the global-statistics path is for batches sharded over ranks: more than one object).  Size the workspace with
+ * mvd_engine_workspace_bytes_args; the reference cache is that of ref_batch = 1. */
 
 /* One MultiViewUNet.forward (mvd_unet.py:179-338).  All tensors fp32, contiguous. */
 typedef struct {
@@ -82,7 +96,8 @@ typedef struct {
   int text_len;              /* 77                                                                       */
   const float* sample;       /* [batch][in_channels][H][W]                                               */
   const float* timesteps;    /* [batch] (already expanded; ints as floats)                               */
-  const float* text;         /* [batch][text_len][cross_attention_dim] (already repeated, :233-237)      */
+  const float* text;         /* [batch][text_len][cross_attention_dim] (already repeated, :233-237);
+                                MVD_SHARE_REF: [batch / views] rows (one per guidance half)               */
   const float* source_camera;/* [batch][cam_rows][4] or NULL                                             */
   const float* target_camera;
   int cam_rows;              /* 3 or 4 (Q8)                                                              */
@@ -95,9 +110,13 @@ typedef struct {
   int ref_batch;
   int flags;
   float* out;                /* [batch][out_channels][H][W]                                              */
+  int views;                 /* MVD_SHARE_REF: views per object (>= 1, divides batch); otherwise 0 or 1   */
 } mvd_forward_args_t;
 
 int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream);
+/* mvd_engine_workspace_bytes for a whole argument block (shapes, flags, ref_batch, cam_batch, views; the pointers are not
+ * read): the only sizing entry for an MVD_SHARE_REF forward, which the positional form cannot describe. */
+int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args);
 
 /* Global Q2 statistics (SURVEY.md 8e mode ii; optional).  The adapter normalises the reference features with statistics
  * over (batch, channel) per pixel (attention.py:95-103), so a batch sharded over GPUs sees per-shard statistics unless the
@@ -203,6 +222,11 @@ int mvd_op_conv3x3_up4(const void* x, int batch, int in_h, int in_w, int cin, co
  * by softmax_scale * log2(e) (the packed to_q / to_q_ref weight rows carry that factor, DESIGN.md "Weight slots"). */
 int mvd_op_attention(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
                      int ldk, int ldv, int ldo, float scale, void* stream);
+/* Grouped K/V: batch element b attends the K/V of K/V batch element b / kv_group, so k / v hold batch / kv_group elements of
+ * nk rows (kv_group views of one object share its reference tokens; kv_group <= 1 is mvd_op_attention).  Every wave-count form
+ * takes it; bit-identical to running the views one by one. */
+int mvd_op_attention_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                             int ldk, int ldv, int ldo, float scale, int kv_group, void* stream);
 /* Split-KV form (batch 1: too few (head, query block) pairs to fill the chip): the keys are cut into nsplit <= 8 ranges, one
  * workgroup each, merged in the kernel by the last workgroup to arrive.  Prescaled queries only (the scale == 0 form). */
 int64_t mvd_op_attention_split_ws_bytes(int batch, int heads, int nq, int nsplit);

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVD_HIP_LIB") or os.path.join(HERE, "libmvd_hip.so")
 
 MVD_MAX_LEVELS = 4
-MVD_USE_CAMERA, MVD_USE_IMAGE, MVD_REUSE_REF, MVD_KEEP_FEATURES = 1, 2, 4, 8
+MVD_USE_CAMERA, MVD_USE_IMAGE, MVD_REUSE_REF, MVD_KEEP_FEATURES, MVD_SHARE_REF = 1, 2, 4, 8, 16
 
 
 class MvdError(RuntimeError):
@@ -87,7 +87,7 @@ class mvd_forward_args_t(C.Structure):
         ("sample", C.c_void_p), ("timesteps", C.c_void_p), ("text", C.c_void_p),
         ("source_camera", C.c_void_p), ("target_camera", C.c_void_p), ("cam_rows", C.c_int), ("cam_batch", C.c_int),
         ("fourier_proj", C.c_void_p), ("source_latents", C.c_void_p), ("encoder_text", C.c_void_p),
-        ("ref_batch", C.c_int), ("flags", C.c_int), ("out", C.c_void_p),
+        ("ref_batch", C.c_int), ("flags", C.c_int), ("out", C.c_void_p), ("views", C.c_int),
     ]
 
 
@@ -98,6 +98,7 @@ _SIGS = {
     "mvd_engine_set_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),
     "mvd_engine_clear_weights": (C.c_int, [C.c_void_p, C.c_int]),
     "mvd_engine_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mvd_engine_workspace_bytes_args": (C.c_int64, [C.c_void_p, C.POINTER(mvd_forward_args_t)]),
     "mvd_engine_refcache_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_engine_bind_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "mvd_unet_forward": (C.c_int, [C.c_void_p, C.POINTER(mvd_forward_args_t), C.c_void_p]),
@@ -130,6 +131,8 @@ _SIGS = {
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "mvd_op_attention_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "mvd_op_attention_split_ws_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_op_attention_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -42,6 +42,7 @@ struct mvd_engine {
   std::vector<bf16_t*> refkv;       // per feature: [ref_batch*hw][4C]
   std::vector<bf16_t*> feat_keep;   // per feature: [ref_batch][hw][C] when kept
   int rc_batch = 0, rc_h = 0, rc_w = 0; bool rc_valid = false; bool rc_keep = false;
+  int rc_views = 0;                 // views of the MVD_SHARE_REF forward that filled the cache (0: an ordinary forward)
   // global Q2 statistics (mvd_engine_reference_encode / _finish): the encoder pass stops before the normalisation
   float* ref_stats_out = nullptr;   // set only while mvd_engine_reference_encode runs
   bool rc_pending = false;          // raw features are in feat_keep, waiting for the merged statistics
@@ -80,11 +81,12 @@ struct mvd_engine {
     std::vector<bf16_t*> refkv, feat_keep;
     int rc_batch, rc_h, rc_w; bool rc_valid, rc_keep;
     float* cam_emb; int cam_batch;
+    int rc_views;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
-    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch;
+    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_views = h.rc_views;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -520,6 +522,8 @@ struct PassOpts {
   bool defer_norm = false;    // capture, global-statistics form: per-pixel local (mean, M2) go to `stats`, the features are
   float* stats = nullptr;     // kept raw and normalisation + K/V projection wait for mvd_engine_reference_finish
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
+  int views = 0;              // MVD_SHARE_REF main pass: views per object -- row r = j * views + v attends the reference tokens and
+                              // the text row of guidance half j (0: an ordinary pass)
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
@@ -535,6 +539,7 @@ struct UNetPass {
   bf16_t* tkv = nullptr;   // [B*L][tkv_total] bf16: text K/V of every attn2 site (one GEMM per pass)
   int resnet_idx = 0;
   int feat_idx = 0;
+  int text_rows = 0;       // rows of `text` when they are fewer than B (MVD_SHARE_REF: one per guidance half); 0: B
 
   int resnet(const std::string& key, const Act& x0, const Act* x1, int cout, Act& out) {
     const int cin0 = x0.C, cin1 = x1 ? x1->C : 0, cin = cin0 + cin1;
@@ -579,8 +584,11 @@ struct UNetPass {
     bf16_t* o_ref = ad ? c.talloc<bf16_t>((size_t)M * C) : nullptr;
     const bf16_t* rkv = ad ? c.e->refkv[feat_idx] : nullptr;
     // Q4: K/V rows of the reference are re-chunked by the HIDDEN batch size
-    const int ref_nk = ad ? (int)((int64_t)o.ref_batch * hw / B_) : 0;
-    if (ad && (int64_t)ref_nk * B_ != (int64_t)o.ref_batch * hw) { mvd_set_error("adapter: ref tokens %d x %d not divisible by batch %d", o.ref_batch, hw, B_); return -12; }
+    // (MVD_SHARE_REF: by the batch g = B / views of ONE view's call -- the views of a guidance half share that half's chunk)
+    const int kvg = o.views > 0 ? o.views : 0;
+    const int Bq = kvg ? B_ / kvg : B_;
+    const int ref_nk = ad ? (int)((int64_t)o.ref_batch * hw / Bq) : 0;
+    if (ad && (int64_t)ref_nk * Bq != (int64_t)o.ref_batch * hw) { mvd_set_error("adapter: ref tokens %d x %d not divisible by batch %d", o.ref_batch, hw, Bq); return -12; }
 
     // (dual-stream forwards: this feature's adapter K/V come from the encoder pass on the side stream)
     if (ad && c.e->dual_now && !c.dry && !c.err && hipStreamWaitEvent(c.s, c.e->feat_ev[feat_idx], 0) != hipSuccess) { mvd_set_error("forward: hipStreamWaitEvent failed"); return -3; }
@@ -593,6 +601,7 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
+      a.kv_group[1] = kvg;
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn1.out.wx"));
@@ -601,13 +610,14 @@ struct UNetPass {
     {
       const int nq = ad ? 2 * C : C;
       bf16_t* q2 = c.talloc<bf16_t>((size_t)M * nq);
-      const bf16_t* kv2 = tkv + c.e->tkv_off[feat_idx];   // [B*L][2C] slice of the fused text K/V
+      const bf16_t* kv2 = tkv + c.e->tkv_off[feat_idx];   // [B*L][2C] slice of the fused text K/V ([text_rows*L] in a shared forward)
       const int ldkv = c.e->tkv_total;
       CHECK(c.ln_linear(h, M, C, key + ".ln2", key + ".attn2.q", (int64_t)(packed ? 2 : 1) * C, nq, nullptr, ln, q2, nq, false));
       MvdAttnArgs a; memset(&a, 0, sizeof(a));
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {q2, kv2, kv2 + C, o_self, nq, ldkv, ldkv, C, (int64_t)hw * nq, (int64_t)L * ldkv, (int64_t)L * ldkv, (int64_t)hw * C, hw, L};
       if (ad) a.p[1] = {q2 + C, rkv + 2 * C, rkv + 3 * C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
+      a.kv_group[0] = kvg; a.kv_group[1] = kvg;       // (the text K/V hold one row per guidance half as well)
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn2.out.w", (int64_t)C * ld_out), c.WF(key + ".attn2" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn2.out.wx"));
@@ -652,8 +662,9 @@ struct UNetPass {
     const int C0 = cfg.block_out_channels[0];
     std::vector<Act> skips;
     // text K/V for all attn2 sites of this pass: one [B*L][xdim] x [tkv_total][xdim]^T GEMM instead of 16 small ones
-    tkv = c.aalloc<bf16_t>((size_t)B * L * c.e->tkv_total);
-    CHECK(c.linear(text, nullptr, cfg.cross_attention_dim, 0, B * L, c.WB("text_kv.w", (int64_t)c.e->tkv_total * cfg.cross_attention_dim), nullptr,
+    const int TB = text_rows > 0 ? text_rows : B;
+    tkv = c.aalloc<bf16_t>((size_t)TB * L * c.e->tkv_total);
+    CHECK(c.linear(text, nullptr, cfg.cross_attention_dim, 0, TB * L, c.WB("text_kv.w", (int64_t)c.e->tkv_total * cfg.cross_attention_dim), nullptr,
                    c.e->tkv_total, nullptr, 0, tkv, c.e->tkv_total));
     Act h = c.new_act(B, H0, W0, C0, true);
     // conv_in: x_in holds im2col rows [B*H*W][64] (k = tap*Cin + ch, zero padded) -> one K=64 MFMA GEMM
@@ -928,6 +939,23 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
     if (!e->ws_ptr) { mvd_set_error("forward: workspace not bound"); return -1; }
   }
   if (use_img && a.ref_batch <= 0) { mvd_set_error("forward: ref_batch must be > 0 with MVD_USE_IMAGE"); return -1; }
+  // ---- MVD_SHARE_REF: `views` views of one object (include/mvd_hip.h); everything is checked here, before any launch
+  const bool share = a.flags & MVD_SHARE_REF;
+  if (!share && a.views > 1) { mvd_set_error("forward: views = %d needs MVD_SHARE_REF", a.views); return -1; }
+  const int V = share ? a.views : 0;
+  if (share) {
+    if (ref_only) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
+    if (!use_img) { mvd_set_error("forward: MVD_SHARE_REF needs MVD_USE_IMAGE"); return -1; }
+    if (V < 1 || a.batch % V) { mvd_set_error("forward: MVD_SHARE_REF: batch %d is not a multiple of views %d", a.batch, V); return -1; }
+    const int g = a.batch / V;
+    if (g > 2) { mvd_set_error("forward: MVD_SHARE_REF: %d rows per view (batch %d / views %d); 1 or 2 (classifier-free guidance) are supported", g, a.batch, V); return -1; }
+    if (a.ref_batch != 1) { mvd_set_error("forward: MVD_SHARE_REF needs ref_batch == 1 (one object), got %d", a.ref_batch); return -1; }
+    if (use_cam && a.cam_batch != 1 && a.cam_batch != V) { mvd_set_error("forward: MVD_SHARE_REF: the cameras must hold 1 or views = %d rows, got %d", V, a.cam_batch); return -1; }
+    for (int lv = 0; lv < cfg.num_levels; ++lv) {
+      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
+      if (hw % g) { mvd_set_error("forward: MVD_SHARE_REF: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
+    }
+  }
   if (use_cam && a.cam_batch > 0 && (a.cam_batch > a.batch || a.batch % a.cam_batch)) { mvd_set_error("forward: camera batch %d must divide the sample batch %d", a.cam_batch, a.batch); return -1; }
   // the input FiLM uses the 4-wide "output" modulator (mvd_unet.py:74-80, 256-258): any other in_channels is a broadcast
   // error in the reference and would read past the [B][4] scale/shift rows here -- reject before any launch
@@ -942,7 +970,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   if (use_img) {
     const bool keep = (a.flags & MVD_KEEP_FEATURES) || ref_only;
     if (reuse) {
-      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
+      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
     } else {
       e->persist.reset(dry);
       e->refkv.assign(e->feats.size(), nullptr);
@@ -954,7 +982,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
         if (keep) e->feat_keep[i] = (bf16_t*)e->persist.alloc((size_t)a.ref_batch * hw * e->feats[i].C * sizeof(bf16_t));
       }
       if (e->persist.overflow()) { mvd_set_error("forward: reference cache too small (%zu > %zu bytes)", e->persist.high, e->persist.cap); return -4; }
-      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd;
+      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_views = V;
       if (!dry) { e->rc_valid = false; e->rc_pending = false; }
     }
   }
@@ -1054,10 +1082,11 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   c.set = 0;
   const float* tproj = tproj_main;
   if (!tproj) CHECK(time_path(c, a.timesteps, B, &tproj));
-  bf16_t* tx = c.aalloc<bf16_t>((size_t)B * L * xd);
+  const int TB = share ? B / V : B;          // text rows: one per guidance half in a shared forward
+  bf16_t* tx = c.aalloc<bf16_t>((size_t)TB * L * xd);
   Act xin = c.new_act(B, H, Wd, 64, true);   // im2col rows for conv_in
   if (!dry && !c.err) {
-    CHECK(mvd_launch_f32_to_bf16(a.text, (int64_t)B * L * xd, tx, s));
+    CHECK(mvd_launch_f32_to_bf16(a.text, (int64_t)TB * L * xd, tx, s));
     const float* sc = nullptr; const float* sh = nullptr;
     if (use_cam) { sc = film_ss["output"].first; sh = film_ss["output"].second; }   // mvd_unet.py:256-258 (input FiLM)
     CHECK(mvd_launch_im2col_in(a.sample, B, cfg.in_channels, H, Wd, sc, sh, 4, xin.p, s));
@@ -1067,7 +1096,9 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   //  measured no difference and has no switch.)
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
+  po.views = V;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
+  pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
   if (e->dual_now) {   // join: everything the side stream did (kept features included) precedes whatever follows on s
     if (hipStreamWaitEvent(s, e->join_ev, 0) != hipSuccess) { mvd_set_error("forward: stream join failed"); return -3; }
@@ -1182,6 +1213,19 @@ int64_t mvd_engine_workspace_bytes(mvd_engine_t* e, int batch, int height, int w
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
 }
 
+int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) {
+  if (!e || !args) { mvd_set_error("workspace_bytes_args: null argument"); return -1; }
+  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("workspace_bytes_args: unknown flag bits 0x%x", args->flags); return -1; }
+  const mvd_engine::HostState before = e->host_state();
+  // (a sizing call must not depend on the cache state: size the forward that runs the encoder pass, the larger of the two)
+  mvd_forward_args_t a = *args;
+  a.flags &= ~MVD_REUSE_REF;
+  int r = forward_impl(e, a, nullptr, true);
+  e->set_host_state(before);
+  if (r) return r;
+  return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
+}
+
 int64_t mvd_engine_refcache_bytes(mvd_engine_t* e, int ref_batch, int height, int width, int keep_features) {
   if (!e || ref_batch <= 0) { mvd_set_error("refcache_bytes: bad argument"); return -1; }
   size_t total = 0;
@@ -1211,6 +1255,7 @@ int64_t mvd_engine_reference_pixels(mvd_engine_t* e, int height, int width) {
 
 int mvd_engine_reference_encode(mvd_engine_t* e, const mvd_forward_args_t* args, float* local_stats, void* stream) {
   if (!e || !args || !local_stats) { mvd_set_error("reference_encode: null argument"); return -1; }
+  if ((args->flags & MVD_SHARE_REF) || args->views > 1) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
   e->drop_graphs();
   mvd_forward_args_t a = *args;
   a.flags = (a.flags & ~MVD_REUSE_REF) | MVD_USE_IMAGE | MVD_KEEP_FEATURES | MVD_REF_ONLY_INTERNAL;
@@ -1267,7 +1312,7 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
   // call with a given key runs as usual (kernels' first-use set-up must not happen inside a capture), the second is
   // captured and instantiated, later ones are one hipGraphLaunch.
   std::string key((const char*)args, sizeof(*args));
-  const int st8[8] = {e->rc_valid, e->rc_batch, e->rc_h, e->rc_w, e->rc_keep, e->share_encoder, 0, 0};
+  const int st8[8] = {e->rc_valid, e->rc_batch, e->rc_h, e->rc_w, e->rc_keep, e->share_encoder, e->rc_views, args->flags & MVD_SHARE_REF};   // (views and the flag are in *args too)
   key.append((const char*)st8, sizeof(st8));
   key.append((const char*)&e->ws_ptr, sizeof(void*));
   key.append((const char*)&e->rc_ptr, sizeof(void*));
@@ -1494,6 +1539,17 @@ int mvd_op_attention(const void* q, const void* k, const void* v, void* o, int b
   a.prescaled = scale == 0.f;   // q already carries softmax_scale * log2(e)
   a.p[0] = {(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
             (int64_t)nq * ldq, (int64_t)nk * ldk, (int64_t)nk * ldv, (int64_t)nq * ldo, nq, nk};
+  return mvd_launch_attention(a, (hipStream_t)stream);
+}
+
+int mvd_op_attention_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                             int ldk, int ldv, int ldo, float scale, int kv_group, void* stream) {
+  MvdAttnArgs a; memset(&a, 0, sizeof(a));
+  a.nprob = 1; a.batch = batch; a.heads = heads; a.scale = scale;
+  a.prescaled = scale == 0.f;
+  a.p[0] = {(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
+            (int64_t)nq * ldq, (int64_t)nk * ldk, (int64_t)nk * ldv, (int64_t)nq * ldo, nq, nk};
+  a.kv_group[0] = kv_group;
   return mvd_launch_attention(a, (hipStream_t)stream);
 }
 

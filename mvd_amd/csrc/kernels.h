@@ -160,6 +160,10 @@ struct MvdAttnArgs {
   int nsplit;                     // <= 1: off
   void* split_ws;                 // mvd_attention_split_ws_bytes(a) bytes
   unsigned int* split_cnt;        // mvd_attention_split_counters(a) ZEROED counters
+  // grouped K/V (per problem): batch element b reads the K/V of K/V batch element b / kv_group[i], so k / v of problem i hold
+  // batch / kv_group[i] elements, bsk / bsv apart (several views attending one reference).  0 or 1: every
+  // batch element has K/V of its own.  Honoured by every form mvd_launch_attention dispatches: the base pointers alone change
+  int kv_group[2];
 };
 // split the engine's heuristic gives this launch (1 = none) and what it then needs
 int mvd_attention_pick_split(const MvdAttnArgs& a);

@@ -111,11 +111,20 @@ class MVDEngine:
         return sum(t.numel() * t.element_size() for d in self._weights for t in d.values())
 
     # ------------------------------------------------------------------ workspace
-    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features):
-        key = (batch, h, w, text_len, ref_batch, keep_features)
+    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0):
+        key = (batch, h, w, text_len, ref_batch, keep_features, views)
         if self._ws_key == key:
             return
-        ws = L.lib().mvd_engine_workspace_bytes(self._h, batch, h, w, text_len, ref_batch)
+        if views:
+            # a shared-reference forward (MVD_SHARE_REF) is sized from its argument block: the positional entry describes
+            # an ordinary forward, whose Q4 re-chunking fails when the views do not divide the reference tokens
+            a = L.mvd_forward_args_t()
+            a.batch, a.height, a.width, a.text_len, a.ref_batch, a.views = batch, h, w, text_len, ref_batch, views
+            a.cam_rows, a.cam_batch = 4, views
+            a.flags = L.MVD_USE_CAMERA | L.MVD_USE_IMAGE | L.MVD_SHARE_REF
+            ws = L.lib().mvd_engine_workspace_bytes_args(self._h, C.byref(a))
+        else:
+            ws = L.lib().mvd_engine_workspace_bytes(self._h, batch, h, w, text_len, ref_batch)
         if ws < 0:
             raise L.MvdError(f"workspace_bytes: {L.last_error()}")
         rc = 0
@@ -139,23 +148,31 @@ class MVDEngine:
                 source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                 fourier_proj: Optional[torch.Tensor] = None, source_latents: Optional[torch.Tensor] = None,
                 encoder_text: Optional[torch.Tensor] = None, reuse_ref: bool = False,
-                keep_features: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """All tensors fp32 contiguous on ``self.device``; returns fp32 NCHW."""
+                keep_features: bool = False, out: Optional[torch.Tensor] = None, views: Optional[int] = None) -> torch.Tensor:
+        """All tensors fp32 contiguous on ``self.device``; returns fp32 NCHW.  ``views`` (an int >= 1): the shared-reference
+        forward (``MVD_SHARE_REF``, include/mvd_hip.h) -- ``sample`` holds g * views rows ``[uncond x views | cond x views]``,
+        ``text`` g rows, ``source_latents`` / ``encoder_text`` one row, the cameras 1 or ``views`` rows."""
         B, Cin, H, W = sample.shape
         Lt = text.shape[1]
         for t in (sample, timesteps, text, source_camera, target_camera, fourier_proj, source_latents, encoder_text):
             if t is not None:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise L.MvdError("engine.forward expects contiguous fp32 CUDA tensors")
-        if text.shape[0] != B or timesteps.shape != (B,):
-            raise L.MvdError(f"engine.forward: text batch {text.shape[0]} / timesteps {tuple(timesteps.shape)} vs batch {B}")
+        views = int(views) if views else 0
+        if views and B % views:
+            raise L.MvdError(f"engine.forward: batch {B} is not a multiple of views {views}")
+        if text.shape[0] != (B // views if views else B) or timesteps.shape != (B,):
+            raise L.MvdError(f"engine.forward: text batch {text.shape[0]} / timesteps {tuple(timesteps.shape)} vs batch {B}"
+                             + (f" in {views} views" if views else ""))
         use_cam = target_camera is not None
         use_img = source_latents is not None or reuse_ref
         ref_batch = 0
         if use_img:
             ref_batch = source_latents.shape[0] if source_latents is not None else self._last_ref_batch
             self._last_ref_batch = ref_batch
-        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features)
+        if views and not use_img:
+            raise L.MvdError("engine.forward: views needs image conditioning (source_latents or reuse_ref)")
+        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views)
         graph = getattr(self, "_graph", False)
         user_out = out
         if graph:
@@ -196,6 +213,9 @@ class MVDEngine:
                 a.source_latents, a.encoder_text = source_latents.data_ptr(), encoder_text.data_ptr()
             if keep_features:
                 flags |= L.MVD_KEEP_FEATURES
+        if views:
+            flags |= L.MVD_SHARE_REF
+            a.views = views
         a.ref_batch, a.flags = ref_batch, flags
         a.out = out.data_ptr()
         if graph:
@@ -208,7 +228,7 @@ class MVDEngine:
         else:
             L.call("mvd_unet_forward", self._h, C.byref(a), L.stream())
         if use_img and not reuse_ref:
-            self._ref_valid = (B, H, W, Lt, ref_batch)
+            self._ref_valid = (B, H, W, Lt, ref_batch) + ((views,) if views else ())
         return out
 
     # ------------------------------------------------------------------ reference pass in two halves (global Q2 statistics)
@@ -274,9 +294,10 @@ class MVDEngine:
             buf.copy_(t)
         return buf
 
-    def reference_cache_valid(self, batch, h, w, text_len, ref_batch) -> bool:
-        """True when the engine still holds reference K/V computed for exactly this shape (Q5 reuse is then legal)."""
-        return getattr(self, "_ref_valid", None) == (batch, h, w, text_len, ref_batch)
+    def reference_cache_valid(self, batch, h, w, text_len, ref_batch, views=0) -> bool:
+        """True when the engine still holds reference K/V computed for exactly this shape (Q5 reuse is then legal); ``views``:
+        by a shared-reference forward of that many views."""
+        return getattr(self, "_ref_valid", None) == (batch, h, w, text_len, ref_batch) + ((views,) if views else ())
 
     # ------------------------------------------------------------------ measurement
     PROFILE_CLASSES = {0: "gemm_256x160", 1: "gemm_256x128", 2: "gemm_128x160", 3: "gemm_128x128", 4: "gemm_128x64",

@@ -286,7 +286,12 @@ class MultiViewUNet(nn.Module):
                 source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                 source_image_latents: Optional[torch.FloatTensor] = None, return_dict: bool = True,
                 timestep_cond: Optional[torch.FloatTensor] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
-                added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None):
+                added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None, *, views: Optional[int] = None):
+        """``views`` (keyword-only, not a reference parameter): V > 1 views of ONE object in one forward.
+        ``sample`` holds g * V rows in the pipeline's order ``[uncond x V | cond x V]`` (g = 1, or 2 under guidance),
+        ``encoder_hidden_states`` g rows, ``source_image_latents`` one row, the cameras 1 or V rows.  Row j * V + v is row j
+        of the batch-g call for view v -- same reference tokens, text row, camera -- from one encoder pass and one copy of
+        the reference K/V.  ``None`` / 1: the ordinary forward."""
         if cross_attention_kwargs:
             cross_attention_kwargs.pop("debug_log_file_path", None)   # accepted, never evaluated (no host syncs)
         eng = self._sync_engine()
@@ -295,7 +300,17 @@ class MultiViewUNet(nn.Module):
         x = self._f32(sample, dev)
         B = x.shape[0]
         text = self._f32(encoder_hidden_states, dev)
-        if B > text.shape[0]:                                          # CFG repeat (:233-237)
+        V = int(views) if views is not None and int(views) > 1 else 0
+        if V:
+            if self.reference_stats_group is not None:
+                raise L.MvdError("views: the shared-reference forward does not go with reference_stats_group (statistics over "
+                                 "the ranks' batches are for many objects; the views of one object share its one reference)")
+            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != 1:
+                raise L.MvdError("views: needs image conditioning with ONE row of source_image_latents (one object)")
+            if B % V or B // V > 2 or text.shape[0] != B // V:
+                raise L.MvdError(f"views={V}: sample must hold g * views rows and encoder_hidden_states g rows (g = 1, or 2 under "
+                                 f"guidance); got {B} and {text.shape[0]}")
+        elif B > text.shape[0]:                                        # CFG repeat (:233-237)
             text = text.repeat(B // text.shape[0], 1, 1)
         t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
         t = t.expand(B).contiguous() if t.numel() == 1 else t.contiguous()
@@ -312,7 +327,9 @@ class MultiViewUNet(nn.Module):
         if self.use_image_conditioning and source_image_latents is not None:
             bs = source_image_latents.shape[0]
             enc_text = text
-            if text.shape[0] == 2 * bs:                                # :280-283
+            if V:                                                      # the batch-g call's choice below: its last row
+                enc_text = text[-1:]
+            elif text.shape[0] == 2 * bs:                              # :280-283
                 enc_text = text[bs:]
             elif text.shape[0] > bs:                                   # :284-285
                 enc_text = text[:bs]
@@ -320,10 +337,10 @@ class MultiViewUNet(nn.Module):
             # is live, so the caching allocator cannot hand their addresses to different data of the same shape (a second
             # object denoised right after the first would otherwise hit the first object's K/V).
             key = (source_image_latents.data_ptr(), source_image_latents._version, tuple(source_image_latents.shape),
-                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B)
+                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V)
             glob = self.reference_stats_group is not None
             hit = (self.cache_reference and self._ref_key == key
-                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs))
+                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, V))
             if glob and self.cache_reference:
                 # the recompute path below contains a collective: the decision must be the same on every rank of the group
                 # (a re-bound workspace or a fresh tensor on ONE rank would otherwise leave the others out of the all-gather)
@@ -342,7 +359,7 @@ class MultiViewUNet(nn.Module):
                     local = eng.reference_encode(img["source_latents"], img["encoder_text"], B)
                     eng.reference_finish(merge_reference_stats(local, group))
                     img = dict(reuse_ref=True, keep_features=True)
-        out = eng.forward(x, t, text, **cam, **img)
+        out = eng.forward(x, t, text, **cam, **img, **({"views": V} if V else {}))
         if cam:
             self.current_camera_embedding = eng.camera_embedding(cam["target_camera"].shape[0])
         hidden_states = out.to(out_dtype)

@@ -384,6 +384,21 @@ def attention(q, k, v, heads, scale=0.125):
     return out
 
 
+def attention_grouped(q, k, v, heads, kv_group, scale=0.125):
+    """``attention`` with grouped K/V: q (B, Nq, heads*64), k / v (B // kv_group, Nk, heads*64) -- batch element b attends the
+    K/V of element b // kv_group (the views of one object share its reference tokens).  kv_group=1 is ``attention``."""
+    _bf16(q, k, v)
+    B, nq, _ = q.shape
+    nk = k.shape[1]
+    assert kv_group >= 1 and B % kv_group == 0 and k.shape[0] == B // kv_group and v.shape[0] == B // kv_group, (B, kv_group, k.shape, v.shape)
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    assert q.stride(0) == nq * q.stride(1) and k.stride(0) == nk * k.stride(1) and v.stride(0) == nk * v.stride(1)
+    out = torch.empty(B, nq, heads * 64, device=q.device, dtype=torch.bfloat16)
+    L.call("mvd_op_attention_grouped", C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), _p(out),
+           B, heads, nq, nk, q.stride(1), k.stride(1), v.stride(1), heads * 64, float(scale), int(kv_group), _s())
+    return out
+
+
 def attention_causal(q, k, v, heads, scale=0.125):
     """The CLIP text encoder's attention: q, k, v (B, n, heads*64) bf16 with n <= 96, key j visible to query i iff j <= i; row
     strides may exceed heads*64 (views of one fused QKV buffer).  scale=0: q already carries 64^-0.5 * log2(e)."""

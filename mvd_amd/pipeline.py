@@ -45,12 +45,21 @@ class MVDDenoiser:
                  source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                  source_image_latents: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
                  height: int = 64, width: int = 64, noise_per_step=None, callback=None, callback_steps: int = 1,
-                 cross_attention_kwargs: Optional[Dict[str, Any]] = None):
+                 cross_attention_kwargs: Optional[Dict[str, Any]] = None, views: Optional[int] = None):
+        """``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
+        source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``)."""
         dev = self.unet._exec_device()
         B = prompt_embeds.shape[0]
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
         embeds = torch.cat([negative_prompt_embeds.to(prompt_embeds.device), prompt_embeds]) if cfg else prompt_embeds
         embeds = embeds.to(dev, torch.float32)
+        views = int(views) if views is not None and int(views) > 1 else 0
+        if views:
+            if B != 1:
+                raise L.MvdError(f"views: one prompt for the one object, got {B} rows of prompt_embeds")
+            if guidance_scale > 1.0 and not cfg:      # the doubled latents against one text row: the repeat of mvd_unet.py:233-237
+                embeds = embeds.repeat(2, 1, 1)
+            B = views
         if latents is None:
             latents = torch.randn(B, 4, height, width, generator=generator, device=dev, dtype=torch.float32)
             latents = latents * self.scheduler.init_noise_sigma
@@ -63,6 +72,8 @@ class MVDDenoiser:
             extra["target_camera"] = target_camera.to(dev)
         if source_image_latents is not None:
             extra["source_image_latents"] = source_image_latents.to(dev)
+        if views:
+            extra["views"] = views
         # Q5: the reference K/V of a previous call (another object) must never be reused by this one
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
@@ -211,6 +222,87 @@ class MVDPipeline:
             if self.vae is None:
                 raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
             image = self.vae.decode(latents / self.vae.config.scaling_factor).sample
+            image = (image / 2 + 0.5).clamp(0, 1)
+            if output_type == "pil":
+                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
+        if not return_dict:
+            return image
+        return {"images": image}
+
+    @torch.no_grad()
+    def generate_views(self, prompt: Optional[str] = None, source_images: Optional[torch.Tensor] = None,
+                       source_camera: Optional[torch.Tensor] = None, target_cameras: Optional[torch.Tensor] = None,
+                       height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
+                       guidance_scale: float = 7.5, negative_prompt: Optional[str] = None,
+                       generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
+                       latents: Optional[torch.FloatTensor] = None, prompt_embeds: Optional[torch.FloatTensor] = None,
+                       negative_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = "pil",
+                       return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
+                       callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
+                       source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None):
+        """V views of ONE object from one source image: what V calls ``pipe(prompt, source_images=, source_camera=,
+        target_camera=target_cameras[v:v+1], ...)`` give (the loop of infer.py:111-122, a turntable), in one denoising loop whose
+        every step is ONE shared-reference forward: the prompt is encoded once, the source VAE-encoded
+        once, the reference encoder pass and its K/V exist once per step (once per call with ``unet.cache_reference``), the V
+        latents are decoded in one VAE call.  Not a method of the reference's pipeline.
+
+        ``target_cameras``: (V, 3|4, 4), e.g. ``mvd_amd.utils.orbit_cameras(V)``; ``source_camera``: (3|4, 4) or (1, 3|4, 4);
+        ``source_images`` / ``source_image_latents``: ONE row.  ``generator``: one generator (the V initial latents are one draw of
+        (V, 4, h, w)) or a list of V (row v is view v's own draw -- equal to the latents of the per-view call with
+        ``generator[v]``); ``latents``: V rows.  Returns V images (or latents) like ``__call__``.
+
+        Ancestral noise (``sampler="ddpm"``): like ``__call__``, the step noise comes from torch's global RNG unless
+        ``noise_per_step`` is given -- here ONE draw of (V, 4, h, w) per step, where V separate calls make V draws of (1, 4, h, w)
+        in call-major order.  The two streams differ, so DDPM results equal the per-view calls' only through
+        ``noise_per_step[i]`` = (V, 4, h, w) whose row v is what view v's call gets as ``noise_per_step[i]``; DDIM (eta 0) and
+        DPM-Solver++ take no step noise.  The camera encoder's per-call random projection (Q1) is drawn once per forward for all
+        views; the per-view calls draw one each unless ``unet.fourier_projection`` pins it."""
+        dev = self.device
+        if target_cameras is None or target_cameras.dim() != 3:
+            raise L.MvdError("generate_views: target_cameras must be (V, 3|4, 4)")
+        V = target_cameras.shape[0]
+        if isinstance(prompt, (list, tuple)):
+            raise L.MvdError("generate_views: one prompt (a str) for the one object")
+        if prompt is None and prompt_embeds is None:
+            raise L.MvdError("MVDPipeline: neither prompt nor prompt_embeds given")
+        if prompt_embeds is None:
+            prompt_embeds = self._encode_prompt(prompt)                           # once for all views
+        if negative_prompt_embeds is None and negative_prompt is not None:
+            negative_prompt_embeds = self._encode_prompt(negative_prompt)
+        if prompt_embeds.shape[0] != 1:
+            raise L.MvdError(f"generate_views: one prompt for the one object, got {prompt_embeds.shape[0]} rows of prompt_embeds")
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        if latents is None:
+            latents = self.prepare_latents(V, 4, height, width, prompt_embeds.dtype, dev, generator)
+        if latents.shape[0] != V:
+            raise L.MvdError(f"generate_views: {latents.shape[0]} rows of latents for {V} target cameras")
+        if source_images is not None:                                             # VAE-encoded once
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
+                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
+            si = source_images.to(device=dev)
+            if bool(si.min() >= 0) and bool(si.max() <= 1):
+                si = 2 * si - 1
+            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
+        if source_image_latents is None or source_image_latents.shape[0] != 1:
+            raise L.MvdError("generate_views: ONE source image (source_images or source_image_latents with one row)")
+        if source_camera is None:
+            raise L.MvdError("generate_views: source_camera is required")
+        src = source_camera if source_camera.dim() == 3 else source_camera.unsqueeze(0)
+        if src.shape[0] != 1 or src.shape[1:] != target_cameras.shape[1:]:
+            raise L.MvdError(f"generate_views: source_camera {tuple(source_camera.shape)} vs target_cameras {tuple(target_cameras.shape)}")
+        den = MVDDenoiser(self.unet, self.scheduler)
+        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
+                      latents=latents, source_camera=src.expand(V, -1, -1), target_camera=target_cameras,
+                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=V)
+        if output_type == "latent":
+            image = latents
+        else:
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
+            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of V rows
             image = (image / 2 + 0.5).clamp(0, 1)
             if output_type == "pil":
                 image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())

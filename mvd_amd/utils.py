@@ -3,7 +3,8 @@
 ``infer.py`` / ``val.py`` run against the drop-in ``src`` package (integration/src/utils.py).  Plain numpy / PIL on the
 host; pinned by golden vectors G5 (cameras) and G6 (images) in tests/test_host_cpu.py.
 
-``look_at`` is this build's own synthetic-camera generator (poses on a radius-2 sphere), used by
+``orbit_cameras`` (the target poses of a turntable, for ``MVDPipeline.generate_views``) and ``look_at`` are this build's own;
+``look_at`` is the synthetic-camera generator (poses on a radius-2 sphere), used by
 bench.py and the parity harness.
 """
 from __future__ import annotations
@@ -64,6 +65,22 @@ def create_camera_matrix(position, target, up=None):
     m = np.zeros((3, 4))
     m[:, 0], m[:, 1], m[:, 2], m[:, 3] = right, np.cross(right, fwd), -fwd, position
     return torch.from_numpy(m).float()
+
+
+def orbit_cameras(n: int, elevation_deg: float = 0.0, radius: float = 2.0, start_deg: float = 0.0) -> torch.Tensor:
+    """``n`` look-at poses on a circle around the origin, as one (n, 3, 4) tensor: the ``target_cameras`` of a turntable
+    (``MVDPipeline.generate_views``).  Row i is ``create_camera_matrix`` of the position at azimuth ``start_deg + 360 i / n``
+    (about +y, from +z towards +x), elevation ``elevation_deg`` and distance ``radius``, looking at the origin; the defaults put
+    row 0 at infer.py's source position (0, 0, 2)."""
+    if n < 1:
+        raise ValueError(f"orbit_cameras: n = {n}")
+    e = math.radians(elevation_deg)
+    rows = []
+    for i in range(n):
+        a = math.radians(start_deg + 360.0 * i / n)
+        pos = [radius * math.cos(e) * math.sin(a), radius * math.sin(e), radius * math.cos(e) * math.cos(a)]
+        rows.append(create_camera_matrix(pos, [0.0, 0.0, 0.0]))
+    return torch.stack(rows)
 
 
 def look_at(azim_deg: float, elev_deg: float = 20.0, radius: float = 2.0) -> torch.Tensor:
