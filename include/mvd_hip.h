@@ -118,6 +118,23 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
  * read): the only sizing entry for an MVD_SHARE_REF forward, which the positional form cannot describe. */
 int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args);
 
+/* Several objects in one MVD_SHARE_REF forward (turntables of a list of objects; mvd_forward_args_t is unchanged, the object
+ * count comes beside it).  A forward of O objects x V = args->views views with g rows per view (1, or 2 under guidance) IS the
+ * O * V independent forwards of batch g, each with a one-row reference.  The sample holds g * O * V rows in the pipeline's
+ * order [uncond x O V | cond x O V], object-major inside a half; row r = j * O * V + o * V + v
+ *   - attends, in both adapter branches and all 16 features, tokens [j * hw / g, (j + 1) * hw / g) of object o's reference only
+ *     (the reference K/V hold O * g elements of hw / g rows, object-major: element o * g + j);
+ *   - attends text row j * O + o (`text` holds g * O rows, [negative x O | positive x O]);
+ *   - takes camera o * V + v (cam_batch = O * V, or 1) and timesteps[r].
+ * The encoder pass runs once at batch O (`source_latents`, `encoder_text`: O rows, row o what object o's own call would use), the
+ * Q2 statistics are taken per object (per pixel over that object's channels only: mvd_op_refnorm at batch 1), the ref_kv
+ * projection runs once over O * hw rows and the reference cache is that of ref_batch = O.  Every object has the same V.
+ * Checked on the host before any launch: MVD_SHARE_REF with MVD_USE_IMAGE; ref_batch == O; batch == g * O * views with g in
+ * {1, 2}; cameras with 0, 1 or O * views rows; hw % g == 0 at every level.  objects <= 1: exactly mvd_unet_forward /
+ * mvd_engine_workspace_bytes_args, with their rejections.  A reference cached by one mode is never served to another. */
+int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream);
+int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects);
+
 /* Global Q2 statistics (SURVEY.md 8e mode ii; optional).  The adapter normalises the reference features with statistics
  * over (batch, channel) per pixel (attention.py:95-103), so a batch sharded over GPUs sees per-shard statistics unless the
  * shards exchange them.  The reference pass is therefore also available in two halves:
@@ -227,6 +244,11 @@ int mvd_op_attention(const void* q, const void* k, const void* v, void* o, int b
  * takes it; bit-identical to running the views one by one. */
 int mvd_op_attention_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
                              int ldk, int ldv, int ldo, float scale, int kv_group, void* stream);
+/* Grouped K/V of several objects: the batch is [half j][object o][view v] (batch = g * kv_objects * kv_group) over K/V stored
+ * object-major, kv_objects * g elements [object o][half j]; with q = b / kv_group, element b attends K/V element
+ * (q % kv_objects) * g + q / kv_objects.  kv_objects <= 1 is mvd_op_attention_grouped; kv_group * kv_objects must divide batch. */
+int mvd_op_attention_objects(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                             int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects, void* stream);
 /* Split-KV form (batch 1: too few (head, query block) pairs to fill the chip): the keys are cut into nsplit <= 8 ranges, one
  * workgroup each, merged in the kernel by the last workgroup to arrive.  Prescaled queries only (the scale == 0 form). */
 int64_t mvd_op_attention_split_ws_bytes(int batch, int heads, int nq, int nsplit);
@@ -237,6 +259,9 @@ int mvd_op_groupnorm(const void* x0, const void* x1, int c0, int c1, int batch, 
 int mvd_op_layernorm(const void* x, int rows, int c, float eps, const float* gamma, const float* beta, void* y,
                      void* stream);
 int mvd_op_refnorm(const void* x, int batch, int hw, int c, void* y, void* stream);
+/* mvd_op_refnorm with statistics over each run of `group` consecutive batch rows (group divides batch); group == batch is
+ * mvd_op_refnorm, group == 1 per object -- bit-identical to mvd_op_refnorm on those rows alone. */
+int mvd_op_refnorm_grouped(const void* x, int batch, int group, int hw, int c, void* y, void* stream);
 int mvd_op_film(const void* x, int batch, int hw, int c, const float* scale, const float* shift, void* y, void* stream);
 int mvd_op_conv_in(const void* x, int batch, int h, int w, int cin, const float* wt, const float* bias, int cout, void* y,
                    void* stream);

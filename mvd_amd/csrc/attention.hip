@@ -4,7 +4,8 @@
 // attention and the MVD adapter's cross-view attention on the same query tokens).
 // Layout: token-major with heads interleaved in the channel dim, q[b][n][head*64 + d],
 // arbitrary row/batch strides so fused QKV GEMM outputs are consumed in place.  A problem's K/V may be shared by groups of
-// consecutive batch elements (MvdAttnArgs::kv_group: the views of one object attending its one reference): only the base pointers
+// consecutive batch elements (MvdAttnArgs::kv_group: the views of one object attending its one reference), and those groups may come
+// guidance-half-major over K/V stored object-major (MvdAttnArgs::kv_objects: the views of several objects): only the base pointers
 // of a workgroup change.
 //
 // Structure (per wave: 32 query rows; per workgroup: NW waves sharing K/V tiles in LDS):
@@ -136,9 +137,23 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
 
   const bf16_t* qp = P.q + (size_t)bz * P.bsq + head * 64;
   // grouped K/V: kv_group consecutive batch elements share one K/V element (workgroup-uniform: one scalar division, taken only
-  // when a group is set)
-  const int kvg = a.kv_group[pi];
-  const int bkv = kvg > 1 ? bz / kvg : bz;
+  // when a group is set).  Object-major K/V (kv_objects): group q = j * O + o of the batch [half j][object o][view] reads element
+  // o * g + j of the K/V [object][half] -- scalar arithmetic again.  The two fields are read together and tested once (both are
+  // >= 0, the host has checked), so a launch that sets neither passes one scalar wait and one branch
+  const int kvg = a.kv_group[pi], kvo = a.kv_objects[pi];
+  int bkv = bz;
+  if ((kvg | kvo) > 1) {
+    if (kvg > 1) bkv = bz / kvg;
+    if (kvo > 1) {
+      const int g = a.batch / ((kvg > 1 ? kvg : 1) * kvo);
+      bkv = (bkv % kvo) * g + bkv / kvo;
+      // 40 bytes of padding on this path, which no launch without kv_objects takes: with the 67 instructions above the set-up is
+      // 320 bytes longer than before the field existed, so every form's loops keep their position within the 64-byte
+      // instruction-fetch line.  Without it the main loop starts 24 bytes further into its line and cfg4 measured 58.58 ms against
+      // 58.46 (three builds alternated, four rounds).  Re-derive after any edit of this set-up
+      asm volatile("s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+    }
+  }
   const bf16_t* kp = P.k + (size_t)bkv * P.bsk + head * 64;
   const bf16_t* vp = P.v + (size_t)bkv * P.bsv + head * 64;
   bf16_t* op = P.o + (size_t)bz * P.bso + head * 64;
@@ -619,7 +634,7 @@ int launch_nw(const MvdAttnArgs& a, int maxq, hipStream_t s) {
   g_last_attn[0] = NW; g_last_attn[1] = (int)grid.x;
 #ifdef MVD_PROBE
   static const int pipe_env = MVD_ENV_INT("MVD_ATTN_PIPE", 0);
-  if (a.prescaled && NW == 4 && NSUB == 2 && (pipe_env || g_attn_pipe_override) && a.kv_group[0] <= 1 && a.kv_group[1] <= 1) {   // (the probe kernels do not read kv_group)
+  if (a.prescaled && NW == 4 && NSUB == 2 && (pipe_env || g_attn_pipe_override) && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1) {   // (the probe kernels read neither kv_group nor kv_objects)
     hipLaunchKernelGGL((attn_pipe_kernel<4>), grid, dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { mvd_set_error("attention launch: %s", hipGetErrorString(e)); return -3; }
@@ -677,6 +692,9 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
     maxq = p.nq > maxq ? p.nq : maxq;
     mink = p.nk < mink ? p.nk : mink;
     if (a.kv_group[i] < 0 || (a.kv_group[i] > 1 && a.batch % a.kv_group[i])) { mvd_set_error("attention: K/V group %d of problem %d does not divide the batch %d", a.kv_group[i], i, a.batch); return -1; }
+    if (a.kv_objects[i] < 0 || (a.kv_objects[i] > 1 && a.batch % ((int64_t)(a.kv_group[i] > 1 ? a.kv_group[i] : 1) * a.kv_objects[i]))) {
+      mvd_set_error("attention: K/V group %d x objects %d of problem %d does not divide the batch %d", a.kv_group[i], a.kv_objects[i], i, a.batch); return -1;
+    }
   }
   // 128-key tiles are an experiment switch only (env MVD_ATTN_KV128=1): at 197 VGPRs / 64 KB LDS they run two
   // waves per SIMD instead of three and measured 3-4 % SLOWER than 64-key tiles on every UNet shape
@@ -689,7 +707,7 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
   static const int use_pp = MVD_ENV_INT("MVD_ATTN_PP", 0);
   const_cast<MvdAttnArgs&>(a).dbg = MVD_ENV_INT("MVD_ATTN_DBG", 0);
   {
-    bool ok = use_pp && a.prescaled && maxq >= 256 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1;
+    bool ok = use_pp && a.prescaled && maxq >= 256 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1;
     for (int i = 0; i < a.nprob && ok; ++i) ok = (size_t)a.p[i].nk * (a.p[i].ldk > a.p[i].ldv ? a.p[i].ldk : a.p[i].ldv) * 2 < ((size_t)1 << 31);
     const long wgs = (long)((maxq + 255) / 256) * a.heads * a.batch * a.nprob;
     if (ok && wgs >= 1024) {
@@ -709,7 +727,7 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
     return launch_nw<4, 2>(a, maxq, s);
   }
 #ifdef MVD_PROBE
-  if (g_attn_q64_override && a.prescaled && maxq >= 256 && a.nsplit <= 1 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1) {     // experiment: 64 queries per wave (see attn_q64_kernel)
+  if (g_attn_q64_override && a.prescaled && maxq >= 256 && a.nsplit <= 1 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1) {     // experiment: 64 queries per wave (see attn_q64_kernel)
     for (int i = 0; i < a.nprob; ++i)
       if ((size_t)a.p[i].nk * (a.p[i].ldk > a.p[i].ldv ? a.p[i].ldk : a.p[i].ldv) * 2 >= ((size_t)1 << 31)) { mvd_set_error("attention: operand too large for buffer addressing"); return -1; }
     return g_attn_q64_override == 1 ? launch_q64<2>(a, maxq, s) : launch_q64<4>(a, maxq, s);

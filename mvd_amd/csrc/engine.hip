@@ -43,6 +43,7 @@ struct mvd_engine {
   std::vector<bf16_t*> feat_keep;   // per feature: [ref_batch][hw][C] when kept
   int rc_batch = 0, rc_h = 0, rc_w = 0; bool rc_valid = false; bool rc_keep = false;
   int rc_views = 0;                 // views of the MVD_SHARE_REF forward that filled the cache (0: an ordinary forward)
+  int rc_objects = 0;               // objects of the mvd_unet_forward_objects call that filled it (0: one reference for the batch)
   // global Q2 statistics (mvd_engine_reference_encode / _finish): the encoder pass stops before the normalisation
   float* ref_stats_out = nullptr;   // set only while mvd_engine_reference_encode runs
   bool rc_pending = false;          // raw features are in feat_keep, waiting for the merged statistics
@@ -81,12 +82,12 @@ struct mvd_engine {
     std::vector<bf16_t*> refkv, feat_keep;
     int rc_batch, rc_h, rc_w; bool rc_valid, rc_keep;
     float* cam_emb; int cam_batch;
-    int rc_views;
+    int rc_views, rc_objects;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views, rc_objects}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
-    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_views = h.rc_views;
+    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_views = h.rc_views; rc_objects = h.rc_objects;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -524,6 +525,8 @@ struct PassOpts {
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
   int views = 0;              // MVD_SHARE_REF main pass: views per object -- row r = j * views + v attends the reference tokens and
                               // the text row of guidance half j (0: an ordinary pass)
+  int objects = 0;            // mvd_unet_forward_objects (> 1): that many objects x `views` views -- main pass: row r = j * O * V + o * V + v
+                              // attends object o's reference tokens; encoder pass: Q2 statistics per object (0: one object)
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
@@ -586,6 +589,8 @@ struct UNetPass {
     // Q4: K/V rows of the reference are re-chunked by the HIDDEN batch size
     // (MVD_SHARE_REF: by the batch g = B / views of ONE view's call -- the views of a guidance half share that half's chunk)
     const int kvg = o.views > 0 ? o.views : 0;
+    // (objects: each object's hw tokens by the batch g = B / (views * objects) of one view's call; K/V elements [object][half])
+    const int kvo = o.objects > 1 ? o.objects : 0;
     const int Bq = kvg ? B_ / kvg : B_;
     const int ref_nk = ad ? (int)((int64_t)o.ref_batch * hw / Bq) : 0;
     if (ad && (int64_t)ref_nk * Bq != (int64_t)o.ref_batch * hw) { mvd_set_error("adapter: ref tokens %d x %d not divisible by batch %d", o.ref_batch, hw, Bq); return -12; }
@@ -601,7 +606,7 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
-      a.kv_group[1] = kvg;
+      a.kv_group[1] = kvg; a.kv_objects[1] = kvo;
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn1.out.wx"));
@@ -617,7 +622,8 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {q2, kv2, kv2 + C, o_self, nq, ldkv, ldkv, C, (int64_t)hw * nq, (int64_t)L * ldkv, (int64_t)L * ldkv, (int64_t)hw * C, hw, L};
       if (ad) a.p[1] = {q2 + C, rkv + 2 * C, rkv + 3 * C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
-      a.kv_group[0] = kvg; a.kv_group[1] = kvg;       // (the text K/V hold one row per guidance half as well)
+      a.kv_group[0] = kvg; a.kv_group[1] = kvg;       // (the text K/V hold one row per guidance half as well -- per half and object,
+      a.kv_objects[1] = kvo;                          //  in the batch's own order: no object map for problem 0)
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn2.out.w", (int64_t)C * ld_out), c.WF(key + ".attn2" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn2.out.wx"));
@@ -637,7 +643,7 @@ struct UNetPass {
       if (o.defer_norm) {
         if (!c.dry && !c.err) CHECK(mvd_launch_refstats(out.p, B_, hw, C, o.stats + 2 * c.e->feat_pixel_off(feat_idx), c.s));
       } else {
-        if (!c.dry && !c.err) CHECK(mvd_launch_refnorm(out.p, B_, hw, C, rn, c.s));
+        if (!c.dry && !c.err) CHECK(o.objects > 1 ? mvd_launch_refnorm_grouped(out.p, B_, 1, hw, C, rn, c.s) : mvd_launch_refnorm(out.p, B_, hw, C, rn, c.s));
         CHECK(c.linear(rn, nullptr, C, 0, M, c.WB(key + ".ref_kv.w", (int64_t)4 * C * C, 0), nullptr, 4 * C, nullptr, 0, c.e->refkv[feat_idx], 4 * C, false, false, 0,
                        key + ".ref_kv.wx", 0));
         if (c.e->dual_now && !c.dry && !c.err && hipEventRecord(c.e->feat_ev[feat_idx], c.s) != hipSuccess) { mvd_set_error("forward: hipEventRecord failed"); return -3; }
@@ -923,7 +929,7 @@ int setup_tile_counters(mvd_engine* e, unsigned int* block, hipStream_t s, bool 
   return 0;
 }
 
-int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry) {
+int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects) {
   const mvd_config_t& cfg = e->cfg;
   if (a.batch <= 0 || a.height <= 0 || a.width <= 0 || a.text_len <= 0) { mvd_set_error("forward: bad shape"); return -1; }
   const int div = 1 << (cfg.num_levels - 1);
@@ -943,7 +949,20 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   const bool share = a.flags & MVD_SHARE_REF;
   if (!share && a.views > 1) { mvd_set_error("forward: views = %d needs MVD_SHARE_REF", a.views); return -1; }
   const int V = share ? a.views : 0;
-  if (share) {
+  // ---- mvd_unet_forward_objects: O > 1 objects x `views` views (include/mvd_hip.h); the same rule: every check before any launch
+  const int O = objects > 1 ? objects : 0;
+  if (O) {
+    if (!share || !use_img) { mvd_set_error("forward_objects: objects = %d needs MVD_SHARE_REF with MVD_USE_IMAGE", O); return -1; }
+    if (V < 1 || a.batch % (O * V)) { mvd_set_error("forward_objects: batch %d is not a multiple of objects %d x views %d", a.batch, O, V); return -1; }
+    const int g = a.batch / (O * V);
+    if (g > 2) { mvd_set_error("forward_objects: %d rows per view (batch %d / (objects %d x views %d)); 1 or 2 (classifier-free guidance) are supported", g, a.batch, O, V); return -1; }
+    if (a.ref_batch != O) { mvd_set_error("forward_objects: needs ref_batch == objects = %d (one reference row per object), got %d", O, a.ref_batch); return -1; }
+    if (use_cam && a.cam_batch != 1 && a.cam_batch != O * V) { mvd_set_error("forward_objects: the cameras must hold 1 or objects x views = %d rows, got %d", O * V, a.cam_batch); return -1; }
+    for (int lv = 0; lv < cfg.num_levels; ++lv) {
+      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
+      if (hw % g) { mvd_set_error("forward_objects: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
+    }
+  } else if (share) {
     if (ref_only) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
     if (!use_img) { mvd_set_error("forward: MVD_SHARE_REF needs MVD_USE_IMAGE"); return -1; }
     if (V < 1 || a.batch % V) { mvd_set_error("forward: MVD_SHARE_REF: batch %d is not a multiple of views %d", a.batch, V); return -1; }
@@ -970,7 +989,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   if (use_img) {
     const bool keep = (a.flags & MVD_KEEP_FEATURES) || ref_only;
     if (reuse) {
-      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
+      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V || e->rc_objects != O) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
     } else {
       e->persist.reset(dry);
       e->refkv.assign(e->feats.size(), nullptr);
@@ -982,7 +1001,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
         if (keep) e->feat_keep[i] = (bf16_t*)e->persist.alloc((size_t)a.ref_batch * hw * e->feats[i].C * sizeof(bf16_t));
       }
       if (e->persist.overflow()) { mvd_set_error("forward: reference cache too small (%zu > %zu bytes)", e->persist.high, e->persist.cap); return -4; }
-      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_views = V;
+      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_views = V; e->rc_objects = O;
       if (!dry) { e->rc_valid = false; e->rc_pending = false; }
     }
   }
@@ -1056,7 +1075,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
       CHECK(mvd_launch_f32_to_bf16(a.encoder_text, (int64_t)Br * L * xd, tx, c.s));
       CHECK(mvd_launch_im2col_in(a.source_latents, Br, cfg.in_channels, H, Wd, nullptr, nullptr, 0, xin.p, c.s));
     }
-    PassOpts po; po.capture = true; po.ref_batch = Br;
+    PassOpts po; po.capture = true; po.ref_batch = Br; po.objects = O;
     po.defer_norm = ref_only; po.stats = e->ref_stats_out;
     UNetPass pass{c, cfg, po, Br, H, Wd, L, tx, tproj};
     CHECK(pass.run(xin, nullptr));
@@ -1096,7 +1115,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   //  measured no difference and has no switch.)
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
-  po.views = V;
+  po.views = V; po.objects = O;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
@@ -1112,8 +1131,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
 // Every exit of a forward that forked the side stream joins it: an error return between fork and join (a failed check in the
 // camera path or a pass, a workspace that is too small) must not leave the encoder pass writing the reference cache and the
 // activation arena while the caller frees or reuses them.  The success path has joined with an event already.
-int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry) {
-  const int r = forward_body(e, a, s, dry);
+int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects = 0) {
+  const int r = forward_body(e, a, s, dry, objects);
   if (e->dual_now) {
     if (e->side) (void)hipStreamSynchronize(e->side);      // error path only: the cheap join is not worth an event here
     e->dual_now = false;
@@ -1213,17 +1232,21 @@ int64_t mvd_engine_workspace_bytes(mvd_engine_t* e, int batch, int height, int w
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
 }
 
-int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) {
+static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args, int objects) {
   if (!e || !args) { mvd_set_error("workspace_bytes_args: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("workspace_bytes_args: unknown flag bits 0x%x", args->flags); return -1; }
   const mvd_engine::HostState before = e->host_state();
   // (a sizing call must not depend on the cache state: size the forward that runs the encoder pass, the larger of the two)
   mvd_forward_args_t a = *args;
   a.flags &= ~MVD_REUSE_REF;
-  int r = forward_impl(e, a, nullptr, true);
+  int r = forward_impl(e, a, nullptr, true, objects);
   e->set_host_state(before);
   if (r) return r;
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
+}
+int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) { return workspace_bytes_args(e, args, 0); }
+int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects) {
+  return workspace_bytes_args(e, args, objects > 1 ? objects : 0);
 }
 
 int64_t mvd_engine_refcache_bytes(mvd_engine_t* e, int ref_batch, int height, int width, int keep_features) {
@@ -1290,12 +1313,13 @@ int mvd_engine_reference_finish(mvd_engine_t* e, const float* mean_k, void* stre
   return 0;
 }
 
-int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) {
+// mvd_unet_forward (objects = 0) and mvd_unet_forward_objects (objects > 1)
+static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
   if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
   // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
   const mvd_engine::HostState before = e->host_state();
-  int r = forward_impl(e, *args, nullptr, true);
+  int r = forward_impl(e, *args, nullptr, true, objects);
   e->set_host_state(before);
   if (r) return r;
   const size_t act_bytes = (e->act.high + 255) & ~size_t(255);
@@ -1306,7 +1330,7 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
   e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
   e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
   hipStream_t st = (hipStream_t)stream;
-  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false);
+  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, objects);
   // ---- hipGraph replay.  A forward is a pure function of the argument block (pointers, shapes, flags), the bound buffers
   // and the reference-cache state it starts from; the host-side state it leaves behind is the same every time.  The first
   // call with a given key runs as usual (kernels' first-use set-up must not happen inside a capture), the second is
@@ -1314,6 +1338,8 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
   std::string key((const char*)args, sizeof(*args));
   const int st8[8] = {e->rc_valid, e->rc_batch, e->rc_h, e->rc_w, e->rc_keep, e->share_encoder, e->rc_views, args->flags & MVD_SHARE_REF};   // (views and the flag are in *args too)
   key.append((const char*)st8, sizeof(st8));
+  const int ob2[2] = {objects, e->rc_objects};
+  key.append((const char*)ob2, sizeof(ob2));
   key.append((const char*)&e->ws_ptr, sizeof(void*));
   key.append((const char*)&e->rc_ptr, sizeof(void*));
   for (auto& ge : e->graphs)
@@ -1325,11 +1351,11 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
     }
   bool seen = false;
   for (auto& k : e->graph_seen) seen |= k == key;
-  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false); }
+  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false, objects); }
   if (e->graphs.size() >= 8) e->drop_graphs();
   hipError_t he = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (he != hipSuccess) { mvd_set_error("forward: hipStreamBeginCapture: %s", hipGetErrorString(he)); return -7; }
-  r = forward_impl(e, *args, st, false);
+  r = forward_impl(e, *args, st, false, objects);
   hipGraph_t g = nullptr;
   he = hipStreamEndCapture(st, &g);
   if (r) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -1341,6 +1367,11 @@ int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stre
   he = hipGraphLaunch(x, st);
   if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
   return 0;
+}
+
+int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) { return unet_forward(e, args, 0, stream); }
+int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
+  return unet_forward(e, args, objects > 1 ? objects : 0, stream);
 }
 
 int mvd_engine_set_graph(mvd_engine_t* e, int enable) {
@@ -1544,12 +1575,17 @@ int mvd_op_attention(const void* q, const void* k, const void* v, void* o, int b
 
 int mvd_op_attention_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
                              int ldk, int ldv, int ldo, float scale, int kv_group, void* stream) {
+  return mvd_op_attention_objects(q, k, v, o, batch, heads, nq, nk, ldq, ldk, ldv, ldo, scale, kv_group, 0, stream);
+}
+
+int mvd_op_attention_objects(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                             int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects, void* stream) {
   MvdAttnArgs a; memset(&a, 0, sizeof(a));
   a.nprob = 1; a.batch = batch; a.heads = heads; a.scale = scale;
   a.prescaled = scale == 0.f;
   a.p[0] = {(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
             (int64_t)nq * ldq, (int64_t)nk * ldk, (int64_t)nk * ldv, (int64_t)nq * ldo, nq, nk};
-  a.kv_group[0] = kv_group;
+  a.kv_group[0] = kv_group; a.kv_objects[0] = kv_objects;
   return mvd_launch_attention(a, (hipStream_t)stream);
 }
 
@@ -1584,6 +1620,9 @@ int mvd_op_layernorm(const void* x, int rows, int c, float eps, const float* gam
 }
 int mvd_op_refnorm(const void* x, int batch, int hw, int c, void* y, void* stream) {
   return mvd_launch_refnorm((const bf16_t*)x, batch, hw, c, (bf16_t*)y, (hipStream_t)stream);
+}
+int mvd_op_refnorm_grouped(const void* x, int batch, int group, int hw, int c, void* y, void* stream) {
+  return mvd_launch_refnorm_grouped((const bf16_t*)x, batch, group, hw, c, (bf16_t*)y, (hipStream_t)stream);
 }
 int mvd_op_film(const void* x, int batch, int hw, int c, const float* scale, const float* shift, void* y, void* stream) {
   return mvd_launch_film((const bf16_t*)x, batch, hw, c, scale, shift, c, (bf16_t*)y, (hipStream_t)stream);

@@ -164,6 +164,10 @@ struct MvdAttnArgs {
   // batch / kv_group[i] elements, bsk / bsv apart (several views attending one reference).  0 or 1: every
   // batch element has K/V of its own.  Honoured by every form mvd_launch_attention dispatches: the base pointers alone change
   int kv_group[2];
+  // object-major K/V (per problem, on top of kv_group): the batch is [guidance half j][object o][view v]
+  // and k / v hold kv_objects[i] * g elements [object o][half j], g = batch / (kv_group[i] * kv_objects[i]).  With
+  // q = b / kv_group[i] (= j * O + o), batch element b reads K/V element (q % O) * g + q / O.  0 or 1: off (element q)
+  int kv_objects[2];
 };
 // split the engine's heuristic gives this launch (1 = none) and what it then needs
 int mvd_attention_pick_split(const MvdAttnArgs& a);
@@ -182,6 +186,9 @@ int mvd_launch_layernorm(const bf16_t* x, int rows, int c, float eps, const floa
                          bf16_t* y, hipStream_t s);
 // Q2 reference normalisation: per pixel over (batch, channel), unbiased std, clamp 1e-6, *0.5
 int mvd_launch_refnorm(const bf16_t* x, int batch, int hw, int c, bf16_t* y, hipStream_t s);
+// the same with statistics over each run of `group` consecutive batch rows (group == batch: mvd_launch_refnorm; group == 1: per
+// object, bit-identical to mvd_launch_refnorm on that row alone)
+int mvd_launch_refnorm_grouped(const bf16_t* x, int batch, int group, int hw, int c, bf16_t* y, hipStream_t s);
 int mvd_launch_refstats(const bf16_t* x, int batch, int hw, int c, float* stats /*[hw][2]: mean, M2*/, hipStream_t s);
 int mvd_launch_refapply(const bf16_t* x, int batch, int hw, int c, const float* mean_k /*[hw][2]*/, bf16_t* y, hipStream_t s);
 

@@ -399,6 +399,56 @@ __global__ __launch_bounds__(256) void refnorm_kernel(const bf16_t* __restrict__
   }
 }
 
+// Grouped form (several objects in one forward, statistics per object): workgroup (pixel, batch group)
+// runs refnorm_kernel's three loops over its `group` consecutive batch rows -- the same element order per thread and the same
+// reduction, so a group's result is bit-identical to refnorm_kernel on those rows alone.
+__global__ __launch_bounds__(256) void refnorm_grouped_kernel(const bf16_t* __restrict__ x, int group, int hw, int c,
+                                                              bf16_t* __restrict__ y) {
+  __shared__ float red[8];
+  const int p = blockIdx.x;
+  const size_t base = (size_t)blockIdx.y * group * hw * c;
+  x += base; y += base;
+  const int vec = c >> 3;
+  const int total = group * vec;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto block_sum = [&](float v) -> float {
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+  };
+  float s = 0.f;
+  for (int e = threadIdx.x; e < total; e += 256) {
+    const int b = e / vec, v = e % vec;
+    float f[8];
+    unpack8(*reinterpret_cast<const u32x4*>(x + ((size_t)b * hw + p) * c + v * 8), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += f[j];
+  }
+  const float n = (float)group * (float)c;
+  const float mean = block_sum(s) / n;
+  float q = 0.f;
+  for (int e = threadIdx.x; e < total; e += 256) {
+    const int b = e / vec, v = e % vec;
+    float f[8];
+    unpack8(*reinterpret_cast<const u32x4*>(x + ((size_t)b * hw + p) * c + v * 8), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float d = f[j] - mean; q = fmaf(d, d, q); }
+  }
+  const float var = block_sum(q) / (n - 1.0f);
+  const float k = 0.5f / fmaxf(sqrtf(var), 1e-6f);
+  for (int e = threadIdx.x; e < total; e += 256) {
+    const int b = e / vec, v = e % vec;
+    float f[8];
+    const size_t off = ((size_t)b * hw + p) * c + v * 8;
+    unpack8(*reinterpret_cast<const u32x4*>(x + off), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = (f[j] - mean) * k;
+    *reinterpret_cast<u32x4*>(y + off) = pack8(f);
+  }
+}
+
 // Q2 with statistics that span several GPUs (SURVEY.md 8e mode ii): the same arithmetic cut in two.  refstats writes, per
 // pixel, the LOCAL mean and the sum of squared deviations from it (M2) over (batch, channel); the host merges the ranks'
 // pairs (Chan's parallel form -- no E[x^2] - mean^2 cancellation) into (mean, k = 0.5 / max(std, 1e-6)) and refapply
@@ -613,6 +663,14 @@ int mvd_launch_refnorm(const bf16_t* x, int batch, int hw, int c, bf16_t* y, hip
   if (!x || !y || batch <= 0 || hw <= 0 || c <= 0 || (c % 8)) { mvd_set_error("refnorm: bad arguments"); return -1; }
   hipLaunchKernelGGL(refnorm_kernel, dim3(hw), dim3(256), 0, s, x, batch, hw, c, y);
   return check_launch("refnorm");
+}
+
+int mvd_launch_refnorm_grouped(const bf16_t* x, int batch, int group, int hw, int c, bf16_t* y, hipStream_t s) {
+  if (!x || !y || batch <= 0 || hw <= 0 || c <= 0 || (c % 8)) { mvd_set_error("refnorm_grouped: bad arguments"); return -1; }
+  if (group <= 0 || batch % group) { mvd_set_error("refnorm_grouped: group %d does not divide the batch %d", group, batch); return -1; }
+  if (batch / group > 65535) { mvd_set_error("refnorm_grouped: %d groups exceed the grid", batch / group); return -1; }
+  hipLaunchKernelGGL(refnorm_grouped_kernel, dim3(hw, batch / group), dim3(256), 0, s, x, group, hw, c, y);
+  return check_launch("refnorm_grouped");
 }
 
 int mvd_launch_layernorm_f32(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, int silu,

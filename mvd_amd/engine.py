@@ -111,8 +111,8 @@ class MVDEngine:
         return sum(t.numel() * t.element_size() for d in self._weights for t in d.values())
 
     # ------------------------------------------------------------------ workspace
-    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0):
-        key = (batch, h, w, text_len, ref_batch, keep_features, views)
+    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0, objects=0):
+        key = (batch, h, w, text_len, ref_batch, keep_features, views) + ((objects,) if objects else ())
         if self._ws_key == key:
             return
         if views:
@@ -120,9 +120,12 @@ class MVDEngine:
             # an ordinary forward, whose Q4 re-chunking fails when the views do not divide the reference tokens
             a = L.mvd_forward_args_t()
             a.batch, a.height, a.width, a.text_len, a.ref_batch, a.views = batch, h, w, text_len, ref_batch, views
-            a.cam_rows, a.cam_batch = 4, views
+            a.cam_rows, a.cam_batch = 4, views * max(objects, 1)
             a.flags = L.MVD_USE_CAMERA | L.MVD_USE_IMAGE | L.MVD_SHARE_REF
-            ws = L.lib().mvd_engine_workspace_bytes_args(self._h, C.byref(a))
+            if objects:
+                ws = L.lib().mvd_engine_workspace_bytes_objects(self._h, C.byref(a), objects)
+            else:
+                ws = L.lib().mvd_engine_workspace_bytes_args(self._h, C.byref(a))
         else:
             ws = L.lib().mvd_engine_workspace_bytes(self._h, batch, h, w, text_len, ref_batch)
         if ws < 0:
@@ -148,10 +151,14 @@ class MVDEngine:
                 source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                 fourier_proj: Optional[torch.Tensor] = None, source_latents: Optional[torch.Tensor] = None,
                 encoder_text: Optional[torch.Tensor] = None, reuse_ref: bool = False,
-                keep_features: bool = False, out: Optional[torch.Tensor] = None, views: Optional[int] = None) -> torch.Tensor:
+                keep_features: bool = False, out: Optional[torch.Tensor] = None, *, views: Optional[int] = None,
+                objects: Optional[int] = None) -> torch.Tensor:
         """All tensors fp32 contiguous on ``self.device``; returns fp32 NCHW.  ``views`` (an int >= 1): the shared-reference
         forward (``MVD_SHARE_REF``, include/mvd_hip.h) -- ``sample`` holds g * views rows ``[uncond x views | cond x views]``,
-        ``text`` g rows, ``source_latents`` / ``encoder_text`` one row, the cameras 1 or ``views`` rows."""
+        ``text`` g rows, ``source_latents`` / ``encoder_text`` one row, the cameras 1 or ``views`` rows.  ``objects`` (O > 1, with
+        ``views``; ``mvd_unet_forward_objects``): O objects x ``views`` views -- ``sample`` holds g * O * views rows, object-major
+        inside a guidance half, ``text`` g * O rows, ``source_latents`` / ``encoder_text`` O rows, the cameras 1 or O * views rows;
+        ``None`` / 1: the forward without it."""
         B, Cin, H, W = sample.shape
         Lt = text.shape[1]
         for t in (sample, timesteps, text, source_camera, target_camera, fourier_proj, source_latents, encoder_text):
@@ -159,6 +166,9 @@ class MVDEngine:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise L.MvdError("engine.forward expects contiguous fp32 CUDA tensors")
         views = int(views) if views else 0
+        objects = int(objects) if objects and int(objects) > 1 else 0
+        if objects and not views:
+            raise L.MvdError(f"engine.forward: objects = {objects} needs views")
         if views and B % views:
             raise L.MvdError(f"engine.forward: batch {B} is not a multiple of views {views}")
         if text.shape[0] != (B // views if views else B) or timesteps.shape != (B,):
@@ -172,7 +182,10 @@ class MVDEngine:
             self._last_ref_batch = ref_batch
         if views and not use_img:
             raise L.MvdError("engine.forward: views needs image conditioning (source_latents or reuse_ref)")
-        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views)
+        if objects and (ref_batch != objects or B % (objects * views)):
+            raise L.MvdError(f"engine.forward: {objects} objects x {views} views need a multiple of {objects * views} sample rows and "
+                             f"{objects} reference rows, got {B} and {ref_batch}")
+        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views, objects)
         graph = getattr(self, "_graph", False)
         user_out = out
         if graph:
@@ -218,17 +231,19 @@ class MVDEngine:
             a.views = views
         a.ref_batch, a.flags = ref_batch, flags
         a.out = out.data_ptr()
+        # (objects: the count travels beside the argument block, which is as it was)
+        entry = ("mvd_unet_forward_objects", self._h, C.byref(a), objects) if objects else ("mvd_unet_forward", self._h, C.byref(a))
         if graph:
             cur = torch.cuda.current_stream(self.device)
             self._gstream.wait_stream(cur)
             with torch.cuda.stream(self._gstream):
-                L.call("mvd_unet_forward", self._h, C.byref(a), L.stream())
+                L.call(*entry, L.stream())
             cur.wait_stream(self._gstream)
             out = out.clone() if user_out is None else user_out.copy_(out)
         else:
-            L.call("mvd_unet_forward", self._h, C.byref(a), L.stream())
+            L.call(*entry, L.stream())
         if use_img and not reuse_ref:
-            self._ref_valid = (B, H, W, Lt, ref_batch) + ((views,) if views else ())
+            self._ref_valid = (B, H, W, Lt, ref_batch) + ((views,) if views else ()) + ((objects,) if objects else ())
         return out
 
     # ------------------------------------------------------------------ reference pass in two halves (global Q2 statistics)
@@ -294,10 +309,11 @@ class MVDEngine:
             buf.copy_(t)
         return buf
 
-    def reference_cache_valid(self, batch, h, w, text_len, ref_batch, views=0) -> bool:
+    def reference_cache_valid(self, batch, h, w, text_len, ref_batch, views=0, objects=0) -> bool:
         """True when the engine still holds reference K/V computed for exactly this shape (Q5 reuse is then legal); ``views``:
-        by a shared-reference forward of that many views."""
-        return getattr(self, "_ref_valid", None) == (batch, h, w, text_len, ref_batch) + ((views,) if views else ())
+        by a shared-reference forward of that many views (of each of ``objects`` objects)."""
+        return getattr(self, "_ref_valid", None) == ((batch, h, w, text_len, ref_batch) + ((views,) if views else ())
+                                                      + ((objects,) if objects else ()))
 
     # ------------------------------------------------------------------ measurement
     PROFILE_CLASSES = {0: "gemm_256x160", 1: "gemm_256x128", 2: "gemm_128x160", 3: "gemm_128x128", 4: "gemm_128x64",

@@ -286,12 +286,19 @@ class MultiViewUNet(nn.Module):
                 source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                 source_image_latents: Optional[torch.FloatTensor] = None, return_dict: bool = True,
                 timestep_cond: Optional[torch.FloatTensor] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
-                added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None, *, views: Optional[int] = None):
+                added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None, *, views: Optional[int] = None,
+                objects: Optional[int] = None):
         """``views`` (keyword-only, not a reference parameter): V > 1 views of ONE object in one forward.
         ``sample`` holds g * V rows in the pipeline's order ``[uncond x V | cond x V]`` (g = 1, or 2 under guidance),
         ``encoder_hidden_states`` g rows, ``source_image_latents`` one row, the cameras 1 or V rows.  Row j * V + v is row j
         of the batch-g call for view v -- same reference tokens, text row, camera -- from one encoder pass and one copy of
-        the reference K/V.  ``None`` / 1: the ordinary forward."""
+        the reference K/V.  ``None`` / 1: the ordinary forward.
+
+        ``objects`` (keyword-only): O > 1 objects x ``views`` views in one forward, which IS the O * V
+        independent batch-g calls.  ``sample`` holds g * O * V rows ``[uncond x O V | cond x O V]``, object-major inside a half
+        (row j * O * V + o * V + v), ``encoder_hidden_states`` g * O rows ``[negative x O | positive x O]``,
+        ``source_image_latents`` O rows, the cameras 1 or O * V rows (row o * V + v).  The encoder pass runs once at batch O
+        with the Q2 statistics per object.  ``None`` / 1: the forward without it."""
         if cross_attention_kwargs:
             cross_attention_kwargs.pop("debug_log_file_path", None)   # accepted, never evaluated (no host syncs)
         eng = self._sync_engine()
@@ -301,7 +308,18 @@ class MultiViewUNet(nn.Module):
         B = x.shape[0]
         text = self._f32(encoder_hidden_states, dev)
         V = int(views) if views is not None and int(views) > 1 else 0
-        if V:
+        O = int(objects) if objects is not None and int(objects) > 1 else 0
+        if O:
+            V = max(V, 1)
+            if self.reference_stats_group is not None:
+                raise L.MvdError("objects: the object forward does not go with reference_stats_group (its Q2 statistics are per "
+                                 "object; statistics over the ranks' batches couple the objects)")
+            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != O:
+                raise L.MvdError(f"objects={O}: needs image conditioning with {O} rows of source_image_latents (one per object)")
+            if B % (O * V) or B // (O * V) > 2 or text.shape[0] != B // V:
+                raise L.MvdError(f"objects={O}, views={V}: sample must hold g * objects * views rows and encoder_hidden_states "
+                                 f"g * objects rows (g = 1, or 2 under guidance); got {B} and {text.shape[0]}")
+        elif V:
             if self.reference_stats_group is not None:
                 raise L.MvdError("views: the shared-reference forward does not go with reference_stats_group (statistics over "
                                  "the ranks' batches are for many objects; the views of one object share its one reference)")
@@ -328,7 +346,7 @@ class MultiViewUNet(nn.Module):
             bs = source_image_latents.shape[0]
             enc_text = text
             if V:                                                      # the batch-g call's choice below: its last row
-                enc_text = text[-1:]
+                enc_text = text[-max(O, 1):]                           # (per object: row (g - 1) * O + o)
             elif text.shape[0] == 2 * bs:                              # :280-283
                 enc_text = text[bs:]
             elif text.shape[0] > bs:                                   # :284-285
@@ -337,10 +355,10 @@ class MultiViewUNet(nn.Module):
             # is live, so the caching allocator cannot hand their addresses to different data of the same shape (a second
             # object denoised right after the first would otherwise hit the first object's K/V).
             key = (source_image_latents.data_ptr(), source_image_latents._version, tuple(source_image_latents.shape),
-                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V)
+                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V, O)
             glob = self.reference_stats_group is not None
             hit = (self.cache_reference and self._ref_key == key
-                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, V))
+                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, V, O))
             if glob and self.cache_reference:
                 # the recompute path below contains a collective: the decision must be the same on every rank of the group
                 # (a re-bound workspace or a fresh tensor on ONE rank would otherwise leave the others out of the all-gather)
@@ -359,7 +377,7 @@ class MultiViewUNet(nn.Module):
                     local = eng.reference_encode(img["source_latents"], img["encoder_text"], B)
                     eng.reference_finish(merge_reference_stats(local, group))
                     img = dict(reuse_ref=True, keep_features=True)
-        out = eng.forward(x, t, text, **cam, **img, **({"views": V} if V else {}))
+        out = eng.forward(x, t, text, **cam, **img, **({"views": V} if V else {}), **({"objects": O} if O else {}))
         if cam:
             self.current_camera_embedding = eng.camera_embedding(cam["target_camera"].shape[0])
         hidden_states = out.to(out_dtype)

@@ -399,6 +399,23 @@ def attention_grouped(q, k, v, heads, kv_group, scale=0.125):
     return out
 
 
+def attention_objects(q, k, v, heads, kv_group, kv_objects, scale=0.125):
+    """``attention_grouped`` for the views of several objects: q (B, Nq, heads*64) with B = g * kv_objects * kv_group rows ordered
+    [half j][object o][view]; k / v (kv_objects * g, Nk, heads*64) ordered [object o][half j] -- batch element b attends K/V
+    element ``(q % O) * g + q // O`` with ``q = b // kv_group``.  kv_objects=1 is ``attention_grouped``."""
+    _bf16(q, k, v)
+    B, nq, _ = q.shape
+    nk = k.shape[1]
+    kvg = max(int(kv_group), 1)
+    assert kv_objects >= 0 and B % (kvg * max(int(kv_objects), 1)) == 0 and k.shape[0] == B // kvg and v.shape[0] == B // kvg, (B, kv_group, kv_objects, k.shape, v.shape)
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    assert q.stride(0) == nq * q.stride(1) and k.stride(0) == nk * k.stride(1) and v.stride(0) == nk * v.stride(1)
+    out = torch.empty(B, nq, heads * 64, device=q.device, dtype=torch.bfloat16)
+    L.call("mvd_op_attention_objects", C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), _p(out),
+           B, heads, nq, nk, q.stride(1), k.stride(1), v.stride(1), heads * 64, float(scale), int(kv_group), int(kv_objects), _s())
+    return out
+
+
 def attention_causal(q, k, v, heads, scale=0.125):
     """The CLIP text encoder's attention: q, k, v (B, n, heads*64) bf16 with n <= 96, key j visible to query i iff j <= i; row
     strides may exceed heads*64 (views of one fused QKV buffer).  scale=0: q already carries 64^-0.5 * log2(e)."""
@@ -451,6 +468,16 @@ def refnorm(x):
     B, hw, c = x.shape
     y = torch.empty_like(x)
     L.call("mvd_op_refnorm", _p(x), B, hw, c, _p(y), _s())
+    return y
+
+
+def refnorm_grouped(x, group):
+    """``refnorm`` with statistics over each run of ``group`` consecutive batch rows: ``group == B`` is ``refnorm``, ``group == 1``
+    normalises every row (object) by itself, bit-identical to ``refnorm`` on that row alone."""
+    _bf16(x)
+    B, hw, c = x.shape
+    y = torch.empty_like(x)
+    L.call("mvd_op_refnorm_grouped", _p(x), B, int(group), hw, c, _p(y), _s())
     return y
 
 

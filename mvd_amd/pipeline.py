@@ -45,16 +45,27 @@ class MVDDenoiser:
                  source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                  source_image_latents: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
                  height: int = 64, width: int = 64, noise_per_step=None, callback=None, callback_steps: int = 1,
-                 cross_attention_kwargs: Optional[Dict[str, Any]] = None, views: Optional[int] = None):
+                 cross_attention_kwargs: Optional[Dict[str, Any]] = None, views: Optional[int] = None,
+                 objects: Optional[int] = None):
         """``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
-        source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``)."""
+        source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``).  ``objects``
+        (MVDPipeline.generate_views_batch): O prompts and O source rows, ``latents`` and the cameras O * views rows, object-major;
+        every step is one object forward (``MultiViewUNet.forward(..., views=, objects=)``)."""
         dev = self.unet._exec_device()
         B = prompt_embeds.shape[0]
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
         embeds = torch.cat([negative_prompt_embeds.to(prompt_embeds.device), prompt_embeds]) if cfg else prompt_embeds
         embeds = embeds.to(dev, torch.float32)
         views = int(views) if views is not None and int(views) > 1 else 0
-        if views:
+        objects = int(objects) if objects is not None and int(objects) > 1 else 0
+        if objects:
+            views = max(views, 1)
+            if B != objects:
+                raise L.MvdError(f"objects: one prompt per object, got {B} rows of prompt_embeds for {objects} objects")
+            if guidance_scale > 1.0 and not cfg:      # as below: [positive x O | positive x O]
+                embeds = embeds.repeat(2, 1, 1)
+            B = objects * views
+        elif views:
             if B != 1:
                 raise L.MvdError(f"views: one prompt for the one object, got {B} rows of prompt_embeds")
             if guidance_scale > 1.0 and not cfg:      # the doubled latents against one text row: the repeat of mvd_unet.py:233-237
@@ -74,6 +85,8 @@ class MVDDenoiser:
             extra["source_image_latents"] = source_image_latents.to(dev)
         if views:
             extra["views"] = views
+        if objects:
+            extra["objects"] = objects
         # Q5: the reference K/V of a previous call (another object) must never be reused by this one
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
@@ -303,6 +316,97 @@ class MVDPipeline:
             if self.vae is None:
                 raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
             image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of V rows
+            image = (image / 2 + 0.5).clamp(0, 1)
+            if output_type == "pil":
+                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
+        if not return_dict:
+            return image
+        return {"images": image}
+
+
+    @torch.no_grad()
+    def generate_views_batch(self, prompts: Optional[List[str]] = None, source_images: Optional[torch.Tensor] = None,
+                             source_cameras: Optional[torch.Tensor] = None, target_cameras: Optional[torch.Tensor] = None,
+                             height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
+                             guidance_scale: float = 7.5, negative_prompt: Optional[Union[str, List[str]]] = None,
+                             generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
+                             latents: Optional[torch.FloatTensor] = None, prompt_embeds: Optional[torch.FloatTensor] = None,
+                             negative_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = "pil",
+                             return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
+                             callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
+                             source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None):
+        """Turntables of O objects, V views each: what O calls of ``generate_views`` (O * V calls of ``pipe(...)``) give, in one
+        denoising loop whose every step is ONE object forward.  The prompts are encoded once, the O
+        sources VAE-encoded in one call, the reference encoder pass runs at batch O (once per call with
+        ``unet.cache_reference``) with per-object statistics, the O * V latents are decoded in one VAE call.  Not a method of
+        the reference's pipeline.
+
+        ``prompts``: a list of O strings, or ``prompt_embeds`` with O rows (``negative_prompt``: one string for all or a list of O;
+        ``negative_prompt_embeds``: 1 or O rows); ``source_images`` / ``source_image_latents``: O rows; ``source_cameras``:
+        (O, 3|4, 4); ``target_cameras``: (O, V, 3|4, 4), or (V, 3|4, 4) for every object.  Every object has the same V.
+        ``generator``: one generator (the initial latents are one draw of (O V, 4, h, w)) or a list of O * V (row o * V + v is that
+        view's own draw); ``latents``: O * V rows, object-major.  Returns O * V images (or latents) in object-major order.
+
+        Ancestral noise (``sampler="ddpm"``): ONE draw of (O V, 4, h, w) per step from torch's global RNG, or ``noise_per_step[i]``
+        of that shape (row o * V + v is what that view's own call gets).  The camera encoder's random projection (Q1) is drawn
+        once per forward for all rows."""
+        dev = self.device
+        if prompts is not None and (isinstance(prompts, str) or not isinstance(prompts, (list, tuple))):
+            raise L.MvdError("generate_views_batch: prompts must be a list of strings, one per object")
+        if prompts is None and prompt_embeds is None:
+            raise L.MvdError("MVDPipeline: neither prompts nor prompt_embeds given")
+        if prompt_embeds is None:
+            prompt_embeds = self._encode_prompt(list(prompts))                    # once for all objects and views
+        O = prompt_embeds.shape[0]
+        if prompts is not None and len(prompts) != O:
+            raise L.MvdError(f"generate_views_batch: {len(prompts)} prompts vs {O} rows of prompt_embeds")
+        if negative_prompt_embeds is None and negative_prompt is not None:
+            neg = [negative_prompt] * O if isinstance(negative_prompt, str) else list(negative_prompt)
+            if len(neg) != O:
+                raise L.MvdError(f"generate_views_batch: {len(neg)} negative prompts for {O} objects")
+            negative_prompt_embeds = self._encode_prompt(neg)
+        if negative_prompt_embeds is not None:
+            if negative_prompt_embeds.shape[0] == 1:
+                negative_prompt_embeds = negative_prompt_embeds.expand(O, -1, -1)
+            if negative_prompt_embeds.shape[0] != O:
+                raise L.MvdError(f"generate_views_batch: {negative_prompt_embeds.shape[0]} rows of negative_prompt_embeds for {O} objects")
+        if target_cameras is None or target_cameras.dim() not in (3, 4):
+            raise L.MvdError("generate_views_batch: target_cameras must be (O, V, 3|4, 4) or (V, 3|4, 4)")
+        tgt = target_cameras if target_cameras.dim() == 4 else target_cameras.unsqueeze(0).expand(O, -1, -1, -1)
+        if tgt.shape[0] != O:
+            raise L.MvdError(f"generate_views_batch: target_cameras for {tgt.shape[0]} objects, prompts for {O}")
+        V = tgt.shape[1]
+        if source_cameras is None or source_cameras.dim() != 3 or source_cameras.shape[0] != O or source_cameras.shape[1:] != tgt.shape[2:]:
+            raise L.MvdError(f"generate_views_batch: source_cameras must be ({O}, {tgt.shape[2]}, 4), one per object")
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        if latents is None:
+            latents = self.prepare_latents(O * V, 4, height, width, prompt_embeds.dtype, dev, generator)
+        if latents.shape[0] != O * V:
+            raise L.MvdError(f"generate_views_batch: {latents.shape[0]} rows of latents for {O} objects x {V} views")
+        if source_images is not None:                                             # the O sources in one VAE call
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
+                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
+            si = source_images.to(device=dev)
+            if bool(si.min() >= 0) and bool(si.max() <= 1):
+                si = 2 * si - 1
+            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
+        if source_image_latents is None or source_image_latents.shape[0] != O:
+            raise L.MvdError(f"generate_views_batch: one source image per object ({O} rows of source_images or source_image_latents)")
+        den = MVDDenoiser(self.unet, self.scheduler)
+        one = O == 1                  # (one object: generate_views' forward, which is the same function)
+        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
+                      latents=latents, source_camera=source_cameras.repeat_interleave(V, 0), target_camera=tgt.reshape(O * V, *tgt.shape[2:]),
+                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=V,
+                      objects=None if one else O)
+        if output_type == "latent":
+            image = latents
+        else:
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
+            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of O * V rows
             image = (image / 2 + 0.5).clamp(0, 1)
             if output_type == "pil":
                 image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
