@@ -135,6 +135,30 @@ int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_
 int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream);
 int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects);
 
+/* Ragged turntables: O objects with view_counts[o] >= 1 views each in one MVD_SHARE_REF forward (mvd_forward_args_t is unchanged
+ * and args->views must be 0: the counts come beside it).  With R = sum of the counts and g rows per view (1, or 2 under
+ * guidance) the forward IS the R independent forwards of batch g, each with a one-row reference -- the definition of
+ * mvd_unet_forward_objects with V per object.  The sample holds g * R rows [uncond x R | cond x R], object-major inside a half;
+ * with c = (views of the objects before o) + v, row r = j * R + c
+ *   - attends, in both adapter branches and all 16 features, tokens [j * hw / g, (j + 1) * hw / g) of object o's reference only
+ *     (K/V element o * g + j of the O * g the ref_kv projection writes object-major);
+ *   - attends text row j * O + o (`text` holds g * O rows, [negative x O | positive x O]);
+ *   - takes camera c (cam_batch = R, or 1) and timesteps[r].
+ * Encoder pass, Q2 statistics, ref_kv projection and reference cache are those of mvd_unet_forward_objects at ref_batch = O.
+ * The two row maps are tables the engine builds from the counts (valid by construction, and checked on the host like any
+ * table: 0 <= entry < g * O) and keeps in device slots keyed by (counts, g).  A slot is written once, by a stream-ordered
+ * upload on the first forward of its layout, which therefore cannot run inside a stream capture of the caller's; no later
+ * forward of that layout uploads or synchronises.  At most 8 layouts are resident: a ninth evicts the least recently used
+ * one after dropping every captured hipGraph of the engine (mvd_engine_set_graph), so a slot a live graph points at is
+ * never rewritten.
+ * Checked on the host before any launch: args->views == 0; every count >= 1; MVD_SHARE_REF with MVD_USE_IMAGE;
+ * ref_batch == objects; batch == g * R with g in {1, 2}; cameras with 0, 1 or R rows; hw % g == 0 at every level.  Equal counts
+ * run mvd_unet_forward_objects (one object: the `views` forward) -- the same code, bit-identical results, their rejections.
+ * The reference-cache record and the hipGraph key carry the counts: a reference encoded under one layout is never served
+ * to another. */
+int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects, void* stream);
+int64_t mvd_engine_workspace_bytes_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects);
+
 /* Global Q2 statistics (SURVEY.md 8e mode ii; optional).  The adapter normalises the reference features with statistics
  * over (batch, channel) per pixel (attention.py:95-103), so a batch sharded over GPUs sees per-shard statistics unless the
  * shards exchange them.  The reference pass is therefore also available in two halves:
@@ -249,6 +273,13 @@ int mvd_op_attention_grouped(const void* q, const void* k, const void* v, void* 
  * (q % kv_objects) * g + q / kv_objects.  kv_objects <= 1 is mvd_op_attention_grouped; kv_group * kv_objects must divide batch. */
 int mvd_op_attention_objects(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
                              int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects, void* stream);
+/* K/V by table: batch element b attends K/V element kv_index_host[b] of the kv_elements elements k / v hold (ragged view counts
+ * per object, any many-to-one map).  kv_index_host is a HOST array of `batch` entries; every entry is checked on the host
+ * (0 <= entry < kv_elements) before anything is uploaded or launched, then the table is copied stream-ordered to a
+ * library-owned device buffer in front of the launch.  The identity table is mvd_op_attention, the table of
+ * mvd_op_attention_objects' map is that entry, bit for bit. */
+int mvd_op_attention_mapped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                            int ldk, int ldv, int ldo, float scale, const int* kv_index_host, int kv_elements, void* stream);
 /* Split-KV form (batch 1: too few (head, query block) pairs to fill the chip): the keys are cut into nsplit <= 8 ranges, one
  * workgroup each, merged in the kernel by the last workgroup to arrive.  Prescaled queries only (the scale == 0 form). */
 int64_t mvd_op_attention_split_ws_bytes(int batch, int heads, int nq, int nsplit);
@@ -301,6 +332,13 @@ int mvd_debug_pick_splitk_conv(int m, int n, int k);
 int mvd_gemm_sm_num_tiles(void);
 /* Measurement hook: log2(waves per attention workgroup) for every later launch of this process; -1 = heuristic. */
 int mvd_debug_set_attention_nw(int nw_log2);
+/* Test hooks of the ragged forward.  The two K/V tables the engine builds for view_counts and g rows per view, into host arrays
+ * of g * sum(view_counts) entries each (adapter: o * g + j; text: j * objects + o); returns that number of entries, or -1. */
+int mvd_debug_ragged_tables(const int* view_counts, int objects, int g, int* adapter, int* text);
+/* mvd_op_attention_mapped with a K/V group beside the table: the combination the host rejects (nothing is uploaded or launched). */
+int mvd_debug_attention_mapped_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk,
+                                       int ldq, int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects,
+                                       const int* kv_index_host, int kv_elements, void* stream);
 /* Measurement / bisection switches (bench.py --debug-flags, tools/, A/B tests): OR them into mvd_debug_set_flags.  Every switch
  * is read per launch or per forward unless it says otherwise, so 0 restores the product's behaviour.  The values are quoted
  * by DESIGN.md and profiles/ and never change; mvd_amd/_lib.py DebugFlag mirrors them (tests/test_cabi_cpu.py compares). */

@@ -104,6 +104,9 @@ _SIGS = {
     "mvd_engine_bind_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "mvd_unet_forward": (C.c_int, [C.c_void_p, C.POINTER(mvd_forward_args_t), C.c_void_p]),
     "mvd_unet_forward_objects": (C.c_int, [C.c_void_p, C.POINTER(mvd_forward_args_t), C.c_int, C.c_void_p]),
+    "mvd_unet_forward_ragged": (C.c_int, [C.c_void_p, C.POINTER(mvd_forward_args_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "mvd_engine_workspace_bytes_ragged": (C.c_int64, [C.c_void_p, C.POINTER(mvd_forward_args_t), C.POINTER(C.c_int), C.c_int]),
+    "mvd_debug_ragged_tables": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mvd_engine_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "mvd_engine_profile_summary": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -137,6 +140,11 @@ _SIGS = {
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "mvd_op_attention_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]),
+    "mvd_op_attention_mapped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "mvd_debug_attention_mapped_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                     C.c_int, C.c_void_p]),
     "mvd_op_attention_split_ws_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_op_attention_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

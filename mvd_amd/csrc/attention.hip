@@ -140,9 +140,13 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
   // when a group is set).  Object-major K/V (kv_objects): group q = j * O + o of the batch [half j][object o][view] reads element
   // o * g + j of the K/V [object][half] -- scalar arithmetic again.  The two fields are read together and tested once (both are
   // >= 0, the host has checked), so a launch that sets neither passes one scalar wait and one branch
+  // K/V map by table (kv_index, ragged view counts): element kv_index[pi][bz], one scalar load through a uniform pointer; the host
+  // has validated every entry and rejects a table together with a group.  The pointer is read in the same clause and folded into
+  // the same test
   const int kvg = a.kv_group[pi], kvo = a.kv_objects[pi];
+  const int* kvi = a.kv_index[pi];
   int bkv = bz;
-  if ((kvg | kvo) > 1) {
+  if (((kvg | kvo) > 1) | (kvi != nullptr)) {
     if (kvg > 1) bkv = bz / kvg;
     if (kvo > 1) {
       const int g = a.batch / ((kvg > 1 ? kvg : 1) * kvo);
@@ -152,6 +156,17 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
       // instruction-fetch line.  Without it the main loop starts 24 bytes further into its line and cfg4 measured 58.58 ms against
       // 58.46 (three builds alternated, four rounds).  Re-derive after any edit of this set-up
       asm volatile("s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+    }
+    if (kvi) {
+      // (read through the constant address space: the table is written before the launch and never during it, and a uniform
+      //  constant-space load is a scalar load wherever the compiler places it)
+      bkv = reinterpret_cast<const __attribute__((address_space(4))) int*>(reinterpret_cast<uintptr_t>(kvi))[bz];
+      // padding, as on the object path above: this path, which no launch without a table takes, makes the set-up 128 bytes longer
+      // than before the field existed, so every form's loops keep their position within the 64-byte instruction-fetch line (five
+      // to seven s_nop: without them the forms' set-ups grew by 108, 104 and 100 bytes).  Re-derive after any edit
+      asm volatile("s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+      if constexpr (!SPLIT) asm volatile("s_nop 0");
+      if constexpr (!DMA) asm volatile("s_nop 0");
     }
   }
   const bf16_t* kp = P.k + (size_t)bkv * P.bsk + head * 64;
@@ -469,6 +484,9 @@ __global__ __launch_bounds__(64 * NW, SPLIT ? 3 : (VSUM ? 4 : ((NW == 4 && NSUB 
 #endif
   if constexpr (SPLIT) {
     if (nsplit > 1) {
+      // (four bytes that a branch island of the compiler's took up after the main loops before MvdAttnArgs::kv_index existed: the
+      //  merge loops below keep their position in the fetch line; once per workgroup.  DESIGN.md section 9 N16)
+      asm volatile("s_nop 0");
       // ---- partial result of this key range -> workspace (write-through): [pair][query block][split][QB queries] rows of 64 bf16
       // (normalised by THIS range's denominator) + (running max, denominator) per query; then one ticket per workgroup on the
       // (pair, query block) counter -- the workgroup that draws the last one merges:
@@ -634,7 +652,7 @@ int launch_nw(const MvdAttnArgs& a, int maxq, hipStream_t s) {
   g_last_attn[0] = NW; g_last_attn[1] = (int)grid.x;
 #ifdef MVD_PROBE
   static const int pipe_env = MVD_ENV_INT("MVD_ATTN_PIPE", 0);
-  if (a.prescaled && NW == 4 && NSUB == 2 && (pipe_env || g_attn_pipe_override) && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1) {   // (the probe kernels read neither kv_group nor kv_objects)
+  if (a.prescaled && NW == 4 && NSUB == 2 && (pipe_env || g_attn_pipe_override) && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1 && !a.kv_index[0] && !a.kv_index[1]) {   // (the probe kernels read none of kv_group, kv_objects, kv_index)
     hipLaunchKernelGGL((attn_pipe_kernel<4>), grid, dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { mvd_set_error("attention launch: %s", hipGetErrorString(e)); return -3; }
@@ -695,6 +713,9 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
     if (a.kv_objects[i] < 0 || (a.kv_objects[i] > 1 && a.batch % ((int64_t)(a.kv_group[i] > 1 ? a.kv_group[i] : 1) * a.kv_objects[i]))) {
       mvd_set_error("attention: K/V group %d x objects %d of problem %d does not divide the batch %d", a.kv_group[i], a.kv_objects[i], i, a.batch); return -1;
     }
+    if (a.kv_index[i] && (a.kv_group[i] > 1 || a.kv_objects[i] > 1)) {
+      mvd_set_error("attention: problem %d sets a K/V table together with K/V group %d / objects %d", i, a.kv_group[i], a.kv_objects[i]); return -1;
+    }
   }
   // 128-key tiles are an experiment switch only (env MVD_ATTN_KV128=1): at 197 VGPRs / 64 KB LDS they run two
   // waves per SIMD instead of three and measured 3-4 % SLOWER than 64-key tiles on every UNet shape
@@ -707,7 +728,7 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
   static const int use_pp = MVD_ENV_INT("MVD_ATTN_PP", 0);
   const_cast<MvdAttnArgs&>(a).dbg = MVD_ENV_INT("MVD_ATTN_DBG", 0);
   {
-    bool ok = use_pp && a.prescaled && maxq >= 256 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1;
+    bool ok = use_pp && a.prescaled && maxq >= 256 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1 && !a.kv_index[0] && !a.kv_index[1];
     for (int i = 0; i < a.nprob && ok; ++i) ok = (size_t)a.p[i].nk * (a.p[i].ldk > a.p[i].ldv ? a.p[i].ldk : a.p[i].ldv) * 2 < ((size_t)1 << 31);
     const long wgs = (long)((maxq + 255) / 256) * a.heads * a.batch * a.nprob;
     if (ok && wgs >= 1024) {
@@ -727,7 +748,7 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
     return launch_nw<4, 2>(a, maxq, s);
   }
 #ifdef MVD_PROBE
-  if (g_attn_q64_override && a.prescaled && maxq >= 256 && a.nsplit <= 1 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1) {     // experiment: 64 queries per wave (see attn_q64_kernel)
+  if (g_attn_q64_override && a.prescaled && maxq >= 256 && a.nsplit <= 1 && a.kv_group[0] <= 1 && a.kv_group[1] <= 1 && a.kv_objects[0] <= 1 && a.kv_objects[1] <= 1 && !a.kv_index[0] && !a.kv_index[1]) {     // experiment: 64 queries per wave (see attn_q64_kernel)
     for (int i = 0; i < a.nprob; ++i)
       if ((size_t)a.p[i].nk * (a.p[i].ldk > a.p[i].ldv ? a.p[i].ldk : a.p[i].ldv) * 2 >= ((size_t)1 << 31)) { mvd_set_error("attention: operand too large for buffer addressing"); return -1; }
     return g_attn_q64_override == 1 ? launch_q64<2>(a, maxq, s) : launch_q64<4>(a, maxq, s);
@@ -746,11 +767,20 @@ int mvd_launch_attention(const MvdAttnArgs& a, hipStream_t s) {
   }
 }
 
+// The kernel reads kv_index[i][b] unchecked: every path that fills a table passes it through here first, on the host, before
+// anything is uploaded or launched
+int mvd_attention_check_index(const int* idx, int n, int elements) {
+  if (!idx || n <= 0 || elements <= 0) { mvd_set_error("attention: K/V table: null table, %d entries or %d K/V elements", n, elements); return -1; }
+  for (int b = 0; b < n; ++b)
+    if (idx[b] < 0 || idx[b] >= elements) { mvd_set_error("attention: K/V table entry %d is %d, outside the %d K/V elements", b, idx[b], elements); return -1; }
+  return 0;
+}
+
 // Split-KV (batch 1): with about one wave per SIMD the kernel runs at a fraction of its rate (one wave's softmax and MFMA
 // phases do not overlap); cutting the keys over several workgroups restores some occupancy.  All problems of a launch get
 // the same split.
 int mvd_attention_pick_split(const MvdAttnArgs& a) {
-  if (!a.prescaled) return 1;
+  if (!a.prescaled || a.kv_index[0] || a.kv_index[1]) return 1;      // (a mapped launch is never split: DESIGN.md section 9 N16)
   int maxq = 0, mink = 1 << 30;
   for (int i = 0; i < a.nprob; ++i) { maxq = a.p[i].nq > maxq ? a.p[i].nq : maxq; mink = a.p[i].nk < mink ? a.p[i].nk : mink; }
   const long waves = (long)a.heads * a.batch * a.nprob * ((maxq + 127) / 128) * 4;

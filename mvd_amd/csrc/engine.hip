@@ -11,11 +11,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "host_util.h"
+#include "ragged.h"
 
 int mvd_launch_silu_to_bf16(const float* x, int64_t n, bf16_t* y, hipStream_t s);
 
@@ -44,6 +46,7 @@ struct mvd_engine {
   int rc_batch = 0, rc_h = 0, rc_w = 0; bool rc_valid = false; bool rc_keep = false;
   int rc_views = 0;                 // views of the MVD_SHARE_REF forward that filled the cache (0: an ordinary forward)
   int rc_objects = 0;               // objects of the mvd_unet_forward_objects call that filled it (0: one reference for the batch)
+  std::vector<int> rc_layout;       // view counts of the mvd_unet_forward_ragged call that filled it (empty: a uniform forward)
   // global Q2 statistics (mvd_engine_reference_encode / _finish): the encoder pass stops before the normalisation
   float* ref_stats_out = nullptr;   // set only while mvd_engine_reference_encode runs
   bool rc_pending = false;          // raw features are in feat_keep, waiting for the merged statistics
@@ -83,11 +86,13 @@ struct mvd_engine {
     int rc_batch, rc_h, rc_w; bool rc_valid, rc_keep;
     float* cam_emb; int cam_batch;
     int rc_views, rc_objects;
+    std::vector<int> rc_layout;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views, rc_objects}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views, rc_objects, rc_layout}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
     rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_views = h.rc_views; rc_objects = h.rc_objects;
+    rc_layout = h.rc_layout;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -98,8 +103,16 @@ struct mvd_engine {
     for (auto& ge : graphs) { (void)hipGraphExecDestroy(ge.x); (void)hipGraphDestroy(ge.g); }
     graphs.clear(); graph_seen.clear();
   }
+  // K/V tables of the ragged forwards (mvd_unet_forward_ragged): one device slot per layout (view counts, g), holding the adapter
+  // table and the text table, g * R entries each.  A slot is written ONCE, by a stream-ordered upload on the first forward of its
+  // layout (never inside a capture), and is not rewritten while a captured graph can point at it: the set is bounded, and making
+  // room for a new layout drops every captured graph first (they are re-captured on their next use).
+  struct KvSlot { std::vector<int> layout /* counts..., g */, host /* [adapter | text] */; int* dev = nullptr; uint64_t used = 0; };
+  static constexpr size_t KV_SLOTS = 8;
+  std::vector<KvSlot> kv_slots; uint64_t kv_tick = 0;
   ~mvd_engine() {
     drop_graphs();
+    for (auto& sl : kv_slots) if (sl.dev) (void)hipFree(sl.dev);
     for (hipEvent_t ev : ev_pool) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : feat_ev) if (ev) (void)hipEventDestroy(ev);
     if (fork_ev) (void)hipEventDestroy(fork_ev);
@@ -527,9 +540,17 @@ struct PassOpts {
                               // the text row of guidance half j (0: an ordinary pass)
   int objects = 0;            // mvd_unet_forward_objects (> 1): that many objects x `views` views -- main pass: row r = j * O * V + o * V + v
                               // attends object o's reference tokens; encoder pass: Q2 statistics per object (0: one object)
+  // mvd_unet_forward_ragged, main pass: device tables of B entries (kernels.h MvdAttnArgs::kv_index) -- row r reads reference K/V
+  // element kvi_ref[r] of the kv_elems = g * O elements [object][half] and text row kvi_text[r]; views / objects are 0 then
+  const int* kvi_ref = nullptr; const int* kvi_text = nullptr; int kv_elems = 0;
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
+
+// mvd_unet_forward_ragged: the layout that comes beside the unchanged mvd_forward_args_t -- O >= 2 objects with view counts that
+// differ (equal counts take the objects body), g rows per view, R = sum of the counts, and the two tables of g * R entries
+// (a device slot of the engine; in a sizing run host pointers, which nothing dereferences: a dry pass launches nothing)
+struct RaggedLayout { const int* counts; int objects, g, rows; const int* kvi_ref; const int* kvi_text; };
 
 // ---------------------------------------------------------------------- one UNet pass
 struct UNetPass {
@@ -591,7 +612,7 @@ struct UNetPass {
     const int kvg = o.views > 0 ? o.views : 0;
     // (objects: each object's hw tokens by the batch g = B / (views * objects) of one view's call; K/V elements [object][half])
     const int kvo = o.objects > 1 ? o.objects : 0;
-    const int Bq = kvg ? B_ / kvg : B_;
+    const int Bq = o.kvi_ref ? o.kv_elems : (kvg ? B_ / kvg : B_);      // (ragged: a table per problem instead of the arithmetic map)
     const int ref_nk = ad ? (int)((int64_t)o.ref_batch * hw / Bq) : 0;
     if (ad && (int64_t)ref_nk * Bq != (int64_t)o.ref_batch * hw) { mvd_set_error("adapter: ref tokens %d x %d not divisible by batch %d", o.ref_batch, hw, Bq); return -12; }
 
@@ -606,7 +627,7 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
-      a.kv_group[1] = kvg; a.kv_objects[1] = kvo;
+      a.kv_group[1] = kvg; a.kv_objects[1] = kvo; a.kv_index[1] = o.kvi_ref;
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn1.out.wx"));
@@ -624,6 +645,7 @@ struct UNetPass {
       if (ad) a.p[1] = {q2 + C, rkv + 2 * C, rkv + 3 * C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
       a.kv_group[0] = kvg; a.kv_group[1] = kvg;       // (the text K/V hold one row per guidance half as well -- per half and object,
       a.kv_objects[1] = kvo;                          //  in the batch's own order: no object map for problem 0)
+      a.kv_index[0] = o.kvi_text; a.kv_index[1] = o.kvi_ref;
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn2.out.w", (int64_t)C * ld_out), c.WF(key + ".attn2" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn2.out.wx"));
@@ -929,7 +951,7 @@ int setup_tile_counters(mvd_engine* e, unsigned int* block, hipStream_t s, bool 
   return 0;
 }
 
-int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects) {
+int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects, const RaggedLayout* rg) {
   const mvd_config_t& cfg = e->cfg;
   if (a.batch <= 0 || a.height <= 0 || a.width <= 0 || a.text_len <= 0) { mvd_set_error("forward: bad shape"); return -1; }
   const int div = 1 << (cfg.num_levels - 1);
@@ -951,7 +973,19 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   const int V = share ? a.views : 0;
   // ---- mvd_unet_forward_objects: O > 1 objects x `views` views (include/mvd_hip.h); the same rule: every check before any launch
   const int O = objects > 1 ? objects : 0;
-  if (O) {
+  // ---- mvd_unet_forward_ragged: O objects with V_o views each (the entry has checked the counts and that args->views is 0)
+  if (rg) {
+    const int R = rg->rows, g = rg->g;
+    if (ref_only) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
+    if (!share || !use_img) { mvd_set_error("forward_ragged: view counts need MVD_SHARE_REF with MVD_USE_IMAGE"); return -1; }
+    if (a.batch != g * R || g < 1 || g > 2) { mvd_set_error("forward_ragged: batch %d is not 1 or 2 (classifier-free guidance) rows for each of the %d views", a.batch, R); return -1; }
+    if (a.ref_batch != O) { mvd_set_error("forward_ragged: needs ref_batch == objects = %d (one reference row per object), got %d", O, a.ref_batch); return -1; }
+    if (use_cam && a.cam_batch != 1 && a.cam_batch != R) { mvd_set_error("forward_ragged: the cameras must hold 1 or sum of the view counts = %d rows, got %d", R, a.cam_batch); return -1; }
+    for (int lv = 0; lv < cfg.num_levels; ++lv) {
+      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
+      if (hw % g) { mvd_set_error("forward_ragged: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
+    }
+  } else if (O) {
     if (!share || !use_img) { mvd_set_error("forward_objects: objects = %d needs MVD_SHARE_REF with MVD_USE_IMAGE", O); return -1; }
     if (V < 1 || a.batch % (O * V)) { mvd_set_error("forward_objects: batch %d is not a multiple of objects %d x views %d", a.batch, O, V); return -1; }
     const int g = a.batch / (O * V);
@@ -989,7 +1023,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   if (use_img) {
     const bool keep = (a.flags & MVD_KEEP_FEATURES) || ref_only;
     if (reuse) {
-      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V || e->rc_objects != O) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
+      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V || e->rc_objects != O ||
+          e->rc_layout != (rg ? std::vector<int>(rg->counts, rg->counts + rg->objects) : std::vector<int>())) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
     } else {
       e->persist.reset(dry);
       e->refkv.assign(e->feats.size(), nullptr);
@@ -1002,6 +1037,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
       }
       if (e->persist.overflow()) { mvd_set_error("forward: reference cache too small (%zu > %zu bytes)", e->persist.high, e->persist.cap); return -4; }
       e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_views = V; e->rc_objects = O;
+      e->rc_layout = rg ? std::vector<int>(rg->counts, rg->counts + rg->objects) : std::vector<int>();
       if (!dry) { e->rc_valid = false; e->rc_pending = false; }
     }
   }
@@ -1101,7 +1137,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   c.set = 0;
   const float* tproj = tproj_main;
   if (!tproj) CHECK(time_path(c, a.timesteps, B, &tproj));
-  const int TB = share ? B / V : B;          // text rows: one per guidance half in a shared forward
+  const int TB = rg ? rg->g * O : (share ? B / V : B);          // text rows: one per guidance half (and object) in a shared forward
   bf16_t* tx = c.aalloc<bf16_t>((size_t)TB * L * xd);
   Act xin = c.new_act(B, H, Wd, 64, true);   // im2col rows for conv_in
   if (!dry && !c.err) {
@@ -1116,6 +1152,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   po.views = V; po.objects = O;
+  if (rg) { po.views = 0; po.objects = 0; po.kvi_ref = rg->kvi_ref; po.kvi_text = rg->kvi_text; po.kv_elems = rg->g * O; }
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
@@ -1131,8 +1168,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
 // Every exit of a forward that forked the side stream joins it: an error return between fork and join (a failed check in the
 // camera path or a pass, a workspace that is too small) must not leave the encoder pass writing the reference cache and the
 // activation arena while the caller frees or reuses them.  The success path has joined with an event already.
-int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects = 0) {
-  const int r = forward_body(e, a, s, dry, objects);
+int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects = 0, const RaggedLayout* rg = nullptr) {
+  const int r = forward_body(e, a, s, dry, objects, rg);
   if (e->dual_now) {
     if (e->side) (void)hipStreamSynchronize(e->side);      // error path only: the cheap join is not worth an event here
     e->dual_now = false;
@@ -1232,14 +1269,14 @@ int64_t mvd_engine_workspace_bytes(mvd_engine_t* e, int batch, int height, int w
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
 }
 
-static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args, int objects) {
+static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, const RaggedLayout* rg = nullptr) {
   if (!e || !args) { mvd_set_error("workspace_bytes_args: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("workspace_bytes_args: unknown flag bits 0x%x", args->flags); return -1; }
   const mvd_engine::HostState before = e->host_state();
   // (a sizing call must not depend on the cache state: size the forward that runs the encoder pass, the larger of the two)
   mvd_forward_args_t a = *args;
   a.flags &= ~MVD_REUSE_REF;
-  int r = forward_impl(e, a, nullptr, true, objects);
+  int r = forward_impl(e, a, nullptr, true, objects, rg);
   e->set_host_state(before);
   if (r) return r;
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
@@ -1313,24 +1350,32 @@ int mvd_engine_reference_finish(mvd_engine_t* e, const float* mean_k, void* stre
   return 0;
 }
 
-// mvd_unet_forward (objects = 0) and mvd_unet_forward_objects (objects > 1)
-static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
-  if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
-  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
-  // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
-  const mvd_engine::HostState before = e->host_state();
-  int r = forward_impl(e, *args, nullptr, true, objects);
-  e->set_host_state(before);
-  if (r) return r;
+// after a dry run: do the two arenas it sized fit the bound workspace?
+static int workspace_fits(mvd_engine_t* e, size_t* act_bytes_out) {
   const size_t act_bytes = (e->act.high + 255) & ~size_t(255);
   if (!e->ws_ptr || act_bytes + e->tmp.high > (size_t)e->ws_bytes) {
     mvd_set_error("forward: workspace too small: need %zu bytes, bound %lld", act_bytes + e->tmp.high, (long long)e->ws_bytes);
     return -4;
   }
+  *act_bytes_out = act_bytes;
+  return 0;
+}
+
+// mvd_unet_forward (objects = 0), mvd_unet_forward_objects (objects > 1) and mvd_unet_forward_ragged (rg: its slot is uploaded)
+static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream, const RaggedLayout* rg = nullptr) {
+  if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
+  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
+  // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
+  const mvd_engine::HostState before = e->host_state();
+  int r = forward_impl(e, *args, nullptr, true, objects, rg);
+  e->set_host_state(before);
+  if (r) return r;
+  size_t act_bytes = 0;
+  if ((r = workspace_fits(e, &act_bytes))) return r;
   e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
   e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
   hipStream_t st = (hipStream_t)stream;
-  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, objects);
+  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, objects, rg);
   // ---- hipGraph replay.  A forward is a pure function of the argument block (pointers, shapes, flags), the bound buffers
   // and the reference-cache state it starts from; the host-side state it leaves behind is the same every time.  The first
   // call with a given key runs as usual (kernels' first-use set-up must not happen inside a capture), the second is
@@ -1340,6 +1385,11 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int obj
   key.append((const char*)st8, sizeof(st8));
   const int ob2[2] = {objects, e->rc_objects};
   key.append((const char*)ob2, sizeof(ob2));
+  // (the ragged layout of this call -- counts, g, the slot its tables live in -- and the one the cached reference was encoded under)
+  if (rg) { key.append((const char*)rg->counts, rg->objects * sizeof(int)); key.append((const char*)&rg->g, sizeof(int)); key.append((const char*)&rg->kvi_ref, sizeof(void*)); }
+  key.push_back('|');
+  key.append((const char*)e->rc_layout.data(), e->rc_layout.size() * sizeof(int));
+  key.push_back('|');
   key.append((const char*)&e->ws_ptr, sizeof(void*));
   key.append((const char*)&e->rc_ptr, sizeof(void*));
   for (auto& ge : e->graphs)
@@ -1351,11 +1401,11 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int obj
     }
   bool seen = false;
   for (auto& k : e->graph_seen) seen |= k == key;
-  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false, objects); }
+  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false, objects, rg); }
   if (e->graphs.size() >= 8) e->drop_graphs();
   hipError_t he = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
   if (he != hipSuccess) { mvd_set_error("forward: hipStreamBeginCapture: %s", hipGetErrorString(he)); return -7; }
-  r = forward_impl(e, *args, st, false, objects);
+  r = forward_impl(e, *args, st, false, objects, rg);
   hipGraph_t g = nullptr;
   he = hipStreamEndCapture(st, &g);
   if (r) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -1372,6 +1422,95 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int obj
 int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) { return unet_forward(e, args, 0, stream); }
 int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
   return unet_forward(e, args, objects > 1 ? objects : 0, stream);
+}
+
+// ---- ragged view counts (include/mvd_hip.h).  The tables are built from the counts, so they are valid by construction; they pass
+// the same host check as a caller's table all the same (mvd_attention_check_index) before a slot is uploaded.
+static int ragged_prepare(const mvd_forward_args_t* args, const int* view_counts, int objects, int* rows, int* g) {
+  if (!args || !view_counts || objects < 1) { mvd_set_error("forward_ragged: null argument or %d objects", objects); return -1; }
+  if (args->views != 0) { mvd_set_error("forward_ragged: args->views must be 0 (the view counts come beside the arguments), got %d", args->views); return -1; }
+  const int R = mvd_ragged_rows(view_counts, objects);
+  if (R < 0) { mvd_set_error("forward_ragged: every object needs at least one view (the counts must be >= 1 and their sum must fit an int)"); return -1; }
+  if (args->batch <= 0 || args->batch % R || args->batch / R > 2) {
+    mvd_set_error("forward_ragged: batch %d is not 1 or 2 (classifier-free guidance) rows for each of the %d views", args->batch, R); return -1;
+  }
+  *rows = R; *g = args->batch / R;
+  return 0;
+}
+static bool ragged_uniform(const int* view_counts, int objects) {
+  for (int o = 1; o < objects; ++o) if (view_counts[o] != view_counts[0]) return false;
+  return true;
+}
+
+int64_t mvd_engine_workspace_bytes_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects) {
+  if (!e) { mvd_set_error("workspace_bytes_ragged: null engine"); return -1; }
+  int R = 0, g = 0;
+  if (ragged_prepare(args, view_counts, objects, &R, &g)) return -1;
+  if (ragged_uniform(view_counts, objects)) {       // equal counts ARE the objects forward (one object: the views forward)
+    mvd_forward_args_t a = *args; a.views = view_counts[0];
+    return workspace_bytes_args(e, &a, objects > 1 ? objects : 0);
+  }
+  std::vector<int> tab((size_t)2 * g * R);
+  mvd_ragged_build_tables(view_counts, objects, g, tab.data(), tab.data() + (size_t)g * R);
+  const RaggedLayout rg{view_counts, objects, g, R, tab.data(), tab.data() + (size_t)g * R};       // (host pointers: a sizing run launches nothing)
+  return workspace_bytes_args(e, args, objects, &rg);
+}
+
+int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects, void* stream) {
+  if (!e) { mvd_set_error("forward_ragged: null engine"); return -1; }
+  int R = 0, g = 0;
+  if (ragged_prepare(args, view_counts, objects, &R, &g)) return -1;
+  if (ragged_uniform(view_counts, objects)) {
+    mvd_forward_args_t a = *args; a.views = view_counts[0];
+    return unet_forward(e, &a, objects > 1 ? objects : 0, stream);
+  }
+  // everything the forward itself checks, the workspace included, before a slot is touched (a dry pass with host tables)
+  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
+  {
+    std::vector<int> tab((size_t)2 * g * R);
+    mvd_ragged_build_tables(view_counts, objects, g, tab.data(), tab.data() + (size_t)g * R);
+    const RaggedLayout dry_rg{view_counts, objects, g, R, tab.data(), tab.data() + (size_t)g * R};
+    const mvd_engine::HostState before = e->host_state();
+    int r = forward_impl(e, *args, nullptr, true, objects, &dry_rg);
+    e->set_host_state(before);
+    size_t act_bytes = 0;
+    if (r || (r = workspace_fits(e, &act_bytes))) return r;
+  }
+  // ---- the layout's slot
+  std::vector<int> layout(view_counts, view_counts + objects); layout.push_back(g);
+  mvd_engine::KvSlot* slot = nullptr;
+  for (auto& sl : e->kv_slots) if (sl.layout == layout) slot = &sl;
+  if (!slot) {
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+      mvd_set_error("forward_ragged: the first forward of a layout uploads its K/V tables and cannot run inside a stream capture"); return -7;
+    }
+    if (e->kv_slots.size() >= mvd_engine::KV_SLOTS) {
+      // no room: the least recently used slot goes -- after every captured graph (one of them may point at it) and after the
+      // device has finished whatever still reads it (hipFree synchronises)
+      e->drop_graphs();
+      size_t lru = 0;
+      for (size_t i = 1; i < e->kv_slots.size(); ++i) if (e->kv_slots[i].used < e->kv_slots[lru].used) lru = i;
+      if (e->kv_slots[lru].dev) (void)hipFree(e->kv_slots[lru].dev);
+      e->kv_slots.erase(e->kv_slots.begin() + lru);
+    }
+    mvd_engine::KvSlot sl;
+    sl.layout = layout;
+    sl.host.resize((size_t)2 * g * R);
+    mvd_ragged_build_tables(view_counts, objects, g, sl.host.data(), sl.host.data() + (size_t)g * R);
+    if (mvd_attention_check_index(sl.host.data(), g * R, g * objects) || mvd_attention_check_index(sl.host.data() + (size_t)g * R, g * R, g * objects)) return -1;
+    if (hipMalloc((void**)&sl.dev, sl.host.size() * sizeof(int)) != hipSuccess) { mvd_set_error("forward_ragged: hipMalloc of the K/V tables failed"); return -3; }
+    e->kv_slots.push_back(std::move(sl));
+    slot = &e->kv_slots.back();
+    if (hipMemcpyAsync(slot->dev, slot->host.data(), slot->host.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) {
+      (void)hipFree(slot->dev); e->kv_slots.pop_back();
+      mvd_set_error("forward_ragged: upload of the K/V tables failed"); return -3;
+    }
+  }
+  slot->used = ++e->kv_tick;
+  const RaggedLayout rg{view_counts, objects, g, R, slot->dev, slot->dev + (size_t)g * R};
+  return unet_forward(e, args, objects, stream, &rg);
 }
 
 int mvd_engine_set_graph(mvd_engine_t* e, int enable) {
@@ -1596,6 +1735,56 @@ int64_t mvd_op_attention_split_ws_bytes(int batch, int heads, int nq, int nsplit
   a.nprob = 1; a.batch = batch; a.heads = heads; a.p[0].nq = nq;
   return (int64_t)mvd_attention_split_ws_bytes(a, nsplit) + (int64_t)mvd_attention_split_counters(a) * 4 + 256;
 }
+// One library-owned device buffer for the operator entry's table (grow-only; growing frees the old one, which synchronises).  The
+// upload is stream-ordered in front of the launch; calls on one stream are ordered among themselves
+static int* g_op_kvi = nullptr; static size_t g_op_kvi_cap = 0; static std::mutex g_op_kvi_mu;
+static int attention_mapped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq, int ldk,
+                            int ldv, int ldo, float scale, int kv_group, int kv_objects, const int* kv_index_host, int kv_elements,
+                            void* stream) {
+  if (batch <= 0) { mvd_set_error("attention: bad problem count/batch/heads"); return -1; }
+  // before anything is uploaded or launched: the entries, and a table together with a group (mvd_launch_attention's own rule)
+  if (mvd_attention_check_index(kv_index_host, batch, kv_elements)) return -1;
+  if (kv_group > 1 || kv_objects > 1) { mvd_set_error("attention: problem 0 sets a K/V table together with K/V group %d / objects %d", kv_group, kv_objects); return -1; }
+  MvdAttnArgs a; memset(&a, 0, sizeof(a));
+  a.nprob = 1; a.batch = batch; a.heads = heads; a.scale = scale;
+  a.prescaled = scale == 0.f;
+  a.p[0] = {(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
+            (int64_t)nq * ldq, (int64_t)nk * ldk, (int64_t)nk * ldv, (int64_t)nq * ldo, nq, nk};
+  std::lock_guard<std::mutex> lk(g_op_kvi_mu);
+  if ((size_t)batch > g_op_kvi_cap) {
+    if (g_op_kvi) (void)hipFree(g_op_kvi);
+    g_op_kvi = nullptr; g_op_kvi_cap = 0;
+    const size_t cap = (size_t)batch < 256 ? 256 : (size_t)batch;
+    if (hipMalloc((void**)&g_op_kvi, cap * sizeof(int)) != hipSuccess) { mvd_set_error("attention: hipMalloc of the K/V table failed"); return -3; }
+    g_op_kvi_cap = cap;
+  }
+  // (pageable source: the call returns once the table has been read)
+  if (hipMemcpyAsync(g_op_kvi, kv_index_host, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("attention: upload of the K/V table failed"); return -3; }
+  a.kv_index[0] = g_op_kvi; a.kv_group[0] = kv_group; a.kv_objects[0] = kv_objects;
+  return mvd_launch_attention(a, (hipStream_t)stream);
+}
+int mvd_op_attention_mapped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
+                            int ldk, int ldv, int ldo, float scale, const int* kv_index_host, int kv_elements, void* stream) {
+  return attention_mapped(q, k, v, o, batch, heads, nq, nk, ldq, ldk, ldv, ldo, scale, 0, 0, kv_index_host, kv_elements, stream);
+}
+// test hook: the same entry with a group beside the table -- a combination the host rejects
+extern "C" int mvd_debug_attention_mapped_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk,
+                                                  int ldq, int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects,
+                                                  const int* kv_index_host, int kv_elements, void* stream) {
+  return attention_mapped(q, k, v, o, batch, heads, nq, nk, ldq, ldk, ldv, ldo, scale, kv_group, kv_objects, kv_index_host, kv_elements, stream);
+}
+
+// measurement / test hook: the two tables the engine builds for a ragged layout (host arrays of g * sum(counts) entries);
+// returns the number of entries, or -1
+extern "C" int mvd_debug_ragged_tables(const int* view_counts, int objects, int g, int* adapter, int* text) {
+  if (!view_counts || !adapter || !text || objects < 1 || g < 1 || g > 2) { mvd_set_error("ragged_tables: bad argument"); return -1; }
+  const int R = mvd_ragged_rows(view_counts, objects);
+  if (R < 0) { mvd_set_error("ragged_tables: every object needs at least one view"); return -1; }
+  mvd_ragged_build_tables(view_counts, objects, g, adapter, text);
+  if (mvd_attention_check_index(adapter, g * R, g * objects) || mvd_attention_check_index(text, g * R, g * objects)) return -1;
+  return g * R;
+}
+
 int mvd_op_attention_split(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq,
                            int ldk, int ldv, int ldo, int nsplit, void* ws, void* stream) {
   MvdAttnArgs a; memset(&a, 0, sizeof(a));

@@ -168,7 +168,14 @@ struct MvdAttnArgs {
   // and k / v hold kv_objects[i] * g elements [object o][half j], g = batch / (kv_group[i] * kv_objects[i]).  With
   // q = b / kv_group[i] (= j * O + o), batch element b reads K/V element (q % O) * g + q / O.  0 or 1: off (element q)
   int kv_objects[2];
+  // K/V map by table (per problem): a DEVICE array of `batch` int32 entries, batch element b reads K/V
+  // element kv_index[i][b] (ragged view counts per object, where no arithmetic gives the element).  nullptr: off.  Not together
+  // with kv_group / kv_objects > 1 on the same problem (the host rejects it).  The kernel does not check the entries: whoever fills
+  // the table validates 0 <= entry < K/V elements on the host first (mvd_attention_check_index)
+  const int* kv_index[2];
 };
+// host check of a K/V table before it is uploaded: n entries, each in [0, elements); 0, or -1 with mvd_set_error
+int mvd_attention_check_index(const int* idx, int n, int elements);
 // split the engine's heuristic gives this launch (1 = none) and what it then needs
 int mvd_attention_pick_split(const MvdAttnArgs& a);
 size_t mvd_attention_split_ws_bytes(const MvdAttnArgs& a, int nsplit);

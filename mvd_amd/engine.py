@@ -4,6 +4,7 @@ libmvd_hip.so.  There is no CPU path: constructing an engine without a GPU raise
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 from typing import Dict, List, Optional
 
@@ -111,11 +112,18 @@ class MVDEngine:
         return sum(t.numel() * t.element_size() for d in self._weights for t in d.values())
 
     # ------------------------------------------------------------------ workspace
-    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0, objects=0):
-        key = (batch, h, w, text_len, ref_batch, keep_features, views) + ((objects,) if objects else ())
+    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0, objects=0, counts=()):
+        key = (batch, h, w, text_len, ref_batch, keep_features, views) + ((objects,) if objects else ()) + ((counts,) if counts else ())
         if self._ws_key == key:
             return
-        if views:
+        if counts:
+            # ragged view counts (mvd_unet_forward_ragged): the counts come beside the argument block, whose `views` stays 0
+            a = L.mvd_forward_args_t()
+            a.batch, a.height, a.width, a.text_len, a.ref_batch = batch, h, w, text_len, ref_batch
+            a.cam_rows, a.cam_batch = 4, sum(counts)
+            a.flags = L.MVD_USE_CAMERA | L.MVD_USE_IMAGE | L.MVD_SHARE_REF
+            ws = L.lib().mvd_engine_workspace_bytes_ragged(self._h, C.byref(a), (C.c_int * len(counts))(*counts), len(counts))
+        elif views:
             # a shared-reference forward (MVD_SHARE_REF) is sized from its argument block: the positional entry describes
             # an ordinary forward, whose Q4 re-chunking fails when the views do not divide the reference tokens
             a = L.mvd_forward_args_t()
@@ -158,34 +166,50 @@ class MVDEngine:
         ``text`` g rows, ``source_latents`` / ``encoder_text`` one row, the cameras 1 or ``views`` rows.  ``objects`` (O > 1, with
         ``views``; ``mvd_unet_forward_objects``): O objects x ``views`` views -- ``sample`` holds g * O * views rows, object-major
         inside a guidance half, ``text`` g * O rows, ``source_latents`` / ``encoder_text`` O rows, the cameras 1 or O * views rows;
-        ``None`` / 1: the forward without it."""
+        ``None`` / 1: the forward without it.  ``views`` a SEQUENCE ``(V_0, .., V_{O-1})`` (``mvd_unet_forward_ragged``): O objects
+        with V_o >= 1 views each, R = sum of the counts -- ``sample`` holds g * R rows, object-major inside a guidance half, the
+        cameras 1 or R rows, everything else as with ``objects = O`` (which ``objects`` must be, or ``None``)."""
         B, Cin, H, W = sample.shape
         Lt = text.shape[1]
         for t in (sample, timesteps, text, source_camera, target_camera, fourier_proj, source_latents, encoder_text):
             if t is not None:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise L.MvdError("engine.forward expects contiguous fp32 CUDA tensors")
+        counts = ()
+        if views is not None and not isinstance(views, numbers.Integral):
+            counts = tuple(int(v) for v in views)
+            if not counts or min(counts) < 1:
+                raise L.MvdError(f"engine.forward: views = {counts}: every object needs at least one view")
+            if objects is not None and int(objects) != len(counts):
+                raise L.MvdError(f"engine.forward: objects = {objects} with {len(counts)} view counts {counts}")
+            R = sum(counts)
+            if B % R or B // R > 2:
+                raise L.MvdError(f"engine.forward: batch {B} is not 1 or 2 rows for each of the {R} views of {counts}")
+            views, objects = 0, None
         views = int(views) if views else 0
         objects = int(objects) if objects and int(objects) > 1 else 0
         if objects and not views:
             raise L.MvdError(f"engine.forward: objects = {objects} needs views")
         if views and B % views:
             raise L.MvdError(f"engine.forward: batch {B} is not a multiple of views {views}")
-        if text.shape[0] != (B // views if views else B) or timesteps.shape != (B,):
+        text_rows = B // sum(counts) * len(counts) if counts else (B // views if views else B)
+        if text.shape[0] != text_rows or timesteps.shape != (B,):
             raise L.MvdError(f"engine.forward: text batch {text.shape[0]} / timesteps {tuple(timesteps.shape)} vs batch {B}"
-                             + (f" in {views} views" if views else ""))
+                             + (f" in {views} views" if views else "") + (f" in views {counts}" if counts else ""))
         use_cam = target_camera is not None
         use_img = source_latents is not None or reuse_ref
         ref_batch = 0
         if use_img:
             ref_batch = source_latents.shape[0] if source_latents is not None else self._last_ref_batch
             self._last_ref_batch = ref_batch
-        if views and not use_img:
+        if (views or counts) and not use_img:
             raise L.MvdError("engine.forward: views needs image conditioning (source_latents or reuse_ref)")
+        if counts and ref_batch != len(counts):
+            raise L.MvdError(f"engine.forward: views {counts} need {len(counts)} reference rows (one per object), got {ref_batch}")
         if objects and (ref_batch != objects or B % (objects * views)):
             raise L.MvdError(f"engine.forward: {objects} objects x {views} views need a multiple of {objects * views} sample rows and "
                              f"{objects} reference rows, got {B} and {ref_batch}")
-        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views, objects)
+        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views, objects, counts)
         graph = getattr(self, "_graph", False)
         user_out = out
         if graph:
@@ -229,10 +253,14 @@ class MVDEngine:
         if views:
             flags |= L.MVD_SHARE_REF
             a.views = views
+        if counts:
+            flags |= L.MVD_SHARE_REF        # (a.views stays 0: the counts travel beside the argument block)
         a.ref_batch, a.flags = ref_batch, flags
         a.out = out.data_ptr()
         # (objects: the count travels beside the argument block, which is as it was)
         entry = ("mvd_unet_forward_objects", self._h, C.byref(a), objects) if objects else ("mvd_unet_forward", self._h, C.byref(a))
+        if counts:
+            entry = ("mvd_unet_forward_ragged", self._h, C.byref(a), (C.c_int * len(counts))(*counts), len(counts))
         if graph:
             cur = torch.cuda.current_stream(self.device)
             self._gstream.wait_stream(cur)
@@ -243,7 +271,7 @@ class MVDEngine:
         else:
             L.call(*entry, L.stream())
         if use_img and not reuse_ref:
-            self._ref_valid = (B, H, W, Lt, ref_batch) + ((views,) if views else ()) + ((objects,) if objects else ())
+            self._ref_valid = self._ref_key(B, H, W, Lt, ref_batch, counts or views, objects)
         return out
 
     # ------------------------------------------------------------------ reference pass in two halves (global Q2 statistics)
@@ -309,11 +337,17 @@ class MVDEngine:
             buf.copy_(t)
         return buf
 
+    @staticmethod
+    def _ref_key(batch, h, w, text_len, ref_batch, views=0, objects=0):
+        if views is not None and not isinstance(views, numbers.Integral):      # ragged view counts: the layout is part of the key
+            return (batch, h, w, text_len, ref_batch, tuple(int(v) for v in views))
+        objects = int(objects) if objects and int(objects) > 1 else 0
+        return (batch, h, w, text_len, ref_batch) + ((views,) if views else ()) + ((objects,) if objects else ())
+
     def reference_cache_valid(self, batch, h, w, text_len, ref_batch, views=0, objects=0) -> bool:
         """True when the engine still holds reference K/V computed for exactly this shape (Q5 reuse is then legal); ``views``:
-        by a shared-reference forward of that many views (of each of ``objects`` objects)."""
-        return getattr(self, "_ref_valid", None) == ((batch, h, w, text_len, ref_batch) + ((views,) if views else ())
-                                                      + ((objects,) if objects else ()))
+        by a shared-reference forward of that many views (of each of ``objects`` objects), or of exactly these view counts."""
+        return getattr(self, "_ref_valid", None) == self._ref_key(batch, h, w, text_len, ref_batch, views, objects)
 
     # ------------------------------------------------------------------ measurement
     PROFILE_CLASSES = {0: "gemm_256x160", 1: "gemm_256x128", 2: "gemm_128x160", 3: "gemm_128x128", 4: "gemm_128x64",

@@ -9,6 +9,7 @@ as hand-written gfx950 kernels.  None of the reference's ~600 per-forward host s
 """
 from __future__ import annotations
 
+import numbers
 import logging
 import os
 from typing import Any, Dict, NamedTuple, Optional
@@ -298,7 +299,20 @@ class MultiViewUNet(nn.Module):
         independent batch-g calls.  ``sample`` holds g * O * V rows ``[uncond x O V | cond x O V]``, object-major inside a half
         (row j * O * V + o * V + v), ``encoder_hidden_states`` g * O rows ``[negative x O | positive x O]``,
         ``source_image_latents`` O rows, the cameras 1 or O * V rows (row o * V + v).  The encoder pass runs once at batch O
-        with the Q2 statistics per object.  ``None`` / 1: the forward without it."""
+        with the Q2 statistics per object.  ``None`` / 1: the forward without it.
+
+        ``views`` a SEQUENCE ``(V_0, .., V_{O-1})``: O objects with V_o >= 1 views each, R = sum V_o, in one
+        forward, which IS the R independent batch-g calls.  ``sample`` holds g * R rows ``[uncond x R | cond x R]``, object-major
+        inside a half, the cameras 1 or R rows; ``encoder_hidden_states`` g * O rows and ``source_image_latents`` O rows as with
+        ``objects = O``, which ``objects`` must be, or ``None``."""
+        counts = ()
+        if views is not None and not isinstance(views, numbers.Integral):
+            counts = tuple(int(v) for v in views)
+            if not counts or min(counts) < 1:
+                raise L.MvdError(f"views={counts}: every object needs at least one view")
+            if objects is not None and int(objects) != len(counts):
+                raise L.MvdError(f"views={counts}: objects must be None or {len(counts)}, got {objects}")
+            views, objects = None, None
         if cross_attention_kwargs:
             cross_attention_kwargs.pop("debug_log_file_path", None)   # accepted, never evaluated (no host syncs)
         eng = self._sync_engine()
@@ -309,7 +323,17 @@ class MultiViewUNet(nn.Module):
         text = self._f32(encoder_hidden_states, dev)
         V = int(views) if views is not None and int(views) > 1 else 0
         O = int(objects) if objects is not None and int(objects) > 1 else 0
-        if O:
+        if counts:
+            R, Oc = sum(counts), len(counts)
+            if self.reference_stats_group is not None:
+                raise L.MvdError("views: the ragged forward does not go with reference_stats_group (its Q2 statistics are per "
+                                 "object; statistics over the ranks' batches couple the objects)")
+            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != Oc:
+                raise L.MvdError(f"views={counts}: needs image conditioning with {Oc} rows of source_image_latents (one per object)")
+            if B % R or B // R > 2 or text.shape[0] != B // R * Oc:
+                raise L.MvdError(f"views={counts}: sample must hold g * {R} rows and encoder_hidden_states g * {Oc} rows (g = 1, or 2 "
+                                 f"under guidance); got {B} and {text.shape[0]}")
+        elif O:
             V = max(V, 1)
             if self.reference_stats_group is not None:
                 raise L.MvdError("objects: the object forward does not go with reference_stats_group (its Q2 statistics are per "
@@ -345,8 +369,8 @@ class MultiViewUNet(nn.Module):
         if self.use_image_conditioning and source_image_latents is not None:
             bs = source_image_latents.shape[0]
             enc_text = text
-            if V:                                                      # the batch-g call's choice below: its last row
-                enc_text = text[-max(O, 1):]                           # (per object: row (g - 1) * O + o)
+            if V or counts:                                            # the batch-g call's choice below: its last row
+                enc_text = text[-max(O, len(counts), 1):]              # (per object: row (g - 1) * O + o)
             elif text.shape[0] == 2 * bs:                              # :280-283
                 enc_text = text[bs:]
             elif text.shape[0] > bs:                                   # :284-285
@@ -355,10 +379,10 @@ class MultiViewUNet(nn.Module):
             # is live, so the caching allocator cannot hand their addresses to different data of the same shape (a second
             # object denoised right after the first would otherwise hit the first object's K/V).
             key = (source_image_latents.data_ptr(), source_image_latents._version, tuple(source_image_latents.shape),
-                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V, O)
+                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V, O) + ((counts,) if counts else ())
             glob = self.reference_stats_group is not None
             hit = (self.cache_reference and self._ref_key == key
-                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, V, O))
+                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, counts or V, O))
             if glob and self.cache_reference:
                 # the recompute path below contains a collective: the decision must be the same on every rank of the group
                 # (a re-bound workspace or a fresh tensor on ONE rank would otherwise leave the others out of the all-gather)
@@ -377,7 +401,7 @@ class MultiViewUNet(nn.Module):
                     local = eng.reference_encode(img["source_latents"], img["encoder_text"], B)
                     eng.reference_finish(merge_reference_stats(local, group))
                     img = dict(reuse_ref=True, keep_features=True)
-        out = eng.forward(x, t, text, **cam, **img, **({"views": V} if V else {}), **({"objects": O} if O else {}))
+        out = eng.forward(x, t, text, **cam, **img, **({"views": counts or V} if V or counts else {}), **({"objects": O} if O else {}))
         if cam:
             self.current_camera_embedding = eng.camera_embedding(cam["target_camera"].shape[0])
         hidden_states = out.to(out_dtype)

@@ -416,6 +416,25 @@ def attention_objects(q, k, v, heads, kv_group, kv_objects, scale=0.125):
     return out
 
 
+def attention_mapped(q, k, v, heads, kv_index, scale=0.125):
+    """``attention`` with a K/V table: q (B, Nq, heads*64); k / v (kv_elements, Nk, heads*64); batch element b attends K/V element
+    ``kv_index[b]`` (a sequence or CPU int tensor of B entries -- ragged view counts per object, any many-to-one map).  The
+    library checks every entry on the host (``0 <= kv_index[b] < kv_elements``) before it uploads the table or launches."""
+    _bf16(q, k, v)
+    B, nq, _ = q.shape
+    nk = k.shape[1]
+    idx = [int(i) for i in (kv_index.tolist() if isinstance(kv_index, torch.Tensor) else kv_index)]
+    if isinstance(kv_index, torch.Tensor):
+        assert not kv_index.is_cuda and not kv_index.is_floating_point(), "kv_index: a CPU int tensor"
+    assert len(idx) == B and k.shape[0] == v.shape[0], (B, len(idx), k.shape, v.shape)
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    assert q.stride(0) == nq * q.stride(1) and k.stride(0) == nk * k.stride(1) and v.stride(0) == nk * v.stride(1)
+    out = torch.empty(B, nq, heads * 64, device=q.device, dtype=torch.bfloat16)
+    L.call("mvd_op_attention_mapped", C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), _p(out),
+           B, heads, nq, nk, q.stride(1), k.stride(1), v.stride(1), heads * 64, float(scale), (C.c_int * B)(*idx), int(k.shape[0]), _s())
+    return out
+
+
 def attention_causal(q, k, v, heads, scale=0.125):
     """The CLIP text encoder's attention: q, k, v (B, n, heads*64) bf16 with n <= 96, key j visible to query i iff j <= i; row
     strides may exceed heads*64 (views of one fused QKV buffer).  scale=0: q already carries 64^-0.5 * log2(e)."""

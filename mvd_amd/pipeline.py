@@ -50,15 +50,29 @@ class MVDDenoiser:
         """``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
         source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``).  ``objects``
         (MVDPipeline.generate_views_batch): O prompts and O source rows, ``latents`` and the cameras O * views rows, object-major;
-        every step is one object forward (``MultiViewUNet.forward(..., views=, objects=)``)."""
+        every step is one object forward (``MultiViewUNet.forward(..., views=, objects=)``).  ``views`` a sequence
+        ``(V_0, .., V_{O-1})``: ragged view counts -- O prompts and O source rows, ``latents`` and the cameras sum(V_o) rows,
+        object-major; every step is one ragged forward (``MultiViewUNet.forward(..., views=(V_0, ..))``)."""
         dev = self.unet._exec_device()
         B = prompt_embeds.shape[0]
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
         embeds = torch.cat([negative_prompt_embeds.to(prompt_embeds.device), prompt_embeds]) if cfg else prompt_embeds
         embeds = embeds.to(dev, torch.float32)
+        counts = ()
+        if views is not None and not isinstance(views, int):
+            counts = tuple(int(v) for v in views)
+            if objects is not None and int(objects) != len(counts):
+                raise L.MvdError(f"views={counts}: objects must be None or {len(counts)}, got {objects}")
+            views, objects = None, None
         views = int(views) if views is not None and int(views) > 1 else 0
         objects = int(objects) if objects is not None and int(objects) > 1 else 0
-        if objects:
+        if counts:
+            if B != len(counts):
+                raise L.MvdError(f"views={counts}: one prompt per object, got {B} rows of prompt_embeds for {len(counts)} objects")
+            if guidance_scale > 1.0 and not cfg:      # as below: [positive x O | positive x O]
+                embeds = embeds.repeat(2, 1, 1)
+            B = sum(counts)
+        elif objects:
             views = max(views, 1)
             if B != objects:
                 raise L.MvdError(f"objects: one prompt per object, got {B} rows of prompt_embeds for {objects} objects")
@@ -87,6 +101,8 @@ class MVDDenoiser:
             extra["views"] = views
         if objects:
             extra["objects"] = objects
+        if counts:
+            extra["views"] = counts
         # Q5: the reference K/V of a previous call (another object) must never be reused by this one
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
@@ -349,7 +365,12 @@ class MVDPipeline:
 
         Ancestral noise (``sampler="ddpm"``): ONE draw of (O V, 4, h, w) per step from torch's global RNG, or ``noise_per_step[i]``
         of that shape (row o * V + v is what that view's own call gets).  The camera encoder's random projection (Q1) is drawn
-        once per forward for all rows."""
+        once per forward for all rows.
+
+        Ragged view counts: ``target_cameras`` a LIST of O tensors ``(V_o, 3|4, 4)``, V_o >= 1 -- object o
+        gets V_o views, R = sum V_o.  Prompts, sources and source cameras stay one per object; ``latents``, a generator list,
+        ``noise_per_step[i]`` and the returned images have R rows, object-major (row sum(V_0 .. V_{o-1}) + v); every step is one
+        ragged forward, which is the R independent calls.  Equal counts give what the tensor form gives, bit for bit."""
         dev = self.device
         if prompts is not None and (isinstance(prompts, str) or not isinstance(prompts, (list, tuple))):
             raise L.MvdError("generate_views_batch: prompts must be a list of strings, one per object")
@@ -370,6 +391,11 @@ class MVDPipeline:
                 negative_prompt_embeds = negative_prompt_embeds.expand(O, -1, -1)
             if negative_prompt_embeds.shape[0] != O:
                 raise L.MvdError(f"generate_views_batch: {negative_prompt_embeds.shape[0]} rows of negative_prompt_embeds for {O} objects")
+        if isinstance(target_cameras, (list, tuple)):
+            return self._generate_views_ragged(list(target_cameras), O, prompt_embeds, negative_prompt_embeds, source_images,
+                                               source_image_latents, source_cameras, height, width, num_inference_steps,
+                                               guidance_scale, generator, latents, output_type, return_dict, callback,
+                                               callback_steps, cross_attention_kwargs, noise_per_step)
         if target_cameras is None or target_cameras.dim() not in (3, 4):
             raise L.MvdError("generate_views_batch: target_cameras must be (O, V, 3|4, 4) or (V, 3|4, 4)")
         tgt = target_cameras if target_cameras.dim() == 4 else target_cameras.unsqueeze(0).expand(O, -1, -1, -1)
@@ -407,6 +433,56 @@ class MVDPipeline:
             if self.vae is None:
                 raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
             image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of O * V rows
+            image = (image / 2 + 0.5).clamp(0, 1)
+            if output_type == "pil":
+                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
+        if not return_dict:
+            return image
+        return {"images": image}
+
+    @torch.no_grad()
+    def _generate_views_ragged(self, cams, O, prompt_embeds, negative_prompt_embeds, source_images, source_image_latents, source_cameras,
+                               height, width, num_inference_steps, guidance_scale, generator, latents, output_type, return_dict,
+                               callback, callback_steps, cross_attention_kwargs, noise_per_step):
+        """``generate_views_batch`` with a list of per-object target cameras (the prompts are encoded already)."""
+        dev = self.device
+        if len(cams) != O:
+            raise L.MvdError(f"generate_views_batch: target_cameras for {len(cams)} objects, prompts for {O}")
+        for c in cams:
+            if not isinstance(c, torch.Tensor) or c.dim() != 3 or c.shape[0] < 1 or c.shape[1:] != cams[0].shape[1:]:
+                raise L.MvdError("generate_views_batch: a list of target_cameras holds one (V_o, 3|4, 4) tensor per object, V_o >= 1")
+        counts = tuple(int(c.shape[0]) for c in cams)
+        R = sum(counts)
+        if source_cameras is None or source_cameras.dim() != 3 or source_cameras.shape[0] != O or source_cameras.shape[1:] != cams[0].shape[1:]:
+            raise L.MvdError(f"generate_views_batch: source_cameras must be ({O}, {cams[0].shape[1]}, 4), one per object")
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        if latents is None:
+            latents = self.prepare_latents(R, 4, height, width, prompt_embeds.dtype, dev, generator)
+        if latents.shape[0] != R:
+            raise L.MvdError(f"generate_views_batch: {latents.shape[0]} rows of latents for the {R} views of counts {counts}")
+        if source_images is not None:                                             # the O sources in one VAE call
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
+                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
+            si = source_images.to(device=dev)
+            if bool(si.min() >= 0) and bool(si.max() <= 1):
+                si = 2 * si - 1
+            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
+        if source_image_latents is None or source_image_latents.shape[0] != O:
+            raise L.MvdError(f"generate_views_batch: one source image per object ({O} rows of source_images or source_image_latents)")
+        den = MVDDenoiser(self.unet, self.scheduler)
+        src = torch.cat([source_cameras[o:o + 1].expand(counts[o], -1, -1) for o in range(O)])
+        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
+                      latents=latents, source_camera=src, target_camera=torch.cat([c.to(src.device) for c in cams]),
+                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=counts)
+        if output_type == "latent":
+            image = latents
+        else:
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
+            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of R rows
             image = (image / 2 + 0.5).clamp(0, 1)
             if output_type == "pil":
                 image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())

@@ -29,7 +29,7 @@ import logging
 import os
 import time
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -215,12 +215,33 @@ def setup_pipeline(config: Dict, checkpoint_path: str, device):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the run
+def source_groups(object_uids, prompts, source_camera) -> List[Tuple[int, int]]:
+    """``[(first row, end row), ...]`` of a loader batch: consecutive rows that share ``object_uid``, prompt and the bytes of their
+    (host) ``source_camera`` are the target views of one source -- one object of a ragged ``generate_views_batch`` call.  The
+    dataset emits the pairs of a source one after the other, so with ``max_views_per_object = 4`` a full object gives the spans
+    of 3, 2 and 1 rows.  Host work only: nothing here touches the device."""
+    cams = [source_camera[i].numpy().tobytes() for i in range(len(object_uids))]
+    spans, first = [], 0
+    for i in range(1, len(object_uids) + 1):
+        if i == len(object_uids) or (object_uids[i], prompts[i], cams[i]) != (object_uids[first], prompts[first], cams[first]):
+            spans.append((first, i))
+            first = i
+    return spans
+
+
 def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *, metrics: Optional[ValidationMetrics] = None,
                    extra_metrics: Sequence[str] = (), metric_kwargs: Optional[Dict] = None, on_batch=None):
     """-> (all_results, overall_metrics) and the two CSV files under ``output_dir``.  ``metrics``: a ready ``ValidationMetrics``
     (otherwise one is built from ``config`` / ``extra_metrics`` / ``metric_kwargs``).  ``on_batch(batch_idx, generated, target,
     prompts)`` (optional) sees every batch's tensors before they are scored.  For a dataset in device mode the loader's workers
-    return the raw samples and ``DeviceCollate`` runs here, in the main process (any ``num_workers``)."""
+    return the raw samples and ``DeviceCollate`` runs here, in the main process (any ``num_workers``).
+
+    ``config["group_sources"]`` (``--group-sources``; default off, and then the run is what it was): the rows of a loader batch that
+    share their source (``source_groups``) run as ONE ``generate_views_batch`` call with a ragged camera list -- one encoder pass
+    and one copy of the reference K/V per source, every row computed as its own ``batch_size: 1`` call would compute it.  That
+    is NOT the default run's result at ``batch_size > 1``, whose ordinary batch couples the rows (Q2 statistics over the batch, Q4
+    re-chunking under guidance) and depends on the batch size; rows, columns, CSV order and the timing
+    window are the same.  Needs both cameras (a dataset without them runs ungrouped)."""
     from torch.utils.data import DataLoader
     output_dir = Path(output_dir)
     output_dir.mkdir(exist_ok=True, parents=True)
@@ -246,16 +267,26 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
                 source_images, target_images = batch["source_image"].to(device), batch["target_image"].to(device)
                 source_camera, target_camera = batch.get("source_camera"), batch.get("target_camera")
                 prompts, object_uids = batch["prompt"], batch["object_uid"]
+                spans = None
+                if config.get("group_sources", False) and source_camera is not None and target_camera is not None:
+                    spans = source_groups(object_uids, prompts, source_camera.cpu())       # (the loader's cameras are host tensors)
                 if source_camera is not None:
                     source_camera = source_camera.to(device)
                 if target_camera is not None:
                     target_camera = target_camera.to(device)
                 # a host clock around the pipeline call; the device is drained inside the window so that the figure is the work's
                 start = time.perf_counter()
-                out = pipeline(prompt=prompts, num_inference_steps=config["num_inference_steps"], source_camera=source_camera,
-                               target_camera=target_camera, source_images=source_images, guidance_scale=config["guidance_scale"],
-                               ref_scale=config["ref_scale"], output_type="pt", use_camera_embeddings=config["use_camera_conditioning"],
-                               use_image_conditioning=config["use_image_conditioning"])
+                if spans is not None:
+                    firsts = [s for s, _ in spans]
+                    out = pipeline.generate_views_batch(prompts=[prompts[s] for s in firsts], source_images=source_images[firsts],
+                                                        source_cameras=source_camera[firsts], target_cameras=[target_camera[s:e] for s, e in spans],
+                                                        num_inference_steps=config["num_inference_steps"], guidance_scale=config["guidance_scale"],
+                                                        output_type="pt")
+                else:
+                    out = pipeline(prompt=prompts, num_inference_steps=config["num_inference_steps"], source_camera=source_camera,
+                                   target_camera=target_camera, source_images=source_images, guidance_scale=config["guidance_scale"],
+                                   ref_scale=config["ref_scale"], output_type="pt", use_camera_embeddings=config["use_camera_conditioning"],
+                                   use_image_conditioning=config["use_image_conditioning"])
                 if on_gpu:
                     torch.cuda.synchronize()
                 batch_time = time.perf_counter() - start
@@ -378,12 +409,17 @@ def main(argv=None) -> int:
     ap.add_argument("--output-dir", type=str, default="outputs/gso_validation", help="Output directory for results")
     ap.add_argument("--extra-metrics", type=str, default=None, help=f"comma-separated subset of {','.join(EXTRA_METRICS)} (default: the config's, else none)")
     ap.add_argument("--frontend", choices=("host", "device"), default=None, help="where composite + resize run (default: the config's, else host)")
+    ap.add_argument("--group-sources", action="store_true", default=None,
+                    help="run the rows of a batch that share their source as one ragged generate_views_batch call: the batch_size 1 "
+                         "result at any batch size (default: the config's group_sources, else off)")
     args = ap.parse_args(argv)
     try:
         config = load_config(args.config)
     except Exception as e:  # noqa: BLE001
         logger.error("Failed to load configuration: %s", e)
         return 1
+    if args.group_sources:
+        config["group_sources"] = True
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     output_dir.mkdir(exist_ok=True, parents=True)
