@@ -386,6 +386,28 @@ int mvd_op_cfg_combine(const float* uncond_cond, float guidance_scale, float* ou
 int mvd_op_sampler_step(const float* model_out, int guided, float guidance_scale, const float* sample, const float* x0_prev,
                         const float* noise, float a0, float a1, float p, float q, float r, float sigma, float* out,
                         float* x0_out, int64_t n, void* stream);
+/* Guidance rescale (Lin et al. 2024, section 3.4; diffusers-0.32.2 rescale_noise_cfg, restated) fused into the guided step.
+ * uncond_cond / model_out hold [uncond | cond] stacked on the batch dim: 2 * rows * n_row floats.  Per row, over its n_row
+ * elements:  m = u + g*(c - u) ; s_c = std(c), s_m = std(m) (unbiased, divisor n_row - 1) ;
+ *            m' = m * (phi * s_c / s_m + 1 - phi)              (= phi * m * s_c / s_m + (1 - phi) * m)
+ * mvd_op_cfg_rescale writes out = m'; mvd_op_sampler_step_rescaled goes on as mvd_op_sampler_step does with m' for m:
+ *   x0 = a0*m' + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; if (x0_out) x0_out = x0.
+ * ONE launch, one workgroup per row; the two statistics are fp64 sums of x and x^2 taken in a fixed order that depends on
+ * n_row alone (no atomics), so a row's output bits do not depend on rows, on the row's index or on the launch.  A row of up
+ * to 36864 floats stays in registers between the statistics and the update (model_out is read once); a longer row is read a
+ * second time.  There is no epsilon: s_m == 0 gives what IEEE arithmetic gives (inf or NaN), as in diffusers; a variance that
+ * rounds below zero counts as zero.  guidance_rescale must lie in [0, 1], n_row % 4 == 0, n_row >= 4; x0_prev / noise as in
+ * mvd_op_sampler_step; out == sample and x0_out == x0_prev are allowed; an out or x0_out that overlaps uncond_cond / model_out
+ * is an error (every element of a row is needed before any output of it is final); otherwise -1 (mvd_last_error). */
+int mvd_op_cfg_rescale(const float* uncond_cond, float guidance_scale, float guidance_rescale, float* out, int64_t rows,
+                       int64_t n_row, void* stream);
+int mvd_op_sampler_step_rescaled(const float* model_out, float guidance_scale, float guidance_rescale, const float* sample,
+                                 const float* x0_prev, const float* noise, float a0, float a1, float p, float q, float r,
+                                 float sigma, float* out, float* x0_out, int64_t rows, int64_t n_row, void* stream);
+/* How the two entry points above partition a row of n_row floats, out[4] = {threads per workgroup, floats per lane access,
+ * lanes per wave, 16-byte vectors per thread kept in registers (0: the row is streamed twice)}: thread t of the row's one
+ * workgroup owns the vectors t, t + threads, t + 2*threads, ... of the row. */
+int mvd_debug_cfg_rescale_plan(int64_t n_row, int* out);
 
 /* ---- checkpoint scoring around the UNet, fp32 ------------------------------------------------ */
 /* Conventions of the helpers above; in addition every quantity that depends on a sample's timestep is read ON THE DEVICE

@@ -179,6 +179,11 @@ _SIGS = {
     "mvd_op_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "mvd_op_sampler_step": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvd_op_cfg_rescale": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mvd_op_sampler_step_rescaled": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                               C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.c_int64, C.c_void_p]),
+    "mvd_debug_cfg_rescale_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
     "mvd_op_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int64, C.c_void_p]),
     "mvd_op_noise_loss_ws_bytes": (C.c_int64, [C.c_int, C.c_int64]),

@@ -569,6 +569,70 @@ def sampler_step(model_out, sample, a0, a1, p, q, r=0.0, sigma=0.0, x0_prev=None
     return out
 
 
+def _rescale_rows(uncond_cond):
+    """(rows, n_row) of a stacked (2 * rows, ...) [uncond | cond] model output: guidance rescale works per batch row."""
+    if uncond_cond.dim() < 2 or uncond_cond.shape[0] % 2:
+        raise L.MvdError(f"guidance rescale: expected [uncond | cond] of shape (2 * rows, ...), got {tuple(uncond_cond.shape)}")
+    if not (uncond_cond.is_cuda and uncond_cond.dtype == torch.float32 and uncond_cond.is_contiguous()):
+        raise L.MvdError(f"guidance rescale: expected a contiguous fp32 CUDA tensor, got {uncond_cond.dtype} on {uncond_cond.device}")
+    rows = uncond_cond.shape[0] // 2
+    return rows, uncond_cond.numel() // (2 * rows)
+
+
+def cfg_rescale(uncond_cond, guidance_scale, guidance_rescale, out=None):
+    """(2B, ...) fp32 [uncond | cond] -> (B, ...): the guided output m = u + g*(c - u) with guidance rescale (Lin et al. 2024, 3.4;
+    diffusers' ``rescale_noise_cfg``): per batch row, m * (phi * std(c) / std(m) + 1 - phi), unbiased std over the row, no
+    epsilon.  One launch (``mvd_op_cfg_rescale``).  ``out`` must not overlap ``uncond_cond``."""
+    rows, n_row = _rescale_rows(uncond_cond)
+    if out is None:
+        out = torch.empty((rows,) + tuple(uncond_cond.shape[1:]), device=uncond_cond.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() == rows * n_row and out.is_contiguous()
+    L.call("mvd_op_cfg_rescale", _p(uncond_cond), float(guidance_scale), float(guidance_rescale), _p(out), rows, n_row, _s())
+    return out
+
+
+def sampler_step_rescaled(model_out, sample, guidance_scale, guidance_rescale, a0, a1, p, q, r=0.0, sigma=0.0, x0_prev=None,
+                          noise=None, out=None, x0_out=None):
+    """``sampler_step`` of the guided and rescaled model output in ONE launch: m' = ``cfg_rescale(model_out, guidance_scale,
+    guidance_rescale)`` ; x0 = a0*m' + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; x0_out = x0.  ``model_out``
+    is the stacked (2B, ...) [uncond | cond]; ``x0_prev`` may be None iff r == 0, ``noise`` iff sigma == 0.  ``out`` may be
+    ``sample`` and ``x0_out`` may be ``x0_prev``; neither may overlap ``model_out``."""
+    rows, n_row = _rescale_rows(model_out)
+    assert sample.dtype == torch.float32 and sample.numel() == rows * n_row, (tuple(model_out.shape), tuple(sample.shape))
+    for t in (x0_prev, noise, out, x0_out):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == sample.numel())
+    if out is None:
+        out = torch.empty_like(sample)
+    L.call("mvd_op_sampler_step_rescaled", _p(model_out), float(guidance_scale), float(guidance_rescale), _p(sample), _p(x0_prev),
+           _p(noise), float(a0), float(a1), float(p), float(q), float(r), float(sigma), _p(out), _p(x0_out), rows, n_row, _s())
+    return out
+
+
+def cfg_rescale_plan(n_row):
+    """How the rescale kernel partitions a row of ``n_row`` floats (``mvd_debug_cfg_rescale_plan``): dict(threads, vec, wave, keep,
+    passes) -- thread t of the row's one workgroup owns the ``vec``-float vectors t, t + threads, ...; ``keep`` vectors per thread
+    stay in registers (0: the row is streamed twice); ``passes`` = vectors per thread."""
+    out = (C.c_int * 4)()
+    L.call("mvd_debug_cfg_rescale_plan", int(n_row), out)
+    per_pass = out[0] * out[1]
+    return dict(threads=out[0], vec=out[1], wave=out[2], keep=out[3], passes=-(-int(n_row) // per_pass))
+
+
+def cfg_rescale_partition(n_row):
+    """The element offsets in (0, n_row) at which the rescale kernel's partition of a row changes hands, sorted: every start of
+    a wave's chunk (``wave * vec`` contiguous floats; a workgroup pass of ``threads * vec`` floats starts on one of them, and so
+    does the last, partial pass), and every start of a lane's ``vec``-float chunk inside the first and the last wave chunk of the
+    row -- the lane pattern repeats in every wave chunk, so the rest of them say nothing new.  Derived from the launcher's
+    constants (``cfg_rescale_plan``)."""
+    plan = cfg_rescale_plan(n_row)
+    n_row, vec, wchunk = int(n_row), plan["vec"], plan["wave"] * plan["vec"]
+    offs = set(range(wchunk, n_row, wchunk))
+    offs.update(range(vec, min(wchunk, n_row), vec))
+    last = (n_row - 1) // wchunk * wchunk
+    offs.update(range(last + vec, n_row, vec))
+    return sorted(offs)
+
+
 PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")       # prediction_type of mvd_op_noise_loss, by index
 
 

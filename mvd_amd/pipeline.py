@@ -46,13 +46,21 @@ class MVDDenoiser:
                  source_image_latents: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
                  height: int = 64, width: int = 64, noise_per_step=None, callback=None, callback_steps: int = 1,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None, views: Optional[int] = None,
-                 objects: Optional[int] = None):
-        """``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
+                 objects: Optional[int] = None, *, guidance_rescale: float = 0.0):
+        """``guidance_rescale`` (diffusers' argument of that name; Lin et al. 2024, section 3.4): with guidance active
+        (``guidance_scale > 1``) and a value in (0, 1], every row's guided output is rescaled towards the standard deviation of its
+        conditional output before the scheduler step -- statistics, rescale and step in ONE launch per step for all three samplers
+        (DESIGN.md section 9 N17).  0.0 (the default), or no guidance: ignored, the loop issues the launches it always did.
+
+        ``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
         source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``).  ``objects``
         (MVDPipeline.generate_views_batch): O prompts and O source rows, ``latents`` and the cameras O * views rows, object-major;
         every step is one object forward (``MultiViewUNet.forward(..., views=, objects=)``).  ``views`` a sequence
         ``(V_0, .., V_{O-1})``: ragged view counts -- O prompts and O source rows, ``latents`` and the cameras sum(V_o) rows,
         object-major; every step is one ragged forward (``MultiViewUNet.forward(..., views=(V_0, ..))``)."""
+        if not 0.0 <= float(guidance_rescale) <= 1.0:
+            raise ValueError(f"guidance_rescale={guidance_rescale!r} must lie in [0, 1]")
+        rescale = float(guidance_rescale) if guidance_scale > 1.0 else 0.0      # without guidance it is ignored, as in diffusers
         dev = self.unet._exec_device()
         B = prompt_embeds.shape[0]
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
@@ -107,6 +115,7 @@ class MVDDenoiser:
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
         guided_step = getattr(self.scheduler, "step_guided", None)              # DDIM / DPM-Solver++ (DDPM has none)
+        rescaled_step = getattr(self.scheduler, "step_guided_rescaled", None)   # DDPM's guided-and-rescaled step
         ts_host = self.scheduler.timesteps.tolist()                             # host ints for the scheduler's coefficients
         ts_dev = torch.tensor(ts_host, dtype=torch.float32, device=dev)         # ONE upload: a per-step scalar upload would make
         for i, t in enumerate(ts_host):                                         # the host wait for the previous step's kernels
@@ -114,7 +123,16 @@ class MVDDenoiser:
             out = self.unet(sample=x_in, timestep=ts_dev[i], encoder_hidden_states=embeds,
                             cross_attention_kwargs=cross_attention_kwargs, **extra).sample
             nz = None if noise_per_step is None else noise_per_step[i]
-            if guidance_scale > 1.0 and guided_step is not None:
+            if rescale > 0.0 and guided_step is not None:
+                # DDIM / DPM-Solver++ with guidance rescale: the row statistics, the combine, the rescale and the step in ONE launch
+                latents = guided_step(out.float().contiguous(), guidance_scale, t, latents, noise=nz,
+                                      guidance_rescale=rescale).prev_sample
+            elif rescale > 0.0 and rescaled_step is not None:                   # DDPM: the same kernel (r = 0), ONE launch
+                latents = rescaled_step(out.float().contiguous(), guidance_scale, rescale, t, latents, noise=nz).prev_sample
+            elif rescale > 0.0:                                                 # a scheduler of the caller's: rescale, then its step
+                out = ops.cfg_rescale(out.float().contiguous(), guidance_scale, rescale)
+                latents = self.scheduler.step(out, t, latents, noise=nz).prev_sample
+            elif guidance_scale > 1.0 and guided_step is not None:
                 # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch
                 latents = guided_step(out.float().contiguous(), guidance_scale, t, latents, noise=nz).prev_sample
             else:
@@ -206,7 +224,8 @@ class MVDPipeline:
                  source_camera: Optional[torch.Tensor] = None, target_camera: Optional[torch.Tensor] = None,
                  source_images: Optional[torch.Tensor] = None, ref_scale: float = 0.1, use_camera_embeddings: bool = True,
                  use_image_conditioning: bool = True, debug_log_file_path: Optional[str] = None, *,
-                 source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None):
+                 source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
+                 guidance_rescale: float = 0.0):
         dev = self.device
         if prompt is not None and isinstance(prompt, str):                       # :45-50
             batch_size = 1
@@ -243,7 +262,7 @@ class MVDPipeline:
                       latents=latents, source_camera=source_camera, target_camera=target_camera,
                       source_image_latents=source_image_latents, generator=generator if isinstance(generator, torch.Generator) else None,
                       noise_per_step=noise_per_step, callback=callback, callback_steps=callback_steps,
-                      cross_attention_kwargs=cross_attention_kwargs or {})
+                      cross_attention_kwargs=cross_attention_kwargs or {}, guidance_rescale=guidance_rescale)
 
         if output_type == "latent":
             image = latents
@@ -268,7 +287,8 @@ class MVDPipeline:
                        negative_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = "pil",
                        return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                        callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
-                       source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None):
+                       source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
+                       guidance_rescale: float = 0.0):
         """V views of ONE object from one source image: what V calls ``pipe(prompt, source_images=, source_camera=,
         target_camera=target_cameras[v:v+1], ...)`` give (the loop of infer.py:111-122, a turntable), in one denoising loop whose
         every step is ONE shared-reference forward: the prompt is encoded once, the source VAE-encoded
@@ -325,7 +345,8 @@ class MVDPipeline:
         latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
                       latents=latents, source_camera=src.expand(V, -1, -1), target_camera=target_cameras,
                       source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=V)
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
+                      guidance_rescale=guidance_rescale, views=V)
         if output_type == "latent":
             image = latents
         else:
@@ -350,7 +371,8 @@ class MVDPipeline:
                              negative_prompt_embeds: Optional[torch.FloatTensor] = None, output_type: Optional[str] = "pil",
                              return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                              callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
-                             source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None):
+                             source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
+                             guidance_rescale: float = 0.0):
         """Turntables of O objects, V views each: what O calls of ``generate_views`` (O * V calls of ``pipe(...)``) give, in one
         denoising loop whose every step is ONE object forward.  The prompts are encoded once, the O
         sources VAE-encoded in one call, the reference encoder pass runs at batch O (once per call with
@@ -395,7 +417,7 @@ class MVDPipeline:
             return self._generate_views_ragged(list(target_cameras), O, prompt_embeds, negative_prompt_embeds, source_images,
                                                source_image_latents, source_cameras, height, width, num_inference_steps,
                                                guidance_scale, generator, latents, output_type, return_dict, callback,
-                                               callback_steps, cross_attention_kwargs, noise_per_step)
+                                               callback_steps, cross_attention_kwargs, noise_per_step, guidance_rescale)
         if target_cameras is None or target_cameras.dim() not in (3, 4):
             raise L.MvdError("generate_views_batch: target_cameras must be (O, V, 3|4, 4) or (V, 3|4, 4)")
         tgt = target_cameras if target_cameras.dim() == 4 else target_cameras.unsqueeze(0).expand(O, -1, -1, -1)
@@ -425,7 +447,8 @@ class MVDPipeline:
         latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
                       latents=latents, source_camera=source_cameras.repeat_interleave(V, 0), target_camera=tgt.reshape(O * V, *tgt.shape[2:]),
                       source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=V,
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
+                      guidance_rescale=guidance_rescale, views=V,
                       objects=None if one else O)
         if output_type == "latent":
             image = latents
@@ -443,7 +466,7 @@ class MVDPipeline:
     @torch.no_grad()
     def _generate_views_ragged(self, cams, O, prompt_embeds, negative_prompt_embeds, source_images, source_image_latents, source_cameras,
                                height, width, num_inference_steps, guidance_scale, generator, latents, output_type, return_dict,
-                               callback, callback_steps, cross_attention_kwargs, noise_per_step):
+                               callback, callback_steps, cross_attention_kwargs, noise_per_step, guidance_rescale=0.0):
         """``generate_views_batch`` with a list of per-object target cameras (the prompts are encoded already)."""
         dev = self.device
         if len(cams) != O:
@@ -476,7 +499,8 @@ class MVDPipeline:
         latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
                       latents=latents, source_camera=src, target_camera=torch.cat([c.to(src.device) for c in cams]),
                       source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {}, views=counts)
+                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
+                      guidance_rescale=guidance_rescale, views=counts)
         if output_type == "latent":
             image = latents
         else:

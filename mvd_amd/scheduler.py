@@ -15,6 +15,13 @@
 Everything here is scalar / length-1000 vector math on the host; the per-step tensor update is one fused HIP
 kernel (``mvd_op_ddpm_step``, ``mvd_op_sampler_step``) whose coefficients are computed here, so the loop never syncs
 the device.
+
+* Guidance rescale (Lin et al. 2024, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4) restates
+  diffusers-0.32.2 ``rescale_noise_cfg``: per batch row, m' = phi * m * std(cond) / std(m) + (1 - phi) * m with torch's unbiased
+  std over the row and no epsilon (std(m) == 0 gives what IEEE arithmetic gives).  It is applied to the guided model output
+  whatever the prediction type, only when guidance is active (``guidance_scale > 1``) and ``guidance_rescale > 0``; the
+  statistics, the rescale and the step are ONE launch (``mvd_op_sampler_step_rescaled``).  Also unpinned against diffusers;
+  pinned by the fp64 restatement in tests/guidance_ref.py and its identities (tests/test_guidance_rescale_cpu.py).
 """
 from __future__ import annotations
 
@@ -161,6 +168,26 @@ class DDPMScheduler(_ForwardDiffusion):
         prev = ops.ddpm_step(model_output, sample, noise, c0, c1, c2, c3, sigma)
         return SimpleNamespace(prev_sample=prev)
 
+    def step_guided_rescaled(self, uncond_cond: torch.Tensor, guidance_scale: float, guidance_rescale: float, timestep,
+                             sample: torch.Tensor, noise: Optional[torch.Tensor] = None,
+                             generator: Optional[torch.Generator] = None):
+        """``step`` of the guided, rescaled model output (``ops.cfg_rescale`` of [uncond | cond] stacked on the batch dim) in ONE
+        launch: the DDPM step is the samplers' affine form with r = 0.  Named apart from the samplers' ``step_guided`` on purpose:
+        this class has none, so the plain guided DDPM loop stays ``cfg_combine`` + ``step``."""
+        from . import ops
+        _check_rescale(guidance_rescale)
+        c0, c1, c2, c3, sigma = self.step_coefficients(int(timestep))
+        if noise is None and sigma != 0.0:
+            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        prev = ops.sampler_step_rescaled(uncond_cond, sample, guidance_scale, guidance_rescale, c0, c1, c3, c2, 0.0, sigma,
+                                         noise=noise if sigma != 0.0 else None)
+        return SimpleNamespace(prev_sample=prev)
+
+
+def _check_rescale(guidance_rescale: float):
+    if not 0.0 <= float(guidance_rescale) <= 1.0:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} must lie in [0, 1]")
+
 
 _PREDICTION_TYPES = ("epsilon", "v_prediction")
 _SPACINGS = ("leading", "linspace", "trailing")
@@ -237,6 +264,19 @@ class _SolverSchedule(_ForwardDiffusion):
         return ops.sampler_step(model_out, sample, a0, a1, p, q, r, sigma, x0_prev=x0_prev if r != 0.0 else None,
                                 noise=noise if sigma != 0.0 else None, guidance_scale=guidance_scale, x0_out=x0_out)
 
+    def _launch_guided(self, model_out, guidance_scale, guidance_rescale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None):
+        """``_launch`` of a guided step; with ``guidance_rescale`` > 0 and guidance active the rescaled kernel, else (as in
+        diffusers, where the argument is then ignored) exactly the call made without it."""
+        _check_rescale(guidance_rescale)
+        if not (guidance_rescale > 0.0 and guidance_scale > 1.0):
+            return self._launch(model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=x0_prev, x0_out=x0_out)
+        from . import ops
+        a0, a1, p, q, r, sigma = coeffs
+        if sigma != 0.0 and noise is None:
+            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        return ops.sampler_step_rescaled(model_out, sample, guidance_scale, guidance_rescale, a0, a1, p, q, r, sigma,
+                                         x0_prev=x0_prev if r != 0.0 else None, noise=noise if sigma != 0.0 else None, x0_out=x0_out)
+
 
 class DDIMScheduler(_SolverSchedule):
     """diffusers-0.32.2 ``DDIMScheduler`` (Song et al. 2021) for epsilon / v_prediction, no sample clipping or
@@ -297,10 +337,12 @@ class DDIMScheduler(_SolverSchedule):
         return SimpleNamespace(prev_sample=self._launch(model_output, None, c, sample, nz, generator))
 
     def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
-                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, eta: float = 0.0):
-        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch."""
+                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, eta: float = 0.0,
+                    guidance_rescale: float = 0.0):
+        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.
+        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch."""
         c = self.step_coefficients(int(timestep), eta)
-        return SimpleNamespace(prev_sample=self._launch(uncond_cond, guidance_scale, c, sample, noise, generator))
+        return SimpleNamespace(prev_sample=self._launch_guided(uncond_cond, guidance_scale, guidance_rescale, c, sample, noise, generator))
 
 
 class DPMSolverMultistepScheduler(_SolverSchedule):
@@ -413,7 +455,7 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
             q, r = q + c, -c
         return a0, a1, p, q, r, 0.0
 
-    def _step(self, model_output, guidance_scale, timestep, sample):
+    def _step(self, model_output, guidance_scale, timestep, sample, guidance_rescale: float = 0.0):
         if self.sigmas is None:
             raise ValueError("call set_timesteps first")
         if self._step_index is None:                           # diffusers' index_for_timestep
@@ -431,7 +473,10 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
                 hist = self._hist[key] = torch.empty(sample.shape, device=sample.device, dtype=torch.float32)
         if c[4] != 0.0 and self._hist_key != key:
             raise ValueError("a second-order step needs the previous step's x0 of the same shape and device")
-        out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist)
+        if guidance_scale is None:
+            out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist)
+        else:
+            out = self._launch_guided(model_output, guidance_scale, guidance_rescale, c, sample, None, None, x0_prev=hist, x0_out=hist)
         self._hist_key = key if hist is not None else None
         self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
         self._step_index = i + 1
@@ -444,9 +489,11 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
         return SimpleNamespace(prev_sample=self._step(model_output, None, timestep, sample))
 
     def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
-                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None):
-        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch."""
-        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample))
+                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                    guidance_rescale: float = 0.0):
+        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.
+        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch."""
+        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample, guidance_rescale))
 
 
 class ShiftSNRScheduler:

@@ -12,8 +12,9 @@ Configuration keys read (the reference ships no ``config/infer_config.yaml``; th
 ``use_memory_efficient_attention`` / ``enable_gradient_checkpointing`` (optional here, no meaning on this engine), ``image_size``
 ([width, height]), ``max_views_per_object``, ``batch_size``, ``num_workers``, ``num_inference_steps``, ``guidance_scale``,
 ``ref_scale``, ``clip_model_name`` (optional); and this project's own optional keys ``cache_dir`` (local huggingface cache of the
-architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics`` and ``metric_weights`` (a
-mapping of the ``ValidationMetrics`` weight keywords to paths).
+architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics``, ``metric_weights`` (a
+mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
+pipeline's argument of that name, ``--guidance-rescale``).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
 of the per-metric aggregates; ``clip_score`` is a per-batch value copied to each of the batch's samples and aggregated apart;
@@ -259,6 +260,8 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     dataloader = DataLoader(dataset, **loader_kw)
     on_gpu = torch.device(device).type == "cuda"
     all_results, batch_metrics = [], []
+    # off (0.0, the default): the pipeline calls are the ones made before the key existed, argument for argument
+    rescale = {"guidance_rescale": float(config["guidance_rescale"])} if float(config.get("guidance_rescale", 0.0) or 0.0) != 0.0 else {}
     with torch.no_grad():
         for batch_idx, batch in enumerate(dataloader):
             try:
@@ -281,12 +284,12 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
                     out = pipeline.generate_views_batch(prompts=[prompts[s] for s in firsts], source_images=source_images[firsts],
                                                         source_cameras=source_camera[firsts], target_cameras=[target_camera[s:e] for s, e in spans],
                                                         num_inference_steps=config["num_inference_steps"], guidance_scale=config["guidance_scale"],
-                                                        output_type="pt")
+                                                        output_type="pt", **rescale)
                 else:
                     out = pipeline(prompt=prompts, num_inference_steps=config["num_inference_steps"], source_camera=source_camera,
                                    target_camera=target_camera, source_images=source_images, guidance_scale=config["guidance_scale"],
                                    ref_scale=config["ref_scale"], output_type="pt", use_camera_embeddings=config["use_camera_conditioning"],
-                                   use_image_conditioning=config["use_image_conditioning"])
+                                   use_image_conditioning=config["use_image_conditioning"], **rescale)
                 if on_gpu:
                     torch.cuda.synchronize()
                 batch_time = time.perf_counter() - start
@@ -412,6 +415,8 @@ def main(argv=None) -> int:
     ap.add_argument("--group-sources", action="store_true", default=None,
                     help="run the rows of a batch that share their source as one ragged generate_views_batch call: the batch_size 1 "
                          "result at any batch size (default: the config's group_sources, else off)")
+    ap.add_argument("--guidance-rescale", type=float, default=None,
+                    help="guidance rescale in [0, 1] (Lin et al. 2024, section 3.4; default: the config's guidance_rescale, else 0.0 = off)")
     args = ap.parse_args(argv)
     try:
         config = load_config(args.config)
@@ -420,6 +425,8 @@ def main(argv=None) -> int:
         return 1
     if args.group_sources:
         config["group_sources"] = True
+    if args.guidance_rescale is not None:
+        config["guidance_rescale"] = args.guidance_rescale
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     output_dir.mkdir(exist_ok=True, parents=True)
