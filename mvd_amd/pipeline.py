@@ -74,25 +74,25 @@ class MVDDenoiser:
             views, objects = None, None
         views = int(views) if views is not None and int(views) > 1 else 0
         objects = int(objects) if objects is not None and int(objects) > 1 else 0
+        # (prompt rows the layout expects, latent rows it makes of them): one prompt per object, one latent row per view
         if counts:
-            if B != len(counts):
-                raise L.MvdError(f"views={counts}: one prompt per object, got {B} rows of prompt_embeds for {len(counts)} objects")
-            if guidance_scale > 1.0 and not cfg:      # as below: [positive x O | positive x O]
-                embeds = embeds.repeat(2, 1, 1)
-            B = sum(counts)
+            expect, rows = len(counts), sum(counts)
+            err = f"views={counts}: one prompt per object, got {B} rows of prompt_embeds for {len(counts)} objects"
         elif objects:
             views = max(views, 1)
-            if B != objects:
-                raise L.MvdError(f"objects: one prompt per object, got {B} rows of prompt_embeds for {objects} objects")
-            if guidance_scale > 1.0 and not cfg:      # as below: [positive x O | positive x O]
-                embeds = embeds.repeat(2, 1, 1)
-            B = objects * views
+            expect, rows = objects, objects * views
+            err = f"objects: one prompt per object, got {B} rows of prompt_embeds for {objects} objects"
         elif views:
-            if B != 1:
-                raise L.MvdError(f"views: one prompt for the one object, got {B} rows of prompt_embeds")
-            if guidance_scale > 1.0 and not cfg:      # the doubled latents against one text row: the repeat of mvd_unet.py:233-237
-                embeds = embeds.repeat(2, 1, 1)
-            B = views
+            expect, rows = 1, views
+            err = f"views: one prompt for the one object, got {B} rows of prompt_embeds"
+        else:
+            expect, rows = B, B
+        if B != expect:
+            raise L.MvdError(err)
+        if (counts or objects or views) and guidance_scale > 1.0 and not cfg:
+            # the doubled latents against one text row per object, [positive x O | positive x O]: the repeat of mvd_unet.py:233-237
+            embeds = embeds.repeat(2, 1, 1)
+        B = rows
         if latents is None:
             latents = torch.randn(B, 4, height, width, generator=generator, device=dev, dtype=torch.float32)
             latents = latents * self.scheduler.init_noise_sigma
@@ -116,31 +116,29 @@ class MVDDenoiser:
             self.unet.reset_reference_cache()
         guided_step = getattr(self.scheduler, "step_guided", None)              # DDIM / DPM-Solver++ (DDPM has none)
         rescaled_step = getattr(self.scheduler, "step_guided_rescaled", None)   # DDPM's guided-and-rescaled step
+        # the keyword goes only with a rescale: a scheduler of the caller's whose step_guided has none keeps working without one
+        guided_kw = {"guidance_rescale": rescale} if rescale > 0.0 else {}
         ts_host = self.scheduler.timesteps.tolist()                             # host ints for the scheduler's coefficients
         ts_dev = torch.tensor(ts_host, dtype=torch.float32, device=dev)         # ONE upload: a per-step scalar upload would make
         for i, t in enumerate(ts_host):                                         # the host wait for the previous step's kernels
             x_in = torch.cat([latents] * 2) if guidance_scale > 1.0 else latents  # pipeline.py:141
             out = self.unet(sample=x_in, timestep=ts_dev[i], encoder_hidden_states=embeds,
-                            cross_attention_kwargs=cross_attention_kwargs, **extra).sample
+                            cross_attention_kwargs=cross_attention_kwargs, **extra).sample.float().contiguous()
             nz = None if noise_per_step is None else noise_per_step[i]
-            if rescale > 0.0 and guided_step is not None:
-                # DDIM / DPM-Solver++ with guidance rescale: the row statistics, the combine, the rescale and the step in ONE launch
-                latents = guided_step(out.float().contiguous(), guidance_scale, t, latents, noise=nz,
-                                      guidance_rescale=rescale).prev_sample
+            if guidance_scale > 1.0 and guided_step is not None:
+                # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch; with guidance
+                # rescale the row statistics and the rescale too
+                latents = guided_step(out, guidance_scale, t, latents, noise=nz, **guided_kw).prev_sample
             elif rescale > 0.0 and rescaled_step is not None:                   # DDPM: the same kernel (r = 0), ONE launch
-                latents = rescaled_step(out.float().contiguous(), guidance_scale, rescale, t, latents, noise=nz).prev_sample
+                latents = rescaled_step(out, guidance_scale, rescale, t, latents, noise=nz).prev_sample
             elif rescale > 0.0:                                                 # a scheduler of the caller's: rescale, then its step
-                out = ops.cfg_rescale(out.float().contiguous(), guidance_scale, rescale)
-                latents = self.scheduler.step(out, t, latents, noise=nz).prev_sample
-            elif guidance_scale > 1.0 and guided_step is not None:
-                # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch
-                latents = guided_step(out.float().contiguous(), guidance_scale, t, latents, noise=nz).prev_sample
+                latents = self.scheduler.step(ops.cfg_rescale(out, guidance_scale, rescale), t, latents, noise=nz).prev_sample
             else:
                 if guidance_scale > 1.0:                                        # pipeline.py:156-158
-                    out = ops.cfg_combine(out.float().contiguous(), guidance_scale)
+                    out = ops.cfg_combine(out, guidance_scale)
                 # pipeline.py:161 calls scheduler.step(noise_pred, t, latents) WITHOUT the generator: the ancestral noise comes
                 # from torch's global RNG (of the latents' device), the caller's generator only seeds the initial latents
-                latents = self.scheduler.step(out.float().contiguous(), t, latents, noise=nz).prev_sample
+                latents = self.scheduler.step(out, t, latents, noise=nz).prev_sample
             if callback is not None and i % callback_steps == 0:                # pipeline.py:165-166
                 callback(i, t, latents)
         return latents
@@ -211,6 +209,63 @@ class MVDPipeline:
                             return_tensors="pt")
         return self.text_encoder(ti.input_ids.to(self.device))[0]
 
+    # ------------------------------------------------------------------ the one generation path under the entry points
+    def _size(self, height, width):
+        side = self.unet.config.sample_size * self.vae_scale_factor            # pipeline.py:82-83
+        return height or side, width or side
+
+    def _encode_sources(self, source_images, repeat_to: int = 0):
+        """``source_images`` -> ``source_image_latents`` (pipeline.py:100-117): all rows in one VAE call.  ``repeat_to``
+        (``__call__`` alone): fewer source rows than that are repeated, as the reference repeats them for its prompts."""
+        if self.vae is None:
+            raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
+                             "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
+        si = source_images.to(device=self.device)
+        if bool(si.min() >= 0) and bool(si.max() <= 1):                          # one host sync, outside the loop
+            si = 2 * si - 1
+        if si.shape[0] < repeat_to:
+            si = si.repeat(repeat_to // si.shape[0], 1, 1, 1)
+        return self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
+
+    def _denoise(self, prompt_embeds, num_inference_steps, guidance_scale, cross_attention_kwargs=None, **kw):
+        return MVDDenoiser(self.unet, self.scheduler)(prompt_embeds, num_inference_steps, guidance_scale,
+                                                      cross_attention_kwargs=cross_attention_kwargs or {}, **kw)
+
+    def _images(self, latents, output_type, return_dict):
+        """The final latents as every entry point returns them: all rows in one VAE decode."""
+        if output_type == "latent":
+            image = latents
+        else:                                                                    # pipeline.py:168-181
+            if self.vae is None:
+                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
+            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample
+            image = (image / 2 + 0.5).clamp(0, 1)
+            if output_type == "pil":
+                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
+        if not return_dict:
+            return image
+        return {"images": image}
+
+    def _turntable(self, prompt_embeds, source_camera, target_camera, layout, *, who, rows, rows_of, sources, sources_of,
+                   source_images, source_image_latents, height, width, generator, latents, output_type, return_dict, **loop):
+        """What ``generate_views`` and both forms of ``generate_views_batch`` do once their arguments are checked and their camera
+        rows built: ``rows`` latent rows (drawn, or the caller's) against ``sources`` source rows (VAE-encoded in one call, or the
+        caller's latents), one denoising loop in the forward that ``layout`` (the denoiser's ``views`` / ``objects``) names, one
+        decode.  ``rows_of`` / ``sources_of`` word the two row-count errors for the caller ``who``; ``loop`` goes to the denoiser
+        as it is."""
+        height, width = self._size(height, width)
+        if latents is None:
+            latents = self.prepare_latents(rows, 4, height, width, prompt_embeds.dtype, self.device, generator)
+        if latents.shape[0] != rows:
+            raise L.MvdError(f"{who}: {latents.shape[0]} rows of latents for {rows_of}")
+        if source_images is not None:
+            source_image_latents = self._encode_sources(source_images)
+        if source_image_latents is None or source_image_latents.shape[0] != sources:
+            raise L.MvdError(f"{who}: {sources_of}")
+        latents = self._denoise(prompt_embeds, latents=latents, source_camera=source_camera, target_camera=target_camera,
+                                source_image_latents=source_image_latents, **loop, **layout)
+        return self._images(latents, output_type, return_dict)
+
     # ------------------------------------------------------------------ pipeline.py:12-186
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, height: Optional[int] = None, width: Optional[int] = None,
@@ -240,42 +295,21 @@ class MVDPipeline:
         if negative_prompt_embeds is None and negative_prompt is not None:       # :64-75
             negative_prompt_embeds = self._encode_prompt(negative_prompt)
 
-        height = height or self.unet.config.sample_size * self.vae_scale_factor  # :82-83
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        height, width = self._size(height, width)                                # :82-83
         if latents is None:                                                      # :85-95
             latents = self.prepare_latents(batch_size * num_images_per_prompt, 4, height, width, prompt_embeds.dtype, dev,
                                            generator)
 
         if source_images is not None:                                            # :100-117
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
-                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
-            si = source_images.to(device=dev)
-            if bool(si.min() >= 0) and bool(si.max() <= 1):                      # one host sync, outside the loop
-                si = 2 * si - 1
-            if si.shape[0] < batch_size:
-                si = si.repeat(batch_size // si.shape[0], 1, 1, 1)
-            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
+            source_image_latents = self._encode_sources(source_images, repeat_to=batch_size)
 
-        den = MVDDenoiser(self.unet, self.scheduler)
-        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
-                      latents=latents, source_camera=source_camera, target_camera=target_camera,
-                      source_image_latents=source_image_latents, generator=generator if isinstance(generator, torch.Generator) else None,
-                      noise_per_step=noise_per_step, callback=callback, callback_steps=callback_steps,
-                      cross_attention_kwargs=cross_attention_kwargs or {}, guidance_rescale=guidance_rescale)
-
-        if output_type == "latent":
-            image = latents
-        else:                                                                    # :168-181
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
-            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample
-            image = (image / 2 + 0.5).clamp(0, 1)
-            if output_type == "pil":
-                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
-        if not return_dict:
-            return image
-        return {"images": image}
+        latents = self._denoise(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
+                                latents=latents, source_camera=source_camera, target_camera=target_camera,
+                                source_image_latents=source_image_latents,
+                                generator=generator if isinstance(generator, torch.Generator) else None,
+                                noise_per_step=noise_per_step, callback=callback, callback_steps=callback_steps,
+                                cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale)
+        return self._images(latents, output_type, return_dict)
 
     @torch.no_grad()
     def generate_views(self, prompt: Optional[str] = None, source_images: Optional[torch.Tensor] = None,
@@ -306,7 +340,6 @@ class MVDPipeline:
         ``noise_per_step[i]`` = (V, 4, h, w) whose row v is what view v's call gets as ``noise_per_step[i]``; DDIM (eta 0) and
         DPM-Solver++ take no step noise.  The camera encoder's per-call random projection (Q1) is drawn once per forward for all
         views; the per-view calls draw one each unless ``unet.fourier_projection`` pins it."""
-        dev = self.device
         if target_cameras is None or target_cameras.dim() != 3:
             raise L.MvdError("generate_views: target_cameras must be (V, 3|4, 4)")
         V = target_cameras.shape[0]
@@ -320,46 +353,20 @@ class MVDPipeline:
             negative_prompt_embeds = self._encode_prompt(negative_prompt)
         if prompt_embeds.shape[0] != 1:
             raise L.MvdError(f"generate_views: one prompt for the one object, got {prompt_embeds.shape[0]} rows of prompt_embeds")
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        if latents is None:
-            latents = self.prepare_latents(V, 4, height, width, prompt_embeds.dtype, dev, generator)
-        if latents.shape[0] != V:
-            raise L.MvdError(f"generate_views: {latents.shape[0]} rows of latents for {V} target cameras")
-        if source_images is not None:                                             # VAE-encoded once
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
-                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
-            si = source_images.to(device=dev)
-            if bool(si.min() >= 0) and bool(si.max() <= 1):
-                si = 2 * si - 1
-            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
-        if source_image_latents is None or source_image_latents.shape[0] != 1:
-            raise L.MvdError("generate_views: ONE source image (source_images or source_image_latents with one row)")
         if source_camera is None:
             raise L.MvdError("generate_views: source_camera is required")
         src = source_camera if source_camera.dim() == 3 else source_camera.unsqueeze(0)
         if src.shape[0] != 1 or src.shape[1:] != target_cameras.shape[1:]:
             raise L.MvdError(f"generate_views: source_camera {tuple(source_camera.shape)} vs target_cameras {tuple(target_cameras.shape)}")
-        den = MVDDenoiser(self.unet, self.scheduler)
-        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
-                      latents=latents, source_camera=src.expand(V, -1, -1), target_camera=target_cameras,
-                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
-                      guidance_rescale=guidance_rescale, views=V)
-        if output_type == "latent":
-            image = latents
-        else:
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
-            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of V rows
-            image = (image / 2 + 0.5).clamp(0, 1)
-            if output_type == "pil":
-                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
-        if not return_dict:
-            return image
-        return {"images": image}
-
+        return self._turntable(
+            prompt_embeds, src.expand(V, -1, -1), target_cameras, dict(views=V), who="generate_views",
+            rows=V, rows_of=f"{V} target cameras",
+            sources=1, sources_of="ONE source image (source_images or source_image_latents with one row)",
+            source_images=source_images, source_image_latents=source_image_latents, height=height, width=width, generator=generator,
+            latents=latents, output_type=output_type, return_dict=return_dict, num_inference_steps=num_inference_steps,
+            guidance_scale=guidance_scale, negative_prompt_embeds=negative_prompt_embeds, noise_per_step=noise_per_step,
+            callback=callback, callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs,
+            guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def generate_views_batch(self, prompts: Optional[List[str]] = None, source_images: Optional[torch.Tensor] = None,
@@ -393,7 +400,6 @@ class MVDPipeline:
         gets V_o views, R = sum V_o.  Prompts, sources and source cameras stay one per object; ``latents``, a generator list,
         ``noise_per_step[i]`` and the returned images have R rows, object-major (row sum(V_0 .. V_{o-1}) + v); every step is one
         ragged forward, which is the R independent calls.  Equal counts give what the tensor form gives, bit for bit."""
-        dev = self.device
         if prompts is not None and (isinstance(prompts, str) or not isinstance(prompts, (list, tuple))):
             raise L.MvdError("generate_views_batch: prompts must be a list of strings, one per object")
         if prompts is None and prompt_embeds is None:
@@ -413,106 +419,42 @@ class MVDPipeline:
                 negative_prompt_embeds = negative_prompt_embeds.expand(O, -1, -1)
             if negative_prompt_embeds.shape[0] != O:
                 raise L.MvdError(f"generate_views_batch: {negative_prompt_embeds.shape[0]} rows of negative_prompt_embeds for {O} objects")
-        if isinstance(target_cameras, (list, tuple)):
-            return self._generate_views_ragged(list(target_cameras), O, prompt_embeds, negative_prompt_embeds, source_images,
-                                               source_image_latents, source_cameras, height, width, num_inference_steps,
-                                               guidance_scale, generator, latents, output_type, return_dict, callback,
-                                               callback_steps, cross_attention_kwargs, noise_per_step, guidance_rescale)
-        if target_cameras is None or target_cameras.dim() not in (3, 4):
-            raise L.MvdError("generate_views_batch: target_cameras must be (O, V, 3|4, 4) or (V, 3|4, 4)")
-        tgt = target_cameras if target_cameras.dim() == 4 else target_cameras.unsqueeze(0).expand(O, -1, -1, -1)
-        if tgt.shape[0] != O:
-            raise L.MvdError(f"generate_views_batch: target_cameras for {tgt.shape[0]} objects, prompts for {O}")
-        V = tgt.shape[1]
-        if source_cameras is None or source_cameras.dim() != 3 or source_cameras.shape[0] != O or source_cameras.shape[1:] != tgt.shape[2:]:
-            raise L.MvdError(f"generate_views_batch: source_cameras must be ({O}, {tgt.shape[2]}, 4), one per object")
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        if latents is None:
-            latents = self.prepare_latents(O * V, 4, height, width, prompt_embeds.dtype, dev, generator)
-        if latents.shape[0] != O * V:
-            raise L.MvdError(f"generate_views_batch: {latents.shape[0]} rows of latents for {O} objects x {V} views")
-        if source_images is not None:                                             # the O sources in one VAE call
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
-                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
-            si = source_images.to(device=dev)
-            if bool(si.min() >= 0) and bool(si.max() <= 1):
-                si = 2 * si - 1
-            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
-        if source_image_latents is None or source_image_latents.shape[0] != O:
-            raise L.MvdError(f"generate_views_batch: one source image per object ({O} rows of source_images or source_image_latents)")
-        den = MVDDenoiser(self.unet, self.scheduler)
-        one = O == 1                  # (one object: generate_views' forward, which is the same function)
-        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
-                      latents=latents, source_camera=source_cameras.repeat_interleave(V, 0), target_camera=tgt.reshape(O * V, *tgt.shape[2:]),
-                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
-                      guidance_rescale=guidance_rescale, views=V,
-                      objects=None if one else O)
-        if output_type == "latent":
-            image = latents
-        else:
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
-            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of O * V rows
-            image = (image / 2 + 0.5).clamp(0, 1)
-            if output_type == "pil":
-                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
-        if not return_dict:
-            return image
-        return {"images": image}
+        def check_source_cameras(cam_shape):
+            if source_cameras is None or source_cameras.dim() != 3 or source_cameras.shape[0] != O or source_cameras.shape[1:] != cam_shape:
+                raise L.MvdError(f"generate_views_batch: source_cameras must be ({O}, {cam_shape[0]}, 4), one per object")
 
-    @torch.no_grad()
-    def _generate_views_ragged(self, cams, O, prompt_embeds, negative_prompt_embeds, source_images, source_image_latents, source_cameras,
-                               height, width, num_inference_steps, guidance_scale, generator, latents, output_type, return_dict,
-                               callback, callback_steps, cross_attention_kwargs, noise_per_step, guidance_rescale=0.0):
-        """``generate_views_batch`` with a list of per-object target cameras (the prompts are encoded already)."""
-        dev = self.device
-        if len(cams) != O:
-            raise L.MvdError(f"generate_views_batch: target_cameras for {len(cams)} objects, prompts for {O}")
-        for c in cams:
-            if not isinstance(c, torch.Tensor) or c.dim() != 3 or c.shape[0] < 1 or c.shape[1:] != cams[0].shape[1:]:
-                raise L.MvdError("generate_views_batch: a list of target_cameras holds one (V_o, 3|4, 4) tensor per object, V_o >= 1")
-        counts = tuple(int(c.shape[0]) for c in cams)
-        R = sum(counts)
-        if source_cameras is None or source_cameras.dim() != 3 or source_cameras.shape[0] != O or source_cameras.shape[1:] != cams[0].shape[1:]:
-            raise L.MvdError(f"generate_views_batch: source_cameras must be ({O}, {cams[0].shape[1]}, 4), one per object")
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        if latents is None:
-            latents = self.prepare_latents(R, 4, height, width, prompt_embeds.dtype, dev, generator)
-        if latents.shape[0] != R:
-            raise L.MvdError(f"generate_views_batch: {latents.shape[0]} rows of latents for the {R} views of counts {counts}")
-        if source_images is not None:                                             # the O sources in one VAE call
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE: pass source_image_latents (scaled by the VAE scaling factor) "
-                                 "instead of source_images, or attach mvd_amd.vae.AutoencoderKLHIP")
-            si = source_images.to(device=dev)
-            if bool(si.min() >= 0) and bool(si.max() <= 1):
-                si = 2 * si - 1
-            source_image_latents = self.vae.encode(si).latent_dist.sample() * self.vae.config.scaling_factor
-        if source_image_latents is None or source_image_latents.shape[0] != O:
-            raise L.MvdError(f"generate_views_batch: one source image per object ({O} rows of source_images or source_image_latents)")
-        den = MVDDenoiser(self.unet, self.scheduler)
-        src = torch.cat([source_cameras[o:o + 1].expand(counts[o], -1, -1) for o in range(O)])
-        latents = den(prompt_embeds, num_inference_steps, guidance_scale, negative_prompt_embeds=negative_prompt_embeds,
-                      latents=latents, source_camera=src, target_camera=torch.cat([c.to(src.device) for c in cams]),
-                      source_image_latents=source_image_latents, noise_per_step=noise_per_step, callback=callback,
-                      callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs or {},
-                      guidance_rescale=guidance_rescale, views=counts)
-        if output_type == "latent":
-            image = latents
+        # the camera rows, object-major: an object's source camera on each of its views' rows
+        if isinstance(target_cameras, (list, tuple)):                             # ragged: one (V_o, 3|4, 4) tensor per object
+            cams = list(target_cameras)
+            if len(cams) != O:
+                raise L.MvdError(f"generate_views_batch: target_cameras for {len(cams)} objects, prompts for {O}")
+            for c in cams:
+                if not isinstance(c, torch.Tensor) or c.dim() != 3 or c.shape[0] < 1 or c.shape[1:] != cams[0].shape[1:]:
+                    raise L.MvdError("generate_views_batch: a list of target_cameras holds one (V_o, 3|4, 4) tensor per object, V_o >= 1")
+            counts = tuple(int(c.shape[0]) for c in cams)
+            check_source_cameras(cams[0].shape[1:])
+            src = torch.cat([source_cameras[o:o + 1].expand(counts[o], -1, -1) for o in range(O)])
+            tgt = torch.cat([c.to(src.device) for c in cams])
+            rows, rows_of, layout = sum(counts), f"the {sum(counts)} views of counts {counts}", dict(views=counts)
         else:
-            if self.vae is None:
-                raise L.MvdError("MVDPipeline has no VAE to decode with: use output_type='latent'")
-            image = self.vae.decode(latents / self.vae.config.scaling_factor).sample      # one decode of R rows
-            image = (image / 2 + 0.5).clamp(0, 1)
-            if output_type == "pil":
-                image = self.numpy_to_pil(image.cpu().permute(0, 2, 3, 1).float().numpy())
-        if not return_dict:
-            return image
-        return {"images": image}
+            if target_cameras is None or target_cameras.dim() not in (3, 4):
+                raise L.MvdError("generate_views_batch: target_cameras must be (O, V, 3|4, 4) or (V, 3|4, 4)")
+            tgt = target_cameras if target_cameras.dim() == 4 else target_cameras.unsqueeze(0).expand(O, -1, -1, -1)
+            if tgt.shape[0] != O:
+                raise L.MvdError(f"generate_views_batch: target_cameras for {tgt.shape[0]} objects, prompts for {O}")
+            V = tgt.shape[1]
+            check_source_cameras(tgt.shape[2:])
+            src, tgt = source_cameras.repeat_interleave(V, 0), tgt.reshape(O * V, *tgt.shape[2:])
+            # (one object: generate_views' forward, which is the same function)
+            rows, rows_of, layout = O * V, f"{O} objects x {V} views", dict(views=V, objects=None if O == 1 else O)
+        return self._turntable(
+            prompt_embeds, src, tgt, layout, who="generate_views_batch", rows=rows, rows_of=rows_of,
+            sources=O, sources_of=f"one source image per object ({O} rows of source_images or source_image_latents)",
+            source_images=source_images, source_image_latents=source_image_latents, height=height, width=width, generator=generator,
+            latents=latents, output_type=output_type, return_dict=return_dict, num_inference_steps=num_inference_steps,
+            guidance_scale=guidance_scale, negative_prompt_embeds=negative_prompt_embeds, noise_per_step=noise_per_step,
+            callback=callback, callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs,
+            guidance_rescale=guidance_rescale)
 
 
 def _scheduler_from_snapshot(path) -> "Any":

@@ -48,8 +48,46 @@ def SNR_to_betas(snr):
 
 
 class _ForwardDiffusion:
-    """diffusers' ``add_noise`` / ``get_velocity`` (the forward process q(x_t | x_0) of the scheduler's own ``alphas_cumprod``)
-    through ``mvd_op_add_noise``: one fused pass, the per-sample coefficients looked up on the device."""
+    """What the three scheduler classes share.  The trained schedule, built by the same torch ops for every class, so
+    ShiftSNRScheduler's betas give bit-identical ``alphas_cumprod`` whichever class receives them; ``from_config``; the uniform
+    ``previous_timestep``; the draw of a step's noise.  And diffusers' ``add_noise`` / ``get_velocity`` (the forward process
+    q(x_t | x_0) of the scheduler's own ``alphas_cumprod``) through ``mvd_op_add_noise``: one fused pass, the per-sample
+    coefficients looked up on the device."""
+
+    init_noise_sigma = 1.0
+
+    def _init_schedule(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas):
+        if trained_betas is not None:
+            self.betas = torch.as_tensor(np.asarray(trained_betas), dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            raise ValueError(f"unsupported beta_schedule {beta_schedule}")
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.one = torch.tensor(1.0)
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
+
+    @classmethod
+    def from_config(cls, config: Any, **overrides):
+        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
+        d.update(overrides)
+        return cls(**d)
+
+    def previous_timestep(self, t: int) -> int:
+        n = self.num_inference_steps or self.config.num_train_timesteps
+        return t - self.config.num_train_timesteps // n
+
+    @staticmethod
+    def _step_noise(sample, sigma, noise, generator):
+        """The noise of one step: the caller's, or, when the step has a noise term and the caller gave none, a draw from
+        ``generator`` (torch's global RNG of the sample's device when None)."""
+        if noise is None and sigma != 0.0:
+            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        return noise
 
     def noise_tables(self, device):
         """(sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)) as fp32 vectors on ``device``: built once per (scheduler, device)."""
@@ -97,28 +135,9 @@ class DDPMScheduler(_ForwardDiffusion):
                                       beta_schedule=beta_schedule, prediction_type=prediction_type,
                                       variance_type=variance_type, clip_sample=clip_sample,
                                       timestep_spacing=timestep_spacing, steps_offset=steps_offset)
-        if trained_betas is not None:
-            self.betas = torch.as_tensor(np.asarray(trained_betas), dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        elif beta_schedule == "linear":
-            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        else:
-            raise ValueError(f"unsupported beta_schedule {beta_schedule}")
+        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
         if variance_type != "fixed_small" or clip_sample:
             raise ValueError("only variance_type='fixed_small' without sample clipping is implemented (SD-2.1 config)")
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.one = torch.tensor(1.0)
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
-        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
-
-    @classmethod
-    def from_config(cls, config: Any, **overrides):
-        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
-        d.update(overrides)
-        return cls(**d)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T = self.config.num_train_timesteps
@@ -131,10 +150,6 @@ class DDPMScheduler(_ForwardDiffusion):
         else:
             raise ValueError(f"unsupported timestep_spacing {self.config.timestep_spacing}")
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-
-    def previous_timestep(self, t: int) -> int:
-        n = self.num_inference_steps or self.config.num_train_timesteps
-        return t - self.config.num_train_timesteps // n
 
     def step_coefficients(self, t: int):
         """(c_x0_from_out, c_x0_from_sample, c_prev_from_x0, c_prev_from_sample, sigma) for one DDPM step:
@@ -163,9 +178,7 @@ class DDPMScheduler(_ForwardDiffusion):
         """One ancestral DDPM step on the GPU (fused HIP kernel); returns an object with ``prev_sample``."""
         from . import ops
         c0, c1, c2, c3, sigma = self.step_coefficients(int(timestep))
-        if noise is None and sigma != 0.0:
-            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        prev = ops.ddpm_step(model_output, sample, noise, c0, c1, c2, c3, sigma)
+        prev = ops.ddpm_step(model_output, sample, self._step_noise(sample, sigma, noise, generator), c0, c1, c2, c3, sigma)
         return SimpleNamespace(prev_sample=prev)
 
     def step_guided_rescaled(self, uncond_cond: torch.Tensor, guidance_scale: float, guidance_rescale: float, timestep,
@@ -177,8 +190,7 @@ class DDPMScheduler(_ForwardDiffusion):
         from . import ops
         _check_rescale(guidance_rescale)
         c0, c1, c2, c3, sigma = self.step_coefficients(int(timestep))
-        if noise is None and sigma != 0.0:
-            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        noise = self._step_noise(sample, sigma, noise, generator)
         prev = ops.sampler_step_rescaled(uncond_cond, sample, guidance_scale, guidance_rescale, c0, c1, c3, c2, 0.0, sigma,
                                          noise=noise if sigma != 0.0 else None)
         return SimpleNamespace(prev_sample=prev)
@@ -199,39 +211,19 @@ def _unsupported(what: str):
 
 
 class _SolverSchedule(_ForwardDiffusion):
-    """What the DDIM and DPM-Solver++ classes share: the trained schedule (built by the same torch ops as
-    ``DDPMScheduler``, so ShiftSNRScheduler's betas give bit-identical ``alphas_cumprod``), ``from_config`` and the
-    timestep grid of diffusers' ``set_timesteps``."""
+    """What the DDIM and DPM-Solver++ classes share: the fp64 host copy of the trained schedule, the timestep grid of
+    diffusers' ``set_timesteps`` and the launch of the step kernel."""
 
     order = 1                       # diffusers' attribute (one model evaluation per step)
-    init_noise_sigma = 1.0
 
-    def _init_schedule(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
-                       timestep_spacing):
+    def _init_solver(self, num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                     timestep_spacing):
         if prediction_type not in _PREDICTION_TYPES:
             _unsupported(f"prediction_type={prediction_type!r}")
         if timestep_spacing not in _SPACINGS:
             _unsupported(f"timestep_spacing={timestep_spacing!r}")
-        if trained_betas is not None:
-            self.betas = torch.as_tensor(np.asarray(trained_betas), dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        elif beta_schedule == "linear":
-            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        else:
-            raise ValueError(f"unsupported beta_schedule {beta_schedule}")
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
         self._acp = self.alphas_cumprod.double().numpy()       # host copy: the coefficients never touch a device tensor
-        self.one = torch.tensor(1.0)
-        self.num_inference_steps = None
-        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
-
-    @classmethod
-    def from_config(cls, config: Any, **overrides):
-        d = dict(vars(config)) if not isinstance(config, dict) else dict(config)
-        d.update(overrides)
-        return cls(**d)
 
     def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
         return sample
@@ -256,26 +248,21 @@ class _SolverSchedule(_ForwardDiffusion):
             return -sigma_bar / alpha, 1.0 / alpha
         return -sigma_bar, alpha                                # v_prediction
 
-    def _launch(self, model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None):
+    def _launch(self, model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None,
+                guidance_rescale=0.0):
+        """One step kernel.  ``guidance_scale`` None: a plain step of ``model_out``; else a guided step of the stacked
+        [uncond | cond] -- with ``guidance_rescale`` > 0 and guidance active the rescaled kernel, else (as in diffusers, where
+        the argument is then ignored) exactly the call made without it."""
         from . import ops
-        a0, a1, p, q, r, sigma = coeffs
-        if sigma != 0.0 and noise is None:
-            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        return ops.sampler_step(model_out, sample, a0, a1, p, q, r, sigma, x0_prev=x0_prev if r != 0.0 else None,
-                                noise=noise if sigma != 0.0 else None, guidance_scale=guidance_scale, x0_out=x0_out)
-
-    def _launch_guided(self, model_out, guidance_scale, guidance_rescale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None):
-        """``_launch`` of a guided step; with ``guidance_rescale`` > 0 and guidance active the rescaled kernel, else (as in
-        diffusers, where the argument is then ignored) exactly the call made without it."""
         _check_rescale(guidance_rescale)
-        if not (guidance_rescale > 0.0 and guidance_scale > 1.0):
-            return self._launch(model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=x0_prev, x0_out=x0_out)
-        from . import ops
         a0, a1, p, q, r, sigma = coeffs
-        if sigma != 0.0 and noise is None:
-            noise = torch.randn(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        return ops.sampler_step_rescaled(model_out, sample, guidance_scale, guidance_rescale, a0, a1, p, q, r, sigma,
-                                         x0_prev=x0_prev if r != 0.0 else None, noise=noise if sigma != 0.0 else None, x0_out=x0_out)
+        noise = self._step_noise(sample, sigma, noise, generator) if sigma != 0.0 else None
+        x0_prev = x0_prev if r != 0.0 else None
+        if guidance_rescale > 0.0 and guidance_scale is not None and guidance_scale > 1.0:
+            return ops.sampler_step_rescaled(model_out, sample, guidance_scale, guidance_rescale, a0, a1, p, q, r, sigma,
+                                             x0_prev=x0_prev, noise=noise, x0_out=x0_out)
+        return ops.sampler_step(model_out, sample, a0, a1, p, q, r, sigma, x0_prev=x0_prev, noise=noise,
+                                guidance_scale=guidance_scale, x0_out=x0_out)
 
 
 class DDIMScheduler(_SolverSchedule):
@@ -295,18 +282,14 @@ class DDIMScheduler(_SolverSchedule):
                                       beta_schedule=beta_schedule, clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
                                       steps_offset=steps_offset, prediction_type=prediction_type, thresholding=thresholding,
                                       timestep_spacing=timestep_spacing, rescale_betas_zero_snr=rescale_betas_zero_snr)
-        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
-                            timestep_spacing)
+        self._init_solver(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                          timestep_spacing)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         self.num_inference_steps = num_inference_steps
         ts = torch.from_numpy(self._grid(num_inference_steps, 0))
         self.timesteps = ts.to(device) if device is not None else ts
-
-    def previous_timestep(self, t: int) -> int:
-        n = self.num_inference_steps or self.config.num_train_timesteps
-        return t - self.config.num_train_timesteps // n
 
     def step_coefficients(self, t: int, eta: float = 0.0):
         """(a0, a1, p, q, r, sigma) of one DDIM step: x0 = a0*model_out + a1*sample ;
@@ -342,7 +325,8 @@ class DDIMScheduler(_SolverSchedule):
         """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.
         ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch."""
         c = self.step_coefficients(int(timestep), eta)
-        return SimpleNamespace(prev_sample=self._launch_guided(uncond_cond, guidance_scale, guidance_rescale, c, sample, noise, generator))
+        return SimpleNamespace(prev_sample=self._launch(uncond_cond, guidance_scale, c, sample, noise, generator,
+                                                        guidance_rescale=guidance_rescale))
 
 
 class DPMSolverMultistepScheduler(_SolverSchedule):
@@ -384,8 +368,8 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
                                       final_sigmas_type=final_sigmas_type, lambda_min_clipped=lambda_min_clipped,
                                       variance_type=variance_type, timestep_spacing=timestep_spacing, steps_offset=steps_offset,
                                       rescale_betas_zero_snr=rescale_betas_zero_snr)
-        self._init_schedule(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
-                            timestep_spacing)
+        self._init_solver(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                          timestep_spacing)
         self.sigmas = None
         self._hist = {}             # (shape, device) -> the x0 history buffer
         self._hist_key = None       # the buffer the previous step of this schedule wrote
@@ -473,10 +457,9 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
                 hist = self._hist[key] = torch.empty(sample.shape, device=sample.device, dtype=torch.float32)
         if c[4] != 0.0 and self._hist_key != key:
             raise ValueError("a second-order step needs the previous step's x0 of the same shape and device")
-        if guidance_scale is None:
-            out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist)
-        else:
-            out = self._launch_guided(model_output, guidance_scale, guidance_rescale, c, sample, None, None, x0_prev=hist, x0_out=hist)
+        # (the keyword goes only with a rescale: a stand-in for ``_launch`` of its leading parameters alone keeps working)
+        out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist,
+                           **({"guidance_rescale": guidance_rescale} if guidance_rescale else {}))
         self._hist_key = key if hist is not None else None
         self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
         self._step_index = i + 1
