@@ -188,6 +188,17 @@ int mvd_engine_set_graph(mvd_engine_t* e, int enable);
  * base UNet's (frozen base), the encoder pass can read weight set 0 and set 1 need not be registered at all. */
 int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable);
 
+/* FreeU (Si et al., CVPR 2024; diffusers-0.32.2 UNet2DConditionModel.enable_freeu(s1, s2, b1, b2), restated) on the MAIN UNet
+ * pass: in front of every resnet of up block 0 (b1, s1) and of up block 1 (b2, s2) the hidden input and the skip input are
+ * replaced by mvd_op_freeu's two outputs (below); up blocks 2 and 3 are untouched.  The encoder pass, the Q2 statistics, the
+ * reference K/V and the reference cache never depend on the setting (also with mvd_engine_share_encoder_weights).  The state
+ * lives on the engine, beside the argument block, which is as it was; every forward entry honours it, and the four
+ * mvd_engine_workspace_bytes* entries size the forward of the CURRENT setting (a workspace bound before FreeU was set may be
+ * too small: the forward then says so before it launches anything).  All four values must be positive and finite, else -1.
+ * Setting or clearing drops the captured hipGraphs.  Clear (the default): the launches of a forward are what they were. */
+int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2);
+int mvd_engine_clear_freeu(mvd_engine_t* e);
+
 /* Per-kernel-class timing with HIP events on the launch stream (measurement only; off by default).
  * classes = kernels: 0..5, 12 lock-step GEMM/conv tile configs (gemm.hip); ping-pong 256x320 kernels (gemm_pp.hip): 7 dense,
  * 13 implicit-GEMM 3x3 convolution, 14 split-K, 6 GEGLU; 8..11 attention (1,2,4,8 waves); 16 groupnorm; 17 layernorm. */
@@ -408,6 +419,18 @@ int mvd_op_sampler_step_rescaled(const float* model_out, float guidance_scale, f
  * lanes per wave, 16-byte vectors per thread kept in registers (0: the row is streamed twice)}: thread t of the row's one
  * workgroup owns the vectors t, t + threads, t + 2*threads, ... of the row. */
 int mvd_debug_cfg_rescale_plan(int64_t n_row, int* out);
+
+/* FreeU on the two inputs of an up-block resnet, ONE launch.  hidden [B][H*W][C] and skip [B][H*W][Cs] are bf16, token-major:
+ *   hidden_out = hidden with channels [0, C / 2) multiplied by b (fp32 product, one rounding to bf16), the rest bit for bit;
+ *   skip_out   = skip with the spatial frequencies {0, -1} x {0, -1} of every (image, channel) map multiplied by s -- diffusers'
+ *                fourier_filter with threshold 1 -- as the closed form
+ *                  x + (s - 1) / (H W) * sum_{k,l in {0,1}} (a_kl cos phi_kl + b_kl sin phi_kl),  phi_kl = 2 pi (k h / H + l w / W),
+ *                a_kl / b_kl the cosine / sine sums of the map: fp32 sums in a fixed order (no atomics: the same bits every
+ *                run), the formula in fp32, one rounding to bf16.  s == 1 copies the skip map bit for bit.
+ * -1 (mvd_last_error), before anything is launched, for H or W < 2, C or Cs no positive multiple of 8, b or s not positive and
+ * finite, a pointer that is null or not 16-byte aligned, or an output that overlaps an input or the other output. */
+int mvd_op_freeu(const void* hidden, int C, const void* skip, int Cs, int B, int H, int W, float b, float s, void* hidden_out,
+                 void* skip_out, void* stream);
 
 /* ---- checkpoint scoring around the UNet, fp32 ------------------------------------------------ */
 /* Conventions of the helpers above; in addition every quantity that depends on a sample's timestep is read ON THE DEVICE

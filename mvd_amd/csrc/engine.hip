@@ -80,6 +80,8 @@ struct mvd_engine {
     return 0;
   }
   bool share_encoder = false;       // N4: the encoder pass reads weight set 0 (base UNet == image-encoder UNet)
+  // FreeU (mvd_engine_set_freeu): the main pass's up blocks 0 and 1 read re-weighted hidden / skip inputs; freeu_b / freeu_s by block
+  bool freeu_on = false; float freeu_b[2] = {1.f, 1.f}, freeu_s[2] = {1.f, 1.f};
   // hipGraph replay of whole forwards (mvd_engine_set_graph): one instantiated graph per distinct (arguments, cache state)
   struct HostState {                  // what a forward leaves behind on the host side
     std::vector<bf16_t*> refkv, feat_keep;
@@ -543,6 +545,7 @@ struct PassOpts {
   // mvd_unet_forward_ragged, main pass: device tables of B entries (kernels.h MvdAttnArgs::kv_index) -- row r reads reference K/V
   // element kvi_ref[r] of the kv_elems = g * O elements [object][half] and text row kvi_text[r]; views / objects are 0 then
   const int* kvi_ref = nullptr; const int* kvi_text = nullptr; int kv_elems = 0;
+  bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
@@ -746,7 +749,16 @@ struct UNetPass {
         Act skip = skips.back(); skips.pop_back();
         if (skip.H != h.H || skip.W != h.W) { mvd_set_error("up block %d: skip %dx%d vs hidden %dx%d (odd latent size unsupported)", i, skip.H, skip.W, h.H, h.W); return -13; }
         Act r = c.new_act(B, h.H, h.W, co, true);
-        CHECK(resnet(bk + ".resnets." + std::to_string(j), h, &skip, co, r));
+        if (o.freeu && i < 2) {
+          // FreeU: the resnet (GroupNorm and the folded 1x1 shortcut alike) reads the re-weighted pair; h and skip stay as they were
+          const size_t fm = c.e->tmp.off;
+          Act hf = c.new_act(B, h.H, h.W, h.C, false), sf = c.new_act(B, skip.H, skip.W, skip.C, false);
+          if (!c.dry && !c.err) CHECK(mvd_launch_freeu(h.p, h.C, skip.p, skip.C, B, h.H, h.W, c.e->freeu_b[i], c.e->freeu_s[i], hf.p, sf.p, c.s));
+          CHECK(resnet(bk + ".resnets." + std::to_string(j), hf, &sf, co, r));
+          c.e->tmp.off = fm;
+        } else {
+          CHECK(resnet(bk + ".resnets." + std::to_string(j), h, &skip, co, r));
+        }
         h = r;
         if (i > 0) {
           Act t = c.new_act(B, h.H, h.W, co, true);
@@ -1009,6 +1021,10 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
       if (hw % g) { mvd_set_error("forward: MVD_SHARE_REF: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
     }
   }
+  // FreeU filters the maps of up blocks 0 and 1 (levels n - 1 and n - 2): a map of one row or column has no frequency -1
+  if (e->freeu_on && !ref_only && ((a.height >> (cfg.num_levels - 1)) < 2 || (a.width >> (cfg.num_levels - 1)) < 2)) {
+    mvd_set_error("forward: FreeU needs maps of at least 2 x 2 in up block 0, latent %dx%d gives %dx%d", a.height, a.width, a.height >> (cfg.num_levels - 1), a.width >> (cfg.num_levels - 1)); return -1;
+  }
   if (use_cam && a.cam_batch > 0 && (a.cam_batch > a.batch || a.batch % a.cam_batch)) { mvd_set_error("forward: camera batch %d must divide the sample batch %d", a.cam_batch, a.batch); return -1; }
   // the input FiLM uses the 4-wide "output" modulator (mvd_unet.py:74-80, 256-258): any other in_channels is a broadcast
   // error in the reference and would read past the [B][4] scale/shift rows here -- reject before any launch
@@ -1152,6 +1168,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   po.views = V; po.objects = O;
+  po.freeu = e->freeu_on;
   if (rg) { po.views = 0; po.objects = 0; po.kvi_ref = rg->kvi_ref; po.kvi_text = rg->kvi_text; po.kv_elems = rg->g * O; }
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
@@ -1572,6 +1589,22 @@ int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable) {
   if (e) e->drop_graphs();
   if (!e) { mvd_set_error("share_encoder_weights: null engine"); return -1; }
   e->share_encoder = enable != 0;
+  return 0;
+}
+
+// FreeU on the main pass (include/mvd_hip.h).  A graph captured under one setting is never replayed under another: both drop them
+int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2) {
+  if (!e) { mvd_set_error("set_freeu: null engine"); return -1; }
+  const float v[4] = {s1, s2, b1, b2};
+  for (float x : v) if (!(x > 0.f) || !(x < INFINITY)) { mvd_set_error("set_freeu: s1, s2, b1, b2 must be positive and finite, got %g, %g, %g, %g", (double)s1, (double)s2, (double)b1, (double)b2); return -1; }
+  e->drop_graphs();
+  e->freeu_on = true; e->freeu_s[0] = s1; e->freeu_s[1] = s2; e->freeu_b[0] = b1; e->freeu_b[1] = b2;
+  return 0;
+}
+int mvd_engine_clear_freeu(mvd_engine_t* e) {
+  if (!e) { mvd_set_error("clear_freeu: null engine"); return -1; }
+  e->drop_graphs();
+  e->freeu_on = false;
   return 0;
 }
 

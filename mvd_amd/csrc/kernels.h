@@ -205,6 +205,10 @@ int mvd_launch_nchw_to_nhwc(const float* x, int batch, int c, int hw, const floa
                             int ld_ss, bf16_t* y, hipStream_t s);
 int mvd_launch_film(const bf16_t* x, int batch, int hw, int c, const float* scale, const float* shift, int ld_ss,
                     bf16_t* y, hipStream_t s);
+// FreeU (freeu.hip; include/mvd_hip.h mvd_op_freeu): hidden [B][H*W][C] -> channels below C / 2 times b; skip [B][H*W][Cs] ->
+// frequencies {0, -1} x {0, -1} times s.  One launch; every argument is checked before it (-1 and a message)
+int mvd_launch_freeu(const bf16_t* hidden, int C, const bf16_t* skip, int Cs, int B, int H, int W, float b, float s, bf16_t* hidden_out,
+                     bf16_t* skip_out, hipStream_t stream);
 // conv_in: 3x3 pad 1, tiny Cin (<=8) -> Cout, NHWC bf16 in/out, weights fp32 [Cout][3][3][Cin]
 int mvd_launch_conv_in(const bf16_t* x, int batch, int h, int w, int cin, const float* wt, const float* bias,
                        int cout, bf16_t* y, hipStream_t s);

@@ -49,6 +49,9 @@ class MVDEngine:
         self._ws = None
         self._rc = None
         self._ws_key = None
+        self._ws_resize = False
+        self._ws_args = None
+        self.freeu = None                                         # (s1, s2, b1, b2) while FreeU is set
 
     def __del__(self):
         try:
@@ -114,8 +117,12 @@ class MVDEngine:
     # ------------------------------------------------------------------ workspace
     def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0, objects=0, counts=()):
         key = (batch, h, w, text_len, ref_batch, keep_features, views) + ((objects,) if objects else ()) + ((counts,) if counts else ())
-        if self._ws_key == key:
+        if self._ws_key == key and not self._ws_resize:
             return
+        # (FreeU was set since the workspace was sized: the same shape may need more.  Buffers that are large enough stay bound as
+        #  they are -- re-binding would drop the cached reference, which does not depend on the setting)
+        keep_bound = self._ws_key == key
+        self._ws_args = (batch, h, w, text_len, ref_batch, keep_features, views, objects, counts)
         if counts:
             # ragged view counts (mvd_unet_forward_ragged): the counts come beside the argument block, whose `views` stays 0
             a = L.mvd_forward_args_t()
@@ -143,6 +150,9 @@ class MVDEngine:
             rc = L.lib().mvd_engine_refcache_bytes(self._h, ref_batch, h, w, int(keep_features))
             if rc < 0:
                 raise L.MvdError(f"refcache_bytes: {L.last_error()}")
+        self._ws_resize = False
+        if keep_bound and self._ws is not None and self._ws.numel() >= ws:
+            return
         if self._ws is None or self._ws.numel() < ws:
             self._ws = None
             self._ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
@@ -327,6 +337,22 @@ class MVDEngine:
         if enable and getattr(self, "_gstream", None) is None:
             self._gstream = torch.cuda.Stream(device=self.device)
             self._gbufs = {}
+
+    def set_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """FreeU on the main UNet pass (``mvd_engine_set_freeu``; diffusers' ``enable_freeu`` argument order): up block 0 scales
+        the lower half of its backbone channels by ``b1`` and the lowest spatial frequencies of its skip maps by ``s1``, up block 1
+        by ``b2`` / ``s2``.  The encoder pass and the cached reference do not depend on it."""
+        L.call("mvd_engine_set_freeu", self._h, float(s1), float(s2), float(b1), float(b2))
+        self.freeu = (float(s1), float(s2), float(b1), float(b2))
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            # now, not in the next forward: whoever asks reference_cache_valid first gets the answer that holds
+            self._ensure_workspace(*self._ws_args)
+
+    def clear_freeu(self) -> None:
+        """Back to the forward without FreeU (``mvd_engine_clear_freeu``): the launches it made before."""
+        L.call("mvd_engine_clear_freeu", self._h)
+        self.freeu = None
 
     def _staged(self, name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
         shape = tuple(t.shape) if shape is None else tuple(shape)

@@ -153,6 +153,7 @@ class MultiViewUNet(nn.Module):
         self.unet_config = cfg
         self.base_unet = _build_unet(cfg, init)
         _load_named_unet(self.base_unet, pretrained_model_name_or_path, snapshot, "MultiViewUNet")
+        self.base_unet._freeu_main = True       # base_unet.enable_freeu(...) is the reference's call site
         self.config = self.base_unet.config
         self.device = torch.device("cpu")
         self.dtype = dtype
@@ -260,7 +261,29 @@ class MultiViewUNet(nn.Module):
             self.reset_reference_cache()
         if bool(getattr(self, "use_hip_graph", False)) != bool(getattr(self._engine, "_graph", False)):
             self._engine.set_graph(bool(getattr(self, "use_hip_graph", False)))
+        if self.freeu != self._engine.freeu:
+            if self.freeu is None:
+                self._engine.clear_freeu()
+            else:
+                self._engine.set_freeu(*self.freeu)
         return self._engine
+
+    # ------------------------------------------------------------------ FreeU (diffusers' names and argument order)
+    @property
+    def freeu(self):
+        """``(s1, s2, b1, b2)`` while FreeU is enabled, else ``None``; kept on ``base_unet`` (``base_unet.enable_freeu`` is the
+        call the reference's users make)."""
+        return self.base_unet.freeu
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al. 2024; diffusers' ``UNet2DConditionModel.enable_freeu``) on the main UNet pass: up block 0 scales the
+        lower half of its backbone channels by ``b1`` and damps the lowest spatial frequencies of its skip features by ``s1``,
+        up block 1 with ``b2`` / ``s2``.  The image-encoder pass and the cached reference do not depend on it.  SD-2.1:
+        ``enable_freeu(s1=0.9, s2=0.2, b1=1.4, b2=1.6)``."""
+        self.base_unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.base_unet.disable_freeu()
 
     def reset_reference_cache(self):
         """Forget the cached reference K/V (Q5): the next forward with image conditioning re-runs the encoder pass."""

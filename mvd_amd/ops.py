@@ -633,6 +633,25 @@ def cfg_rescale_partition(n_row):
     return sorted(offs)
 
 
+def freeu(hidden, skip, H, W, b, s, hidden_out=None, skip_out=None):
+    """FreeU (diffusers' ``apply_freeu``, threshold 1) on the two inputs of an up-block resnet, ONE launch (``mvd_op_freeu``).
+    ``hidden`` (B, H*W, C) and ``skip`` (B, H*W, Cs) bf16, token-major -> ``(hidden', skip')``: channels [0, C // 2) of
+    ``hidden`` times ``b`` (the rest bit for bit), and ``skip`` with its spatial frequencies {0, -1} x {0, -1} times ``s``.  The
+    outputs must overlap neither input nor each other."""
+    _bf16(hidden, skip, hidden_out, skip_out)
+    if hidden.dim() != 3 or skip.dim() != 3 or hidden.shape[:2] != skip.shape[:2] or hidden.shape[1] != int(H) * int(W):
+        raise L.MvdError(f"freeu: expected hidden (B, H*W, C) and skip (B, H*W, Cs) with H*W = {int(H) * int(W)}, got "
+                         f"{tuple(hidden.shape)} and {tuple(skip.shape)}")
+    if hidden_out is None:
+        hidden_out = torch.empty_like(hidden)
+    if skip_out is None:
+        skip_out = torch.empty_like(skip)
+    assert hidden_out.numel() == hidden.numel() and skip_out.numel() == skip.numel()
+    L.call("mvd_op_freeu", _p(hidden), hidden.shape[2], _p(skip), skip.shape[2], hidden.shape[0], int(H), int(W), float(b), float(s),
+           _p(hidden_out), _p(skip_out), _s())
+    return hidden_out, skip_out
+
+
 PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")       # prediction_type of mvd_op_noise_loss, by index
 
 

@@ -176,6 +176,14 @@ class MVDPipeline:
     def progress_bar(self, iterable):
         return iterable
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' ``StableDiffusionPipeline.enable_freeu``: FreeU on the UNet's main pass for every call that follows
+        (``MultiViewUNet.enable_freeu``).  SD-2.1: ``s1=0.9, s2=0.2, b1=1.4, b2=1.6``."""
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
         """StableDiffusionPipeline.prepare_latents: N(0,1) of the latent shape times ``init_noise_sigma``."""
         shape = (batch_size, num_channels_latents, int(height) // self.vae_scale_factor, int(width) // self.vae_scale_factor)

@@ -154,3 +154,26 @@ class UNet2DConditionParams(_NoForward):
 
     def enable_gradient_checkpointing(self):   # accepted for API compatibility; inference-only engine
         pass
+
+    # diffusers' UNet2DConditionModel.enable_freeu / disable_freeu (same names and argument order).  The mirror only keeps the
+    # setting: the MultiViewUNet that owns this module as its ``base_unet`` hands it to the engine before its next forward.
+    freeu = None                # (s1, s2, b1, b2) while enabled
+    _freeu_main = False         # set by MultiViewUNet on its base_unet: the UNet of the main pass
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        if not self._freeu_main:
+            raise ValueError("enable_freeu: FreeU applies to the main pass only -- call it on MultiViewUNet.base_unet (the image "
+                             "encoder's UNet runs without it, as in the reference)")
+        self.freeu = check_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.freeu = None
+
+
+def check_freeu(s1, s2, b1, b2):
+    """(s1, s2, b1, b2) as floats; ValueError unless all four are positive and finite."""
+    import math
+    vals = tuple(float(v) for v in (s1, s2, b1, b2))
+    if not all(math.isfinite(v) and v > 0.0 for v in vals):
+        raise ValueError(f"FreeU: s1, s2, b1, b2 must be positive and finite, got {vals}")
+    return vals

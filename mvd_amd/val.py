@@ -14,7 +14,8 @@ Configuration keys read (the reference ships no ``config/infer_config.yaml``; th
 ``ref_scale``, ``clip_model_name`` (optional); and this project's own optional keys ``cache_dir`` (local huggingface cache of the
 architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics``, ``metric_weights`` (a
 mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
-pipeline's argument of that name, ``--guidance-rescale``).
+pipeline's argument of that name, ``--guidance-rescale``) and ``freeu`` (default absent: off; ``"s1,s2,b1,b2"`` or four numbers in
+diffusers' ``enable_freeu`` order, ``--freeu``).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
 of the per-metric aggregates; ``clip_score`` is a per-batch value copied to each of the batch's samples and aggregated apart;
@@ -262,6 +263,10 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     all_results, batch_metrics = [], []
     # off (0.0, the default): the pipeline calls are the ones made before the key existed, argument for argument
     rescale = {"guidance_rescale": float(config["guidance_rescale"])} if float(config.get("guidance_rescale", 0.0) or 0.0) != 0.0 else {}
+    # FreeU: absent (the default), the pipeline is not touched
+    freeu = parse_freeu(config.get("freeu"))
+    if freeu is not None:
+        pipeline.enable_freeu(*freeu)
     with torch.no_grad():
         for batch_idx, batch in enumerate(dataloader):
             try:
@@ -403,6 +408,18 @@ def save_results(all_results: List[Dict], overall_metrics: Dict, output_dir: Pat
             w.writerow([metric, value])
 
 
+def parse_freeu(value):
+    """The ``freeu`` config key / ``--freeu`` flag: ``"s1,s2,b1,b2"`` or a sequence of four numbers, in diffusers' ``enable_freeu``
+    order -> ``(s1, s2, b1, b2)``; ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
+    if value is None or value == "" or value is False:
+        return None
+    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else list(value)
+    if len(parts) != 4:
+        raise ValueError(f"freeu: expected four values s1,s2,b1,b2 (SD-2.1: 0.9,0.2,1.4,1.6), got {value!r}")
+    from .unet_params import check_freeu
+    return check_freeu(*parts)
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
     ap = argparse.ArgumentParser(description="Validation of a checkpoint on an Objaverse render tree")
@@ -417,7 +434,15 @@ def main(argv=None) -> int:
                          "result at any batch size (default: the config's group_sources, else off)")
     ap.add_argument("--guidance-rescale", type=float, default=None,
                     help="guidance rescale in [0, 1] (Lin et al. 2024, section 3.4; default: the config's guidance_rescale, else 0.0 = off)")
+    ap.add_argument("--freeu", type=str, default=None, metavar="s1,s2,b1,b2",
+                    help="FreeU on the UNet's main pass, diffusers' enable_freeu order (SD-2.1: 0.9,0.2,1.4,1.6; default: the config's "
+                         "freeu, else off)")
     args = ap.parse_args(argv)
+    if args.freeu is not None:
+        try:
+            parse_freeu(args.freeu)
+        except ValueError as e:
+            ap.error(str(e))
     try:
         config = load_config(args.config)
     except Exception as e:  # noqa: BLE001
@@ -427,7 +452,9 @@ def main(argv=None) -> int:
         config["group_sources"] = True
     if args.guidance_rescale is not None:
         config["guidance_rescale"] = args.guidance_rescale
-    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    if args.freeu is not None:
+        config["freeu"] = args.freeu
+    device =torch.device("cuda" if torch.cuda.is_available() else "cpu")
     output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     output_dir.mkdir(exist_ok=True, parents=True)
     extras = args.extra_metrics.split(",") if args.extra_metrics else list(config.get("extra_metrics", ()))
