@@ -419,6 +419,34 @@ int mvd_op_sampler_step_rescaled(const float* model_out, float guidance_scale, f
  * lanes per wave, 16-byte vectors per thread kept in registers (0: the row is streamed twice)}: thread t of the row's one
  * workgroup owns the vectors t, t + threads, t + 2*threads, ... of the row. */
 int mvd_debug_cfg_rescale_plan(int64_t n_row, int* out);
+/* Adaptive projected guidance (Sadat, Hilliges and Weber, ICLR 2025; diffusers' normalized_guidance with
+ * use_original_formulation=True, restated) fused into the guided step.  uncond_cond / model_out hold [uncond | cond] stacked on the
+ * batch dim: 2 * rows * n_row floats; momentum_buffer M holds rows * n_row floats and is updated in place.  Per row, over its
+ * n_row elements, with g = guidance_scale, tau = norm_threshold, beta = momentum, phi = guidance_rescale:
+ *   d = (c - u) + beta*M ; M = d                         (fp32, one fma; beta == 0: M is neither read nor written and may be NULL)
+ *   s = tau > 0 ? min(1, tau / sqrt(sum d^2)) : 1         (sum d^2 == 0: s = 1)
+ *   alpha = sum c^2 > 0 ? s * sum(d c) / sum c^2 : 0      (the coefficient of c in the part of s*d parallel to c)
+ *   m = c + (g - 1)*(s*d - (1 - eta)*alpha*c) = A*c + B*d ,  A = 1 - (g - 1)(1 - eta) alpha ,  B = (g - 1) s
+ *   phi > 0:  m = m * (phi * std(c) / std(m) + 1 - phi)   (mvd_op_cfg_rescale's rescale: unbiased std, no epsilon)
+ * eta = 1, tau = 0, beta = 0, phi = 0 is plain classifier-free guidance.  mvd_op_apg writes out = m.  mvd_op_sampler_step_apg goes
+ * on as mvd_op_sampler_step does:  x0 = a0*m + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; if (x0_out) x0_out = x0.
+ * space 0 ("output"): as above, on the model output.  space 1 ("x0", the paper's setting): c = a0*c + a1*sample and d = a0*(c - u)
+ * + beta*M first, so the projection, the cap and M live in denoised-prediction space, and m is the step's x0 directly; phi must
+ * then be 0.  ONE launch, one workgroup per row; the five statistics (sum c, sum d, sum c^2, sum d^2, sum c d) are fp64 sums in a
+ * fixed order that depends on n_row alone (no atomics), and the moments of m follow from them, so a row's output bits do not
+ * depend on rows, on the row's index or on the launch.  A row of up to 36864 floats stays in registers between the statistics
+ * and the update; a longer row is read a second time (d from M when beta != 0).  eta and phi must lie in [0, 1], tau must be
+ * finite and >= 0, beta must lie in (-1, 1), n_row % 4 == 0; M is required when beta != 0; x0_prev / noise as in
+ * mvd_op_sampler_step; out == sample and x0_out == x0_prev are allowed; an out, x0_out or M that overlaps the model output, or an M
+ * that overlaps any other argument, is an error; otherwise -1 (mvd_last_error), before anything is launched. */
+int mvd_op_apg(const float* uncond_cond, float guidance_scale, float eta, float norm_threshold, float momentum,
+               float guidance_rescale, float* momentum_buffer, float* out, int64_t rows, int64_t n_row, void* stream);
+int mvd_op_sampler_step_apg(const float* model_out, float guidance_scale, float eta, float norm_threshold, float momentum,
+                            float guidance_rescale, int space, float* momentum_buffer, const float* sample, const float* x0_prev,
+                            const float* noise, float a0, float a1, float p, float q, float r, float sigma, float* out,
+                            float* x0_out, int64_t rows, int64_t n_row, void* stream);
+/* The partition of a row by the two entry points above, out[4] as mvd_debug_cfg_rescale_plan. */
+int mvd_debug_apg_plan(int64_t n_row, int* out);
 
 /* FreeU on the two inputs of an up-block resnet, ONE launch.  hidden [B][H*W][C] and skip [B][H*W][Cs] are bf16, token-major:
  *   hidden_out = hidden with channels [0, C / 2) multiplied by b (fp32 product, one rounding to bf16), the rest bit for bit;

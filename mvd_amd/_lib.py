@@ -184,6 +184,12 @@ _SIGS = {
                                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                                C.c_int64, C.c_int64, C.c_void_p]),
     "mvd_debug_cfg_rescale_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
+    "mvd_op_apg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64,
+                             C.c_int64, C.c_void_p]),
+    "mvd_op_sampler_step_apg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mvd_debug_apg_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
     "mvd_engine_set_freeu": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mvd_engine_clear_freeu": (C.c_int, [C.c_void_p]),
     "mvd_op_freeu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,

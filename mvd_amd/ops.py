@@ -633,6 +633,68 @@ def cfg_rescale_partition(n_row):
     return sorted(offs)
 
 
+APG_SPACES = ("output", "x0")                  # ``space`` of mvd_op_sampler_step_apg, by index
+
+
+def _apg_momentum(momentum, momentum_buffer, rows, n_row):
+    """The momentum buffer as the C entry gets it: required (the C side says so) when momentum != 0, not passed when it is 0."""
+    if float(momentum) == 0.0 or momentum_buffer is None:
+        return None
+    if not (momentum_buffer.is_cuda and momentum_buffer.dtype == torch.float32 and momentum_buffer.is_contiguous()
+            and momentum_buffer.numel() == rows * n_row):
+        raise L.MvdError(f"apg: momentum_buffer must be a contiguous fp32 CUDA tensor of {rows} x {n_row} floats, got "
+                         f"{tuple(momentum_buffer.shape)} {momentum_buffer.dtype} on {momentum_buffer.device}")
+    return momentum_buffer
+
+
+def apg(uncond_cond, guidance_scale, eta=0.0, norm_threshold=0.0, momentum=0.0, guidance_rescale=0.0, momentum_buffer=None,
+        out=None):
+    """(2B, ...) fp32 [uncond | cond] -> (B, ...): the guided output under adaptive projected guidance (Sadat et al., ICLR 2025;
+    diffusers' ``normalized_guidance`` with ``use_original_formulation=True``), per batch row:
+    d = (c - u) + momentum*M, M <- d ; s = min(1, norm_threshold / |d|) (0: no cap) ; m = c + (g - 1)*(s*d - (1 - eta)*par), par the
+    part of s*d parallel to c ; then ``cfg_rescale``'s rescale when ``guidance_rescale`` > 0.  ``momentum_buffer`` (B, ...) fp32 is
+    updated in place; it is required when ``momentum`` != 0 and untouched otherwise.  One launch (``mvd_op_apg``).  ``out`` and
+    ``momentum_buffer`` must not overlap ``uncond_cond``."""
+    rows, n_row = _rescale_rows(uncond_cond)
+    if out is None:
+        out = torch.empty((rows,) + tuple(uncond_cond.shape[1:]), device=uncond_cond.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() == rows * n_row and out.is_contiguous()
+    L.call("mvd_op_apg", _p(uncond_cond), float(guidance_scale), float(eta), float(norm_threshold), float(momentum),
+           float(guidance_rescale), _p(_apg_momentum(momentum, momentum_buffer, rows, n_row)), _p(out), rows, n_row, _s())
+    return out
+
+
+def sampler_step_apg(model_out, sample, guidance_scale, a0, a1, p, q, r=0.0, sigma=0.0, eta=0.0, norm_threshold=0.0, momentum=0.0,
+                     guidance_rescale=0.0, space="output", momentum_buffer=None, x0_prev=None, noise=None, out=None, x0_out=None):
+    """``sampler_step`` of the guided output under adaptive projected guidance in ONE launch: m = ``apg(model_out, ...)`` ;
+    x0 = a0*m + a1*sample ; out = p*sample + q*x0 + r*x0_prev + sigma*noise ; x0_out = x0.  ``space="x0"`` (the paper's setting):
+    the projection, the cap and the momentum buffer live in denoised-prediction space -- c <- a0*c + a1*sample, d <- a0*(c - u)
+    first -- and m is the step's x0; ``guidance_rescale`` must then be 0.  ``model_out`` is the stacked (2B, ...) [uncond | cond];
+    ``x0_prev`` may be None iff r == 0, ``noise`` iff sigma == 0, ``momentum_buffer`` iff momentum == 0.  ``out`` may be ``sample``
+    and ``x0_out`` may be ``x0_prev``; no output may overlap ``model_out`` and ``momentum_buffer`` overlaps nothing."""
+    rows, n_row = _rescale_rows(model_out)
+    if space not in APG_SPACES:
+        raise L.MvdError(f"sampler_step_apg: space={space!r}: expected one of {APG_SPACES}")
+    assert sample.dtype == torch.float32 and sample.numel() == rows * n_row, (tuple(model_out.shape), tuple(sample.shape))
+    for t in (x0_prev, noise, out, x0_out):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == sample.numel())
+    if out is None:
+        out = torch.empty_like(sample)
+    L.call("mvd_op_sampler_step_apg", _p(model_out), float(guidance_scale), float(eta), float(norm_threshold), float(momentum),
+           float(guidance_rescale), APG_SPACES.index(space), _p(_apg_momentum(momentum, momentum_buffer, rows, n_row)), _p(sample),
+           _p(x0_prev), _p(noise), float(a0), float(a1), float(p), float(q), float(r), float(sigma), _p(out), _p(x0_out), rows, n_row,
+           _s())
+    return out
+
+
+def apg_plan(n_row):
+    """How the APG kernel partitions a row of ``n_row`` floats (``mvd_debug_apg_plan``): the dict of ``cfg_rescale_plan``."""
+    out = (C.c_int * 4)()
+    L.call("mvd_debug_apg_plan", int(n_row), out)
+    per_pass = out[0] * out[1]
+    return dict(threads=out[0], vec=out[1], wave=out[2], keep=out[3], passes=-(-int(n_row) // per_pass))
+
+
 def freeu(hidden, skip, H, W, b, s, hidden_out=None, skip_out=None):
     """FreeU (diffusers' ``apply_freeu``, threshold 1) on the two inputs of an up-block resnet, ONE launch (``mvd_op_freeu``).
     ``hidden`` (B, H*W, C) and ``skip`` (B, H*W, Cs) bf16, token-major -> ``(hidden', skip')``: channels [0, C // 2) of

@@ -20,6 +20,7 @@ eta = 0; a caller who wants the stochastic form drives ``DDIMScheduler.step(...,
 """
 from __future__ import annotations
 
+import inspect
 import json
 import os
 from types import SimpleNamespace
@@ -46,11 +47,17 @@ class MVDDenoiser:
                  source_image_latents: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
                  height: int = 64, width: int = 64, noise_per_step=None, callback=None, callback_steps: int = 1,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None, views: Optional[int] = None,
-                 objects: Optional[int] = None, *, guidance_rescale: float = 0.0):
+                 objects: Optional[int] = None, *, guidance_rescale: float = 0.0, apg=None):
         """``guidance_rescale`` (diffusers' argument of that name; Lin et al. 2024, section 3.4): with guidance active
         (``guidance_scale > 1``) and a value in (0, 1], every row's guided output is rescaled towards the standard deviation of its
         conditional output before the scheduler step -- statistics, rescale and step in ONE launch per step for all three samplers
         (DESIGN.md section 9 N17).  0.0 (the default), or no guidance: ignored, the loop issues the launches it always did.
+
+        ``apg`` (``mvd_amd.scheduler.APG``, or a dict / tuple ``APG.of`` takes; Sadat et al. 2025, diffusers'
+        ``AdaptiveProjectedGuidance``): with guidance active, adaptive projected guidance replaces the plain combine -- projection,
+        norm cap, momentum, the optional rescale and the step in ONE launch per step for all three samplers (DESIGN.md section 9
+        N19).  The momentum buffer belongs to this call: allocated and zeroed here, only when the momentum is not 0.  ``None`` (the
+        default), or no guidance: the loop issues the launches it always did.
 
         ``views`` (MVDPipeline.generate_views): ``latents`` and the target cameras hold that many rows for ONE prompt and ONE
         source row; every step is one shared-reference forward (``MultiViewUNet.forward(..., views=)``).  ``objects``
@@ -61,6 +68,10 @@ class MVDDenoiser:
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale={guidance_rescale!r} must lie in [0, 1]")
         rescale = float(guidance_rescale) if guidance_scale > 1.0 else 0.0      # without guidance it is ignored, as in diffusers
+        from .scheduler import _check_apg
+        apg = _check_apg(apg, guidance_rescale)
+        if guidance_scale <= 1.0:                                               # without guidance there is no update to project
+            apg = None
         dev = self.unet._exec_device()
         B = prompt_embeds.shape[0]
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
@@ -118,6 +129,17 @@ class MVDDenoiser:
         rescaled_step = getattr(self.scheduler, "step_guided_rescaled", None)   # DDPM's guided-and-rescaled step
         # the keyword goes only with a rescale: a scheduler of the caller's whose step_guided has none keeps working without one
         guided_kw = {"guidance_rescale": rescale} if rescale > 0.0 else {}
+        apg_step = None
+        if apg is not None:
+            # the momentum buffer is this call's own: zero at the first step, updated in place by every step's launch
+            momentum = torch.zeros_like(latents) if apg.momentum != 0.0 else None
+            if guided_step is not None and "apg" in inspect.signature(guided_step).parameters:
+                guided_kw.update(apg=apg, momentum_buffer=momentum)
+            else:
+                guided_step, apg_step = None, getattr(self.scheduler, "step_guided_apg", None)  # DDPM's; else a caller's scheduler
+                if apg_step is None and apg.space != "output":
+                    raise L.MvdError('apg: space="x0" needs a scheduler with step_guided(..., apg=) or step_guided_apg '
+                                     f"({type(self.scheduler).__name__} has neither)")
         ts_host = self.scheduler.timesteps.tolist()                             # host ints for the scheduler's coefficients
         ts_dev = torch.tensor(ts_host, dtype=torch.float32, device=dev)         # ONE upload: a per-step scalar upload would make
         for i, t in enumerate(ts_host):                                         # the host wait for the previous step's kernels
@@ -129,6 +151,12 @@ class MVDDenoiser:
                 # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch; with guidance
                 # rescale the row statistics and the rescale too
                 latents = guided_step(out, guidance_scale, t, latents, noise=nz, **guided_kw).prev_sample
+            elif apg_step is not None:                                          # DDPM under APG: the APG kernel (r = 0), ONE launch
+                latents = apg_step(out, guidance_scale, apg, t, latents, noise=nz, momentum_buffer=momentum,
+                                   guidance_rescale=rescale).prev_sample
+            elif apg is not None:                                               # a scheduler of the caller's: APG, then its step
+                m = ops.apg(out, guidance_scale, **apg.kwargs(), guidance_rescale=rescale, momentum_buffer=momentum)
+                latents = self.scheduler.step(m, t, latents, noise=nz).prev_sample
             elif rescale > 0.0 and rescaled_step is not None:                   # DDPM: the same kernel (r = 0), ONE launch
                 latents = rescaled_step(out, guidance_scale, rescale, t, latents, noise=nz).prev_sample
             elif rescale > 0.0:                                                 # a scheduler of the caller's: rescale, then its step
@@ -288,7 +316,7 @@ class MVDPipeline:
                  source_images: Optional[torch.Tensor] = None, ref_scale: float = 0.1, use_camera_embeddings: bool = True,
                  use_image_conditioning: bool = True, debug_log_file_path: Optional[str] = None, *,
                  source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
-                 guidance_rescale: float = 0.0):
+                 guidance_rescale: float = 0.0, apg=None):
         dev = self.device
         if prompt is not None and isinstance(prompt, str):                       # :45-50
             batch_size = 1
@@ -316,7 +344,8 @@ class MVDPipeline:
                                 source_image_latents=source_image_latents,
                                 generator=generator if isinstance(generator, torch.Generator) else None,
                                 noise_per_step=noise_per_step, callback=callback, callback_steps=callback_steps,
-                                cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale)
+                                cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale,
+                                **({"apg": apg} if apg is not None else {}))
         return self._images(latents, output_type, return_dict)
 
     @torch.no_grad()
@@ -330,7 +359,7 @@ class MVDPipeline:
                        return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                        callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
                        source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
-                       guidance_rescale: float = 0.0):
+                       guidance_rescale: float = 0.0, apg=None):
         """V views of ONE object from one source image: what V calls ``pipe(prompt, source_images=, source_camera=,
         target_camera=target_cameras[v:v+1], ...)`` give (the loop of infer.py:111-122, a turntable), in one denoising loop whose
         every step is ONE shared-reference forward: the prompt is encoded once, the source VAE-encoded
@@ -374,7 +403,7 @@ class MVDPipeline:
             latents=latents, output_type=output_type, return_dict=return_dict, num_inference_steps=num_inference_steps,
             guidance_scale=guidance_scale, negative_prompt_embeds=negative_prompt_embeds, noise_per_step=noise_per_step,
             callback=callback, callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs,
-            guidance_rescale=guidance_rescale)
+            guidance_rescale=guidance_rescale, **({"apg": apg} if apg is not None else {}))
 
     @torch.no_grad()
     def generate_views_batch(self, prompts: Optional[List[str]] = None, source_images: Optional[torch.Tensor] = None,
@@ -387,7 +416,7 @@ class MVDPipeline:
                              return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                              callback_steps: int = 1, cross_attention_kwargs: Optional[Dict[str, Any]] = None, *,
                              source_image_latents: Optional[torch.Tensor] = None, noise_per_step=None,
-                             guidance_rescale: float = 0.0):
+                             guidance_rescale: float = 0.0, apg=None):
         """Turntables of O objects, V views each: what O calls of ``generate_views`` (O * V calls of ``pipe(...)``) give, in one
         denoising loop whose every step is ONE object forward.  The prompts are encoded once, the O
         sources VAE-encoded in one call, the reference encoder pass runs at batch O (once per call with
@@ -462,7 +491,7 @@ class MVDPipeline:
             latents=latents, output_type=output_type, return_dict=return_dict, num_inference_steps=num_inference_steps,
             guidance_scale=guidance_scale, negative_prompt_embeds=negative_prompt_embeds, noise_per_step=noise_per_step,
             callback=callback, callback_steps=callback_steps, cross_attention_kwargs=cross_attention_kwargs,
-            guidance_rescale=guidance_rescale)
+            guidance_rescale=guidance_rescale, **({"apg": apg} if apg is not None else {}))
 
 
 def _scheduler_from_snapshot(path) -> "Any":

@@ -22,6 +22,11 @@ the device.
   whatever the prediction type, only when guidance is active (``guidance_scale > 1``) and ``guidance_rescale > 0``; the
   statistics, the rescale and the step are ONE launch (``mvd_op_sampler_step_rescaled``).  Also unpinned against diffusers;
   pinned by the fp64 restatement in tests/guidance_ref.py and its identities (tests/test_guidance_rescale_cpu.py).
+* Adaptive projected guidance (Sadat, Hilliges and Weber, ICLR 2025, "Eliminating Oversaturation and Artifacts of High Guidance
+  Scales in Diffusion Models") restates diffusers' ``normalized_guidance`` with ``use_original_formulation=True``: ``APG`` holds
+  the setting, the update itself is in the docstring of ``ops.apg``.  Applied only when guidance is active; the projection, the
+  norm cap, the momentum update, the optional rescale and the step are ONE launch (``mvd_op_sampler_step_apg``).  The schedulers
+  hold no APG state: the momentum buffer is the caller's.  Unpinned against diffusers; pinned by tests/apg_ref.py.
 """
 from __future__ import annotations
 
@@ -31,6 +36,77 @@ from typing import Any, Optional
 
 import numpy as np
 import torch
+
+
+class APG:
+    """The setting of adaptive projected guidance: ``eta`` in [0, 1] scales the part of the guidance update parallel to the
+    conditional prediction (1: plain guidance, 0: the orthogonal part alone), ``norm_threshold`` >= 0 caps the update's norm per
+    batch row (0: no cap), ``momentum`` in (-1, 1) is the running average's coefficient over the steps (the paper uses negative
+    values; 0: none), ``space`` is "output" (the projection on the raw model output, as diffusers applies it) or "x0" (on the
+    denoised prediction, the paper's setting).  ``APG.of(value)`` also takes a dict of these keys, a tuple / list in this order,
+    or ``"eta,norm_threshold,momentum[,space]"``; ``None`` stays ``None``."""
+
+    SPACES = ("output", "x0")
+    __slots__ = ("eta", "norm_threshold", "momentum", "space")
+
+    def __init__(self, eta: float = 0.0, norm_threshold: float = 0.0, momentum: float = 0.0, space: str = "output"):
+        try:
+            eta, norm_threshold, momentum = float(eta), float(norm_threshold), float(momentum)
+        except (TypeError, ValueError):
+            raise ValueError(f"apg: eta, norm_threshold and momentum must be numbers, got {(eta, norm_threshold, momentum)!r}") from None
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"apg: eta={eta!r} must lie in [0, 1]")
+        if not 0.0 <= norm_threshold < math.inf:
+            raise ValueError(f"apg: norm_threshold={norm_threshold!r} must be finite and >= 0 (0: off)")
+        if not -1.0 < momentum < 1.0:
+            raise ValueError(f"apg: momentum={momentum!r} must lie in (-1, 1)")
+        if space not in self.SPACES:
+            raise ValueError(f"apg: space={space!r}: expected one of {self.SPACES}")
+        object.__setattr__(self, "eta", eta)
+        object.__setattr__(self, "norm_threshold", norm_threshold)
+        object.__setattr__(self, "momentum", momentum)
+        object.__setattr__(self, "space", space)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("APG is immutable")
+
+    @classmethod
+    def of(cls, value) -> "Optional[APG]":
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            unknown = set(value) - set(cls.__slots__)
+            if unknown:
+                raise ValueError(f"apg: unknown keys {sorted(unknown)} (expected {cls.__slots__})")
+            return cls(**value)
+        if isinstance(value, str):
+            value = [v.strip() for v in value.split(",")]
+        if isinstance(value, (tuple, list)) and 1 <= len(value) <= 4:
+            return cls(*value)
+        raise ValueError(f"apg: expected APG, a dict, or eta,norm_threshold,momentum[,space], got {value!r}")
+
+    def kwargs(self):
+        """the keywords of ``ops.apg`` / ``ops.sampler_step_apg`` (without ``space``, which only the step takes)"""
+        return dict(eta=self.eta, norm_threshold=self.norm_threshold, momentum=self.momentum)
+
+    def _key(self):
+        return (self.eta, self.norm_threshold, self.momentum, self.space)
+
+    def __eq__(self, other):
+        return isinstance(other, APG) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"APG(eta={self.eta!r}, norm_threshold={self.norm_threshold!r}, momentum={self.momentum!r}, space={self.space!r})"
+
+
+def _check_apg(apg, guidance_rescale: float = 0.0):
+    apg = APG.of(apg)
+    if apg is not None and apg.space == "x0" and float(guidance_rescale) > 0.0:
+        raise ValueError('apg: space="x0" with guidance_rescale > 0 is not defined (the rescale is defined on the model output)')
+    return apg
 
 
 def compute_snr(timesteps, noise_scheduler):
@@ -195,6 +271,25 @@ class DDPMScheduler(_ForwardDiffusion):
                                          noise=noise if sigma != 0.0 else None)
         return SimpleNamespace(prev_sample=prev)
 
+    def step_guided_apg(self, uncond_cond: torch.Tensor, guidance_scale: float, apg, timestep, sample: torch.Tensor,
+                        noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                        momentum_buffer: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
+        """``step`` of the guided model output under adaptive projected guidance (``ops.apg`` of [uncond | cond] stacked on the
+        batch dim, ``apg`` an ``APG`` or what ``APG.of`` takes) in ONE launch: the DDPM step is the samplers' affine form with
+        r = 0.  ``momentum_buffer`` (the caller's, zero at the first step) is updated in place; required when the momentum is
+        not 0.  Named apart like ``step_guided_rescaled``: the plain guided DDPM loop stays ``cfg_combine`` + ``step``."""
+        from . import ops
+        _check_rescale(guidance_rescale)
+        apg = _check_apg(apg, guidance_rescale)
+        if apg is None:
+            raise ValueError("step_guided_apg: apg is required (an APG, a dict or a tuple)")
+        c0, c1, c2, c3, sigma = self.step_coefficients(int(timestep))
+        noise = self._step_noise(sample, sigma, noise, generator)
+        prev = ops.sampler_step_apg(uncond_cond, sample, guidance_scale, c0, c1, c3, c2, 0.0, sigma, **apg.kwargs(),
+                                    guidance_rescale=guidance_rescale, space=apg.space, momentum_buffer=momentum_buffer,
+                                    noise=noise if sigma != 0.0 else None)
+        return SimpleNamespace(prev_sample=prev)
+
 
 def _check_rescale(guidance_rescale: float):
     if not 0.0 <= float(guidance_rescale) <= 1.0:
@@ -249,15 +344,21 @@ class _SolverSchedule(_ForwardDiffusion):
         return -sigma_bar, alpha                                # v_prediction
 
     def _launch(self, model_out, guidance_scale, coeffs, sample, noise, generator, x0_prev=None, x0_out=None,
-                guidance_rescale=0.0):
+                guidance_rescale=0.0, apg=None, momentum_buffer=None):
         """One step kernel.  ``guidance_scale`` None: a plain step of ``model_out``; else a guided step of the stacked
         [uncond | cond] -- with ``guidance_rescale`` > 0 and guidance active the rescaled kernel, else (as in diffusers, where
-        the argument is then ignored) exactly the call made without it."""
+        the argument is then ignored) exactly the call made without it.  ``apg`` with guidance active: the APG kernel (which
+        takes the rescale along); without guidance it is ignored like the rescale."""
         from . import ops
         _check_rescale(guidance_rescale)
+        apg = _check_apg(apg, guidance_rescale)
         a0, a1, p, q, r, sigma = coeffs
         noise = self._step_noise(sample, sigma, noise, generator) if sigma != 0.0 else None
         x0_prev = x0_prev if r != 0.0 else None
+        if apg is not None and guidance_scale is not None and guidance_scale > 1.0:
+            return ops.sampler_step_apg(model_out, sample, guidance_scale, a0, a1, p, q, r, sigma, **apg.kwargs(),
+                                        guidance_rescale=guidance_rescale, space=apg.space, momentum_buffer=momentum_buffer,
+                                        x0_prev=x0_prev, noise=noise, x0_out=x0_out)
         if guidance_rescale > 0.0 and guidance_scale is not None and guidance_scale > 1.0:
             return ops.sampler_step_rescaled(model_out, sample, guidance_scale, guidance_rescale, a0, a1, p, q, r, sigma,
                                              x0_prev=x0_prev, noise=noise, x0_out=x0_out)
@@ -321,12 +422,16 @@ class DDIMScheduler(_SolverSchedule):
 
     def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
                     noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, eta: float = 0.0,
-                    guidance_rescale: float = 0.0):
+                    guidance_rescale: float = 0.0, apg=None, momentum_buffer: Optional[torch.Tensor] = None):
         """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.
-        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch."""
+        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch.
+        ``apg`` (an ``APG``, or what ``APG.of`` takes; with ``guidance_scale`` > 1): adaptive projected guidance in place of the
+        plain combine, in the same launch; ``momentum_buffer`` is the caller's (zero at the first step, updated in place),
+        required when the momentum is not 0."""
         c = self.step_coefficients(int(timestep), eta)
+        kw = {"apg": apg, "momentum_buffer": momentum_buffer} if apg is not None else {}
         return SimpleNamespace(prev_sample=self._launch(uncond_cond, guidance_scale, c, sample, noise, generator,
-                                                        guidance_rescale=guidance_rescale))
+                                                        guidance_rescale=guidance_rescale, **kw))
 
 
 class DPMSolverMultistepScheduler(_SolverSchedule):
@@ -439,7 +544,7 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
             q, r = q + c, -c
         return a0, a1, p, q, r, 0.0
 
-    def _step(self, model_output, guidance_scale, timestep, sample, guidance_rescale: float = 0.0):
+    def _step(self, model_output, guidance_scale, timestep, sample, guidance_rescale: float = 0.0, apg=None, momentum_buffer=None):
         if self.sigmas is None:
             raise ValueError("call set_timesteps first")
         if self._step_index is None:                           # diffusers' index_for_timestep
@@ -457,9 +562,10 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
                 hist = self._hist[key] = torch.empty(sample.shape, device=sample.device, dtype=torch.float32)
         if c[4] != 0.0 and self._hist_key != key:
             raise ValueError("a second-order step needs the previous step's x0 of the same shape and device")
-        # (the keyword goes only with a rescale: a stand-in for ``_launch`` of its leading parameters alone keeps working)
+        # (the keywords go only with a rescale / APG: a stand-in for ``_launch`` of its leading parameters alone keeps working)
         out = self._launch(model_output, guidance_scale, c, sample, None, None, x0_prev=hist, x0_out=hist,
-                           **({"guidance_rescale": guidance_rescale} if guidance_rescale else {}))
+                           **({"guidance_rescale": guidance_rescale} if guidance_rescale else {}),
+                           **({"apg": apg, "momentum_buffer": momentum_buffer} if apg is not None else {}))
         self._hist_key = key if hist is not None else None
         self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
         self._step_index = i + 1
@@ -473,10 +579,12 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
 
     def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
                     noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                    guidance_rescale: float = 0.0):
+                    guidance_rescale: float = 0.0, apg=None, momentum_buffer: Optional[torch.Tensor] = None):
         """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.
-        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch."""
-        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample, guidance_rescale))
+        ``guidance_rescale`` > 0 (with ``guidance_scale`` > 1): the guided output is rescaled per row first, in the same launch.
+        ``apg`` / ``momentum_buffer``: as ``DDIMScheduler.step_guided``."""
+        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample, guidance_rescale, apg,
+                                                      momentum_buffer))
 
 
 class ShiftSNRScheduler:

@@ -15,7 +15,8 @@ Configuration keys read (the reference ships no ``config/infer_config.yaml``; th
 architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics``, ``metric_weights`` (a
 mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
 pipeline's argument of that name, ``--guidance-rescale``) and ``freeu`` (default absent: off; ``"s1,s2,b1,b2"`` or four numbers in
-diffusers' ``enable_freeu`` order, ``--freeu``).
+diffusers' ``enable_freeu`` order, ``--freeu``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
+sequence or a mapping, ``--apg``: adaptive projected guidance, the pipeline's argument of that name).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
 of the per-metric aggregates; ``clip_score`` is a per-batch value copied to each of the batch's samples and aggregated apart;
@@ -267,6 +268,10 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     freeu = parse_freeu(config.get("freeu"))
     if freeu is not None:
         pipeline.enable_freeu(*freeu)
+    # adaptive projected guidance: absent (the default), the pipeline calls carry no such argument; it rides with the rescale's
+    apg = parse_apg(config.get("apg"))
+    if apg is not None:
+        rescale = dict(rescale, apg=apg)
     with torch.no_grad():
         for batch_idx, batch in enumerate(dataloader):
             try:
@@ -420,6 +425,17 @@ def parse_freeu(value):
     return check_freeu(*parts)
 
 
+def parse_apg(value):
+    """The ``apg`` config key / ``--apg`` flag: ``"eta,norm_threshold,momentum[,space]"``, a sequence in that order or a mapping of
+    those names -> ``mvd_amd.scheduler.APG``; ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
+    if value is None or value == "" or value is False:
+        return None
+    from .scheduler import APG
+    if isinstance(value, str) and len(value.split(",")) not in (3, 4):
+        raise ValueError(f"apg: expected eta,norm_threshold,momentum[,space] (e.g. 0,15,-0.5), got {value!r}")
+    return APG.of(value)
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
     ap = argparse.ArgumentParser(description="Validation of a checkpoint on an Objaverse render tree")
@@ -437,7 +453,15 @@ def main(argv=None) -> int:
     ap.add_argument("--freeu", type=str, default=None, metavar="s1,s2,b1,b2",
                     help="FreeU on the UNet's main pass, diffusers' enable_freeu order (SD-2.1: 0.9,0.2,1.4,1.6; default: the config's "
                          "freeu, else off)")
+    ap.add_argument("--apg", type=str, default=None, metavar="eta,norm_threshold,momentum[,space]",
+                    help="adaptive projected guidance (Sadat et al. 2025): eta in [0, 1], norm_threshold >= 0 (0: off), momentum in "
+                         "(-1, 1), space output|x0 (e.g. 0,15,-0.5; default: the config's apg, else off)")
     args = ap.parse_args(argv)
+    if args.apg is not None:
+        try:
+            parse_apg(args.apg)
+        except ValueError as e:
+            ap.error(str(e))
     if args.freeu is not None:
         try:
             parse_freeu(args.freeu)
@@ -454,6 +478,8 @@ def main(argv=None) -> int:
         config["guidance_rescale"] = args.guidance_rescale
     if args.freeu is not None:
         config["freeu"] = args.freeu
+    if args.apg is not None:
+        config["apg"] = args.apg
     device =torch.device("cuda" if torch.cuda.is_available() else "cpu")
     output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     output_dir.mkdir(exist_ok=True, parents=True)
