@@ -336,6 +336,11 @@ int mvd_debug_last_gemm_nowait(void);
 int mvd_debug_pick_splitk(int m, int n, int k, int geglu);
 /* The same for a 3x3 convolution run as an implicit GEMM (k = 9 * Cin + fused shortcut channels). */
 int mvd_debug_pick_splitk_conv(int m, int n, int k);
+/* The route the engine's single-stream schedule gives a dense GEMM over one or two sources ([a | a2], k1 + k2; k2 = 0: one) with a
+ * residual, by host arithmetic alone: out[5] = {1 small-M kernels / 0 tiled kernels, small-M tile / tile config, split-K factor,
+ * small-M ring depth (0: tiled), column tiles per group of the 256x320 kernel's tile walk (0: row-major)}.  -1: no dense launch
+ * takes the shape (each source width must be a multiple of the 64-deep K slab). */
+int mvd_debug_dense_route(int m, int n, int k1, int k2, int* out);
 /* Small-M kernels (gemm_sm.hip, the batch-1 path): force_cfg = 100 + 10 * tile + ring depth in mvd_op_linear / mvd_op_conv3x3
  * (tiles 0..6 = 64x64, 128x64, 64x128, 128x128, 64x160, 128x160, 64x320; + 1000: the weight is in the blocked LDS-image
  * layout of mvd_amd.packing.block_weight).  With splitk > 1 these kernels combine the slices themselves: splitk_ws then

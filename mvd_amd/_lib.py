@@ -171,6 +171,7 @@ _SIGS = {
     "mvd_debug_last_groupnorm_plan": (C.c_int, [C.POINTER(C.c_int)]),
     "mvd_debug_pick_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_debug_pick_splitk_conv": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "mvd_debug_dense_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mvd_gemm_sm_num_tiles": (C.c_int, []),
     "mvd_debug_set_attention_nw": (C.c_int, [C.c_int]),
     "mvd_debug_set_flags": (C.c_int, [C.c_int]),

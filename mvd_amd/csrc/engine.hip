@@ -216,6 +216,7 @@ struct Ctx {
   bool dry;
   int err = 0;
   bool nowait = false;   // split-K combines must not wait for other workgroups (kernels of two streams share the chip)
+  int tag_base = -1;     // >= 0: the shape table's tag of the next GEMM launches instead of mode * 100 + geglu * 10 (the split is added)
 
   const void* W(const std::string& name, int dtype, int64_t numel, int set_override = -1) {
     if (dry) return nullptr;  // sizing run: weights need not be registered
@@ -279,7 +280,7 @@ struct Ctx {
       int r = 0;
       if (!dry) {
         const double fl = 2.0 * g.M * (double)g.N * g.Ktot;
-        e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = g.seg[0].mode * 100 + g.geglu * 10 + (sm_S > 1 ? sm_S : 0);
+        e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = (tag_base >= 0 ? tag_base : g.seg[0].mode * 100 + g.geglu * 10) + (sm_S > 1 ? sm_S : 0);
         r = profiled(MVD_PC_SM_64X64 + sm_tile, fl, 0.0, [&] { return mvd_launch_gemm_sm(g, s, sm_tile, sm_ns); });
       }
       e->tmp.off = mark;
@@ -294,7 +295,7 @@ struct Ctx {
     int r = 0;
     if (!dry) {
       const double fl = 2.0 * g.M * (double)g.N * g.Ktot;
-      e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = g.seg[0].mode * 100 + g.geglu * 10 + (S > 1 ? S : 0);
+      e->prof_M = g.M; e->prof_N = g.N; e->prof_K = g.Ktot; e->prof_tag = (tag_base >= 0 ? tag_base : g.seg[0].mode * 100 + g.geglu * 10) + (S > 1 ? S : 0);
       r = launch_tiled(g, s, fc, [&](auto&& launch) { return profiled(e->prof ? gemm_class(g, mvd_gemm_pick_config(g), S) : 0, fl, 0.0, launch); });
     }
     e->tmp.off = mark;
@@ -657,9 +658,23 @@ struct UNetPass {
     {
       bf16_t* ff = c.talloc<bf16_t>((size_t)M * 4 * C);
       CHECK(c.ln_linear(h, M, C, key + ".ln3", key + ".ff1", (int64_t)8 * C, 8 * C, c.WF(key + ".ff1.b", 8 * C), ln, ff, 4 * C, true));
-      CHECK(c.linear(ff, nullptr, 4 * C, 0, M, c.WB(key + ".ff2.w", (int64_t)C * 4 * C), c.WF(key + ".ff2.b", C), C, h, C, h, C));
+      // Tail of the block.  h = h + ff.W2^T + b2 and out = x + h.Wp^T + bp have nothing non-linear between them and h dies here, so
+      // with the composed slot `<key>.tail.w` = [Wp.W2 | Wp] registered (packing.fold_tail; bias Wp.b2 + bp) both are ONE GEMM over
+      // the two sources [ff | h], K = 4C + C -- the form of the attention out-projections.  Without the slot: the two launches.
+      // (a sizing run reads the same weight table as the run it sizes and takes the same branch; one that comes before any weight
+      //  is registered -- mvd_engine_workspace_bytes on a fresh engine -- sizes BOTH forms: their split-K partials may differ)
+      const bool tail = c.has(key + ".tail.w");
+      if (tail || c.dry) {
+        c.tag_base = 50;      // (shape table: 50 + split, next to no other dense launch's tag)
+        const int r = c.linear(ff, h, 4 * C, C, M, c.WB(key + ".tail.w", (int64_t)C * 5 * C), c.WF(key + ".tail.b", C), C, x.p, C, out.p, C);
+        c.tag_base = -1;
+        CHECK(r);
+      }
+      if (!tail) {
+        CHECK(c.linear(ff, nullptr, 4 * C, 0, M, c.WB(key + ".ff2.w", (int64_t)C * 4 * C), c.WF(key + ".ff2.b", C), C, h, C, h, C));
+        CHECK(c.linear(h, nullptr, C, 0, M, c.WB(key + ".proj_out.w", (int64_t)C * C), c.WF(key + ".proj_out.b", C), C, x.p, C, out.p, C, false, false, 0, key + ".proj_out.wx"));
+      }
     }
-    CHECK(c.linear(h, nullptr, C, 0, M, c.WB(key + ".proj_out.w", (int64_t)C * C), c.WF(key + ".proj_out.b", C), C, x.p, C, out.p, C, false, false, 0, key + ".proj_out.wx"));
     c.e->tmp.off = mark;
 
     if (o.capture) {  // encoder pass: reference normalisation (Q2) + adapter K/V for both processors of this feature

@@ -315,6 +315,28 @@ extern "C" int mvd_debug_pick_splitk_conv(int m, int n, int k) {
   return mvd_gemm_pick_splitk(a);
 }
 
+// The route the engine's single-stream schedule gives a dense GEMM [a | a2][m][k1 + k2] . W[n][k1 + k2]^T with a residual (pure host
+// arithmetic): out[5] = {family: 1 small-M kernels (gemm_sm.hip) / 0 tiled kernels, small-M tile / tile config, split-K factor,
+// small-M ring depth (0: tiled), column tiles per group of the ping-pong kernel's walk (0: row-major)}.  -1 for a shape no dense
+// launch takes (a source width that is no multiple of the 64-deep slab, N % 64).
+extern "C" int mvd_debug_dense_route(int m, int n, int k1, int k2, int* out) {
+  if (!out || m <= 0 || n <= 0 || k1 <= 0 || k2 < 0 || k1 % 64 || k2 % 64 || n % 64) { mvd_set_error("dense_route: bad shape M=%d N=%d K=%d+%d", m, n, k1, k2); return -1; }
+  static const float dummy[4] = {};
+  const bf16_t* p = reinterpret_cast<const bf16_t*>(dummy);      // (the planners look at shapes and at WHICH operands exist, never through them)
+  MvdGemmArgs g; memset(&g, 0, sizeof(g));
+  g.seg[0].p0 = p; g.seg[0].p1 = k2 ? p : nullptr; g.seg[0].c0 = k1; g.seg[0].c1 = k2; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k1 + k2;
+  g.nseg = 1; g.W = p; g.ldw = g.Ktot = k1 + k2; g.M = m; g.N = n; g.rows_per_batch = m; g.outH = 1; g.outW = m;
+  g.bias = dummy; g.alpha = 1.f; g.out = const_cast<float*>(dummy); g.ldo = n; g.res = p; g.ldres = n;
+  int tile = 0, ns = 0, S = 1;
+  if (mvd_gemm_sm_plan(g, &tile, &ns, &S)) { out[0] = 1; out[1] = tile; out[2] = S; out[3] = ns; out[4] = 0; return 0; }
+  const int cfg = mvd_gemm_pick_config(g);
+  if (cfg < 0) { mvd_set_error("dense_route: no tile config for N=%d", n); return -1; }
+  S = mvd_gemm_pick_splitk(g);
+  g.splitk = S;
+  out[0] = 0; out[1] = cfg; out[2] = S; out[3] = 0; out[4] = (cfg == 7 && mvd_gemm_pp_applicable(g)) ? mvd_gemm_pp_walk(g) : 0;
+  return 0;
+}
+
 int mvd_launch_splitk_reduce(const MvdGemmArgs& a, hipStream_t s) {
   if (a.splitk < 2 || !a.part || (a.N & 3)) { mvd_set_error("splitk_reduce: bad arguments"); return -1; }
   const long nvec = (long)a.M * (a.N >> 2);

@@ -539,6 +539,10 @@ bool mvd_gemm_sm_applicable(const MvdGemmArgs& a, int tile) {
   for (int i = 0; i < a.nseg; ++i) {
     const MvdASeg& g = a.seg[i];
     if (g.mode == MVD_A_DENSE) {
+      // a 64-deep slab is fetched from ONE source (the loader picks it per slab): the boundary between two sources -- slab
+      // 4C / 64 of the K-concatenated transformer tail [ff | h] -- must fall between slabs.  The engine launches these kernels
+      // without passing mvd_launch_gemm, which checks the same for the tiled ones.
+      if (g.c0 % 64 || g.c1 % 64 || g.c0 + g.c1 != g.ksize) return false;
       if ((size_t)a.M * (g.c0 > g.c1 ? g.c0 : g.c1) * 2 >= lim) return false;
     } else {
       const size_t bytes = (size_t)(a.M / a.rows_per_batch) * g.inH * g.inW * g.c0 * 2 + (size_t)(g.inW + 1) * g.c0 * 2;

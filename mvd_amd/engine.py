@@ -22,7 +22,7 @@ def _ptr(t: Optional[torch.Tensor]):
 class MVDEngine:
     def __init__(self, cfg: UNetConfig, cam_output_dim: int = 1024, cam_hidden_dim: int = 512,
                  simple_cam_encoder: bool = False, cam_modulation_strength: float = 0.2, device="cuda:0",
-                 small_batch_twins: Optional[bool] = None):
+                 small_batch_twins: Optional[bool] = None, fold_tail: bool = True):
         if not torch.cuda.is_available():
             raise L.MvdError("MVDEngine needs a MI355X (torch.cuda.is_available() is False); there is no CPU fallback")
         self.cfg = cfg
@@ -30,6 +30,9 @@ class MVDEngine:
         # second packed copies only a batch-1 forward reads (packing.pack_unet): on unless MVD_PACK_SMALL_BATCH_TWINS=0
         self.small_batch_twins = (os.environ.get("MVD_PACK_SMALL_BATCH_TWINS", "1") != "0") if small_batch_twins is None \
             else bool(small_batch_twins)
+        # ff.net.2 and proj_out of every transformer block packed as one K-concatenated GEMM (packing.compose_tail); False packs the
+        # two separate layers and the engine runs two launches (the A/B switch: the route follows the registered slots)
+        self.fold_tail = bool(fold_tail)
         c = L.mvd_config_t()
         c.in_channels, c.out_channels, c.num_levels = cfg.in_channels, cfg.out_channels, cfg.num_levels
         for i in range(cfg.num_levels):
@@ -72,7 +75,7 @@ class MVDEngine:
     def load_base(self, sd: Dict[str, torch.Tensor], adapter: bool, ref_scale: float):
         """``sd``: diffusers keys of base_unet (+ ``...processor.*`` adapter keys when ``adapter``)."""
         with torch.no_grad():
-            self._register(0, pack_unet(sd, self.cfg, self.device, adapter, ref_scale, self.small_batch_twins))
+            self._register(0, pack_unet(sd, self.cfg, self.device, adapter, ref_scale, self.small_batch_twins, self.fold_tail))
 
     def load_camera(self, sd: Dict[str, torch.Tensor]):
         with torch.no_grad():
@@ -80,7 +83,7 @@ class MVDEngine:
 
     def load_image_encoder(self, sd: Dict[str, torch.Tensor]):
         with torch.no_grad():
-            self._register(1, pack_unet(sd, self.cfg, self.device, False, 0.0, self.small_batch_twins))
+            self._register(1, pack_unet(sd, self.cfg, self.device, False, 0.0, self.small_batch_twins, self.fold_tail))
         self.share_encoder_weights(False)
 
     def share_encoder_weights(self, enable: bool = True):

@@ -124,7 +124,7 @@ class MultiViewUNet(nn.Module):
                  cam_hidden_dim: int = 512, use_camera_conditioning: bool = True, use_image_conditioning: bool = True,
                  simple_cam_encoder: bool = False, *, unet_config: Optional[UNetConfig] = None, init: str = "default",
                  cache_reference: bool = False, dedup_encoder_weights="auto", cache_dir=None,
-                 small_batch_twins: Optional[bool] = None):
+                 small_batch_twins: Optional[bool] = None, fold_tail: bool = True):
         super().__init__()
         self.use_camera_conditioning = use_camera_conditioning
         self.use_image_conditioning = use_image_conditioning
@@ -143,6 +143,9 @@ class MultiViewUNet(nn.Module):
         # default (on unless MVD_PACK_SMALL_BATCH_TWINS=0); False for a deployment that only runs many-image batches -- the
         # data-parallel shards of BASELINE configs[3] / [4] then pack, hold and BROADCAST 3.7 GB instead of 6.5 GB
         self.small_batch_twins = small_batch_twins
+        # every transformer block's ff.net.2 and proj_out as ONE packed GEMM (packing.compose_tail).  False keeps the two
+        # layers apart: same result up to bf16 rounding, one launch more per block (for A/B runs)
+        self.fold_tail = fold_tail
 
         # mvd_unet.py:46-52: UNet2DConditionModel.from_pretrained(name, subfolder="unet").  Here: a snapshot directory or a
         # hub name already in a local huggingface cache (hub.resolve_snapshot); a name nothing local answers to RAISES
@@ -237,7 +240,8 @@ class MultiViewUNet(nn.Module):
         dev = self._exec_device()
         if self._engine is None or self._engine.device != dev:
             self._engine = MVDEngine(self.unet_config, self.cam_output_dim, self.cam_hidden_dim, self.simple_cam_encoder,
-                                     self.cam_modulation_strength, device=dev, small_batch_twins=self.small_batch_twins)
+                                     self.cam_modulation_strength, device=dev, small_batch_twins=self.small_batch_twins,
+                                     fold_tail=self.fold_tail)
             self._dirty = True
         if self._dirty:
             sd = self.base_unet.state_dict()

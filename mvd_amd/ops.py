@@ -853,3 +853,14 @@ def engine_splitk(m, n, k, geglu=False, conv=False):
     if conv:
         return L.lib().mvd_debug_pick_splitk_conv(m, n, k)
     return L.lib().mvd_debug_pick_splitk(m, n, k, int(geglu))
+
+
+def engine_dense_route(m, n, k1, k2=0):
+    """The route the engine's single-stream schedule gives a dense GEMM ``[a | a2] @ w.T`` (+ bias, residual) of this size, from
+    host arithmetic alone (no GPU needed): dict(sm, cfg, splitk, depth, walk_cg, force_cfg) -- ``sm``: the small-M kernels take it
+    (``cfg`` is then their tile and ``depth`` the ring depth); ``force_cfg``: what ``linear(..., force_cfg=, splitk=)`` needs to
+    run that route (-1: the tiled kernels' own heuristic)."""
+    out = (C.c_int * 5)()
+    L.call("mvd_debug_dense_route", m, n, k1, k2, out)
+    sm = bool(out[0])
+    return dict(sm=sm, cfg=out[1], splitk=out[2], depth=out[3], walk_cg=out[4], force_cfg=100 + 10 * out[1] + out[3] if sm else -1)

@@ -11,6 +11,7 @@ One-time host work (torch is used as plumbing for the permutes / casts).  Slot l
   ref_kv        [to_k_ref(self); to_v_ref(self); to_k_ref(cross); to_v_ref(cross)]
   ff1           GEGLU rows interleaved in blocks of 16: (16 value rows, 16 gate rows)
   temb_proj     every resnet's time_emb_proj stacked in module order (one GEMM per forward)
+  tail          [proj_out . ff.net.2 | proj_out]          K concatenated over [ff | h], bias = Wp.b2 + bp (compose_tail; replaces ff2 / proj_out)
   <slot>.wf/.cf LayerNorm-folded twins of attn1.qkv / attn2.q / ff1 (fold_layernorm): the fused LayerNorm GEMM reads the
                 un-normalised rows; packed for C <= LN_FOLD_MAX_C (the levels whose GEMMs are big enough for that kernel)
 """
@@ -179,6 +180,31 @@ def fold_layernorm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bia
     return wf.to(device).contiguous(), torch.stack([c1, c2], 0).to(device=device, dtype=torch.float32).contiguous()
 
 
+def round_bf16(t: torch.Tensor) -> torch.Tensor:
+    """fp64 -> bf16 with ONE round-to-nearest-even.  torch converts through fp32, which rounds twice: a value that the fp32 step
+    moves exactly onto the midpoint of two bf16 neighbours (the low half-word 0x8000) then goes to the even one, whichever side
+    it came from.  Those elements -- about one in 2^16 -- take the neighbour on their own side instead."""
+    assert t.dtype == torch.float64, t.dtype
+    f = t.to(torch.float32)
+    bits = f.contiguous().view(torch.int32)
+    back = f.to(torch.float64)
+    fix = ((bits & 0xFFFF) == 0x8000) & (back != t) & torch.isfinite(f)
+    away = (t.abs() > back.abs()).to(torch.int32) << 16          # (sign-magnitude: + 0x10000 steps away from zero)
+    fixed = (((bits >> 16) << 16) + away).view(torch.float32)   # an exact bf16 value: the conversion below keeps it
+    return torch.where(fix, fixed, f).to(torch.bfloat16)
+
+
+def compose_tail(w2: torch.Tensor, b2: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor):
+    """ff.net.2 (``w2`` [C][4C], ``b2``) followed by proj_out (``wp`` [C][C], ``bp``) as ONE linear map over the two sources [ff | h]:
+
+        h' = h + ff.W2^T + b2;  out = x + h'.Wp^T + bp   ==   out = x + [ff | h].[Wp.W2 | Wp]^T + (Wp.b2 + bp)
+
+    composed on the host in fp64 from the master weights.  Returns (weight [C][5C] fp64 -- the caller rounds it to bf16 once, with
+    ``round_bf16`` -- and bias [C] fp64)."""
+    w2, b2, wp, bp = (t.detach().to(device="cpu", dtype=torch.float64) for t in (w2, b2, wp, bp))
+    return torch.cat([wp @ w2, wp], dim=1), wp @ b2 + bp
+
+
 def ws_twin_shapes_ok(c: int, n: int, scc0: int, scc1: int) -> bool:
     """The channel rules of conv_ws.hip ``mvd_conv_ws_applicable``: input width a multiple of 128 (a round), output width a multiple
     of 16 (a column tile), and EACH source of a fused 1x1 shortcut a multiple of 128 on its own (the halves of a skip
@@ -187,8 +213,13 @@ def ws_twin_shapes_ok(c: int, n: int, scc0: int, scc1: int) -> bool:
 
 
 def pack_unet(sd: Dict[str, torch.Tensor], cfg: UNetConfig, device, adapter: bool, ref_scale: float = 0.0,
-              small_batch_twins: bool = True) -> Dict[str, torch.Tensor]:
+              small_batch_twins: bool = True, fold_tail: bool = True) -> Dict[str, torch.Tensor]:
     """``sd`` holds diffusers keys (no wrapper prefix) and, when ``adapter``, the ``...processor.*`` keys.
+
+    ``fold_tail`` (the default): every transformer site gets ``<key>.tail.w`` / ``.tail.b`` -- ff.net.2 and proj_out composed into one
+    K-concatenated GEMM (``compose_tail``) -- INSTEAD of ``ff2.w/.b`` and ``proj_out.w/.b/.wx``: the same number of weight elements,
+    one launch less per site.  ``fold_tail=False`` packs the five old slots and the engine runs the two launches (the A/B switch:
+    the engine picks the route by which slots are registered).
 
     ``small_batch_twins=False`` leaves out the second copies only a batch-1 forward reads -- the weight-streaming ``.ws``
     convolution twins (conv_ws.hip) and the LayerNorm-folded ``.wf/.cf`` twins above C = 640 (gemm_sm.hip): ~1.4 GB per SD-2.1
@@ -242,8 +273,15 @@ def pack_unet(sd: Dict[str, torch.Tensor], cfg: UNetConfig, device, adapter: boo
         out[f"{key}.norm.b"] = _f32(sd[f"{key}.norm.bias"], device)
         out[f"{key}.proj_in.w"] = _bf(sd[f"{key}.proj_in.weight"], device)
         out[f"{key}.proj_in.b"] = _f32(sd[f"{key}.proj_in.bias"], device)
-        out[f"{key}.proj_out.w"] = _bf(sd[f"{key}.proj_out.weight"], device)
-        out[f"{key}.proj_out.b"] = _f32(sd[f"{key}.proj_out.bias"], device)
+        if fold_tail:
+            wt, bt = compose_tail(sd[f"{b}.ff.net.2.weight"], sd[f"{b}.ff.net.2.bias"], sd[f"{key}.proj_out.weight"], sd[f"{key}.proj_out.bias"])
+            out[f"{key}.tail.w"] = round_bf16(wt).to(device).contiguous()
+            out[f"{key}.tail.b"] = _f32(bt, device)
+        else:
+            out[f"{key}.proj_out.w"] = _bf(sd[f"{key}.proj_out.weight"], device)
+            out[f"{key}.proj_out.b"] = _f32(sd[f"{key}.proj_out.bias"], device)
+            out[f"{key}.ff2.w"] = _bf(sd[f"{b}.ff.net.2.weight"], device)
+            out[f"{key}.ff2.b"] = _f32(sd[f"{b}.ff.net.2.bias"], device)
         for i in (1, 2, 3):
             out[f"{key}.ln{i}.g"] = _f32(sd[f"{b}.norm{i}.weight"], device)
             out[f"{key}.ln{i}.b"] = _f32(sd[f"{b}.norm{i}.bias"], device)
@@ -281,7 +319,8 @@ def pack_unet(sd: Dict[str, torch.Tensor], cfg: UNetConfig, device, adapter: boo
         if C == XS_K:
             # twins for the X-stationary kernels (gemm_xs.hip): the K = 320 projections of the 64x64 level
             out[f"{key}.proj_in.wx"] = pack_xs(f(f"{key}.proj_in.weight"), f(f"{key}.proj_in.bias"), device=device)
-            out[f"{key}.proj_out.wx"] = pack_xs(f(f"{key}.proj_out.weight"), f(f"{key}.proj_out.bias"), device=device)
+            if not fold_tail:
+                out[f"{key}.proj_out.wx"] = pack_xs(f(f"{key}.proj_out.weight"), f(f"{key}.proj_out.bias"), device=device)
             for a in ("attn1", "attn2"):   # the out-projection of a pass WITHOUT the adapter branch (K = C)
                 out[f"{key}.{a}.out.wx"] = pack_xs(f(f"{b}.{a}.to_out.0.weight"), f(f"{b}.{a}.to_out.0.bias"), device=device)
             if adapter:
@@ -292,8 +331,6 @@ def pack_unet(sd: Dict[str, torch.Tensor], cfg: UNetConfig, device, adapter: boo
                     inv = torch.argsort(_geglu_rows(torch.arange(wf.shape[0], device=wf.device)))
                     wf, cf = wf[inv], cf[:, inv]
                 out[f"{slot}.wx"] = pack_xs(wf, cf[1], geglu=geglu, device=device)
-        out[f"{key}.ff2.w"] = _bf(sd[f"{b}.ff.net.2.weight"], device)
-        out[f"{key}.ff2.b"] = _f32(sd[f"{b}.ff.net.2.bias"], device)
 
     out["text_kv.w"] = _bf(torch.cat(tkv, 0), device)
     n = cfg.num_levels
