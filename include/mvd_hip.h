@@ -222,6 +222,14 @@ int mvd_engine_apply_modulation(mvd_engine_t* e, const char* name, const float* 
                                 int channels, int hw, float* out_nchw, void* stream);
 /* Camera embedding of the last forward ([batch][cam_output_dim] fp32), for parity tests. */
 int mvd_engine_get_camera_embedding(mvd_engine_t* e, float* out, void* stream);
+/* FiLM parameters of every hooked modulator (down_i, up_i, output: the forward's order) from an embedding emb [cam_batch][
+ * cam_output_dim], through the function the forward's camera path runs (the concatenated form when the cam.modcat.* slots are
+ * registered, else one modulator at a time).  out, in the engine's own layout: per modulator scale [out_rows][dim] | shift
+ * [out_rows][dim]; rows beyond cam_batch repeat the cameras cyclically (row r = camera r % cam_batch). */
+int mvd_engine_film_params(mvd_engine_t* e, const float* emb, int cam_batch, int out_rows, float* out, void* stream);
+/* The forward's time path on weight set 0: timesteps [batch] -> out [batch][sum of resnet cout] fp32, every resnet's
+ * time_emb_proj output (bias included) in module order. */
+int mvd_engine_time_projection(mvd_engine_t* e, const float* timesteps, int batch, float* out, void* stream);
 
 /* ---- operator-level entry points (same kernels the engine schedules; used by tests) -- */
 /* out[M][N] = alpha*(A[M][K] . W[N][K]^T + bias + rowvec[m/rows_per_batch]) + res ; bf16 A/W/res
@@ -317,6 +325,33 @@ int mvd_op_f32_to_bf16(const float* x, int64_t n, void* y, void* stream);
  * sum_k act(x[b][k]) W[o][k] + bias[o]; W fp32 [n][k], or bf16 with wbf16 = 1; act_in = 1 applies SiLU to the inputs. */
 int mvd_op_skinny_linear(const float* x, int ldx, int batch, int k, const void* w, int wbf16, const float* bias, int n, int act_in,
                          float* y, int ldy, void* stream);
+/* The other kernels of the fp32 camera / time conditioning path, one launcher each.
+ * timestep_embedding: y [batch][dim] = [cos | sin] of t * 10000^(-i / (dim/2)), dim even.
+ * camera_features: cameras [batch][cam_rows][4] (cam_rows 3 or 4) -> rflat [batch][9] = tR . sR^T, enc [batch][6 nfreq] =
+ *   per axis of T = tT - R sT: [sin nfreq | cos nfreq] of T * max_freq^(i / (nfreq - 1)).
+ * layernorm_f32: rows of c floats; row r takes gamma / beta + (r % nseg) * c; silu = 1 applies SiLU to the result.
+ * skinny_linear_grouped: output feature o of segment g (seg_end[g-1] <= o < seg_end[g], nseg <= 16, even ends, the last = n)
+ *   reads the input row x + b * ldx + g * xseg; fp32 weights [n][k], k % 4 == 0.
+ * film_params: raw [batch][2 dim] -> scale = 2 strength sigmoid(raw[:dim]), shift = strength raw[dim:], [out_rows][dim] each,
+ *   output row r from raw row r % batch.  _grouped: raw [batch][seg_end[nseg-1]] holds 2 dim_g features per segment; segment
+ *   g's scale | shift [out_rows][dim_g] start at out + out_rows * seg_end[g-1].
+ * im2col_in: x NCHW fp32 (c <= 7), optionally x * scale[b * ld_ss + ch] + shift[b * ld_ss + ch], -> bf16 rows [pixel][64] with
+ *   column tap * c + ch of the 3x3 pad-1 window, zero for padding taps and for columns 9 c .. 63.
+ * film_nchw_f32: y = x * scale[b][ch] + shift[b][ch] on x [batch][c][hw] fp32. */
+int mvd_op_timestep_embedding(const float* t, int batch, int dim, float* y, void* stream);
+int mvd_op_camera_features(const float* src, const float* tgt, int batch, int cam_rows, int nfreq, float max_freq, float* rflat,
+                           float* enc, void* stream);
+int mvd_op_layernorm_f32(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, int silu, int nseg,
+                         float* y, void* stream);
+int mvd_op_skinny_linear_grouped(const float* x, int ldx, int xseg, int batch, int k, const float* w, const float* bias, int n,
+                                 const int* seg_end, int nseg, float* y, int ldy, void* stream);
+int mvd_op_film_params(const float* raw, int batch, int dim, float strength, float* scale, float* shift, int out_rows,
+                       void* stream);
+int mvd_op_film_params_grouped(const float* raw, int batch, const int* seg_end, int nseg, float strength, float* out, int out_rows,
+                               void* stream);
+int mvd_op_im2col_in(const float* x, int batch, int c, int h, int w, const float* scale, const float* shift, int ld_ss, void* y,
+                     void* stream);
+int mvd_op_film_nchw_f32(const float* x, int batch, int c, int hw, const float* scale, const float* shift, float* y, void* stream);
 int mvd_gemm_num_configs(void);
 /* What the calling thread's last GEMM/conv launch did: out[5] = {tile config, split-K, work items, workgroups, workgroups
  * per CU}; last attention launch: out[2] = {waves per workgroup, workgroups}.  Parity tests assert with these that the

@@ -912,19 +912,15 @@ std::vector<std::pair<std::string, int>> modulator_dims(const mvd_config_t& cfg,
   return mods;
 }
 
-// The camera batch Bc may be smaller than the sample batch B (classifier-free guidance doubles the latents but not the
-// cameras, pipeline.py:141-152): the (Bc, C, 1, 1) scale/shift then broadcasts over the sample rows like torch does for
-// Bc == 1; for 1 < Bc < B (Bc | B) row b takes camera b % Bc, i.e. the [uncond | cond] halves share their cameras.
-int camera_path(Ctx& c, const mvd_forward_args_t& a, std::unordered_map<std::string, std::pair<float*, float*>>& ss) {
+// FiLM scale/shift of every hooked modulator: emb [Bc][D] -> ss[name] = {scale [B][dim], shift [B][dim]}, rows beyond Bc
+// replicated cyclically (B >= Bc).  The forward (camera_path) and mvd_engine_film_params both run this.  `concat`: the
+// concatenated slots are there (a sizing pass that cannot know assumes so; one that can must size the form that will run).
+int film_params_all(Ctx& c, const float* emb, int Bc, int B, std::unordered_map<std::string, std::pair<float*, float*>>& ss, bool concat) {
   const mvd_config_t& cfg = c.e->cfg;
-  const int B = a.batch, D = cfg.cam_output_dim;
-  const int Bc = a.cam_batch > 0 ? a.cam_batch : B;
-  float* emb = c.aalloc<float>((size_t)Bc * D);
-  c.e->cam_emb = emb; c.e->cam_batch = Bc;
-  CHECK(camera_embed(c, a.source_camera, a.target_camera, a.cam_rows, a.fourier_proj, Bc, emb));
+  const int D = cfg.cam_output_dim;
   // all hooked modulators at once when the concatenated slots are registered (packing.pack_camera): 4 launches instead of 4 each
   const auto mods = modulator_dims(cfg, false);
-  if ((c.dry || c.has("cam.modcat.w0", 0)) && mods.size() <= 16) {
+  if (concat && mods.size() <= 16) {
     const int nm = (int)mods.size(), Hh = D / 2;
     MvdSegTable seg; memset(&seg, 0, sizeof(seg));
     seg.n = nm;
@@ -956,7 +952,7 @@ int camera_path(Ctx& c, const mvd_forward_args_t& a, std::unordered_map<std::str
     }
     return c.err;
   }
-  for (auto& m : modulator_dims(cfg, false)) {
+  for (auto& m : mods) {
     float* sc = c.aalloc<float>((size_t)B * m.second);
     float* sh = c.aalloc<float>((size_t)B * m.second);
     const size_t mk = c.e->tmp.off;
@@ -965,6 +961,19 @@ int camera_path(Ctx& c, const mvd_forward_args_t& a, std::unordered_map<std::str
     ss[m.first] = {sc, sh};
   }
   return c.err;
+}
+
+// The camera batch Bc may be smaller than the sample batch B (classifier-free guidance doubles the latents but not the
+// cameras, pipeline.py:141-152): the (Bc, C, 1, 1) scale/shift then broadcasts over the sample rows like torch does for
+// Bc == 1; for 1 < Bc < B (Bc | B) row b takes camera b % Bc, i.e. the [uncond | cond] halves share their cameras.
+int camera_path(Ctx& c, const mvd_forward_args_t& a, std::unordered_map<std::string, std::pair<float*, float*>>& ss) {
+  const mvd_config_t& cfg = c.e->cfg;
+  const int B = a.batch, D = cfg.cam_output_dim;
+  const int Bc = a.cam_batch > 0 ? a.cam_batch : B;
+  float* emb = c.aalloc<float>((size_t)Bc * D);
+  c.e->cam_emb = emb; c.e->cam_batch = Bc;
+  CHECK(camera_embed(c, a.source_camera, a.target_camera, a.cam_rows, a.fourier_proj, Bc, emb));
+  return film_params_all(c, emb, Bc, B, ss, c.dry || c.has("cam.modcat.w0", 0));
 }
 
 // Split-K arrival counters for one entry call: a block of the workspace, zeroed once (one memset node in front of the
@@ -1682,6 +1691,56 @@ int mvd_engine_get_camera_embedding(mvd_engine_t* e, float* out, void* stream) {
   return (int)hipMemcpyAsync(out, e->cam_emb, (size_t)e->cam_batch * e->cfg.cam_output_dim * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
+// Both arenas of a stand-alone entry that runs forward code: sized by the dry pass that precedes it, laid out like unet_forward's.
+static int bind_standalone_arenas(mvd_engine_t* e) {
+  size_t act_bytes = 0;
+  if (int r = workspace_fits(e, &act_bytes)) return r;
+  e->act.reset(false); e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
+  e->tmp.reset(false); e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
+  return 0;
+}
+
+// Stand-alone FiLM parameters of every hooked modulator, through the function the forward's camera path runs.
+int mvd_engine_film_params(mvd_engine_t* e, const float* emb, int cam_batch, int out_rows, float* out, void* stream) {
+  if (!e || !emb || !out || cam_batch <= 0 || out_rows < cam_batch) { mvd_set_error("film_params: bad argument"); return -1; }
+  if (!e->ws_ptr) { mvd_set_error("film_params: workspace not bound"); return -1; }
+  std::unordered_map<std::string, std::pair<float*, float*>> ss;
+  const bool concat = e->w[0].has("cam.modcat.w0");
+  {   // dry sizing pass first (see encode_cameras)
+    e->tmp.reset(true); e->act.reset(true);
+    Ctx d{e, nullptr, 0, true};
+    if (int r = film_params_all(d, emb, cam_batch, out_rows, ss, concat)) return r;
+  }
+  if (int r = bind_standalone_arenas(e)) return r;
+  Ctx c{e, (hipStream_t)stream, 0, false};
+  ss.clear();
+  if (int r = film_params_all(c, emb, cam_batch, out_rows, ss, concat)) return r;
+  for (auto& m : modulator_dims(e->cfg, false)) {   // the engine's layout: per modulator scale [out_rows][dim] | shift [out_rows][dim]
+    const size_t n = (size_t)out_rows * m.second;
+    const auto& p = ss[m.first];
+    if (hipMemcpyAsync(out, p.first, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
+        hipMemcpyAsync(out + n, p.second, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("film_params: hipMemcpyAsync failed"); return -3; }
+    out += 2 * n;
+  }
+  return 0;
+}
+
+// Stand-alone time path (weight set 0): timesteps [batch] -> out [batch][temb_total], every resnet's time_emb_proj output.
+int mvd_engine_time_projection(mvd_engine_t* e, const float* timesteps, int batch, float* out, void* stream) {
+  if (!e || !timesteps || !out || batch <= 0) { mvd_set_error("time_projection: bad argument"); return -1; }
+  if (!e->ws_ptr) { mvd_set_error("time_projection: workspace not bound"); return -1; }
+  const float* tproj = nullptr;
+  for (int dry = 1; dry >= 0; --dry) {   // dry sizing pass first (see encode_cameras)
+    if (dry) { e->tmp.reset(true); e->act.reset(true); }
+    else if (int r = bind_standalone_arenas(e)) return r;
+    Ctx c{e, dry ? nullptr : (hipStream_t)stream, 0, dry != 0};
+    if (int r = setup_tile_counters(e, (unsigned int*)e->act.alloc(MVD_TILE_COUNTERS * sizeof(unsigned int)), c.s, c.dry)) return r;
+    if (int r = time_path(c, timesteps, batch, &tproj)) return r;
+  }
+  if (hipMemcpyAsync(out, tproj, (size_t)batch * e->temb_total * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("time_projection: hipMemcpyAsync failed"); return -3; }
+  return 0;
+}
+
 // ------------------------------------------------------------------ operator-level entry points
 // small-M kernels with split-K (force_cfg >= 100): the tile counters live behind the partials in the caller's split-K
 // workspace (MVD_OP_SPLITK_COUNTERS extra 4-byte words, zeroed here per call); the kernel combines the slices itself
@@ -1884,6 +1943,50 @@ int mvd_op_f32_to_bf16(const float* x, int64_t n, void* y, void* stream) {
 int mvd_op_skinny_linear(const float* x, int ldx, int batch, int k, const void* w, int wbf16, const float* bias, int n, int act_in,
                          float* y, int ldy, void* stream) {
   return mvd_launch_skinny_linear(x, ldx, batch, k, w, wbf16, bias, n, act_in, y, ldy, (hipStream_t)stream);
+}
+/* the remaining kernels of the fp32 camera / time conditioning path, one launcher each (the launchers check the arguments) */
+int mvd_op_timestep_embedding(const float* t, int batch, int dim, float* y, void* stream) {
+  return mvd_launch_timestep_embedding(t, batch, dim, y, (hipStream_t)stream);
+}
+int mvd_op_camera_features(const float* src, const float* tgt, int batch, int cam_rows, int nfreq, float max_freq, float* rflat, float* enc,
+                           void* stream) {
+  return mvd_launch_camera_features(src, tgt, batch, cam_rows, nfreq, max_freq, rflat, enc, (hipStream_t)stream);
+}
+int mvd_op_layernorm_f32(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, int silu, int nseg, float* y,
+                         void* stream) {
+  return mvd_launch_layernorm_f32(x, rows, c, eps, gamma, beta, silu, y, (hipStream_t)stream, nseg);
+}
+static int op_seg_table(const int* seg_end, int nseg, MvdSegTable* seg, const char* what) {
+  if (!seg_end || nseg < 1 || nseg > 16) { mvd_set_error("%s: 1..16 segment ends", what); return -1; }
+  memset(seg, 0, sizeof(*seg));
+  seg->n = nseg;
+  for (int g = 0; g < nseg; ++g) {
+    if (seg_end[g] <= (g ? seg_end[g - 1] : 0)) { mvd_set_error("%s: segment ends must increase", what); return -1; }
+    seg->end[g] = seg_end[g];
+  }
+  return 0;
+}
+int mvd_op_skinny_linear_grouped(const float* x, int ldx, int xseg, int batch, int k, const float* w, const float* bias, int n,
+                                 const int* seg_end, int nseg, float* y, int ldy, void* stream) {
+  MvdSegTable seg;
+  if (int r = op_seg_table(seg_end, nseg, &seg, "skinny_linear_grouped")) return r;
+  return mvd_launch_skinny_linear_grouped(x, ldx, xseg, batch, k, w, bias, n, seg, y, ldy, (hipStream_t)stream);
+}
+int mvd_op_film_params(const float* raw, int batch, int dim, float strength, float* scale, float* shift, int out_rows, void* stream) {
+  return mvd_launch_film_params(raw, batch, dim, strength, scale, shift, out_rows, (hipStream_t)stream);
+}
+int mvd_op_film_params_grouped(const float* raw, int batch, const int* seg_end, int nseg, float strength, float* out, int out_rows,
+                               void* stream) {
+  MvdSegTable seg;
+  if (int r = op_seg_table(seg_end, nseg, &seg, "film_params_grouped")) return r;
+  return mvd_launch_film_params_grouped(raw, batch, seg, strength, out, out_rows, (hipStream_t)stream);
+}
+int mvd_op_im2col_in(const float* x, int batch, int c, int h, int w, const float* scale, const float* shift, int ld_ss, void* y,
+                     void* stream) {
+  return mvd_launch_im2col_in(x, batch, c, h, w, scale, shift, ld_ss, (bf16_t*)y, (hipStream_t)stream);
+}
+int mvd_op_film_nchw_f32(const float* x, int batch, int c, int hw, const float* scale, const float* shift, float* y, void* stream) {
+  return mvd_launch_film_nchw_f32(x, batch, c, hw, scale, shift, y, (hipStream_t)stream);
 }
 
 }  // extern "C"

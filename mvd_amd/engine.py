@@ -431,3 +431,44 @@ class MVDEngine:
         t = torch.empty(batch, self.cam_output_dim, dtype=torch.float32, device=self.device)
         L.call("mvd_engine_get_camera_embedding", self._h, _ptr(t), L.stream())
         return t
+
+    def hooked_modulators(self):
+        """[(name, dim)] of the modulators the hooks address, in the engine's order (``mid`` is never addressed, Q3)."""
+        ch = list(self.cfg.block_out_channels)
+        n = len(ch)
+        return [(f"down_{i}", ch[i]) for i in range(n)] + [(f"up_{i}", ch[n - 1 - i]) for i in range(n)] + [("output", 4)]
+
+    def film_params(self, emb: torch.Tensor, out_rows: Optional[int] = None) -> Dict[str, tuple]:
+        """{modulator: (scale, shift)}, (out_rows, dim) fp32 each, from a camera embedding (cam_batch, cam_output_dim): the FiLM
+        parameters as the forward's camera path computes them (same function, same launches); rows beyond cam_batch repeat the
+        cameras cyclically."""
+        emb = emb.to(device=self.device, dtype=torch.float32).contiguous()
+        assert emb.dim() == 2 and emb.shape[1] == self.cam_output_dim
+        bc = emb.shape[0]
+        rows = bc if out_rows is None else int(out_rows)
+        if self._ws is None:
+            self._ensure_workspace(max(rows, 1), 8, 8, 8, 0, False)
+        mods = self.hooked_modulators()
+        out = torch.empty(rows * 2 * sum(d for _, d in mods), dtype=torch.float32, device=self.device)
+        L.call("mvd_engine_film_params", self._h, _ptr(emb), bc, rows, _ptr(out), L.stream())
+        res, off = {}, 0
+        for name, d in mods:
+            res[name] = (out[off:off + rows * d].view(rows, d), out[off + rows * d:off + 2 * rows * d].view(rows, d))
+            off += 2 * rows * d
+        return res
+
+    def time_projection(self, timesteps: torch.Tensor) -> Dict[int, torch.Tensor]:
+        """{resnet index (module order): (B, cout) fp32}: every resnet's ``time_emb_proj(silu(time_embedding(t)))`` as the forward's
+        time path computes it on the base weights."""
+        t = timesteps.to(device=self.device, dtype=torch.float32).contiguous().view(-1)
+        b = t.shape[0]
+        if self._ws is None:
+            self._ensure_workspace(max(b, 1), 8, 8, 8, 0, False)
+        couts = [cout for _key, _cin, cout in self.cfg.resnets()]
+        out = torch.empty(b, sum(couts), dtype=torch.float32, device=self.device)
+        L.call("mvd_engine_time_projection", self._h, _ptr(t), b, _ptr(out), L.stream())
+        res, off = {}, 0
+        for i, c in enumerate(couts):
+            res[i] = out[:, off:off + c]
+            off += c
+        return res

@@ -787,14 +787,116 @@ def image_metrics(x, y, data_range, ssim=True, per_image=False):
     return result, pi
 
 
-def skinny_linear(x, w, bias=None, silu_in=False):
-    """fp32 linear layer of the camera / time MLPs: x (B, K) fp32, w (N, K) fp32 or bf16 -> (B, N) fp32."""
-    assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 2 and w.dim() == 2 and w.shape[1] == x.shape[1]
-    assert w.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous() and w.is_contiguous()
+def _rows(t):
+    """(pointer, row stride) of a 2-D fp32 CUDA tensor whose rows are dense: a column slice or an offset view of a wider
+    buffer is passed as it is, its ``stride(0)`` as the leading dimension."""
+    assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), "rows must be dense fp32"
+    return C.c_void_p(t.data_ptr()), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def skinny_linear(x, w, bias=None, silu_in=False, out=None):
+    """fp32 linear layer of the camera / time MLPs: x (B, K) fp32, w (N, K) fp32 or bf16 -> (B, N) fp32.  ``x`` may be a view with
+    ``stride(0) > K`` (ldx); ``out`` a (B, N) view of a wider buffer, ``stride(0)`` its ldy (the engine writes the two halves of
+    its concatenated input that way) -- the columns of the buffer outside the view are not written."""
+    assert x.dim() == 2 and w.dim() == 2 and w.shape[1] == x.shape[1]
+    assert w.dtype in (torch.float32, torch.bfloat16) and w.is_contiguous()
     b, k = x.shape
     n = w.shape[0]
+    y = torch.empty(b, n, device=x.device, dtype=torch.float32) if out is None else out
+    assert tuple(y.shape) == (b, n)
+    (xp, ldx), (yp, ldy) = _rows(x), _rows(y)
+    L.call("mvd_op_skinny_linear", xp, ldx, b, k, _p(w), int(w.dtype == torch.bfloat16), _p(bias), n, int(silu_in), yp, ldy, _s())
+    return y
+
+
+def _seg(seg_end):
+    return (C.c_int * len(seg_end))(*[int(v) for v in seg_end]), len(seg_end)
+
+
+def skinny_linear_grouped(x, w, seg_end, bias=None, xseg=None):
+    """x (B, nseg * K) fp32 (or any row-dense view; segment g's input row starts ``g * xseg`` floats in, default K), w (N, K) fp32,
+    ``seg_end``: the ends of the output-feature segments (the last one N) -> (B, N) fp32."""
+    assert w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and x.dim() == 2
+    n, k = w.shape
+    b = x.shape[0]
     y = torch.empty(b, n, device=x.device, dtype=torch.float32)
-    L.call("mvd_op_skinny_linear", _p(x), k, b, k, _p(w), int(w.dtype == torch.bfloat16), _p(bias), n, int(silu_in), _p(y), n, _s())
+    xp, ldx = _rows(x)
+    se, ns = _seg(seg_end)
+    xseg = k if xseg is None else int(xseg)
+    assert xseg >= 0 and (ns - 1) * xseg + k <= x.shape[1] and (bias is None or bias.numel() == n), "a segment's input lies outside the row"
+    L.call("mvd_op_skinny_linear_grouped", xp, ldx, xseg, b, k, _p(w), _p(bias), n, se, ns, _p(y), n, _s())
+    return y
+
+
+def timestep_embedding(t, dim):
+    """t (B,) fp32 -> (B, dim) fp32 [cos | sin] (diffusers ``Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)``)."""
+    assert t.dtype == torch.float32 and t.dim() == 1
+    y = torch.empty(t.shape[0], dim, device=t.device, dtype=torch.float32)
+    L.call("mvd_op_timestep_embedding", _p(t), t.shape[0], int(dim), _p(y), _s())
+    return y
+
+
+def camera_features(src, tgt, nfreq, max_freq=10.0):
+    """cameras (B, 3 or 4, 4) fp32 -> (rflat (B, 9), enc (B, 6 * nfreq)): the relative rotation and the Fourier features of the
+    relative translation, per axis [sin nfreq | cos nfreq]."""
+    assert src.dtype == torch.float32 and tgt.dtype == torch.float32 and src.shape == tgt.shape and src.dim() == 3 and src.shape[2] == 4
+    b, rows = src.shape[0], src.shape[1]
+    rflat = torch.empty(b, 9, device=src.device, dtype=torch.float32)
+    enc = torch.empty(b, 6 * nfreq, device=src.device, dtype=torch.float32)
+    L.call("mvd_op_camera_features", _p(src), _p(tgt), b, rows, int(nfreq), float(max_freq), _p(rflat), _p(enc), _s())
+    return rflat, enc
+
+
+def layernorm_f32(x, gamma, beta, eps=1e-5, silu=False, nseg=1):
+    """x (rows, c) fp32; gamma / beta (c,) or, grouped, (nseg, c): row r takes the affine of segment r % nseg."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and gamma.numel() == nseg * x.shape[1] and beta.numel() == nseg * x.shape[1]
+    y = torch.empty_like(x)
+    L.call("mvd_op_layernorm_f32", _p(x), x.shape[0], x.shape[1], float(eps), _p(gamma), _p(beta), int(silu), int(nseg), _p(y), _s())
+    return y
+
+
+def film_params(raw, strength, out_rows=None):
+    """raw (B, 2 * dim) fp32 -> (scale, shift), (out_rows, dim) each; output row r comes from raw row r % B."""
+    assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.shape[1] % 2 == 0
+    b, dim = raw.shape[0], raw.shape[1] // 2
+    rows = b if out_rows is None else int(out_rows)
+    scale = torch.empty(rows, dim, device=raw.device, dtype=torch.float32)
+    shift = torch.empty(rows, dim, device=raw.device, dtype=torch.float32)
+    L.call("mvd_op_film_params", _p(raw), b, dim, float(strength), _p(scale), _p(shift), rows, _s())
+    return scale, shift
+
+
+def film_params_grouped(raw, seg_end, strength, out_rows=None):
+    """raw (B, seg_end[-1]) fp32, segment g holding 2 * dim_g features -> the flat engine layout (out_rows * seg_end[-1],): per
+    segment scale (out_rows, dim_g) | shift (out_rows, dim_g)."""
+    assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.shape[1] == seg_end[-1]
+    b = raw.shape[0]
+    rows = b if out_rows is None else int(out_rows)
+    out = torch.empty(rows * seg_end[-1], device=raw.device, dtype=torch.float32)
+    se, ns = _seg(seg_end)
+    L.call("mvd_op_film_params_grouped", _p(raw), b, se, ns, float(strength), _p(out), rows, _s())
+    return out
+
+
+def im2col_in(x, scale=None, shift=None, ld_ss=0):
+    """x (B, C, H, W) fp32, C <= 7 (+ FiLM ``x * scale[b * ld_ss + ch] + shift[b * ld_ss + ch]``) -> (B, H, W, 64) bf16 rows of the
+    3x3 pad-1 window, column tap * C + ch."""
+    assert x.dtype == torch.float32 and x.dim() == 4
+    B, c, H, W = x.shape
+    if scale is not None:
+        need = (B - 1) * ld_ss + c
+        assert scale.dtype == torch.float32 and shift.dtype == torch.float32 and scale.numel() >= need and shift.numel() >= need
+    y = torch.empty(B, H, W, 64, device=x.device, dtype=torch.bfloat16)
+    L.call("mvd_op_im2col_in", _p(x), B, c, H, W, _p(scale), _p(shift), int(ld_ss), _p(y), _s())
+    return y
+
+
+def film_nchw_f32(x, scale, shift):
+    """x (B, C, HW) fp32, scale / shift (B, C) fp32 -> x * scale + shift."""
+    assert x.dtype == torch.float32 and x.dim() == 3 and tuple(scale.shape) == tuple(x.shape[:2]) == tuple(shift.shape)
+    assert scale.dtype == torch.float32 and shift.dtype == torch.float32
+    y = torch.empty_like(x)
+    L.call("mvd_op_film_nchw_f32", _p(x), x.shape[0], x.shape[1], x.shape[2], _p(scale), _p(shift), _p(y), _s())
     return y
 
 
