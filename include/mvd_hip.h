@@ -76,18 +76,23 @@ enum {
   MVD_SHARE_REF = 16        /* `views` views of ONE object in one forward, sharing one reference (below)  */
 };
 
-/* MVD_SHARE_REF (with MVD_USE_IMAGE; no counterpart in the reference, whose infer.py:111-122 makes one batch-1 call per
+/* The batch layout of a forward, described once for the three entries below (the engine holds it as one value, csrc/ragged.h):
+ * O objects, object o seen from V_o views, R = sum of the V_o, g rows per view (1, or 2 under classifier-free guidance).  The
+ * sample holds g * R rows [uncond x R | cond x R], object-major inside a half: row r = j * R + c, c = (views of the objects before
+ * o) + v, is row j of the batch-g call of view v of object o with a one-row reference.  It attends tokens [j * hw / g,
+ * (j + 1) * hw / g) of object o's reference and text row j * O + o, takes camera c (or the one camera) and timesteps[r];
+ * `source_latents` / `encoder_text` hold O rows, `text` g * O, the cameras 0, 1 or R; hw % g == 0 at every level; all of it is
+ * checked on the host before any launch, in the words of the entry that was called.  The forms: one object and V views --
+ * MVD_SHARE_REF with args->views = V on mvd_unet_forward; O objects x V views -- the object count beside the block,
+ * mvd_unet_forward_objects; counts that differ -- the counts beside the block, mvd_unet_forward_ragged, where equal counts are the
+ * objects form and one object the views form, rejections included.  A reference cached under one layout is never served to another.
+ *
+ * MVD_SHARE_REF (with MVD_USE_IMAGE; no counterpart in the reference, whose infer.py:111-122 makes one batch-1 call per
  * view): the forward computes what `views` independent forwards of batch g = batch / views (1, or 2 under classifier-free
- * guidance) with a ONE-row reference compute, from one encoder pass and one copy of the reference K/V.  The sample rows come
- * in the pipeline's order [uncond x views | cond x views]: row r = j * views + v is row j of view v's own call, so it
- *   - attends reference tokens [j * hw / g, (j + 1) * hw / g) of the single reference in both adapter branches (Q4 at
- *     batch g), and text row j;
- *   - takes camera v (cam_batch = views: the existing r % cam_batch rule), timesteps[r];
- * the encoder pass, the Q2 statistics and the ref_kv projection run once, at ref_batch = 1.  Shapes: batch = g * views with
- * g in {1, 2}; ref_batch = 1; `text` holds g rows and `encoder_text` 1 row; the cameras hold 0, 1 or `views` rows; hw % g == 0 at
- * every level.  Anything else is rejected on the host before any launch, as is the flag on mvd_engine_reference_encode
- * (the global-statistics path is for batches sharded over ranks: more than one object).  Size the workspace with
- * mvd_engine_workspace_bytes_args; the reference cache is that of ref_batch = 1. */
+ * guidance) with a ONE-row reference compute, from one encoder pass and one copy of the reference K/V: the layout above with
+ * O = 1, R = views (Q4 at batch g in both adapter branches; camera v by the existing r % cam_batch rule).  The encoder pass, the
+ * Q2 statistics and the ref_kv projection run once, at ref_batch = 1.  The flag is rejected on mvd_engine_reference_encode too (the global-statistics path is for batches
+ * sharded over ranks: more than one object).  Size the workspace with mvd_engine_workspace_bytes_args. */
 
 /* One MultiViewUNet.forward (mvd_unet.py:179-338).  All tensors fp32, contiguous. */
 typedef struct {
@@ -129,21 +134,16 @@ int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_
  * The encoder pass runs once at batch O (`source_latents`, `encoder_text`: O rows, row o what object o's own call would use), the
  * Q2 statistics are taken per object (per pixel over that object's channels only: mvd_op_refnorm at batch 1), the ref_kv
  * projection runs once over O * hw rows and the reference cache is that of ref_batch = O.  Every object has the same V.
- * Checked on the host before any launch: MVD_SHARE_REF with MVD_USE_IMAGE; ref_batch == O; batch == g * O * views with g in
- * {1, 2}; cameras with 0, 1 or O * views rows; hw % g == 0 at every level.  objects <= 1: exactly mvd_unet_forward /
- * mvd_engine_workspace_bytes_args, with their rejections.  A reference cached by one mode is never served to another. */
+ * Shapes and checks: the layout above with R = O * views.  objects <= 1: exactly mvd_unet_forward /
+ * mvd_engine_workspace_bytes_args, with their rejections. */
 int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream);
 int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects);
 
 /* Ragged turntables: O objects with view_counts[o] >= 1 views each in one MVD_SHARE_REF forward (mvd_forward_args_t is unchanged
  * and args->views must be 0: the counts come beside it).  With R = sum of the counts and g rows per view (1, or 2 under
  * guidance) the forward IS the R independent forwards of batch g, each with a one-row reference -- the definition of
- * mvd_unet_forward_objects with V per object.  The sample holds g * R rows [uncond x R | cond x R], object-major inside a half;
- * with c = (views of the objects before o) + v, row r = j * R + c
- *   - attends, in both adapter branches and all 16 features, tokens [j * hw / g, (j + 1) * hw / g) of object o's reference only
- *     (K/V element o * g + j of the O * g the ref_kv projection writes object-major);
- *   - attends text row j * O + o (`text` holds g * O rows, [negative x O | positive x O]);
- *   - takes camera c (cam_batch = R, or 1) and timesteps[r].
+ * mvd_unet_forward_objects with V per object, and the layout above as it stands (row r reads K/V element o * g + j of the O * g
+ * the ref_kv projection writes object-major).
  * Encoder pass, Q2 statistics, ref_kv projection and reference cache are those of mvd_unet_forward_objects at ref_batch = O.
  * The two row maps are tables the engine builds from the counts (valid by construction, and checked on the host like any
  * table: 0 <= entry < g * O) and keeps in device slots keyed by (counts, g).  A slot is written once, by a stream-ordered
@@ -151,11 +151,9 @@ int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_ar
  * forward of that layout uploads or synchronises.  At most 8 layouts are resident: a ninth evicts the least recently used
  * one after dropping every captured hipGraph of the engine (mvd_engine_set_graph), so a slot a live graph points at is
  * never rewritten.
- * Checked on the host before any launch: args->views == 0; every count >= 1; MVD_SHARE_REF with MVD_USE_IMAGE;
- * ref_batch == objects; batch == g * R with g in {1, 2}; cameras with 0, 1 or R rows; hw % g == 0 at every level.  Equal counts
- * run mvd_unet_forward_objects (one object: the `views` forward) -- the same code, bit-identical results, their rejections.
- * The reference-cache record and the hipGraph key carry the counts: a reference encoded under one layout is never served
- * to another. */
+ * Shapes and checks: the layout above, and before it args->views == 0, every count >= 1 and batch == g * R.  Equal counts run
+ * mvd_unet_forward_objects (one object: the `views` forward) -- the same code, bit-identical results, their rejections.
+ * The reference-cache record and the hipGraph key carry the counts. */
 int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects, void* stream);
 int64_t mvd_engine_workspace_bytes_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects);
 

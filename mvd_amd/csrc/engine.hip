@@ -44,9 +44,7 @@ struct mvd_engine {
   std::vector<bf16_t*> refkv;       // per feature: [ref_batch*hw][4C]
   std::vector<bf16_t*> feat_keep;   // per feature: [ref_batch][hw][C] when kept
   int rc_batch = 0, rc_h = 0, rc_w = 0; bool rc_valid = false; bool rc_keep = false;
-  int rc_views = 0;                 // views of the MVD_SHARE_REF forward that filled the cache (0: an ordinary forward)
-  int rc_objects = 0;               // objects of the mvd_unet_forward_objects call that filled it (0: one reference for the batch)
-  std::vector<int> rc_layout;       // view counts of the mvd_unet_forward_ragged call that filled it (empty: a uniform forward)
+  std::vector<int> rc_layout;       // ViewLayout::key() of the forward that filled the cache (ragged.h)
   // global Q2 statistics (mvd_engine_reference_encode / _finish): the encoder pass stops before the normalisation
   float* ref_stats_out = nullptr;   // set only while mvd_engine_reference_encode runs
   bool rc_pending = false;          // raw features are in feat_keep, waiting for the merged statistics
@@ -87,14 +85,12 @@ struct mvd_engine {
     std::vector<bf16_t*> refkv, feat_keep;
     int rc_batch, rc_h, rc_w; bool rc_valid, rc_keep;
     float* cam_emb; int cam_batch;
-    int rc_views, rc_objects;
     std::vector<int> rc_layout;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_views, rc_objects, rc_layout}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_layout}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
-    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_views = h.rc_views; rc_objects = h.rc_objects;
-    rc_layout = h.rc_layout;
+    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_layout = h.rc_layout;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -539,22 +535,11 @@ struct PassOpts {
   bool defer_norm = false;    // capture, global-statistics form: per-pixel local (mean, M2) go to `stats`, the features are
   float* stats = nullptr;     // kept raw and normalisation + K/V projection wait for mvd_engine_reference_finish
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
-  int views = 0;              // MVD_SHARE_REF main pass: views per object -- row r = j * views + v attends the reference tokens and
-                              // the text row of guidance half j (0: an ordinary pass)
-  int objects = 0;            // mvd_unet_forward_objects (> 1): that many objects x `views` views -- main pass: row r = j * O * V + o * V + v
-                              // attends object o's reference tokens; encoder pass: Q2 statistics per object (0: one object)
-  // mvd_unet_forward_ragged, main pass: device tables of B entries (kernels.h MvdAttnArgs::kv_index) -- row r reads reference K/V
-  // element kvi_ref[r] of the kv_elems = g * O elements [object][half] and text row kvi_text[r]; views / objects are 0 then
-  const int* kvi_ref = nullptr; const int* kvi_text = nullptr; int kv_elems = 0;
+  const ViewLayout* layout = nullptr;   // the forward's batch layout (ragged.h): the adapter pass's K/V maps, the encoder pass's statistics
   bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
-
-// mvd_unet_forward_ragged: the layout that comes beside the unchanged mvd_forward_args_t -- O >= 2 objects with view counts that
-// differ (equal counts take the objects body), g rows per view, R = sum of the counts, and the two tables of g * R entries
-// (a device slot of the engine; in a sizing run host pointers, which nothing dereferences: a dry pass launches nothing)
-struct RaggedLayout { const int* counts; int objects, g, rows; const int* kvi_ref; const int* kvi_text; };
 
 // ---------------------------------------------------------------------- one UNet pass
 struct UNetPass {
@@ -611,12 +596,9 @@ struct UNetPass {
     bf16_t* o_self = c.talloc<bf16_t>((size_t)M * C);
     bf16_t* o_ref = ad ? c.talloc<bf16_t>((size_t)M * C) : nullptr;
     const bf16_t* rkv = ad ? c.e->refkv[feat_idx] : nullptr;
-    // Q4: K/V rows of the reference are re-chunked by the HIDDEN batch size
-    // (MVD_SHARE_REF: by the batch g = B / views of ONE view's call -- the views of a guidance half share that half's chunk)
-    const int kvg = o.views > 0 ? o.views : 0;
-    // (objects: each object's hw tokens by the batch g = B / (views * objects) of one view's call; K/V elements [object][half])
-    const int kvo = o.objects > 1 ? o.objects : 0;
-    const int Bq = o.kvi_ref ? o.kv_elems : (kvg ? B_ / kvg : B_);      // (ragged: a table per problem instead of the arithmetic map)
+    // Q4: K/V rows of the reference are re-chunked by the HIDDEN batch size (a shared forward: by the batch g of ONE view's call --
+    // the views of a guidance half share that half's chunk; objects: each object's hw tokens, K/V elements [object][half])
+    const int Bq = ad ? o.layout->text_rows(B_) : B_;
     const int ref_nk = ad ? (int)((int64_t)o.ref_batch * hw / Bq) : 0;
     if (ad && (int64_t)ref_nk * Bq != (int64_t)o.ref_batch * hw) { mvd_set_error("adapter: ref tokens %d x %d not divisible by batch %d", o.ref_batch, hw, Bq); return -12; }
 
@@ -631,7 +613,7 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
-      a.kv_group[1] = kvg; a.kv_objects[1] = kvo; a.kv_index[1] = o.kvi_ref;
+      if (ad) o.layout->fill_map(true, &a.kv_group[1], &a.kv_objects[1], &a.kv_index[1]);
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn1.out.wx"));
@@ -647,9 +629,8 @@ struct UNetPass {
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {q2, kv2, kv2 + C, o_self, nq, ldkv, ldkv, C, (int64_t)hw * nq, (int64_t)L * ldkv, (int64_t)L * ldkv, (int64_t)hw * C, hw, L};
       if (ad) a.p[1] = {q2 + C, rkv + 2 * C, rkv + 3 * C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
-      a.kv_group[0] = kvg; a.kv_group[1] = kvg;       // (the text K/V hold one row per guidance half as well -- per half and object,
-      a.kv_objects[1] = kvo;                          //  in the batch's own order: no object map for problem 0)
-      a.kv_index[0] = o.kvi_text; a.kv_index[1] = o.kvi_ref;
+      if (ad) o.layout->fill_map(false, &a.kv_group[0], &a.kv_objects[0], &a.kv_index[0]);     // (the text K/V: one row per half and object)
+      if (ad) o.layout->fill_map(true, &a.kv_group[1], &a.kv_objects[1], &a.kv_index[1]);
       CHECK(c.attention(a));
       CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, M, c.WB(key + ".attn2.out.w", (int64_t)C * ld_out), c.WF(key + ".attn2" + bias_slot, C), C, h, C, h, C, false, false, ld_out,
                      ad ? std::string() : key + ".attn2.out.wx"));
@@ -683,7 +664,7 @@ struct UNetPass {
       if (o.defer_norm) {
         if (!c.dry && !c.err) CHECK(mvd_launch_refstats(out.p, B_, hw, C, o.stats + 2 * c.e->feat_pixel_off(feat_idx), c.s));
       } else {
-        if (!c.dry && !c.err) CHECK(o.objects > 1 ? mvd_launch_refnorm_grouped(out.p, B_, 1, hw, C, rn, c.s) : mvd_launch_refnorm(out.p, B_, hw, C, rn, c.s));
+        if (!c.dry && !c.err) CHECK(o.layout->per_object_stats() ? mvd_launch_refnorm_grouped(out.p, B_, 1, hw, C, rn, c.s) : mvd_launch_refnorm(out.p, B_, hw, C, rn, c.s));
         CHECK(c.linear(rn, nullptr, C, 0, M, c.WB(key + ".ref_kv.w", (int64_t)4 * C * C, 0), nullptr, 4 * C, nullptr, 0, c.e->refkv[feat_idx], 4 * C, false, false, 0,
                        key + ".ref_kv.wx", 0));
         if (c.e->dual_now && !c.dry && !c.err && hipEventRecord(c.e->feat_ev[feat_idx], c.s) != hipSuccess) { mvd_set_error("forward: hipEventRecord failed"); return -3; }
@@ -987,7 +968,7 @@ int setup_tile_counters(mvd_engine* e, unsigned int* block, hipStream_t s, bool 
   return 0;
 }
 
-int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects, const RaggedLayout* rg) {
+int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, const ViewLayout& lay) {
   const mvd_config_t& cfg = e->cfg;
   if (a.batch <= 0 || a.height <= 0 || a.width <= 0 || a.text_len <= 0) { mvd_set_error("forward: bad shape"); return -1; }
   const int div = 1 << (cfg.num_levels - 1);
@@ -1003,48 +984,10 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
     if (!e->ws_ptr) { mvd_set_error("forward: workspace not bound"); return -1; }
   }
   if (use_img && a.ref_batch <= 0) { mvd_set_error("forward: ref_batch must be > 0 with MVD_USE_IMAGE"); return -1; }
-  // ---- MVD_SHARE_REF: `views` views of one object (include/mvd_hip.h); everything is checked here, before any launch
-  const bool share = a.flags & MVD_SHARE_REF;
-  if (!share && a.views > 1) { mvd_set_error("forward: views = %d needs MVD_SHARE_REF", a.views); return -1; }
-  const int V = share ? a.views : 0;
-  // ---- mvd_unet_forward_objects: O > 1 objects x `views` views (include/mvd_hip.h); the same rule: every check before any launch
-  const int O = objects > 1 ? objects : 0;
-  // ---- mvd_unet_forward_ragged: O objects with V_o views each (the entry has checked the counts and that args->views is 0)
-  if (rg) {
-    const int R = rg->rows, g = rg->g;
-    if (ref_only) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
-    if (!share || !use_img) { mvd_set_error("forward_ragged: view counts need MVD_SHARE_REF with MVD_USE_IMAGE"); return -1; }
-    if (a.batch != g * R || g < 1 || g > 2) { mvd_set_error("forward_ragged: batch %d is not 1 or 2 (classifier-free guidance) rows for each of the %d views", a.batch, R); return -1; }
-    if (a.ref_batch != O) { mvd_set_error("forward_ragged: needs ref_batch == objects = %d (one reference row per object), got %d", O, a.ref_batch); return -1; }
-    if (use_cam && a.cam_batch != 1 && a.cam_batch != R) { mvd_set_error("forward_ragged: the cameras must hold 1 or sum of the view counts = %d rows, got %d", R, a.cam_batch); return -1; }
-    for (int lv = 0; lv < cfg.num_levels; ++lv) {
-      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
-      if (hw % g) { mvd_set_error("forward_ragged: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
-    }
-  } else if (O) {
-    if (!share || !use_img) { mvd_set_error("forward_objects: objects = %d needs MVD_SHARE_REF with MVD_USE_IMAGE", O); return -1; }
-    if (V < 1 || a.batch % (O * V)) { mvd_set_error("forward_objects: batch %d is not a multiple of objects %d x views %d", a.batch, O, V); return -1; }
-    const int g = a.batch / (O * V);
-    if (g > 2) { mvd_set_error("forward_objects: %d rows per view (batch %d / (objects %d x views %d)); 1 or 2 (classifier-free guidance) are supported", g, a.batch, O, V); return -1; }
-    if (a.ref_batch != O) { mvd_set_error("forward_objects: needs ref_batch == objects = %d (one reference row per object), got %d", O, a.ref_batch); return -1; }
-    if (use_cam && a.cam_batch != 1 && a.cam_batch != O * V) { mvd_set_error("forward_objects: the cameras must hold 1 or objects x views = %d rows, got %d", O * V, a.cam_batch); return -1; }
-    for (int lv = 0; lv < cfg.num_levels; ++lv) {
-      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
-      if (hw % g) { mvd_set_error("forward_objects: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
-    }
-  } else if (share) {
-    if (ref_only) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
-    if (!use_img) { mvd_set_error("forward: MVD_SHARE_REF needs MVD_USE_IMAGE"); return -1; }
-    if (V < 1 || a.batch % V) { mvd_set_error("forward: MVD_SHARE_REF: batch %d is not a multiple of views %d", a.batch, V); return -1; }
-    const int g = a.batch / V;
-    if (g > 2) { mvd_set_error("forward: MVD_SHARE_REF: %d rows per view (batch %d / views %d); 1 or 2 (classifier-free guidance) are supported", g, a.batch, V); return -1; }
-    if (a.ref_batch != 1) { mvd_set_error("forward: MVD_SHARE_REF needs ref_batch == 1 (one object), got %d", a.ref_batch); return -1; }
-    if (use_cam && a.cam_batch != 1 && a.cam_batch != V) { mvd_set_error("forward: MVD_SHARE_REF: the cameras must hold 1 or views = %d rows, got %d", V, a.cam_batch); return -1; }
-    for (int lv = 0; lv < cfg.num_levels; ++lv) {
-      const int64_t hw = (int64_t)(a.height >> lv) * (a.width >> lv);
-      if (hw % g) { mvd_set_error("forward: MVD_SHARE_REF: the %lld reference tokens of level %d do not divide over %d rows per view", (long long)hw, lv, g); return -1; }
-    }
-  }
+  // ---- the batch layout (ragged.h; include/mvd_hip.h): everything is checked here, before any launch
+  if (!(a.flags & MVD_SHARE_REF) && a.views > 1) { mvd_set_error("forward: views = %d needs MVD_SHARE_REF", a.views); return -1; }
+  char msg[256];
+  if (lay.validate(a.flags & MVD_SHARE_REF, use_img, a.batch, a.ref_batch, use_cam ? a.cam_batch : INT_MIN, a.height, a.width, cfg.num_levels, msg, sizeof(msg))) { mvd_set_error("%s", msg); return -1; }
   // FreeU filters the maps of up blocks 0 and 1 (levels n - 1 and n - 2): a map of one row or column has no frequency -1
   if (e->freeu_on && !ref_only && ((a.height >> (cfg.num_levels - 1)) < 2 || (a.width >> (cfg.num_levels - 1)) < 2)) {
     mvd_set_error("forward: FreeU needs maps of at least 2 x 2 in up block 0, latent %dx%d gives %dx%d", a.height, a.width, a.height >> (cfg.num_levels - 1), a.width >> (cfg.num_levels - 1)); return -1;
@@ -1063,8 +1006,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   if (use_img) {
     const bool keep = (a.flags & MVD_KEEP_FEATURES) || ref_only;
     if (reuse) {
-      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_views != V || e->rc_objects != O ||
-          e->rc_layout != (rg ? std::vector<int>(rg->counts, rg->counts + rg->objects) : std::vector<int>())) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
+      if (!e->rc_valid || e->rc_batch != a.ref_batch || e->rc_h != H || e->rc_w != Wd || e->rc_layout != lay.key()) { mvd_set_error("forward: MVD_REUSE_REF without a matching cached reference"); return -1; }
     } else {
       e->persist.reset(dry);
       e->refkv.assign(e->feats.size(), nullptr);
@@ -1076,8 +1018,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
         if (keep) e->feat_keep[i] = (bf16_t*)e->persist.alloc((size_t)a.ref_batch * hw * e->feats[i].C * sizeof(bf16_t));
       }
       if (e->persist.overflow()) { mvd_set_error("forward: reference cache too small (%zu > %zu bytes)", e->persist.high, e->persist.cap); return -4; }
-      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_views = V; e->rc_objects = O;
-      e->rc_layout = rg ? std::vector<int>(rg->counts, rg->counts + rg->objects) : std::vector<int>();
+      e->rc_keep = keep; e->rc_batch = a.ref_batch; e->rc_h = H; e->rc_w = Wd; e->rc_layout = lay.key();
       if (!dry) { e->rc_valid = false; e->rc_pending = false; }
     }
   }
@@ -1151,7 +1092,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
       CHECK(mvd_launch_f32_to_bf16(a.encoder_text, (int64_t)Br * L * xd, tx, c.s));
       CHECK(mvd_launch_im2col_in(a.source_latents, Br, cfg.in_channels, H, Wd, nullptr, nullptr, 0, xin.p, c.s));
     }
-    PassOpts po; po.capture = true; po.ref_batch = Br; po.objects = O;
+    PassOpts po; po.capture = true; po.ref_batch = Br; po.layout = &lay;
     po.defer_norm = ref_only; po.stats = e->ref_stats_out;
     UNetPass pass{c, cfg, po, Br, H, Wd, L, tx, tproj};
     CHECK(pass.run(xin, nullptr));
@@ -1177,7 +1118,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   c.set = 0;
   const float* tproj = tproj_main;
   if (!tproj) CHECK(time_path(c, a.timesteps, B, &tproj));
-  const int TB = rg ? rg->g * O : (share ? B / V : B);          // text rows: one per guidance half (and object) in a shared forward
+  const int TB = lay.text_rows(B);          // text rows: one per guidance half (and object) in a shared forward
   bf16_t* tx = c.aalloc<bf16_t>((size_t)TB * L * xd);
   Act xin = c.new_act(B, H, Wd, 64, true);   // im2col rows for conv_in
   if (!dry && !c.err) {
@@ -1191,9 +1132,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   //  measured no difference and has no switch.)
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
-  po.views = V; po.objects = O;
+  po.layout = &lay;
   po.freeu = e->freeu_on;
-  if (rg) { po.views = 0; po.objects = 0; po.kvi_ref = rg->kvi_ref; po.kvi_text = rg->kvi_text; po.kv_elems = rg->g * O; }
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
@@ -1209,8 +1149,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
 // Every exit of a forward that forked the side stream joins it: an error return between fork and join (a failed check in the
 // camera path or a pass, a workspace that is too small) must not leave the encoder pass writing the reference cache and the
 // activation arena while the caller frees or reuses them.  The success path has joined with an event already.
-int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, int objects = 0, const RaggedLayout* rg = nullptr) {
-  const int r = forward_body(e, a, s, dry, objects, rg);
+int forward_impl(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool dry, const ViewLayout& lay = ViewLayout()) {
+  const int r = forward_body(e, a, s, dry, lay);
   if (e->dual_now) {
     if (e->side) (void)hipStreamSynchronize(e->side);      // error path only: the cheap join is not worth an event here
     e->dual_now = false;
@@ -1310,21 +1250,26 @@ int64_t mvd_engine_workspace_bytes(mvd_engine_t* e, int batch, int height, int w
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
 }
 
-static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, const RaggedLayout* rg = nullptr) {
+// The layout of mvd_unet_forward (objects = 0) / mvd_unet_forward_objects and their sizing entries (null args: the callee says so)
+static ViewLayout uniform_layout(const mvd_forward_args_t* args, int objects) {
+  return args ? ViewLayout::uniform(objects, args->views, args->flags & MVD_SHARE_REF) : ViewLayout();
+}
+
+static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args, const ViewLayout& lay) {
   if (!e || !args) { mvd_set_error("workspace_bytes_args: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("workspace_bytes_args: unknown flag bits 0x%x", args->flags); return -1; }
   const mvd_engine::HostState before = e->host_state();
   // (a sizing call must not depend on the cache state: size the forward that runs the encoder pass, the larger of the two)
   mvd_forward_args_t a = *args;
   a.flags &= ~MVD_REUSE_REF;
-  int r = forward_impl(e, a, nullptr, true, objects, rg);
+  int r = forward_impl(e, a, nullptr, true, lay);
   e->set_host_state(before);
   if (r) return r;
   return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
 }
-int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) { return workspace_bytes_args(e, args, 0); }
+int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) { return workspace_bytes_args(e, args, uniform_layout(args, 0)); }
 int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects) {
-  return workspace_bytes_args(e, args, objects > 1 ? objects : 0);
+  return workspace_bytes_args(e, args, uniform_layout(args, objects));
 }
 
 int64_t mvd_engine_refcache_bytes(mvd_engine_t* e, int ref_batch, int height, int width, int keep_features) {
@@ -1402,127 +1347,14 @@ static int workspace_fits(mvd_engine_t* e, size_t* act_bytes_out) {
   return 0;
 }
 
-// mvd_unet_forward (objects = 0), mvd_unet_forward_objects (objects > 1) and mvd_unet_forward_ragged (rg: its slot is uploaded)
-static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream, const RaggedLayout* rg = nullptr) {
-  if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
-  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
-  // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
-  const mvd_engine::HostState before = e->host_state();
-  int r = forward_impl(e, *args, nullptr, true, objects, rg);
-  e->set_host_state(before);
-  if (r) return r;
-  size_t act_bytes = 0;
-  if ((r = workspace_fits(e, &act_bytes))) return r;
-  e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
-  e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
-  hipStream_t st = (hipStream_t)stream;
-  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, objects, rg);
-  // ---- hipGraph replay.  A forward is a pure function of the argument block (pointers, shapes, flags), the bound buffers
-  // and the reference-cache state it starts from; the host-side state it leaves behind is the same every time.  The first
-  // call with a given key runs as usual (kernels' first-use set-up must not happen inside a capture), the second is
-  // captured and instantiated, later ones are one hipGraphLaunch.
-  std::string key((const char*)args, sizeof(*args));
-  const int st8[8] = {e->rc_valid, e->rc_batch, e->rc_h, e->rc_w, e->rc_keep, e->share_encoder, e->rc_views, args->flags & MVD_SHARE_REF};   // (views and the flag are in *args too)
-  key.append((const char*)st8, sizeof(st8));
-  const int ob2[2] = {objects, e->rc_objects};
-  key.append((const char*)ob2, sizeof(ob2));
-  // (the ragged layout of this call -- counts, g, the slot its tables live in -- and the one the cached reference was encoded under)
-  if (rg) { key.append((const char*)rg->counts, rg->objects * sizeof(int)); key.append((const char*)&rg->g, sizeof(int)); key.append((const char*)&rg->kvi_ref, sizeof(void*)); }
-  key.push_back('|');
-  key.append((const char*)e->rc_layout.data(), e->rc_layout.size() * sizeof(int));
-  key.push_back('|');
-  key.append((const char*)&e->ws_ptr, sizeof(void*));
-  key.append((const char*)&e->rc_ptr, sizeof(void*));
-  for (auto& ge : e->graphs)
-    if (ge.key == key) {
-      hipError_t he = hipGraphLaunch(ge.x, st);
-      if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
-      e->set_host_state(ge.after);        // (same key => the captured run started from this state and ended in that one)
-      return 0;
-    }
-  bool seen = false;
-  for (auto& k : e->graph_seen) seen |= k == key;
-  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false, objects, rg); }
-  if (e->graphs.size() >= 8) e->drop_graphs();
-  hipError_t he = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-  if (he != hipSuccess) { mvd_set_error("forward: hipStreamBeginCapture: %s", hipGetErrorString(he)); return -7; }
-  r = forward_impl(e, *args, st, false, objects, rg);
-  hipGraph_t g = nullptr;
-  he = hipStreamEndCapture(st, &g);
-  if (r) { if (g) (void)hipGraphDestroy(g); return r; }
-  if (he != hipSuccess || !g) { mvd_set_error("forward: hipStreamEndCapture: %s", hipGetErrorString(he)); return -7; }
-  hipGraphExec_t x = nullptr;
-  he = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-  if (he != hipSuccess) { (void)hipGraphDestroy(g); mvd_set_error("forward: hipGraphInstantiate: %s", hipGetErrorString(he)); return -7; }
-  e->graphs.push_back({key, g, x, e->host_state()});
-  he = hipGraphLaunch(x, st);
-  if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
-  return 0;
-}
-
-int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) { return unet_forward(e, args, 0, stream); }
-int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
-  return unet_forward(e, args, objects > 1 ? objects : 0, stream);
-}
-
-// ---- ragged view counts (include/mvd_hip.h).  The tables are built from the counts, so they are valid by construction; they pass
-// the same host check as a caller's table all the same (mvd_attention_check_index) before a slot is uploaded.
-static int ragged_prepare(const mvd_forward_args_t* args, const int* view_counts, int objects, int* rows, int* g) {
-  if (!args || !view_counts || objects < 1) { mvd_set_error("forward_ragged: null argument or %d objects", objects); return -1; }
-  if (args->views != 0) { mvd_set_error("forward_ragged: args->views must be 0 (the view counts come beside the arguments), got %d", args->views); return -1; }
-  const int R = mvd_ragged_rows(view_counts, objects);
-  if (R < 0) { mvd_set_error("forward_ragged: every object needs at least one view (the counts must be >= 1 and their sum must fit an int)"); return -1; }
-  if (args->batch <= 0 || args->batch % R || args->batch / R > 2) {
-    mvd_set_error("forward_ragged: batch %d is not 1 or 2 (classifier-free guidance) rows for each of the %d views", args->batch, R); return -1;
-  }
-  *rows = R; *g = args->batch / R;
-  return 0;
-}
-static bool ragged_uniform(const int* view_counts, int objects) {
-  for (int o = 1; o < objects; ++o) if (view_counts[o] != view_counts[0]) return false;
-  return true;
-}
-
-int64_t mvd_engine_workspace_bytes_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects) {
-  if (!e) { mvd_set_error("workspace_bytes_ragged: null engine"); return -1; }
-  int R = 0, g = 0;
-  if (ragged_prepare(args, view_counts, objects, &R, &g)) return -1;
-  if (ragged_uniform(view_counts, objects)) {       // equal counts ARE the objects forward (one object: the views forward)
-    mvd_forward_args_t a = *args; a.views = view_counts[0];
-    return workspace_bytes_args(e, &a, objects > 1 ? objects : 0);
-  }
-  std::vector<int> tab((size_t)2 * g * R);
-  mvd_ragged_build_tables(view_counts, objects, g, tab.data(), tab.data() + (size_t)g * R);
-  const RaggedLayout rg{view_counts, objects, g, R, tab.data(), tab.data() + (size_t)g * R};       // (host pointers: a sizing run launches nothing)
-  return workspace_bytes_args(e, args, objects, &rg);
-}
-
-int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects, void* stream) {
-  if (!e) { mvd_set_error("forward_ragged: null engine"); return -1; }
-  int R = 0, g = 0;
-  if (ragged_prepare(args, view_counts, objects, &R, &g)) return -1;
-  if (ragged_uniform(view_counts, objects)) {
-    mvd_forward_args_t a = *args; a.views = view_counts[0];
-    return unet_forward(e, &a, objects > 1 ? objects : 0, stream);
-  }
-  // everything the forward itself checks, the workspace included, before a slot is touched (a dry pass with host tables)
-  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
-  {
-    std::vector<int> tab((size_t)2 * g * R);
-    mvd_ragged_build_tables(view_counts, objects, g, tab.data(), tab.data() + (size_t)g * R);
-    const RaggedLayout dry_rg{view_counts, objects, g, R, tab.data(), tab.data() + (size_t)g * R};
-    const mvd_engine::HostState before = e->host_state();
-    int r = forward_impl(e, *args, nullptr, true, objects, &dry_rg);
-    e->set_host_state(before);
-    size_t act_bytes = 0;
-    if (r || (r = workspace_fits(e, &act_bytes))) return r;
-  }
-  // ---- the layout's slot
-  std::vector<int> layout(view_counts, view_counts + objects); layout.push_back(g);
+// A ragged layout gets the device tables of its slot (mvd_engine::kv_slots), uploaded from its host tables on first use
+static int kv_slot_tables(mvd_engine_t* e, ViewLayout* host, hipStream_t st) {
+  const ViewLayout& lay = *host;
+  const int O = lay.objects, n = lay.g * lay.rows;
+  std::vector<int> layout(lay.counts, lay.counts + O); layout.push_back(lay.g);
   mvd_engine::KvSlot* slot = nullptr;
   for (auto& sl : e->kv_slots) if (sl.layout == layout) slot = &sl;
   if (!slot) {
-    hipStream_t st = (hipStream_t)stream;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
       mvd_set_error("forward_ragged: the first forward of a layout uploads its K/V tables and cannot run inside a stream capture"); return -7;
@@ -1538,9 +1370,9 @@ int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, con
     }
     mvd_engine::KvSlot sl;
     sl.layout = layout;
-    sl.host.resize((size_t)2 * g * R);
-    mvd_ragged_build_tables(view_counts, objects, g, sl.host.data(), sl.host.data() + (size_t)g * R);
-    if (mvd_attention_check_index(sl.host.data(), g * R, g * objects) || mvd_attention_check_index(sl.host.data() + (size_t)g * R, g * R, g * objects)) return -1;
+    sl.host.assign(lay.kvi_ref, lay.kvi_ref + (size_t)2 * n);          // [adapter | text], as ragged_layout built them
+    // (valid by construction; they pass the same host check as a caller's table all the same before they are uploaded)
+    if (mvd_attention_check_index(sl.host.data(), n, lay.g * O) || mvd_attention_check_index(sl.host.data() + n, n, lay.g * O)) return -1;
     if (hipMalloc((void**)&sl.dev, sl.host.size() * sizeof(int)) != hipSuccess) { mvd_set_error("forward_ragged: hipMalloc of the K/V tables failed"); return -3; }
     e->kv_slots.push_back(std::move(sl));
     slot = &e->kv_slots.back();
@@ -1550,8 +1382,110 @@ int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, con
     }
   }
   slot->used = ++e->kv_tick;
-  const RaggedLayout rg{view_counts, objects, g, R, slot->dev, slot->dev + (size_t)g * R};
-  return unet_forward(e, args, objects, stream, &rg);
+  *host = lay.with_tables(slot->dev);
+  return 0;
+}
+
+// The three forward entries.  `host`: the layout as its entry built it -- a ragged one with HOST tables, which size the call; the
+// launches read the device tables of its slot, which is touched only once the call has passed every check and fits its workspace.
+static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const ViewLayout& host, void* stream) {
+  if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
+  if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
+  // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
+  const mvd_engine::HostState before = e->host_state();
+  int r = forward_impl(e, *args, nullptr, true, host);
+  e->set_host_state(before);
+  if (r) return r;
+  size_t act_bytes = 0;
+  if ((r = workspace_fits(e, &act_bytes))) return r;
+  hipStream_t st = (hipStream_t)stream;
+  ViewLayout lay = host;
+  if (host.counts && (r = kv_slot_tables(e, &lay, st))) return r;
+  e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
+  e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
+  if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, lay);
+  // ---- hipGraph replay.  A forward is a pure function of the argument block (pointers, shapes, flags), its layout, the bound
+  // buffers and the reference-cache state it starts from; the host-side state it leaves behind is the same every time.  The
+  // first call with a given key runs as usual (kernels' first-use set-up must not happen inside a capture), the second is
+  // captured and instantiated, later ones are one hipGraphLaunch.
+  std::string key((const char*)args, sizeof(*args));
+  const int st6[6] = {e->rc_valid, e->rc_batch, e->rc_h, e->rc_w, e->rc_keep, e->share_encoder};
+  key.append((const char*)st6, sizeof(st6));
+  // (the layout of this call -- objects, views, counts, g, the slot its tables live in -- and the one the cached reference was encoded under)
+  const std::vector<int> lk = lay.key();
+  key.append((const char*)lk.data(), lk.size() * sizeof(int));
+  key.append((const char*)&lay.g, sizeof(int));
+  key.append((const char*)&lay.kvi_ref, sizeof(void*));
+  key.push_back('|');
+  key.append((const char*)e->rc_layout.data(), e->rc_layout.size() * sizeof(int));
+  key.push_back('|');
+  key.append((const char*)&e->ws_ptr, sizeof(void*));
+  key.append((const char*)&e->rc_ptr, sizeof(void*));
+  for (auto& ge : e->graphs)
+    if (ge.key == key) {
+      hipError_t he = hipGraphLaunch(ge.x, st);
+      if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
+      e->set_host_state(ge.after);        // (same key => the captured run started from this state and ended in that one)
+      return 0;
+    }
+  bool seen = false;
+  for (auto& k : e->graph_seen) seen |= k == key;
+  if (!seen) { e->graph_seen.push_back(key); return forward_impl(e, *args, st, false, lay); }
+  if (e->graphs.size() >= 8) e->drop_graphs();
+  hipError_t he = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+  if (he != hipSuccess) { mvd_set_error("forward: hipStreamBeginCapture: %s", hipGetErrorString(he)); return -7; }
+  r = forward_impl(e, *args, st, false, lay);
+  hipGraph_t g = nullptr;
+  he = hipStreamEndCapture(st, &g);
+  if (r) { if (g) (void)hipGraphDestroy(g); return r; }
+  if (he != hipSuccess || !g) { mvd_set_error("forward: hipStreamEndCapture: %s", hipGetErrorString(he)); return -7; }
+  hipGraphExec_t x = nullptr;
+  he = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+  if (he != hipSuccess) { (void)hipGraphDestroy(g); mvd_set_error("forward: hipGraphInstantiate: %s", hipGetErrorString(he)); return -7; }
+  e->graphs.push_back({key, g, x, e->host_state()});
+  he = hipGraphLaunch(x, st);
+  if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
+  return 0;
+}
+
+int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) { return unet_forward(e, args, uniform_layout(args, 0), stream); }
+int mvd_unet_forward_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects, void* stream) {
+  return unet_forward(e, args, uniform_layout(args, objects), stream);
+}
+
+// ---- ragged view counts (include/mvd_hip.h): the counts' own rules, then the layout.  Equal counts ARE the objects forward (one object:
+// the views forward): *a is the call with `views` set.  Counts that differ: *a is the call as it came, `tab` the layout's two host tables.
+static int ragged_layout(const mvd_forward_args_t* args, const int* view_counts, int objects, mvd_forward_args_t* a, std::vector<int>* tab, ViewLayout* lay) {
+  if (!args || !view_counts || objects < 1) { mvd_set_error("forward_ragged: null argument or %d objects", objects); return -1; }
+  if (args->views != 0) { mvd_set_error("forward_ragged: args->views must be 0 (the view counts come beside the arguments), got %d", args->views); return -1; }
+  const int R = mvd_ragged_rows(view_counts, objects);
+  if (R < 0) { mvd_set_error("forward_ragged: every object needs at least one view (the counts must be >= 1 and their sum must fit an int)"); return -1; }
+  if (args->batch <= 0 || args->batch % R || args->batch / R > 2) {
+    mvd_set_error("forward_ragged: batch %d is not 1 or 2 (classifier-free guidance) rows for each of the %d views", args->batch, R); return -1;
+  }
+  const int g = args->batch / R;
+  *a = *args;
+  bool uniform = true;
+  for (int o = 1; o < objects; ++o) uniform &= view_counts[o] == view_counts[0];
+  if (uniform) { a->views = view_counts[0]; *lay = uniform_layout(a, objects); return 0; }
+  tab->resize((size_t)2 * g * R);
+  mvd_ragged_build_tables(view_counts, objects, g, tab->data(), tab->data() + (size_t)g * R);
+  *lay = ViewLayout::ragged(view_counts, objects, g, R, tab->data());
+  return 0;
+}
+
+int64_t mvd_engine_workspace_bytes_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects) {
+  if (!e) { mvd_set_error("workspace_bytes_ragged: null engine"); return -1; }
+  mvd_forward_args_t a; std::vector<int> tab; ViewLayout lay;
+  if (ragged_layout(args, view_counts, objects, &a, &tab, &lay)) return -1;
+  return workspace_bytes_args(e, &a, lay);
+}
+
+int mvd_unet_forward_ragged(mvd_engine_t* e, const mvd_forward_args_t* args, const int* view_counts, int objects, void* stream) {
+  if (!e) { mvd_set_error("forward_ragged: null engine"); return -1; }
+  mvd_forward_args_t a; std::vector<int> tab; ViewLayout lay;
+  if (ragged_layout(args, view_counts, objects, &a, &tab, &lay)) return -1;
+  return unet_forward(e, &a, lay, stream);
 }
 
 int mvd_engine_set_graph(mvd_engine_t* e, int enable) {

@@ -4,7 +4,6 @@ libmvd_hip.so.  There is no CPU path: constructing an engine without a GPU raise
 from __future__ import annotations
 
 import ctypes as C
-import numbers
 import os
 from typing import Dict, List, Optional
 
@@ -12,6 +11,7 @@ import torch
 
 from . import _lib as L
 from .config import UNetConfig
+from .layout import ViewLayout
 from .packing import pack_camera, pack_unet
 
 
@@ -118,32 +118,23 @@ class MVDEngine:
         return sum(t.numel() * t.element_size() for d in self._weights for t in d.values())
 
     # ------------------------------------------------------------------ workspace
-    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, views=0, objects=0, counts=()):
-        key = (batch, h, w, text_len, ref_batch, keep_features, views) + ((objects,) if objects else ()) + ((counts,) if counts else ())
+    def _ensure_workspace(self, batch, h, w, text_len, ref_batch, keep_features, lay=ViewLayout()):
+        key = (batch, h, w, text_len, ref_batch, keep_features) + (() if lay.views else (0,)) + lay.key()
         if self._ws_key == key and not self._ws_resize:
             return
         # (FreeU was set since the workspace was sized: the same shape may need more.  Buffers that are large enough stay bound as
         #  they are -- re-binding would drop the cached reference, which does not depend on the setting)
         keep_bound = self._ws_key == key
-        self._ws_args = (batch, h, w, text_len, ref_batch, keep_features, views, objects, counts)
-        if counts:
-            # ragged view counts (mvd_unet_forward_ragged): the counts come beside the argument block, whose `views` stays 0
-            a = L.mvd_forward_args_t()
-            a.batch, a.height, a.width, a.text_len, a.ref_batch = batch, h, w, text_len, ref_batch
-            a.cam_rows, a.cam_batch = 4, sum(counts)
-            a.flags = L.MVD_USE_CAMERA | L.MVD_USE_IMAGE | L.MVD_SHARE_REF
-            ws = L.lib().mvd_engine_workspace_bytes_ragged(self._h, C.byref(a), (C.c_int * len(counts))(*counts), len(counts))
-        elif views:
+        self._ws_args = (batch, h, w, text_len, ref_batch, keep_features, lay)
+        if lay.rows:
             # a shared-reference forward (MVD_SHARE_REF) is sized from its argument block: the positional entry describes
             # an ordinary forward, whose Q4 re-chunking fails when the views do not divide the reference tokens
             a = L.mvd_forward_args_t()
-            a.batch, a.height, a.width, a.text_len, a.ref_batch, a.views = batch, h, w, text_len, ref_batch, views
-            a.cam_rows, a.cam_batch = 4, views * max(objects, 1)
+            a.batch, a.height, a.width, a.text_len, a.ref_batch, a.views = batch, h, w, text_len, ref_batch, lay.views
+            a.cam_rows, a.cam_batch = 4, lay.rows
             a.flags = L.MVD_USE_CAMERA | L.MVD_USE_IMAGE | L.MVD_SHARE_REF
-            if objects:
-                ws = L.lib().mvd_engine_workspace_bytes_objects(self._h, C.byref(a), objects)
-            else:
-                ws = L.lib().mvd_engine_workspace_bytes_args(self._h, C.byref(a))
+            suffix, beside = self._entry(lay)
+            ws = getattr(L.lib(), "mvd_engine_workspace_bytes" + (suffix or "_args"))(self._h, C.byref(a), *beside)
         else:
             ws = L.lib().mvd_engine_workspace_bytes(self._h, batch, h, w, text_len, ref_batch)
         if ws < 0:
@@ -188,25 +179,13 @@ class MVDEngine:
             if t is not None:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise L.MvdError("engine.forward expects contiguous fp32 CUDA tensors")
-        counts = ()
-        if views is not None and not isinstance(views, numbers.Integral):
-            counts = tuple(int(v) for v in views)
-            if not counts or min(counts) < 1:
-                raise L.MvdError(f"engine.forward: views = {counts}: every object needs at least one view")
-            if objects is not None and int(objects) != len(counts):
-                raise L.MvdError(f"engine.forward: objects = {objects} with {len(counts)} view counts {counts}")
-            R = sum(counts)
-            if B % R or B // R > 2:
-                raise L.MvdError(f"engine.forward: batch {B} is not 1 or 2 rows for each of the {R} views of {counts}")
-            views, objects = 0, None
-        views = int(views) if views else 0
-        objects = int(objects) if objects and int(objects) > 1 else 0
-        if objects and not views:
-            raise L.MvdError(f"engine.forward: objects = {objects} needs views")
+        lay = ViewLayout.parse(views, objects, "engine")
+        views, objects, counts = lay
+        if counts and lay.g(B) not in (1, 2):
+            raise L.MvdError(f"engine.forward: batch {B} is not 1 or 2 rows for each of the {lay.rows} views of {counts}")
         if views and B % views:
             raise L.MvdError(f"engine.forward: batch {B} is not a multiple of views {views}")
-        text_rows = B // sum(counts) * len(counts) if counts else (B // views if views else B)
-        if text.shape[0] != text_rows or timesteps.shape != (B,):
+        if text.shape[0] != lay.text_rows(B) or timesteps.shape != (B,):
             raise L.MvdError(f"engine.forward: text batch {text.shape[0]} / timesteps {tuple(timesteps.shape)} vs batch {B}"
                              + (f" in {views} views" if views else "") + (f" in views {counts}" if counts else ""))
         use_cam = target_camera is not None
@@ -215,14 +194,14 @@ class MVDEngine:
         if use_img:
             ref_batch = source_latents.shape[0] if source_latents is not None else self._last_ref_batch
             self._last_ref_batch = ref_batch
-        if (views or counts) and not use_img:
+        if lay.rows and not use_img:
             raise L.MvdError("engine.forward: views needs image conditioning (source_latents or reuse_ref)")
         if counts and ref_batch != len(counts):
             raise L.MvdError(f"engine.forward: views {counts} need {len(counts)} reference rows (one per object), got {ref_batch}")
         if objects and (ref_batch != objects or B % (objects * views)):
             raise L.MvdError(f"engine.forward: {objects} objects x {views} views need a multiple of {objects * views} sample rows and "
                              f"{objects} reference rows, got {B} and {ref_batch}")
-        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, views, objects, counts)
+        self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, lay)
         graph = getattr(self, "_graph", False)
         user_out = out
         if graph:
@@ -263,17 +242,13 @@ class MVDEngine:
                 a.source_latents, a.encoder_text = source_latents.data_ptr(), encoder_text.data_ptr()
             if keep_features:
                 flags |= L.MVD_KEEP_FEATURES
-        if views:
+        if lay.rows:
             flags |= L.MVD_SHARE_REF
-            a.views = views
-        if counts:
-            flags |= L.MVD_SHARE_REF        # (a.views stays 0: the counts travel beside the argument block)
+            a.views = views                 # (0 with counts: they travel beside the argument block, like the object count)
         a.ref_batch, a.flags = ref_batch, flags
         a.out = out.data_ptr()
-        # (objects: the count travels beside the argument block, which is as it was)
-        entry = ("mvd_unet_forward_objects", self._h, C.byref(a), objects) if objects else ("mvd_unet_forward", self._h, C.byref(a))
-        if counts:
-            entry = ("mvd_unet_forward_ragged", self._h, C.byref(a), (C.c_int * len(counts))(*counts), len(counts))
+        suffix, beside = self._entry(lay)
+        entry = ("mvd_unet_forward" + suffix, self._h, C.byref(a), *beside)
         if graph:
             cur = torch.cuda.current_stream(self.device)
             self._gstream.wait_stream(cur)
@@ -284,7 +259,7 @@ class MVDEngine:
         else:
             L.call(*entry, L.stream())
         if use_img and not reuse_ref:
-            self._ref_valid = self._ref_key(B, H, W, Lt, ref_batch, counts or views, objects)
+            self._ref_valid = (B, H, W, Lt, ref_batch) + lay.key()
         return out
 
     # ------------------------------------------------------------------ reference pass in two halves (global Q2 statistics)
@@ -367,11 +342,15 @@ class MVDEngine:
         return buf
 
     @staticmethod
+    def _entry(lay):
+        # (suffix of the C entries for this layout, forward and sizing -- whose plain form is ``_args`` --, what goes beside the block)
+        if lay.counts:
+            return "_ragged", ((C.c_int * len(lay.counts))(*lay.counts), len(lay.counts))
+        return ("_objects", (lay.objects,)) if lay.objects else ("", ())
+
+    @staticmethod
     def _ref_key(batch, h, w, text_len, ref_batch, views=0, objects=0):
-        if views is not None and not isinstance(views, numbers.Integral):      # ragged view counts: the layout is part of the key
-            return (batch, h, w, text_len, ref_batch, tuple(int(v) for v in views))
-        objects = int(objects) if objects and int(objects) > 1 else 0
-        return (batch, h, w, text_len, ref_batch) + ((views,) if views else ()) + ((objects,) if objects else ())
+        return (batch, h, w, text_len, ref_batch) + ViewLayout.parse(views, objects, "key").key()
 
     def reference_cache_valid(self, batch, h, w, text_len, ref_batch, views=0, objects=0) -> bool:
         """True when the engine still holds reference K/V computed for exactly this shape (Q5 reuse is then legal); ``views``:

@@ -9,7 +9,6 @@ as hand-written gfx950 kernels.  None of the reference's ~600 per-forward host s
 """
 from __future__ import annotations
 
-import numbers
 import logging
 import os
 from typing import Any, Dict, NamedTuple, Optional
@@ -21,6 +20,7 @@ from . import _lib as L
 from .attention import get_attention_processor_for_module
 from .camera_encoder import CameraEncoder
 from .config import UNetConfig
+from .layout import ViewLayout
 from .unet_params import UNet2DConditionParams
 
 logger = logging.getLogger(__name__)
@@ -78,6 +78,21 @@ def _load_named_unet(module: nn.Module, name, snapshot, what: str):
         return
     if not _load_local_unet_weights(module, snapshot):
         raise L.MvdError(f"{what}: {name!r} resolved to {snapshot!r}, which has no unet/diffusion_pytorch_model.safetensors")
+
+
+_PER_OBJECT = "does not go with reference_stats_group (its Q2 statistics are per object; statistics over the ranks' batches couple the objects)"
+# the words of MultiViewUNet.forward's three shared forms: (reference_stats_group is set, the source rows, the sample and text rows)
+_LAYOUT_WORDS = {
+    "views": ("views: the shared-reference forward does not go with reference_stats_group (statistics over the ranks' batches are for many objects; the views of one object share its one reference)",
+              "views: needs image conditioning with ONE row of source_image_latents (one object)",
+              "views={V}: sample must hold g * views rows and encoder_hidden_states g rows"),
+    "objects": ("objects: the object forward " + _PER_OBJECT,
+                "objects={n}: needs image conditioning with {n} rows of source_image_latents (one per object)",
+                "objects={n}, views={V}: sample must hold g * objects * views rows and encoder_hidden_states g * objects rows"),
+    "ragged": ("views: the ragged forward " + _PER_OBJECT,
+               "views={c}: needs image conditioning with {n} rows of source_image_latents (one per object)",
+               "views={c}: sample must hold g * {R} rows and encoder_hidden_states g * {n} rows"),
+}
 
 
 class ImageEncoder(nn.Module):
@@ -332,14 +347,8 @@ class MultiViewUNet(nn.Module):
         forward, which IS the R independent batch-g calls.  ``sample`` holds g * R rows ``[uncond x R | cond x R]``, object-major
         inside a half, the cameras 1 or R rows; ``encoder_hidden_states`` g * O rows and ``source_image_latents`` O rows as with
         ``objects = O``, which ``objects`` must be, or ``None``."""
-        counts = ()
-        if views is not None and not isinstance(views, numbers.Integral):
-            counts = tuple(int(v) for v in views)
-            if not counts or min(counts) < 1:
-                raise L.MvdError(f"views={counts}: every object needs at least one view")
-            if objects is not None and int(objects) != len(counts):
-                raise L.MvdError(f"views={counts}: objects must be None or {len(counts)}, got {objects}")
-            views, objects = None, None
+        lay = ViewLayout.parse(views, objects)
+        V, O, counts = lay
         if cross_attention_kwargs:
             cross_attention_kwargs.pop("debug_log_file_path", None)   # accepted, never evaluated (no host syncs)
         eng = self._sync_engine()
@@ -348,37 +357,14 @@ class MultiViewUNet(nn.Module):
         x = self._f32(sample, dev)
         B = x.shape[0]
         text = self._f32(encoder_hidden_states, dev)
-        V = int(views) if views is not None and int(views) > 1 else 0
-        O = int(objects) if objects is not None and int(objects) > 1 else 0
-        if counts:
-            R, Oc = sum(counts), len(counts)
+        if lay.rows:
+            stats, image, rows = _LAYOUT_WORDS["ragged" if counts else "objects" if O else "views"]
             if self.reference_stats_group is not None:
-                raise L.MvdError("views: the ragged forward does not go with reference_stats_group (its Q2 statistics are per "
-                                 "object; statistics over the ranks' batches couple the objects)")
-            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != Oc:
-                raise L.MvdError(f"views={counts}: needs image conditioning with {Oc} rows of source_image_latents (one per object)")
-            if B % R or B // R > 2 or text.shape[0] != B // R * Oc:
-                raise L.MvdError(f"views={counts}: sample must hold g * {R} rows and encoder_hidden_states g * {Oc} rows (g = 1, or 2 "
-                                 f"under guidance); got {B} and {text.shape[0]}")
-        elif O:
-            V = max(V, 1)
-            if self.reference_stats_group is not None:
-                raise L.MvdError("objects: the object forward does not go with reference_stats_group (its Q2 statistics are per "
-                                 "object; statistics over the ranks' batches couple the objects)")
-            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != O:
-                raise L.MvdError(f"objects={O}: needs image conditioning with {O} rows of source_image_latents (one per object)")
-            if B % (O * V) or B // (O * V) > 2 or text.shape[0] != B // V:
-                raise L.MvdError(f"objects={O}, views={V}: sample must hold g * objects * views rows and encoder_hidden_states "
-                                 f"g * objects rows (g = 1, or 2 under guidance); got {B} and {text.shape[0]}")
-        elif V:
-            if self.reference_stats_group is not None:
-                raise L.MvdError("views: the shared-reference forward does not go with reference_stats_group (statistics over "
-                                 "the ranks' batches are for many objects; the views of one object share its one reference)")
-            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != 1:
-                raise L.MvdError("views: needs image conditioning with ONE row of source_image_latents (one object)")
-            if B % V or B // V > 2 or text.shape[0] != B // V:
-                raise L.MvdError(f"views={V}: sample must hold g * views rows and encoder_hidden_states g rows (g = 1, or 2 under "
-                                 f"guidance); got {B} and {text.shape[0]}")
+                raise L.MvdError(stats)
+            if not self.use_image_conditioning or source_image_latents is None or source_image_latents.shape[0] != lay.sources:
+                raise L.MvdError(image.format(c=counts, n=lay.sources))
+            if lay.g(B) not in (1, 2) or text.shape[0] != lay.text_rows(B):
+                raise L.MvdError(rows.format(c=counts, n=lay.sources, V=V, R=lay.rows) + f" (g = 1, or 2 under guidance); got {B} and {text.shape[0]}")
         elif B > text.shape[0]:                                        # CFG repeat (:233-237)
             text = text.repeat(B // text.shape[0], 1, 1)
         t = torch.as_tensor(timestep, device=dev).to(torch.float32).reshape(-1)
@@ -396,8 +382,8 @@ class MultiViewUNet(nn.Module):
         if self.use_image_conditioning and source_image_latents is not None:
             bs = source_image_latents.shape[0]
             enc_text = text
-            if V or counts:                                            # the batch-g call's choice below: its last row
-                enc_text = text[-max(O, len(counts), 1):]              # (per object: row (g - 1) * O + o)
+            if lay.rows:                                               # the batch-g call's choice below: its last row
+                enc_text = text[-lay.sources:]                         # (per object: row (g - 1) * O + o)
             elif text.shape[0] == 2 * bs:                              # :280-283
                 enc_text = text[bs:]
             elif text.shape[0] > bs:                                   # :284-285
@@ -406,10 +392,10 @@ class MultiViewUNet(nn.Module):
             # is live, so the caching allocator cannot hand their addresses to different data of the same shape (a second
             # object denoised right after the first would otherwise hit the first object's K/V).
             key = (source_image_latents.data_ptr(), source_image_latents._version, tuple(source_image_latents.shape),
-                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B, V, O) + ((counts,) if counts else ())
+                   encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B) + tuple(lay)
             glob = self.reference_stats_group is not None
             hit = (self.cache_reference and self._ref_key == key
-                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, counts or V, O))
+                   and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, **lay.kwargs()))
             if glob and self.cache_reference:
                 # the recompute path below contains a collective: the decision must be the same on every rank of the group
                 # (a re-bound workspace or a fresh tensor on ONE rank would otherwise leave the others out of the all-gather)
@@ -428,7 +414,7 @@ class MultiViewUNet(nn.Module):
                     local = eng.reference_encode(img["source_latents"], img["encoder_text"], B)
                     eng.reference_finish(merge_reference_stats(local, group))
                     img = dict(reuse_ref=True, keep_features=True)
-        out = eng.forward(x, t, text, **cam, **img, **({"views": counts or V} if V or counts else {}), **({"objects": O} if O else {}))
+        out = eng.forward(x, t, text, **cam, **img, **lay.kwargs())
         if cam:
             self.current_camera_embedding = eng.camera_embedding(cam["target_camera"].shape[0])
         hidden_states = out.to(out_dtype)

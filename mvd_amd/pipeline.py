@@ -32,6 +32,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .layout import ViewLayout
 
 
 class MVDDenoiser:
@@ -77,33 +78,16 @@ class MVDDenoiser:
         cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None       # pipeline.py:77-80
         embeds = torch.cat([negative_prompt_embeds.to(prompt_embeds.device), prompt_embeds]) if cfg else prompt_embeds
         embeds = embeds.to(dev, torch.float32)
-        counts = ()
-        if views is not None and not isinstance(views, int):
-            counts = tuple(int(v) for v in views)
-            if objects is not None and int(objects) != len(counts):
-                raise L.MvdError(f"views={counts}: objects must be None or {len(counts)}, got {objects}")
-            views, objects = None, None
-        views = int(views) if views is not None and int(views) > 1 else 0
-        objects = int(objects) if objects is not None and int(objects) > 1 else 0
-        # (prompt rows the layout expects, latent rows it makes of them): one prompt per object, one latent row per view
-        if counts:
-            expect, rows = len(counts), sum(counts)
-            err = f"views={counts}: one prompt per object, got {B} rows of prompt_embeds for {len(counts)} objects"
-        elif objects:
-            views = max(views, 1)
-            expect, rows = objects, objects * views
-            err = f"objects: one prompt per object, got {B} rows of prompt_embeds for {objects} objects"
-        elif views:
-            expect, rows = 1, views
-            err = f"views: one prompt for the one object, got {B} rows of prompt_embeds"
-        else:
-            expect, rows = B, B
-        if B != expect:
-            raise L.MvdError(err)
-        if (counts or objects or views) and guidance_scale > 1.0 and not cfg:
-            # the doubled latents against one text row per object, [positive x O | positive x O]: the repeat of mvd_unet.py:233-237
-            embeds = embeds.repeat(2, 1, 1)
-        B = rows
+        lay = ViewLayout.parse(views, objects)
+        if lay.rows:
+            # one prompt per object, one latent row per view
+            if B != lay.sources:
+                raise L.MvdError(f"views: one prompt for the one object, got {B} rows of prompt_embeds" if not (lay.counts or lay.objects) else
+                                 f"{f'views={lay.counts}' if lay.counts else 'objects'}: one prompt per object, got {B} rows of prompt_embeds for {lay.sources} objects")
+            if guidance_scale > 1.0 and not cfg:
+                # the doubled latents against one text row per object, [positive x O | positive x O]: the repeat of mvd_unet.py:233-237
+                embeds = embeds.repeat(2, 1, 1)
+            B = lay.rows
         if latents is None:
             latents = torch.randn(B, 4, height, width, generator=generator, device=dev, dtype=torch.float32)
             latents = latents * self.scheduler.init_noise_sigma
@@ -116,12 +100,7 @@ class MVDDenoiser:
             extra["target_camera"] = target_camera.to(dev)
         if source_image_latents is not None:
             extra["source_image_latents"] = source_image_latents.to(dev)
-        if views:
-            extra["views"] = views
-        if objects:
-            extra["objects"] = objects
-        if counts:
-            extra["views"] = counts
+        extra.update(lay.kwargs())
         # Q5: the reference K/V of a previous call (another object) must never be reused by this one
         if hasattr(self.unet, "reset_reference_cache"):
             self.unet.reset_reference_cache()
