@@ -388,6 +388,16 @@ int mvd_debug_ragged_tables(const int* view_counts, int objects, int g, int* ada
 int mvd_debug_attention_mapped_grouped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk,
                                        int ldq, int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects,
                                        const int* kv_index_host, int kv_elements, void* stream);
+/* Test hook: ONE attention launch of two problems, exactly as an image-conditioned transformer block issues them (self + reference
+ * attention, text + reference cross-attention).  ptrs[8] = {q0, k0, v0, o0, q1, k1, v1, o1} (device); dims[18] = per problem
+ * {nq, nk, ldq, ldk, ldv, ldo, kv_group, kv_objects, kv_elements}, batch strides n * ld; table0 / table1: null, or `batch` host
+ * entries in [0, kv_elements) of that problem -- checked on the host before anything is uploaded or launched, like a table beside
+ * a group.  scale = 0: prescaled queries.  nsplit: 1 = no split-KV, 2..8 = that many key ranges, 0 = the engine's own choice for
+ * these arguments.  ws: _ws_bytes(...) bytes of device memory (0: none needed); the call zeroes the arrival counters in it. */
+int64_t mvd_debug_attention_pair_ws_bytes(const int* dims, const int* table0, const int* table1, int batch, int heads, float scale,
+                                          int nsplit);
+int mvd_debug_attention_pair(const void* const* ptrs, const int* dims, const int* table0, const int* table1, int batch, int heads,
+                             float scale, int nsplit, void* ws, void* stream);
 /* Measurement / bisection switches (bench.py --debug-flags, tools/, A/B tests): OR them into mvd_debug_set_flags.  Every switch
  * is read per launch or per forward unless it says otherwise, so 0 restores the product's behaviour.  The values are quoted
  * by DESIGN.md and profiles/ and never change; mvd_amd/_lib.py DebugFlag mirrors them (tests/test_cabi_cpu.py compares). */

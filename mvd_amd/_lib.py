@@ -147,6 +147,10 @@ _SIGS = {
     "mvd_debug_attention_mapped_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int),
                                                      C.c_int, C.c_void_p]),
+    "mvd_debug_attention_pair_ws_bytes": (C.c_int64, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                      C.c_float, C.c_int]),
+    "mvd_debug_attention_pair": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                           C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_attention_split_ws_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_op_attention_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

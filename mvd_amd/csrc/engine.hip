@@ -1776,9 +1776,20 @@ int64_t mvd_op_attention_split_ws_bytes(int batch, int heads, int nq, int nsplit
   a.nprob = 1; a.batch = batch; a.heads = heads; a.p[0].nq = nq;
   return (int64_t)mvd_attention_split_ws_bytes(a, nsplit) + (int64_t)mvd_attention_split_counters(a) * 4 + 256;
 }
-// One library-owned device buffer for the operator entry's table (grow-only; growing frees the old one, which synchronises).  The
+// One library-owned device buffer for the operator entries' tables (grow-only; growing frees the old one, which synchronises): two
+// regions of g_op_kvi_cap entries, one per problem of a launch (region 1 starts at g_op_kvi + g_op_kvi_cap).  The
 // upload is stream-ordered in front of the launch; calls on one stream are ordered among themselves
 static int* g_op_kvi = nullptr; static size_t g_op_kvi_cap = 0; static std::mutex g_op_kvi_mu;
+// (under g_op_kvi_mu) both regions hold at least n entries; 0, or -3 with mvd_set_error
+static int op_kvi_reserve(size_t n) {
+  if (n <= g_op_kvi_cap) return 0;
+  if (g_op_kvi) (void)hipFree(g_op_kvi);
+  g_op_kvi = nullptr; g_op_kvi_cap = 0;
+  const size_t cap = n < 256 ? 256 : n;
+  if (hipMalloc((void**)&g_op_kvi, 2 * cap * sizeof(int)) != hipSuccess) { mvd_set_error("attention: hipMalloc of the K/V table failed"); return -3; }
+  g_op_kvi_cap = cap;
+  return 0;
+}
 static int attention_mapped(const void* q, const void* k, const void* v, void* o, int batch, int heads, int nq, int nk, int ldq, int ldk,
                             int ldv, int ldo, float scale, int kv_group, int kv_objects, const int* kv_index_host, int kv_elements,
                             void* stream) {
@@ -1792,13 +1803,7 @@ static int attention_mapped(const void* q, const void* k, const void* v, void* o
   a.p[0] = {(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ldq, ldk, ldv, ldo,
             (int64_t)nq * ldq, (int64_t)nk * ldk, (int64_t)nk * ldv, (int64_t)nq * ldo, nq, nk};
   std::lock_guard<std::mutex> lk(g_op_kvi_mu);
-  if ((size_t)batch > g_op_kvi_cap) {
-    if (g_op_kvi) (void)hipFree(g_op_kvi);
-    g_op_kvi = nullptr; g_op_kvi_cap = 0;
-    const size_t cap = (size_t)batch < 256 ? 256 : (size_t)batch;
-    if (hipMalloc((void**)&g_op_kvi, cap * sizeof(int)) != hipSuccess) { mvd_set_error("attention: hipMalloc of the K/V table failed"); return -3; }
-    g_op_kvi_cap = cap;
-  }
+  if (op_kvi_reserve((size_t)batch)) return -3;
   // (pageable source: the call returns once the table has been read)
   if (hipMemcpyAsync(g_op_kvi, kv_index_host, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("attention: upload of the K/V table failed"); return -3; }
   a.kv_index[0] = g_op_kvi; a.kv_group[0] = kv_group; a.kv_objects[0] = kv_objects;
@@ -1813,6 +1818,80 @@ extern "C" int mvd_debug_attention_mapped_grouped(const void* q, const void* k, 
                                                   int ldq, int ldk, int ldv, int ldo, float scale, int kv_group, int kv_objects,
                                                   const int* kv_index_host, int kv_elements, void* stream) {
   return attention_mapped(q, k, v, o, batch, heads, nq, nk, ldq, ldk, ldv, ldo, scale, kv_group, kv_objects, kv_index_host, kv_elements, stream);
+}
+
+// test hook: ONE launch of two problems, as transformer() issues them for an image-conditioned block (MvdAttnArgs::nprob = 2) --
+// the arguments go into one MvdAttnArgs and to mvd_launch_attention, no other path.  ptrs = {q0, k0, v0, o0, q1, k1, v1, o1};
+// dims = per problem MVD_PAIR_DIMS ints {nq, nk, ldq, ldk, ldv, ldo, kv_group, kv_objects, kv_elements}; table0 / table1: null, or
+// `batch` host entries naming one of that problem's kv_elements K/V elements.  Batch strides are n * ld.  scale == 0: the
+// prescaled engine form.  nsplit: 1 off, 2..8 forced, 0 = mvd_attention_pick_split on these arguments.
+enum { MVD_PAIR_DIMS = 9 };
+static int pair_args(MvdAttnArgs& a, const void* const* ptrs, const int* dims, int batch, int heads, float scale) {
+  if (!dims || batch <= 0 || heads <= 0) { mvd_set_error("attention: bad problem count/batch/heads"); return -1; }
+  memset(&a, 0, sizeof(a));
+  a.nprob = 2; a.batch = batch; a.heads = heads; a.scale = scale;
+  a.prescaled = scale == 0.f;
+  for (int i = 0; i < 2; ++i) {
+    const int* d = dims + i * MVD_PAIR_DIMS;
+    const int nq = d[0], nk = d[1], ldq = d[2], ldk = d[3], ldv = d[4], ldo = d[5];
+    if (ptrs) a.p[i] = {(const bf16_t*)ptrs[4 * i], (const bf16_t*)ptrs[4 * i + 1], (const bf16_t*)ptrs[4 * i + 2], (bf16_t*)ptrs[4 * i + 3]};
+    a.p[i].ldq = ldq; a.p[i].ldk = ldk; a.p[i].ldv = ldv; a.p[i].ldo = ldo;
+    a.p[i].bsq = (int64_t)nq * ldq; a.p[i].bsk = (int64_t)nk * ldk; a.p[i].bsv = (int64_t)nk * ldv; a.p[i].bso = (int64_t)nq * ldo;
+    a.p[i].nq = nq; a.p[i].nk = nk;
+    a.kv_group[i] = d[6]; a.kv_objects[i] = d[7];
+  }
+  return 0;
+}
+// the split this launch gets (nsplit == 0: the engine's heuristic, which never splits a launch with a table)
+static int pair_split(MvdAttnArgs& a, const int* table0, const int* table1, int nsplit) {
+  if (nsplit) return nsplit;
+  a.kv_index[0] = table0; a.kv_index[1] = table1;       // (host pointers: the heuristic only tests them)
+  const int ns = mvd_attention_pick_split(a);
+  a.kv_index[0] = a.kv_index[1] = nullptr;
+  return ns;
+}
+// bytes of the workspace of such a launch: the partials, then the arrival counters (which the call zeroes); 0 without a split
+extern "C" int64_t mvd_debug_attention_pair_ws_bytes(const int* dims, const int* table0, const int* table1, int batch, int heads,
+                                                     float scale, int nsplit) {
+  MvdAttnArgs a;
+  if (pair_args(a, nullptr, dims, batch, heads, scale)) return -1;
+  const int ns = pair_split(a, table0, table1, nsplit);
+  if (ns <= 1) return 0;
+  return (int64_t)((mvd_attention_split_ws_bytes(a, ns) + 255) & ~size_t(255)) + (int64_t)mvd_attention_split_counters(a) * 4 + 256;
+}
+extern "C" int mvd_debug_attention_pair(const void* const* ptrs, const int* dims, const int* table0, const int* table1, int batch,
+                                        int heads, float scale, int nsplit, void* ws, void* stream) {
+  MvdAttnArgs a;
+  if (!ptrs) { mvd_set_error("attention_pair: null argument"); return -1; }
+  if (pair_args(a, ptrs, dims, batch, heads, scale)) return -1;
+  // before anything is uploaded or launched: the entries, and a table together with a group (mvd_launch_attention's own rule)
+  const int* tables[2] = {table0, table1};
+  for (int i = 0; i < 2; ++i) {
+    if (!tables[i]) continue;
+    if (mvd_attention_check_index(tables[i], batch, dims[i * MVD_PAIR_DIMS + 8])) return -1;
+    if (a.kv_group[i] > 1 || a.kv_objects[i] > 1) { mvd_set_error("attention: problem %d sets a K/V table together with K/V group %d / objects %d", i, a.kv_group[i], a.kv_objects[i]); return -1; }
+  }
+  const int ns = pair_split(a, table0, table1, nsplit);
+  if (ns > 1) {     // (a split the launcher refuses -- more than 8 ranges, a null workspace ... -- goes to the launcher as it is)
+    a.nsplit = ns; a.split_ws = ws;
+    if (ws && ns <= 8) {
+      const size_t pb = (mvd_attention_split_ws_bytes(a, ns) + 255) & ~size_t(255);
+      a.split_cnt = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(ws) + pb);
+    }
+  }
+  std::unique_lock<std::mutex> lk(g_op_kvi_mu, std::defer_lock);
+  if (table0 || table1) {
+    lk.lock();
+    if (op_kvi_reserve((size_t)batch)) return -3;
+    for (int i = 0; i < 2; ++i) {
+      if (!tables[i]) continue;
+      int* dst = g_op_kvi + (size_t)i * g_op_kvi_cap;
+      if (hipMemcpyAsync(dst, tables[i], (size_t)batch * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("attention: upload of the K/V table failed"); return -3; }
+      a.kv_index[i] = dst;
+    }
+  }
+  if (a.split_cnt && hipMemsetAsync(a.split_cnt, 0, (size_t)mvd_attention_split_counters(a) * 4, (hipStream_t)stream) != hipSuccess) { mvd_set_error("attention_pair: hipMemsetAsync failed"); return -3; }
+  return mvd_launch_attention(a, (hipStream_t)stream);
 }
 
 // measurement / test hook: the two tables the engine builds for a ragged layout (host arrays of g * sum(counts) entries);

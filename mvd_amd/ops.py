@@ -461,6 +461,60 @@ def attention_split(q, k, v, heads, nsplit):
     return out
 
 
+def _pair_args(p0, p1, heads):
+    """ctypes arguments of mvd_debug_attention_pair for two problem dicts (see ``attention_pair``): (ptrs, dims, table0, table1,
+    batch, outputs, keep-alive list)"""
+    B = p0["q"].shape[0]
+    ptrs, dims, tables, outs = [], [], [], []
+    for p in (p0, p1):
+        q, k, v = p["q"], p["k"], p["v"]
+        _bf16(q, k, v)
+        nq, nk = q.shape[1], k.shape[1]
+        out = p.get("out")
+        if out is None:
+            out = torch.empty(B, nq, heads * 64, device=q.device, dtype=torch.bfloat16)
+        _bf16(out)
+        assert q.shape[0] == B and out.shape == (B, nq, heads * 64) and k.shape[0] == v.shape[0] and v.shape[1] == nk, (q.shape, k.shape, v.shape, out.shape)
+        for t, n in ((q, nq), (k, nk), (v, nk), (out, nq)):      # (batch strides are n * ld in the hook; one element needs none)
+            assert t.is_cuda and t.stride(2) == 1 and (t.shape[0] == 1 or t.stride(0) == n * t.stride(1)), (t.shape, t.stride())
+        idx = p.get("kv_index")
+        if idx is not None:
+            idx = [int(i) for i in (idx.tolist() if isinstance(idx, torch.Tensor) else idx)]
+            assert len(idx) == B, (B, len(idx))
+        ptrs += [q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()]
+        dims += [nq, nk, q.stride(1), k.stride(1), v.stride(1), out.stride(1), int(p.get("kv_group", 0)), int(p.get("kv_objects", 0)), int(k.shape[0])]
+        tables.append(None if idx is None else (C.c_int * B)(*idx))
+        outs.append(out)
+    return (C.c_void_p * 8)(*ptrs), (C.c_int * 18)(*dims), tables[0], tables[1], B, outs
+
+
+def attention_pair_ws(p0, p1, heads, scale=0.125, nsplit=1):
+    """the workspace ``attention_pair`` would allocate for these arguments: uint8, or None where the launch is not split"""
+    _, dims, t0, t1, B, _ = _pair_args(p0, p1, heads)
+    n = int(L.lib().mvd_debug_attention_pair_ws_bytes(dims, t0, t1, B, heads, float(scale), int(nsplit)))
+    if n < 0:
+        raise L.MvdError(f"mvd_debug_attention_pair_ws_bytes: {L.last_error()}")
+    return torch.empty(n, device=p0["q"].device, dtype=torch.uint8) if n else None
+
+
+def attention_pair(p0, p1, heads, scale=0.125, nsplit=1, ws="own", check=True):
+    """Test hook: ONE launch of two attention problems, as the engine issues them for an image-conditioned transformer block.
+    ``p0`` / ``p1``: dicts with ``q`` (B, Nq_i, heads*64), ``k`` / ``v`` (E_i, Nk_i, heads*64) -- row strides may exceed heads*64 -- and
+    optionally ``out`` (B, Nq_i, heads*64; may be a column range of wider rows), ``kv_group``, ``kv_objects`` (as ``attention_objects``)
+    or ``kv_index`` (as ``attention_mapped``).  ``nsplit``: 1 = no split-KV, 2..8 forced, 0 = the engine's own choice.  ``ws``: the
+    workspace (``attention_pair_ws``), None for a null pointer; by default one is allocated.  Returns the two outputs;
+    ``check=False``: (rc, out0, out1) without raising."""
+    ptrs, dims, t0, t1, B, outs = _pair_args(p0, p1, heads)
+    if isinstance(ws, str):
+        ws = attention_pair_ws(p0, p1, heads, scale, nsplit)
+    rc = L.lib().mvd_debug_attention_pair(ptrs, dims, t0, t1, B, heads, float(scale), int(nsplit), _p(ws), _s())
+    if not check:
+        return rc, outs[0], outs[1]
+    if rc != 0:
+        raise L.MvdError(f"mvd_debug_attention_pair failed (rc={rc}): {L.last_error()}")
+    return outs[0], outs[1]
+
+
 def groupnorm(x, gamma, beta, groups=32, eps=1e-5, silu=False, x2=None):
     """x: (B,HW,C0) bf16 [, x2: (B,HW,C1) concatenated on channels] -> (B,HW,C0+C1)"""
     _bf16(x, x2)

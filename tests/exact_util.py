@@ -14,7 +14,8 @@ problems here leave no such room:
 
 * Routing problems (attention): keys are +-1 codes, query i is gain * code[pi(i)], V elements are +-(1 + m/128).  The softmax
   mass of every key but pi(i) is at most 2^-12 (checked here in fp64), which moves the output by less than 2^-11 relative --
-  inside the half-ulp of bf16 -- so the correct output is v[pi(i)], bit for bit.
+  inside the half-ulp of bf16 -- so the correct output is v[pi(i)], bit for bit.  ``routing_pair`` gives two such problems for one
+  two-problem launch, every K/V element of both with values of its own.
 
 Plain helper module (like parity_util.py), no fixtures."""
 import functools
@@ -304,6 +305,30 @@ def routing_problem(B, heads, nq, nk, gain, prescaled=False, nsplit=1, causal=Fa
     k = codes.permute(1, 0, 2).reshape(1, nk, heads * 64).expand(B, nk, heads * 64)
     return SimpleNamespace(q=bf(q), k=bf(k.contiguous()), v=bf(v), want=bf(want.permute(0, 2, 1, 3).reshape(B, nq, heads * 64)),
                            pi=pi, mass=mass, lift=lift, scale=0.0 if prescaled else 0.125)
+
+
+@functools.lru_cache(maxsize=8)
+def routing_pair(E0, E1, heads, nq0, nk0, nq1, nk1, gain, prescaled=False, nsplit=1):
+    """Two routing problems for ONE launch of two problems (MvdAttnArgs::nprob = 2): problem i has E_i K/V elements with nq_i
+    queries and nk_i keys each.  ``routing_values`` hashes V from (element, head, key, dim) alone, so two ``routing_problem``s of
+    one shape hold the same V and a launch that read problem 0's V for problem 1 would return the wanted bits; here ONE
+    ``routing_values`` call over the E0 + E1 elements of both problems gives every element values of its own, and ``want`` is
+    taken from them.  The key codes and the routing maps differ too (seeds 0 and 1; asserted).  The per-problem checks are
+    ``routing_problem``'s: off-target mass <= 2^-12, ``lift``, ``must_hit(nk_i, nsplit)``.  Returns (p0, p1), fields as
+    ``routing_problem``'s."""
+    ps = [routing_problem(E, heads, nq, nk, gain, prescaled, nsplit, False, seed) for seed, (E, nq, nk) in enumerate(((E0, nq0, nk0), (E1, nq1, nk1)))]
+    v = routing_values(E0 + E1, heads, max(nk0, nk1))
+    out = []
+    for p, vv in zip(ps, (v[:E0, :nk0], v[E0:, :nk1])):
+        E, nk, _ = vv.shape
+        want = vv.reshape(E, nk, heads, 64).permute(0, 2, 1, 3)[torch.arange(E)[:, None, None], torch.arange(heads)[None, :, None], p.pi]
+        out.append(SimpleNamespace(q=p.q, k=p.k, v=bf(vv.contiguous()), want=bf(want.permute(0, 2, 1, 3).reshape(E, -1, heads * 64)), pi=p.pi,
+                                   mass=p.mass, lift=p.lift, scale=p.scale))
+    n, e, m = min(nk0, nk1), min(E0, E1), min(nq0, nq1)
+    assert not torch.equal(out[0].k[:e, :n], out[1].k[:e, :n]), "the two problems share their key codes"
+    assert not torch.equal(out[0].pi[:e, :, :m], out[1].pi[:e, :, :m]), "the two problems share their routing map"
+    assert not torch.equal(out[0].v[:e, :n], out[1].v[:e, :n])
+    return tuple(out)
 
 
 # gains of the three regimes: LAZY -- the engine form may keep its first tile's maximum (lift <= 90; the kernel re-runs from a

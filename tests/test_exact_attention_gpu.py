@@ -5,7 +5,11 @@ wrong split-KV merge shows as a wrong row; at nk = 1024 the tolerance tests see 
 
 Three regimes by the query gain: LAZY (the engine form may keep its first tile's maximum: P = 2^lift, lift <= 90),
 STRICT_LAZY (lift < 60: below the kernel's acceptance bound of 2^64 on the denominators, so the unchecked loop's own result is
-stored) and RERUN (lift >= 140: the unchecked loop overflows and the workgroup takes the checked loop)."""
+stored) and RERUN (lift >= 140: the unchecked loop overflows and the workgroup takes the checked loop).
+
+Every launch here has ONE problem (every mvd_op_attention* entry sets nprob = 1).  The two-problem launches of the image-conditioned
+transformer blocks -- the pair decode of the workgroup id, the per-problem fields, the split-KV workspace over both problems -- are
+covered by test_exact_attention_pair_gpu.py through ops.attention_pair."""
 import pytest
 import torch
 
