@@ -239,6 +239,17 @@ int mvd_op_linear(const void* a, const void* a2, int k1, int k2, const void* w, 
                   int ld_rowvec, int rows_per_batch, const void* res, float alpha, int geglu, void* out, int out_f32,
                   int m, int n, int force_cfg, int splitk, float* splitk_ws /* splitk*m*n floats when splitk > 1 */,
                   void* stream);
+/* mvd_op_linear with the leading dimensions of the engine's own call sites: W is [n][ldw] with ldw >= k1 + k2 (only the first
+ * k1 + k2 elements of a row are read, only the first n rows), res is [m][ldres] and out [m][ldo] -- column slices of wider
+ * buffers; res == out runs in place.  ldw % 8 == 0, ldres % 4 == 0, ldo % 4 == 0; the row vector's base is 16-byte aligned
+ * and ld_rowvec % 4 == 0.  A stride some kernel family cannot take is an error, or another kernel of the same tile, never a
+ * misaligned access: the ping-pong kernels (config 6 / 7) need ldo % 8 == 0 and ldres % 8 == 0 and leave other strides to the
+ * lock-step 256x320 tile; the blocked weight layout (force_cfg + 1000) has no row stride: ldw == k1 + k2.
+ * tests/test_exact_strides_gpu.py compares these forms bitwise. */
+int mvd_op_linear_ld(const void* a, const void* a2, int k1, int k2, const void* w, int ldw, const float* bias, const float* rowvec,
+                     int ld_rowvec, int rows_per_batch, const void* res, int ldres, float alpha, int geglu, void* out, int ldo,
+                     int out_f32, int m, int n, int force_cfg, int splitk, float* splitk_ws /* splitk*m*n floats when splitk > 1 */,
+                     void* stream);
 /* out[M][N] = LayerNorm(x[M][K]; gamma, beta, eps) . W^T + b in ONE kernel (geglu = 1: followed by value*gelu(gate), width
  * N/2, rows interleaved as for mvd_op_linear).  w_folded = W.diag(gamma) in bf16, c1[n] = sum_k w_folded[n][k] (of the bf16
  * values, fp32), c2[n] = sum_k beta[k].W[n][k] + b[n]: mvd_amd/packing.py::fold_layernorm.  Shapes: K <= 1280, N % 320 == 0
@@ -374,6 +385,10 @@ int mvd_debug_pick_splitk_conv(int m, int n, int k);
  * small-M ring depth (0: tiled), column tiles per group of the 256x320 kernel's tile walk (0: row-major)}.  -1: no dense launch
  * takes the shape (each source width must be a multiple of the 64-deep K slab). */
 int mvd_debug_dense_route(int m, int n, int k1, int k2, int* out);
+/* 1 when the ping-pong kernel (tile config 7) takes a dense bf16 launch [m][k] . W[n][ldw]^T (+ res[m][ldres]; ldres 0: none) ->
+ * out[m][ldo], 0 when it leaves it to the lock-step 256x320 tile, -1 for a bad shape (pure host arithmetic).  Its epilogue moves
+ * 16 bytes per access: ldo and ldres must be multiples of 8 elements. */
+int mvd_debug_gemm_pp_takes(int m, int n, int k, int ldw, int ldres, int ldo);
 /* Small-M kernels (gemm_sm.hip, the batch-1 path): force_cfg = 100 + 10 * tile + ring depth in mvd_op_linear / mvd_op_conv3x3
  * (tiles 0..6 = 64x64, 128x64, 64x128, 128x128, 64x160, 128x160, 64x320; + 1000: the weight is in the blocked LDS-image
  * layout of mvd_amd.packing.block_weight).  With splitk > 1 these kernels combine the slices themselves: splitk_ws then

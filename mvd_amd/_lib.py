@@ -127,6 +127,9 @@ _SIGS = {
     "mvd_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_op_linear_ld": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_op_ln_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
                                    C.c_int, C.c_int, C.c_void_p]),
     "mvd_op_linear_xs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
@@ -188,6 +191,7 @@ _SIGS = {
     "mvd_debug_pick_splitk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_debug_pick_splitk_conv": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mvd_debug_dense_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "mvd_debug_gemm_pp_takes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mvd_gemm_sm_num_tiles": (C.c_int, []),
     "mvd_debug_set_attention_nw": (C.c_int, [C.c_int]),
     "mvd_debug_set_flags": (C.c_int, [C.c_int]),

@@ -299,7 +299,7 @@ bool mvd_conv_ws_applicable(const MvdWsArgs& a) {
   if (a.C % 128 || a.C <= 0 || a.N % 16 || a.N <= 0) return false;
   if ((a.scc0 % 128) || (a.scc1 % 128) || (a.scc0 && !a.sc0) || (a.scc1 && !a.sc1) || (a.scc1 && !a.scc0)) return false;
   if ((a.ldo % 4) || a.ldo < a.N || (a.res && ((a.ldres % 4) || a.ldres < a.N))) return false;
-  if (a.rowvec && (a.ld_rowvec % 4)) return false;
+  if (a.rowvec && ((a.ld_rowvec % 4) || ((uintptr_t)a.rowvec & 15))) return false;      // f32x4 loads at rowvec + image * ld_rowvec + n
   const size_t lim = (size_t)1 << 31;
   if ((size_t)a.M * a.C * 2 >= lim || (size_t)a.M * (a.scc0 > a.scc1 ? a.scc0 : a.scc1) * 2 >= lim) return false;
   if ((size_t)a.N / 16 * (size_t)((a.C / 128) * 9 + a.scc0 / 128 + a.scc1 / 128) * 4096 >= lim) return false;

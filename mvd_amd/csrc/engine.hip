@@ -1702,6 +1702,20 @@ int mvd_op_linear(const void* a, const void* a2, int k1, int k2, const void* w, 
   g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res; g.ldres = on; g.alpha = alpha; g.geglu = geglu; g.out_f32 = out_f32;
   return op_launch(g, force_cfg, splitk, splitk_ws, (hipStream_t)stream);
 }
+// the same with the leading dimensions the engine's call sites use: a weight read with a row stride ldw >= k1 + k2 (a packed
+// [o_self | o_ref] out-projection with the adapter off), res / out as column slices of wider buffers, res == out (in place)
+int mvd_op_linear_ld(const void* a, const void* a2, int k1, int k2, const void* w, int ldw, const float* bias, const float* rowvec,
+                     int ld_rowvec, int rows_per_batch, const void* res, int ldres, float alpha, int geglu, void* out, int ldo,
+                     int out_f32, int m, int n, int force_cfg, int splitk, float* splitk_ws, void* stream) {
+  const int on = geglu ? n / 2 : n;
+  if (!a || !w || !out || m <= 0 || n <= 0 || k1 <= 0 || k2 < 0) { mvd_set_error("mvd_op_linear_ld: bad argument"); return -1; }
+  if (ldw < k1 + k2 || ldo < on || (res && ldres < on)) { mvd_set_error("mvd_op_linear_ld: a leading dimension is shorter than its row (ldw=%d ldres=%d ldo=%d)", ldw, ldres, ldo); return -1; }
+  if (splitk > 1 && !splitk_ws) { mvd_set_error("mvd_op_linear_ld: split-K needs a workspace"); return -1; }
+  MvdGemmArgs g = gemm_dense((const bf16_t*)a, (const bf16_t*)a2, k1, k2, m, (const bf16_t*)w, ldw, bias, n, out, ldo);
+  if (rows_per_batch > 0) g.rows_per_batch = g.outW = rows_per_batch;
+  g.rowvec = rowvec; g.ld_rowvec = ld_rowvec; g.res = (const bf16_t*)res; g.ldres = ldres; g.alpha = alpha; g.geglu = geglu; g.out_f32 = out_f32;
+  return op_launch(g, force_cfg, splitk, splitk_ws, (hipStream_t)stream);
+}
 
 int mvd_op_ln_linear(const void* x, int k, const void* w_folded, const float* c1, const float* c2, float eps, int geglu,
                      void* out, int m, int n, void* stream) {

@@ -198,6 +198,7 @@ int mvd_launch_gemm(const MvdGemmArgs& a, hipStream_t s, int force_cfg) {
   }
   const int on = a.geglu ? a.N / 2 : a.N;
   if (a.ldo < on || (a.ldo % 4) || (a.res && (a.ldres % 4))) { mvd_set_error("gemm: bad leading dims"); return -1; }
+  if (!mvd_gemm_rowvec_aligned(a)) { mvd_set_error("gemm: the row vector is read 16 bytes at a time: ld_rowvec=%d must be a multiple of 4 and the base 16-byte aligned", a.ld_rowvec); return -1; }
 
   // force_cfg: -1 = heuristic; 0..5 = tile config with register staging; 8..13 = same tiles with LDS-DMA staging
   static const int default_glds = MVD_ENV_INT("MVD_GEMM_GLDS", 1);
@@ -335,6 +336,19 @@ extern "C" int mvd_debug_dense_route(int m, int n, int k1, int k2, int* out) {
   g.splitk = S;
   out[0] = 0; out[1] = cfg; out[2] = S; out[3] = 0; out[4] = (cfg == 7 && mvd_gemm_pp_applicable(g)) ? mvd_gemm_pp_walk(g) : 0;
   return 0;
+}
+
+// Whether the ping-pong kernel takes a dense bf16 launch [m][k] . W[n][ldw]^T + res[m][ldres] -> out[m][ldo] (pure host arithmetic:
+// mvd_gemm_pp_applicable); a forced tile config 7 that it does not take runs on the lock-step 256x320 tile.  ldres 0: no residual.
+extern "C" int mvd_debug_gemm_pp_takes(int m, int n, int k, int ldw, int ldres, int ldo) {
+  if (m <= 0 || n <= 0 || k <= 0 || ldw < k || ldo < n || ldres < 0) { mvd_set_error("gemm_pp_takes: bad shape M=%d N=%d K=%d ldw=%d ldres=%d ldo=%d", m, n, k, ldw, ldres, ldo); return -1; }
+  alignas(16) static const float dummy[4] = {};
+  const bf16_t* p = reinterpret_cast<const bf16_t*>(dummy);
+  MvdGemmArgs g; memset(&g, 0, sizeof(g));
+  g.seg[0].p0 = p; g.seg[0].c0 = k; g.seg[0].mode = MVD_A_DENSE; g.seg[0].ksize = k;
+  g.nseg = 1; g.W = p; g.ldw = ldw; g.Ktot = k; g.M = m; g.N = n; g.rows_per_batch = m; g.outH = 1; g.outW = m;
+  g.bias = dummy; g.alpha = 1.f; g.out = const_cast<float*>(dummy); g.ldo = ldo; g.res = ldres ? p : nullptr; g.ldres = ldres; g.splitk = 1;
+  return mvd_gemm_pp_applicable(g) ? 1 : 0;
 }
 
 int mvd_launch_splitk_reduce(const MvdGemmArgs& a, hipStream_t s) {

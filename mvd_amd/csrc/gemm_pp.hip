@@ -772,6 +772,10 @@ bool mvd_gemm_pp_applicable(const MvdGemmArgs& a) {
   const size_t lim = (size_t)1 << 31;
   if (a.N % BN || a.Ktot % 64 || a.out_f32) return false;      // (fp32 outputs exist at M = batch only: gemm.hip)
   if (a.relu) return false;                                     // (no ReLU epilogue here: the lock-step tiles of gemm.hip have it)
+  // the epilogue stores (and fetches the residual) 16 bytes at a time at row * ld + a column that is a multiple of 8: a row
+  // stride that is no multiple of 8 elements would put every other row's accesses on an 8-byte boundary (the lock-step tile
+  // of the same shape moves 8 bytes per access and takes such a launch)
+  if ((a.ldo % 8) || (a.res && (a.ldres % 8))) return false;
   if ((size_t)a.N * a.ldw * 2 >= lim) return false;
   if ((size_t)(a.M + BM) * a.ldo * 2 >= lim || (a.res && (size_t)(a.M + BM) * a.ldres * 2 >= lim)) return false;
   if (a.splitk > 1 && (size_t)(a.M + BM) * a.N * 4 >= lim) return false;

@@ -600,6 +600,8 @@ bool mvd_gemm_sm_plan(const MvdGemmArgs& a, int* tile, int* nstage, int* splitk)
 // tile: index into {64x64, 128x64, 64x128, 128x128, 64x160, 128x160, 64x320}; nstage: ring depth 2..8, clamped to what 160 KB
 // of LDS hold (arguments already validated by mvd_launch_gemm)
 int mvd_launch_gemm_sm(const MvdGemmArgs& a, hipStream_t s, int tile, int nstage) {
+  if (!mvd_gemm_rowvec_aligned(a)) { mvd_set_error("gemm_sm: the row vector is read 16 bytes at a time: ld_rowvec=%d must be a multiple of 4 and the base 16-byte aligned", a.ld_rowvec); return -1; }
+  if (a.w_blocked && a.ldw != a.Ktot) { mvd_set_error("gemm_sm: the blocked weight layout has no row stride (ldw=%d, K=%d): pack the [N][K] weight itself", a.ldw, a.Ktot); return -1; }
   if (!mvd_gemm_sm_applicable(a, tile)) { mvd_set_error("gemm_sm: tile %d does not take M=%d N=%d K=%d geglu=%d splitk=%d", tile, a.M, a.N, a.Ktot, a.geglu, a.splitk); return -1; }
   const int stage_bytes = (kSmTiles[tile].bm + kSmTiles[tile].bn) * 128;
   int maxst = 160 * 1024 / stage_bytes;

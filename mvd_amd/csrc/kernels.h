@@ -70,6 +70,9 @@ struct MvdGemmArgs {
 };
 static_assert(sizeof(MvdGemmArgs) == 280, "MvdGemmArgs is a kernel argument: a size change moves the hidden arguments of every GEMM kernel");
 
+// every kernel family reads the row vector as f32x4 at rowvec + batch * ld_rowvec + n (n a multiple of 4): the base and the row
+// stride must keep those 16-byte loads aligned.  Checked by mvd_launch_gemm and mvd_launch_gemm_sm (the engine calls both).
+inline bool mvd_gemm_rowvec_aligned(const MvdGemmArgs& a) { return !a.rowvec || (a.ld_rowvec % 4 == 0 && ((uintptr_t)a.rowvec & 15) == 0); }
 int mvd_launch_gemm(const MvdGemmArgs& a, hipStream_t s, int force_cfg = -1);
 int mvd_gemm_pick_config(const MvdGemmArgs& a);   // tile config the heuristic gives this problem
 // gemm_relu.hip: the ReLU forms (a.relu == 1) of tile configs 3, 4, 5, unsplit, and the reduce pass of a split ReLU launch;

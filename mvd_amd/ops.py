@@ -59,6 +59,40 @@ def linear(a, w, bias=None, a2=None, rowvec=None, rows_per_batch=0, res=None, al
     return out
 
 
+def _pv(t):
+    """pointer of a view (None passes): the caller hands over the leading dimension"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def linear_ld(a, w, bias=None, a2=None, rowvec=None, rows_per_batch=0, res=None, out=None, alpha=1.0, geglu=False,
+              out_f32=False, force_cfg=-1, splitk=1, blocked=None):
+    """``linear`` in the forms the engine launches (mvd_op_linear_ld): ``w`` (n, k1 + k2), ``rowvec``, ``res`` and ``out`` may be views
+    with ``stride(-1) == 1`` -- row / column slices of wider buffers; the pointers and leading dimensions are read from the views.
+    ``out=res`` runs in place; ``out=None`` allocates a dense result.  ``blocked=(n, k, ldw)``: ``w`` is packing.block_weight of
+    the (n, k) weight, to be read as if its rows were ``ldw`` apart (the kernels refuse ldw != k: the layout has no row stride)."""
+    _bf16(a, a2, w, res)
+    m, k1 = a.shape
+    k2 = a2.shape[1] if a2 is not None else 0
+    ldw = w.stride(0)
+    if blocked is not None:
+        ldw = blocked[2] if len(blocked) > 2 else k1 + k2
+        assert w.is_contiguous()
+    else:
+        assert w.dim() == 2 and w.shape[1] == k1 + k2 and w.stride(1) == 1, (tuple(w.shape), w.stride())
+    n, force_cfg = _blocked(w, None if blocked is None else blocked[:2], k1 + k2, force_cfg)
+    on = n // 2 if geglu else n
+    if out is None:
+        out = torch.empty(m, on, device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    assert out.shape == (m, on) and out.stride(1) == 1 and out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
+    assert res is None or (res.shape == (m, on) and res.stride(1) == 1)
+    assert rowvec is None or (rowvec.dtype == torch.float32 and rowvec.dim() == 2 and rowvec.shape[1] == n and rowvec.stride(1) == 1)
+    ws = torch.empty(splitk * m * n + 4096, device=a.device, dtype=torch.float32) if splitk > 1 else None
+    L.call("mvd_op_linear_ld", _p(a), _p(a2), k1, k2, _pv(w), ldw, _p(bias), _pv(rowvec),
+           rowvec.stride(0) if rowvec is not None else 0, rows_per_batch, _pv(res), res.stride(0) if res is not None else 0,
+           float(alpha), int(geglu), _pv(out), out.stride(0), int(out_f32), m, n, force_cfg, splitk, _p(ws), _s())
+    return out
+
+
 def ln_linear(x, w_folded, cf, eps=1e-5, geglu=False):
     """LayerNorm(x).W^T + b (optionally GEGLU) in one kernel; (w_folded, cf) from packing.fold_layernorm."""
     _bf16(x, w_folded)
@@ -118,8 +152,12 @@ def conv3x3(x, w_packed, bias=None, stride=1, upsample=False, rowvec=None, res=N
     c1 = shortcut.shape[-1] if shortcut is not None else 0
     c2 = shortcut2.shape[-1] if shortcut2 is not None else 0
     ws = torch.empty(splitk * B * oh * ow * cout + 4096, device=x.device, dtype=torch.float32) if splitk > 1 else None
-    L.call("mvd_op_conv3x3", _p(x), B, H, W, Cin, stride, int(upsample), int(asym_pad), _p(w_packed), _p(bias), _p(rowvec),
-           rowvec.shape[1] if rowvec is not None else 0, _p(res), _p(shortcut), _p(shortcut2), c1, c2, _p(out), cout,
+    # (the row vector may be a column slice of a wider fp32 buffer, as the engine's fused time_emb_proj output is)
+    assert rowvec is None or (rowvec.is_cuda and rowvec.dtype == torch.float32 and rowvec.dim() == 2 and rowvec.shape[1] == cout
+                              and rowvec.stride(1) == 1 and (rowvec.shape[0] == 1 or rowvec.stride(0) >= cout)), \
+        "rowvec: (B, cout) fp32 with stride(1) == 1 and stride(0) >= cout"
+    L.call("mvd_op_conv3x3", _p(x), B, H, W, Cin, stride, int(upsample), int(asym_pad), _p(w_packed), _p(bias), _pv(rowvec),
+           rowvec.stride(0) if rowvec is not None else 0, _p(res), _p(shortcut), _p(shortcut2), c1, c2, _p(out), cout,
            force_cfg, splitk, _p(ws), _s())
     return out
 

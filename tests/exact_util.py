@@ -369,6 +369,32 @@ def assert_same_bits(got, want, what=""):
     assert ok, describe_mismatch(got, want, what)
 
 
+# ------------------------------------------------------------------------------------------------ views of wider buffers
+SENTINEL_BITS = {torch.bfloat16: 0x5A5A, torch.float32: 0x5A5A5A5A}     # 1.5e16: finite, beyond any partial_sum_bound
+
+
+def sentinel(dtype):
+    """the guard value of ``dtype`` (bf16 / fp32) as a 0-d tensor: one known bit pattern that no reference value has"""
+    return torch.tensor(SENTINEL_BITS[dtype], dtype=torch.int16 if dtype == torch.bfloat16 else torch.int32).view(dtype)
+
+
+def embed(t, ld, off, fill):
+    """(rows, n) tensor -> a new (rows, ld) buffer of the same dtype and device with ``t`` in columns [off, off + n) and ``fill`` (a
+    number, NaN included, or a 0-d tensor such as ``sentinel``) everywhere else; the operand is then ``buf[:, off:off + n]``"""
+    rows, n = t.shape
+    assert 0 <= off and off + n <= ld, (off, n, ld)
+    buf = torch.empty(rows, ld, dtype=t.dtype, device=t.device)
+    buf[:] = fill.to(t.device) if torch.is_tensor(fill) else fill
+    buf[:, off:off + n] = t
+    return buf
+
+
+def outside_unchanged(buf, before, off, n):
+    """the guard columns of ``buf`` -- everything outside [off, off + n) -- hold the bit patterns they hold in ``before``"""
+    b, a = _bits(buf.detach().cpu()), _bits(before.detach().cpu())
+    return b.shape == a.shape and torch.equal(b[:, :off], a[:, :off]) and torch.equal(b[:, off + n:], a[:, off + n:])
+
+
 def dev(x64):
     """fp64 bf16-valued tensor (or None) -> bf16 on the GPU"""
     return None if x64 is None else bf(x64).contiguous().cuda()
