@@ -73,7 +73,9 @@ enum {
   MVD_USE_IMAGE = 2,        /* use_image_conditioning and source_image_latents is not None (:269)      */
   MVD_REUSE_REF = 4,        /* reuse reference K/V computed by a previous call (inputs step-invariant)  */
   MVD_KEEP_FEATURES = 8,    /* keep the 16 encoder feature maps for mvd_engine_get_feature               */
-  MVD_SHARE_REF = 16        /* `views` views of ONE object in one forward, sharing one reference (below)  */
+  MVD_SHARE_REF = 16,       /* `views` views of ONE object in one forward, sharing one reference (below)  */
+  MVD_DEEPCACHE_REFRESH = 32, /* the ordinary forward, which also stores the deep feature (DeepCache, below)  */
+  MVD_DEEPCACHE_SHALLOW = 64  /* the shallow forward: the stored deep feature in place of the deep layers       */
 };
 
 /* The batch layout of a forward, described once for the three entries below (the engine holds it as one value, csrc/ragged.h):
@@ -196,6 +198,39 @@ int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable);
  * Setting or clearing drops the captured hipGraphs.  Clear (the default): the launches of a forward are what they were. */
 int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2);
 int mvd_engine_clear_freeu(mvd_engine_t* e);
+
+/* DeepCache (Ma et al., CVPR 2024; the DeepCacheSDHelper used with diffusers, restated): the deep, low-resolution features of
+ * the main pass change little between neighbouring denoising steps, so a step may reuse them.  With n = num_levels,
+ * Lb = layers_per_block, a branch b in [0, Lb) (DeepCache's cache_branch_id) and j0 = Lb - 1 - b, the DEEP FEATURE is the hidden
+ * (not the skip) input of up_blocks.{n-1}.resnets.{j0} in the main pass: for j0 >= 1 the output of up_blocks.{n-1}.attentions.{j0-1},
+ * for j0 = 0 the up-sampled output of up block n-2 after its FiLM hook; [batch][H][W][C] bf16, C = block_out_channels[0] (j0 >= 1) or
+ * block_out_channels[1] (j0 = 0).
+ *   MVD_DEEPCACHE_REFRESH  the ordinary forward (every flag and layout as without the bit, the same output bit for bit), which also
+ *                          copies the deep feature into the bound buffer (one device-to-device copy on the forward's stream).
+ *   MVD_DEEPCACHE_SHALLOW  the front matter (time, camera and text paths, im2col with the input FiLM), the text K/V GEMM, conv_in,
+ *                          down_blocks.0 layers 0..b (resnet + transformer each; no downsampler, no down_0 hook), then
+ *                          up_blocks.{n-1} layers j0..Lb starting from the STORED feature (layer j reads the skip of down layer
+ *                          Lb - j, conv_in's output for j = Lb), the up_{n-1} hook, conv_norm_out, conv_out.  Nothing else runs: it is
+ *                          the full forward with that one tensor replaced by the stored one.  Every executed layer reads the time
+ *                          projection, text K/V, reference K/V and per-row K/V maps of its position in the FULL schedule.  With
+ *                          MVD_USE_IMAGE it needs MVD_REUSE_REF and a matching cached reference: the encoder pass never runs and
+ *                          the side stream is never forked.  FreeU applies to the executed resnets it applies to in a full forward.
+ * Both bits together, either bit without mvd_engine_set_deepcache, or on mvd_engine_reference_encode: -1, nothing is launched.
+ * The stored feature carries a record -- batch, height, width, the batch layout, the MVD_USE_CAMERA / MVD_USE_IMAGE bits, the
+ * branch and a weight generation that mvd_engine_set_weight / mvd_engine_clear_weights bump -- and a shallow forward whose
+ * arguments do not match it is rejected before any launch, in words that name the mismatch.  The timestep is not part of the
+ * record: reusing the feature at another step is the point.  The bits are part of the argument block and so of the hipGraph key.
+ *   mvd_engine_set_deepcache / _clear_deepcache   set the branch (outside [0, Lb): -1) / switch off; both drop the captured
+ *                          hipGraphs and invalidate the stored feature.
+ *   mvd_engine_deepcache_bytes / _bind_deepcache  the buffer of the stored feature for a forward of this shape (any branch), apart
+ *                          from the reference cache (whose allocator every cold forward resets); 256-byte aligned.  Binding drops
+ *                          the captured hipGraphs and invalidates the stored feature.
+ * The mvd_engine_workspace_bytes_args / _objects / _ragged entries size the forward the bits describe; a shallow forward never
+ * needs more than the full forward of the same arguments (checked there). */
+int mvd_engine_set_deepcache(mvd_engine_t* e, int branch);
+int mvd_engine_clear_deepcache(mvd_engine_t* e);
+int64_t mvd_engine_deepcache_bytes(mvd_engine_t* e, int batch, int height, int width);
+int mvd_engine_bind_deepcache(mvd_engine_t* e, void* ptr, int64_t bytes);
 
 /* Per-kernel-class timing with HIP events on the launch stream (measurement only; off by default).
  * classes = kernels: 0..5, 12 lock-step GEMM/conv tile configs (gemm.hip); ping-pong 256x320 kernels (gemm_pp.hip): 7 dense,

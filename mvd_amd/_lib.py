@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("MVD_HIP_LIB") or os.path.join(HERE, "libmvd_hip.so")
 
 MVD_MAX_LEVELS = 4
 MVD_USE_CAMERA, MVD_USE_IMAGE, MVD_REUSE_REF, MVD_KEEP_FEATURES, MVD_SHARE_REF = 1, 2, 4, 8, 16
+MVD_DEEPCACHE_REFRESH, MVD_DEEPCACHE_SHALLOW = 32, 64
 
 
 class MvdError(RuntimeError):
@@ -213,6 +214,10 @@ _SIGS = {
     "mvd_debug_apg_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
     "mvd_engine_set_freeu": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mvd_engine_clear_freeu": (C.c_int, [C.c_void_p]),
+    "mvd_engine_set_deepcache": (C.c_int, [C.c_void_p, C.c_int]),
+    "mvd_engine_clear_deepcache": (C.c_int, [C.c_void_p]),
+    "mvd_engine_deepcache_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mvd_engine_bind_deepcache": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "mvd_op_freeu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "mvd_op_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -80,6 +80,16 @@ struct mvd_engine {
   bool share_encoder = false;       // N4: the encoder pass reads weight set 0 (base UNet == image-encoder UNet)
   // FreeU (mvd_engine_set_freeu): the main pass's up blocks 0 and 1 read re-weighted hidden / skip inputs; freeu_b / freeu_s by block
   bool freeu_on = false; float freeu_b[2] = {1.f, 1.f}, freeu_s[2] = {1.f, 1.f};
+  // DeepCache (mvd_engine_set_deepcache; include/mvd_hip.h): the stored deep feature lives in a buffer of its own (the reference
+  // cache's allocator is reset by every cold forward) and carries the record of the refresh forward that wrote it.  The record is
+  // NOT part of HostState: it is written by unet_forward once a refresh forward has been issued (launched, captured or replayed),
+  // so replaying some other forward's graph cannot roll it back.
+  bool dc_on = false; int dc_branch = 0;
+  void* dc_ptr = nullptr; int64_t dc_bytes = 0;
+  uint64_t weight_gen = 0;          // bumped by mvd_engine_set_weight / mvd_engine_clear_weights
+  struct DeepRecord { bool valid = false; int batch = 0, h = 0, w = 0, cam = 0, img = 0, branch = 0; uint64_t wgen = 0; std::vector<int> layout; } dc_rec;
+  bool dc_sizing = false;           // a sizing entry's dry run of a shallow forward: no stored feature is needed to size one
+  int dc_hidden_channels() const { return cfg.layers_per_block - 1 - dc_branch >= 1 ? cfg.block_out_channels[0] : cfg.block_out_channels[1]; }
   // hipGraph replay of whole forwards (mvd_engine_set_graph): one instantiated graph per distinct (arguments, cache state)
   struct HostState {                  // what a forward leaves behind on the host side
     std::vector<bf16_t*> refkv, feat_keep;
@@ -537,6 +547,9 @@ struct PassOpts {
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
   const ViewLayout* layout = nullptr;   // the forward's batch layout (ragged.h): the adapter pass's K/V maps, the encoder pass's statistics
   bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
+  int deep = 0;               // main pass, DeepCache: MVD_DEEPCACHE_REFRESH (store the deep feature) / _SHALLOW (start from it); 0: neither
+  int deep_branch = 0;        // the branch b: down_blocks.0 layers 0..b and up_blocks.{n-1} layers Lb-1-b..Lb are the shallow forward
+  bf16_t* deep_buf = nullptr; // the bound buffer: [B][H0][W0][C of the deep feature]
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
 };
@@ -684,11 +697,27 @@ struct UNetPass {
     return mvd_launch_film(x.p, x.B, x.hw(), x.C, it->second.first, it->second.second, x.C, out.p, c.s);
   }
 
+  // positions of a layer in the FULL schedule (the order of enumerate_resnets / enumerate_features): what temb_off, tkv_off, refkv
+  // and feat_ev are indexed by.  run() SETS resnet_idx / feat_idx from these in front of every layer it executes -- a shallow
+  // (DeepCache) pass skips layers, and a count from 0 would hand its up block the down blocks' slices.
+  int down_resnet_pos(int i, int j) const { return i * cfg.layers_per_block + j; }
+  int mid_resnet_pos(int j) const { return cfg.num_levels * cfg.layers_per_block + j; }
+  int up_resnet_pos(int i, int j) const { return cfg.num_levels * cfg.layers_per_block + 2 + i * (cfg.layers_per_block + 1) + j; }
+  int down_feat_pos(int i, int j) const { return i * cfg.layers_per_block + j; }
+  int mid_feat_pos() const { return (cfg.num_levels - 1) * cfg.layers_per_block; }
+  int up_feat_pos(int i, int j) const { return (cfg.num_levels - 1) * cfg.layers_per_block + 1 + (i - 1) * (cfg.layers_per_block + 1) + j; }
+
   int run(const Act& x_in, float* out_nchw) {
     const int n = cfg.num_levels, Lb = cfg.layers_per_block;
     const int C0 = cfg.block_out_channels[0];
+    // DeepCache (include/mvd_hip.h): `shallow` runs down_blocks.0 layers 0..b and up_blocks.{n-1} layers j0..Lb around the stored
+    // deep feature; `refresh` is the full pass, which copies that feature out where the shallow pass will put it in
+    const bool shallow = o.deep == MVD_DEEPCACHE_SHALLOW, refresh = o.deep == MVD_DEEPCACHE_REFRESH;
+    const int j0 = Lb - 1 - o.deep_branch;
     std::vector<Act> skips;
     // text K/V for all attn2 sites of this pass: one [B*L][xdim] x [tkv_total][xdim]^T GEMM instead of 16 small ones
+    // (a shallow pass computes all of it as well: the GEMM is small, and the executed sites read the slices of their full-schedule
+    //  positions from a buffer laid out as ever)
     const int TB = text_rows > 0 ? text_rows : B;
     tkv = c.aalloc<bf16_t>((size_t)TB * L * c.e->tkv_total);
     CHECK(c.linear(text, nullptr, cfg.cross_attention_dim, 0, TB * L, c.WB("text_kv.w", (int64_t)c.e->tkv_total * cfg.cross_attention_dim), nullptr,
@@ -697,20 +726,23 @@ struct UNetPass {
     // conv_in: x_in holds im2col rows [B*H*W][64] (k = tap*Cin + ch, zero padded) -> one K=64 MFMA GEMM
     CHECK(c.linear(x_in.p, nullptr, 64, 0, B * H0 * W0, c.WB("conv_in.w", (int64_t)C0 * 64), c.WF("conv_in.b", C0), C0, nullptr, 0, h.p, C0));
     skips.push_back(h);
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < (shallow ? 1 : n); ++i) {
       const int co = cfg.block_out_channels[i];
       const std::string bk = "down_blocks." + std::to_string(i);
-      for (int j = 0; j < Lb; ++j) {
+      for (int j = 0; j < (shallow ? o.deep_branch + 1 : Lb); ++j) {
         Act r = c.new_act(B, h.H, h.W, co, true);
+        resnet_idx = down_resnet_pos(i, j);
         CHECK(resnet(bk + ".resnets." + std::to_string(j), h, nullptr, co, r));
         h = r;
         if (i + 1 < n) {
           Act t = c.new_act(B, h.H, h.W, co, true);
+          feat_idx = down_feat_pos(i, j);
           CHECK(transformer(bk + ".attentions." + std::to_string(j), h, cfg.num_heads[i], t));
           h = t;
         }
         skips.push_back(h);
       }
+      if (shallow) break;     // (no downsampler, no down_0 hook: the hook modulates what goes DOWN, which a shallow pass never reads)
       if (i + 1 < n) {
         Act d = c.new_act(B, (h.H + 1) / 2, (h.W + 1) / 2, co, true);
         CHECK(c.conv3(h, 2, 0, c.WB(bk + ".down.w", (int64_t)co * 9 * co), c.WF(bk + ".down.b", co), nullptr, 0, nullptr, nullptr, nullptr, 0, 0, d));
@@ -724,27 +756,36 @@ struct UNetPass {
         h = res;
       }
     }
-    {
+    if (!shallow) {
       const int cm = cfg.block_out_channels[n - 1];
       Act r = c.new_act(B, h.H, h.W, cm, true);
+      resnet_idx = mid_resnet_pos(0);
       CHECK(resnet("mid_block.resnets.0", h, nullptr, cm, r));
       Act t = c.new_act(B, h.H, h.W, cm, true);
+      feat_idx = mid_feat_pos();
       CHECK(transformer("mid_block.attentions.0", r, cfg.num_heads[n - 1], t));
       Act r2 = c.new_act(B, h.H, h.W, cm, true);
+      resnet_idx = mid_resnet_pos(1);
       CHECK(resnet("mid_block.resnets.1", t, nullptr, cm, r2));
       h = r2;
       if (o.film) { Act res = h; CHECK(film("mid_0", h, res)); h = res; }
+    } else {
+      // the stored deep feature, read where it lies (nothing below writes its hidden input: the resnet and FreeU only read it)
+      h = Act{o.deep_buf, B, H0, W0, c.e->dc_hidden_channels()};
     }
-    for (int i = 0; i < n; ++i) {
+    for (int i = shallow ? n - 1 : 0; i < n; ++i) {
       const int co = cfg.block_out_channels[n - 1 - i];
       const std::string bk = "up_blocks." + std::to_string(i);
       // main pass of a two-stream forward: from up block `late_from` on the encoder pass (41 % of the work, ahead by design
       // and on the higher-priority stream) has normally drained -- launches must fill the chip by themselves again
       if (!o.capture && i >= o.late_from) c.e->dual_late = true;
-      for (int j = 0; j <= Lb; ++j) {
+      for (int j = (shallow ? j0 : 0); j <= Lb; ++j) {
         Act skip = skips.back(); skips.pop_back();
         if (skip.H != h.H || skip.W != h.W) { mvd_set_error("up block %d: skip %dx%d vs hidden %dx%d (odd latent size unsupported)", i, skip.H, skip.W, h.H, h.W); return -13; }
+        if (refresh && i == n - 1 && j == j0 && !c.dry && !c.err)
+          CHECK((int)hipMemcpyAsync(o.deep_buf, h.p, (size_t)h.rows() * h.C * sizeof(bf16_t), hipMemcpyDeviceToDevice, c.s));
         Act r = c.new_act(B, h.H, h.W, co, true);
+        resnet_idx = up_resnet_pos(i, j);
         if (o.freeu && i < 2) {
           // FreeU: the resnet (GroupNorm and the folded 1x1 shortcut alike) reads the re-weighted pair; h and skip stay as they were
           const size_t fm = c.e->tmp.off;
@@ -758,6 +799,7 @@ struct UNetPass {
         h = r;
         if (i > 0) {
           Act t = c.new_act(B, h.H, h.W, co, true);
+          feat_idx = up_feat_pos(i, j);
           CHECK(transformer(bk + ".attentions." + std::to_string(j), h, cfg.num_heads[n - 1 - i], t));
           h = t;
         }
@@ -977,6 +1019,32 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   const bool ref_only = a.flags & MVD_REF_ONLY_INTERNAL;
   const bool use_cam = (a.flags & MVD_USE_CAMERA) && !ref_only, use_img = a.flags & MVD_USE_IMAGE, reuse = a.flags & MVD_REUSE_REF;
   if (ref_only && (!use_img || reuse)) { mvd_set_error("reference_encode: needs MVD_USE_IMAGE without MVD_REUSE_REF"); return -1; }
+  // ---- DeepCache (include/mvd_hip.h): every rejection comes here, in the dry run that precedes any launch
+  const int deep = a.flags & (MVD_DEEPCACHE_REFRESH | MVD_DEEPCACHE_SHALLOW);
+  const bool shallow = deep == MVD_DEEPCACHE_SHALLOW;
+  if (deep) {
+    if (deep == (MVD_DEEPCACHE_REFRESH | MVD_DEEPCACHE_SHALLOW)) { mvd_set_error("forward: MVD_DEEPCACHE_REFRESH and MVD_DEEPCACHE_SHALLOW are one or the other, got both"); return -1; }
+    if (!e->dc_on) { mvd_set_error("forward: %s without mvd_engine_set_deepcache", shallow ? "MVD_DEEPCACHE_SHALLOW" : "MVD_DEEPCACHE_REFRESH"); return -1; }
+    if (e->dc_branch < 0 || e->dc_branch >= cfg.layers_per_block) { mvd_set_error("forward: DeepCache branch %d outside [0, %d)", e->dc_branch, cfg.layers_per_block); return -1; }
+    if (shallow && use_img && !reuse) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW with MVD_USE_IMAGE needs MVD_REUSE_REF (a shallow forward never runs the encoder pass)"); return -1; }
+    if (shallow && !e->dc_sizing) {
+      const mvd_engine::DeepRecord& r = e->dc_rec;
+      if (!r.valid) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW without a stored deep feature (run a MVD_DEEPCACHE_REFRESH forward first)"); return -1; }
+      if (r.batch != a.batch) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of batch %d, this forward of batch %d", r.batch, a.batch); return -1; }
+      if (r.h != a.height || r.w != a.width) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of latent size %dx%d, this forward of %dx%d", r.h, r.w, a.height, a.width); return -1; }
+      if (r.layout != lay.key()) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of another batch layout (views / objects / view counts)"); return -1; }
+      if (r.cam != (use_cam ? 1 : 0) || r.img != (use_img ? 1 : 0)) {
+        mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of a forward with camera conditioning %s and image conditioning %s, this one has them %s and %s",
+                      r.cam ? "on" : "off", r.img ? "on" : "off", use_cam ? "on" : "off", use_img ? "on" : "off"); return -1;
+      }
+      if (r.branch != e->dc_branch) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of branch %d, the engine is set to branch %d", r.branch, e->dc_branch); return -1; }
+      if (r.wgen != e->weight_gen) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: weights were registered or cleared since the deep feature was stored"); return -1; }
+    }
+    if (!e->dc_sizing) {
+      const int64_t need = (int64_t)a.batch * a.height * a.width * e->dc_hidden_channels() * (int64_t)sizeof(bf16_t);
+      if (!e->dc_ptr || e->dc_bytes < need) { mvd_set_error("forward: DeepCache buffer not bound or too small (%lld bytes bound, %lld needed; mvd_engine_bind_deepcache)", (long long)e->dc_bytes, (long long)need); return -1; }
+    }
+  }
   if (!dry) {
     if (!ref_only && (!a.sample || !a.timesteps || !a.text || !a.out)) { mvd_set_error("forward: null sample/timesteps/text/out"); return -1; }
     if (use_cam && (!a.source_camera || !a.target_camera || !a.fourier_proj || (a.cam_rows != 3 && a.cam_rows != 4))) { mvd_set_error("forward: camera inputs missing"); return -1; }
@@ -1134,6 +1202,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   po.layout = &lay;
   po.freeu = e->freeu_on;
+  po.deep = deep; po.deep_branch = e->dc_branch; po.deep_buf = (bf16_t*)e->dc_ptr;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
@@ -1224,12 +1293,14 @@ int mvd_engine_set_weight(mvd_engine_t* e, int set, const char* slot, const void
   if (!e || set < 0 || set > 1 || !slot || !ptr || numel <= 0 || dtype < 0 || dtype > 1) { mvd_set_error("set_weight: bad argument"); return -1; }
   if ((uintptr_t)ptr & 15) { mvd_set_error("set_weight: '%s' must be 16-byte aligned", slot); return -1; }
   e->w[set].m[slot] = Weight{ptr, numel, dtype};
+  ++e->weight_gen;
   return 0;
 }
 int mvd_engine_clear_weights(mvd_engine_t* e, int set) {
   if (e) e->drop_graphs();
   if (!e || set < 0 || set > 1) { mvd_set_error("clear_weights: bad argument"); return -1; }
   e->w[set].m.clear();
+  ++e->weight_gen;
   return 0;
 }
 
@@ -1262,10 +1333,33 @@ static int64_t workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* a
   // (a sizing call must not depend on the cache state: size the forward that runs the encoder pass, the larger of the two)
   mvd_forward_args_t a = *args;
   a.flags &= ~MVD_REUSE_REF;
+  auto total = [&]() { return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096); };
+  if (a.flags & MVD_DEEPCACHE_SHALLOW) {
+    // a shallow forward is sized as what it is -- no encoder pass (MVD_REUSE_REF stays, the cache state is not consulted: dc_sizing
+    // and a cache record that matches by construction) -- and must never need more than the full forward of the same arguments
+    mvd_forward_args_t f = a;
+    f.flags &= ~(MVD_DEEPCACHE_SHALLOW | MVD_DEEPCACHE_REFRESH);
+    int r = forward_impl(e, f, nullptr, true, lay);
+    const int64_t full = total();
+    if (!r) {
+      if (a.flags & MVD_USE_IMAGE) a.flags |= MVD_REUSE_REF;   // (the dry run above left a matching record: rc_batch, rc_h, rc_w, rc_layout)
+      const bool was_valid = e->rc_valid;
+      e->rc_valid = true; e->dc_sizing = true;
+      r = forward_impl(e, a, nullptr, true, lay);
+      e->dc_sizing = false; e->rc_valid = was_valid;
+    }
+    const int64_t sh = total();
+    e->set_host_state(before);
+    if (r) return r;
+    if (sh > full) { mvd_set_error("workspace_bytes: a shallow forward needs %lld bytes, more than the full forward's %lld", (long long)sh, (long long)full); return -1; }
+    return sh;
+  }
+  e->dc_sizing = true;          // (a refresh forward is sized without a bound buffer)
   int r = forward_impl(e, a, nullptr, true, lay);
+  e->dc_sizing = false;
   e->set_host_state(before);
   if (r) return r;
-  return (int64_t)(((e->act.high + 255) & ~size_t(255)) + e->tmp.high + 4096);
+  return total();
 }
 int64_t mvd_engine_workspace_bytes_args(mvd_engine_t* e, const mvd_forward_args_t* args) { return workspace_bytes_args(e, args, uniform_layout(args, 0)); }
 int64_t mvd_engine_workspace_bytes_objects(mvd_engine_t* e, const mvd_forward_args_t* args, int objects) {
@@ -1302,6 +1396,7 @@ int64_t mvd_engine_reference_pixels(mvd_engine_t* e, int height, int width) {
 int mvd_engine_reference_encode(mvd_engine_t* e, const mvd_forward_args_t* args, float* local_stats, void* stream) {
   if (!e || !args || !local_stats) { mvd_set_error("reference_encode: null argument"); return -1; }
   if ((args->flags & MVD_SHARE_REF) || args->views > 1) { mvd_set_error("reference_encode: MVD_SHARE_REF does not go with the global-statistics path (one object, one rank)"); return -1; }
+  if (args->flags & (MVD_DEEPCACHE_REFRESH | MVD_DEEPCACHE_SHALLOW)) { mvd_set_error("reference_encode: the DeepCache bits do not go with the encoder pass alone"); return -1; }
   e->drop_graphs();
   mvd_forward_args_t a = *args;
   a.flags = (a.flags & ~MVD_REUSE_REF) | MVD_USE_IMAGE | MVD_KEEP_FEATURES | MVD_REF_ONLY_INTERNAL;
@@ -1388,7 +1483,7 @@ static int kv_slot_tables(mvd_engine_t* e, ViewLayout* host, hipStream_t st) {
 
 // The three forward entries.  `host`: the layout as its entry built it -- a ragged one with HOST tables, which size the call; the
 // launches read the device tables of its slot, which is touched only once the call has passed every check and fits its workspace.
-static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const ViewLayout& host, void* stream) {
+static int unet_forward_issue(mvd_engine_t* e, const mvd_forward_args_t* args, const ViewLayout& host, void* stream) {
   if (!e || !args) { mvd_set_error("forward: null argument"); return -1; }
   if (args->flags & MVD_REF_ONLY_INTERNAL) { mvd_set_error("forward: unknown flag bits 0x%x", args->flags); return -1; }
   // size the two arenas for this shape with a dry run (pure host arithmetic), then run for real
@@ -1401,6 +1496,8 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const V
   hipStream_t st = (hipStream_t)stream;
   ViewLayout lay = host;
   if (host.counts && (r = kv_slot_tables(e, &lay, st))) return r;
+  // (a refresh forward that has passed every check overwrites the stored deep feature: unet_forward writes its record afterwards)
+  if (args->flags & MVD_DEEPCACHE_REFRESH) e->dc_rec.valid = false;
   e->act.base = (char*)e->ws_ptr; e->act.cap = act_bytes;
   e->tmp.base = (char*)e->ws_ptr + act_bytes; e->tmp.cap = (size_t)e->ws_bytes - act_bytes;
   if (!e->graph_on || e->prof || !st) return forward_impl(e, *args, st, false, lay);
@@ -1446,6 +1543,19 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const V
   he = hipGraphLaunch(x, st);
   if (he != hipSuccess) { mvd_set_error("forward: hipGraphLaunch: %s", hipGetErrorString(he)); return -7; }
   return 0;
+}
+
+// The record of the stored deep feature follows the forward that wrote it, however that forward was issued (launched, captured,
+// replayed): it is host state of the engine beside the graphs' HostState (see mvd_engine::dc_rec)
+static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const ViewLayout& host, void* stream) {
+  const int r = unet_forward_issue(e, args, host, stream);
+  if (!r && (args->flags & MVD_DEEPCACHE_REFRESH)) {
+    mvd_engine::DeepRecord& d = e->dc_rec;
+    d.batch = args->batch; d.h = args->height; d.w = args->width; d.layout = host.key();
+    d.cam = (args->flags & MVD_USE_CAMERA) ? 1 : 0; d.img = (args->flags & MVD_USE_IMAGE) ? 1 : 0;
+    d.branch = e->dc_branch; d.wgen = e->weight_gen; d.valid = true;
+  }
+  return r;
 }
 
 int mvd_unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, void* stream) { return unet_forward(e, args, uniform_layout(args, 0), stream); }
@@ -1563,6 +1673,35 @@ int mvd_engine_clear_freeu(mvd_engine_t* e) {
   if (!e) { mvd_set_error("clear_freeu: null engine"); return -1; }
   e->drop_graphs();
   e->freeu_on = false;
+  return 0;
+}
+
+// DeepCache (include/mvd_hip.h).  Setting, clearing and binding drop the captured graphs (their nodes hold the branch's schedule and
+// the buffer's address) and invalidate the stored feature
+int mvd_engine_set_deepcache(mvd_engine_t* e, int branch) {
+  if (!e) { mvd_set_error("set_deepcache: null engine"); return -1; }
+  if (branch < 0 || branch >= e->cfg.layers_per_block) { mvd_set_error("set_deepcache: branch %d outside [0, %d) (layers_per_block)", branch, e->cfg.layers_per_block); return -1; }
+  e->drop_graphs();
+  e->dc_on = true; e->dc_branch = branch; e->dc_rec.valid = false;
+  return 0;
+}
+int mvd_engine_clear_deepcache(mvd_engine_t* e) {
+  if (!e) { mvd_set_error("clear_deepcache: null engine"); return -1; }
+  e->drop_graphs();
+  e->dc_on = false; e->dc_branch = 0; e->dc_rec.valid = false;
+  return 0;
+}
+int64_t mvd_engine_deepcache_bytes(mvd_engine_t* e, int batch, int height, int width) {
+  if (!e || batch <= 0 || height <= 0 || width <= 0) { mvd_set_error("deepcache_bytes: bad argument"); return -1; }
+  // (any branch: the wider of the two channel counts a deep feature can have)
+  const int c = e->cfg.block_out_channels[0] > e->cfg.block_out_channels[1] ? e->cfg.block_out_channels[0] : e->cfg.block_out_channels[1];
+  return (((int64_t)batch * height * width * c * (int64_t)sizeof(bf16_t)) + 255) & ~(int64_t)255;
+}
+int mvd_engine_bind_deepcache(mvd_engine_t* e, void* ptr, int64_t bytes) {
+  if (e) { e->drop_graphs(); e->dc_rec.valid = false; }
+  if (!e || (ptr && bytes <= 0)) { mvd_set_error("bind_deepcache: bad argument"); return -1; }
+  if ((uintptr_t)ptr & 255) { mvd_set_error("bind_deepcache: the buffer must be 256-byte aligned"); return -1; }
+  e->dc_ptr = ptr; e->dc_bytes = ptr ? bytes : 0;
   return 0;
 }
 

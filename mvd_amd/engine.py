@@ -55,6 +55,8 @@ class MVDEngine:
         self._ws_resize = False
         self._ws_args = None
         self.freeu = None                                         # (s1, s2, b1, b2) while FreeU is set
+        self.deepcache = None                                     # the branch while DeepCache is set
+        self._dc = None                                           # the bound buffer of the stored deep feature
 
     def __del__(self):
         try:
@@ -164,7 +166,7 @@ class MVDEngine:
                 fourier_proj: Optional[torch.Tensor] = None, source_latents: Optional[torch.Tensor] = None,
                 encoder_text: Optional[torch.Tensor] = None, reuse_ref: bool = False,
                 keep_features: bool = False, out: Optional[torch.Tensor] = None, *, views: Optional[int] = None,
-                objects: Optional[int] = None) -> torch.Tensor:
+                objects: Optional[int] = None, deep_cache: Optional[str] = None) -> torch.Tensor:
         """All tensors fp32 contiguous on ``self.device``; returns fp32 NCHW.  ``views`` (an int >= 1): the shared-reference
         forward (``MVD_SHARE_REF``, include/mvd_hip.h) -- ``sample`` holds g * views rows ``[uncond x views | cond x views]``,
         ``text`` g rows, ``source_latents`` / ``encoder_text`` one row, the cameras 1 or ``views`` rows.  ``objects`` (O > 1, with
@@ -172,7 +174,13 @@ class MVDEngine:
         inside a guidance half, ``text`` g * O rows, ``source_latents`` / ``encoder_text`` O rows, the cameras 1 or O * views rows;
         ``None`` / 1: the forward without it.  ``views`` a SEQUENCE ``(V_0, .., V_{O-1})`` (``mvd_unet_forward_ragged``): O objects
         with V_o >= 1 views each, R = sum of the counts -- ``sample`` holds g * R rows, object-major inside a guidance half, the
-        cameras 1 or R rows, everything else as with ``objects = O`` (which ``objects`` must be, or ``None``)."""
+        cameras 1 or R rows, everything else as with ``objects = O`` (which ``objects`` must be, or ``None``).
+
+        ``deep_cache`` (DeepCache, after ``set_deepcache``): ``"refresh"`` -- this forward, which also stores its deep feature
+        (``MVD_DEEPCACHE_REFRESH``); ``"reuse"`` -- the shallow forward around the stored feature (``MVD_DEEPCACHE_SHALLOW``; with
+        image conditioning it needs ``reuse_ref``); ``None``: neither."""
+        if deep_cache not in (None, "refresh", "reuse"):
+            raise L.MvdError(f"engine.forward: deep_cache={deep_cache!r}: expected None, 'refresh' or 'reuse'")
         B, Cin, H, W = sample.shape
         Lt = text.shape[1]
         for t in (sample, timesteps, text, source_camera, target_camera, fourier_proj, source_latents, encoder_text):
@@ -202,6 +210,9 @@ class MVDEngine:
             raise L.MvdError(f"engine.forward: {objects} objects x {views} views need a multiple of {objects * views} sample rows and "
                              f"{objects} reference rows, got {B} and {ref_batch}")
         self._ensure_workspace(B, H, W, Lt, ref_batch, keep_features, lay)
+        if deep_cache == "refresh":
+            # (a shallow forward reads the buffer its refresh forward bound: growing it here would throw the stored feature away)
+            self._ensure_deepcache(B, H, W)
         graph = getattr(self, "_graph", False)
         user_out = out
         if graph:
@@ -245,6 +256,8 @@ class MVDEngine:
         if lay.rows:
             flags |= L.MVD_SHARE_REF
             a.views = views                 # (0 with counts: they travel beside the argument block, like the object count)
+        if deep_cache is not None:
+            flags |= L.MVD_DEEPCACHE_REFRESH if deep_cache == "refresh" else L.MVD_DEEPCACHE_SHALLOW
         a.ref_batch, a.flags = ref_batch, flags
         a.out = out.data_ptr()
         suffix, beside = self._entry(lay)
@@ -326,6 +339,29 @@ class MVDEngine:
         if self._ws_key is not None and self._ws_args is not None:
             # now, not in the next forward: whoever asks reference_cache_valid first gets the answer that holds
             self._ensure_workspace(*self._ws_args)
+
+    def set_deepcache(self, branch: int = 0) -> None:
+        """DeepCache on the main UNet pass (``mvd_engine_set_deepcache``): ``forward(..., deep_cache="refresh")`` stores the hidden
+        input of ``up_blocks.{n-1}.resnets.{Lb-1-branch}``, ``deep_cache="reuse"`` runs only ``down_blocks.0`` layers ``0..branch``
+        and the last ``branch + 2`` layers of the last up block around it.  Setting invalidates a stored feature."""
+        L.call("mvd_engine_set_deepcache", self._h, int(branch))
+        self.deepcache = int(branch)
+
+    def clear_deepcache(self) -> None:
+        """Back to the engine without DeepCache (``mvd_engine_clear_deepcache``); the buffer is released."""
+        L.call("mvd_engine_clear_deepcache", self._h)
+        L.call("mvd_engine_bind_deepcache", self._h, None, 0)
+        self.deepcache, self._dc = None, None
+
+    def _ensure_deepcache(self, batch, h, w):
+        # (a buffer that is large enough stays bound: binding invalidates the stored feature)
+        need = L.lib().mvd_engine_deepcache_bytes(self._h, batch, h, w)
+        if need < 0:
+            raise L.MvdError(f"deepcache_bytes: {L.last_error()}")
+        if self._dc is None or self._dc.numel() < need:
+            self._dc = None
+            self._dc = torch.empty(need, dtype=torch.uint8, device=self.device)
+            L.call("mvd_engine_bind_deepcache", self._h, _ptr(self._dc), self._dc.numel())
 
     def clear_freeu(self) -> None:
         """Back to the forward without FreeU (``mvd_engine_clear_freeu``): the launches it made before."""

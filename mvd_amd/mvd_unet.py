@@ -198,6 +198,11 @@ class MultiViewUNet(nn.Module):
         self._dirty = True
         self._ref_key = None
         self._ref_hold = None              # strong references to the tensors _ref_key was computed from
+        # DeepCache (enable_deepcache): (cache_interval, cache_branch_id) while enabled; the key of the refresh forward whose deep
+        # feature the engine holds (False: none), and strong references to the tensors that key names
+        self.deepcache = None
+        self._deep_key = False
+        self._deep_hold = None
         # Q2 statistics across data-parallel shards: None = replica-local (what the reference's DDP replicas
         # compute); True = the default process group, or a torch.distributed group = statistics over ALL ranks' batches
         # (one 323 KB all-gather per reference pass), which makes the sharded result equal the unsharded one
@@ -285,6 +290,13 @@ class MultiViewUNet(nn.Module):
                 self._engine.clear_freeu()
             else:
                 self._engine.set_freeu(*self.freeu)
+        branch = None if self.deepcache is None else self.deepcache[1]
+        if branch != getattr(self._engine, "deepcache", None):
+            self._deep_key, self._deep_hold = False, None
+            if branch is None:
+                self._engine.clear_deepcache()
+            else:
+                self._engine.set_deepcache(branch)
         return self._engine
 
     # ------------------------------------------------------------------ FreeU (diffusers' names and argument order)
@@ -304,10 +316,26 @@ class MultiViewUNet(nn.Module):
     def disable_freeu(self):
         self.base_unet.disable_freeu()
 
+    # ------------------------------------------------------------------ DeepCache (DeepCacheSDHelper's parameter names)
+    def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):
+        """DeepCache (Ma et al. 2024; ``DeepCacheSDHelper.set_params(cache_interval=, cache_branch_id=)``): ``MVDDenoiser`` runs the
+        whole UNet at every ``cache_interval``-th step (``forward(..., deep_cache="refresh")``, which also stores the hidden state
+        entering the last ``cache_branch_id + 2`` layers of the last up block) and, at the steps in between, only the first
+        ``cache_branch_id + 1`` layers of ``down_blocks.0`` and those last layers around the stored state
+        (``deep_cache="reuse"``).  ``cache_interval=1`` runs every step in full.  A forward without the
+        keyword is what it was."""
+        self.deepcache = check_deepcache(cache_interval, cache_branch_id, self.unet_config.layers_per_block)
+
+    def disable_deepcache(self):
+        self.deepcache = None
+
     def reset_reference_cache(self):
-        """Forget the cached reference K/V (Q5): the next forward with image conditioning re-runs the encoder pass."""
+        """Forget the cached reference K/V (Q5): the next forward with image conditioning re-runs the encoder pass.  The stored
+        DeepCache feature goes with it: nothing of one call serves another."""
         self._ref_key = None
         self._ref_hold = None
+        self._deep_key = False
+        self._deep_hold = None
 
     @staticmethod
     def _f32(t: torch.Tensor, dev) -> torch.Tensor:
@@ -330,7 +358,7 @@ class MultiViewUNet(nn.Module):
                 source_image_latents: Optional[torch.FloatTensor] = None, return_dict: bool = True,
                 timestep_cond: Optional[torch.FloatTensor] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                 added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None, *, views: Optional[int] = None,
-                objects: Optional[int] = None):
+                objects: Optional[int] = None, deep_cache: Optional[str] = None):
         """``views`` (keyword-only, not a reference parameter): V > 1 views of ONE object in one forward.
         ``sample`` holds g * V rows in the pipeline's order ``[uncond x V | cond x V]`` (g = 1, or 2 under guidance),
         ``encoder_hidden_states`` g rows, ``source_image_latents`` one row, the cameras 1 or V rows.  Row j * V + v is row j
@@ -346,7 +374,17 @@ class MultiViewUNet(nn.Module):
         ``views`` a SEQUENCE ``(V_0, .., V_{O-1})``: O objects with V_o >= 1 views each, R = sum V_o, in one
         forward, which IS the R independent batch-g calls.  ``sample`` holds g * R rows ``[uncond x R | cond x R]``, object-major
         inside a half, the cameras 1 or R rows; ``encoder_hidden_states`` g * O rows and ``source_image_latents`` O rows as with
-        ``objects = O``, which ``objects`` must be, or ``None``."""
+        ``objects = O``, which ``objects`` must be, or ``None``.
+
+        ``deep_cache`` (keyword-only; after ``enable_deepcache``): ``"refresh"`` -- this forward, bit for bit,
+        which also stores its deep feature in the engine; ``"reuse"`` -- the shallow forward around the feature the preceding
+        ``"refresh"`` call stored.  With image conditioning ``source_image_latents`` and ``encoder_hidden_states`` must be that
+        call's tensors (``cache_reference``'s test); the reference K/V it left are reused, the encoder pass does not run.
+        ``None``: the forward without it."""
+        if deep_cache not in (None, "refresh", "reuse"):
+            raise L.MvdError(f"deep_cache={deep_cache!r}: expected None, 'refresh' or 'reuse'")
+        if deep_cache is not None and self.deepcache is None:
+            raise L.MvdError(f"deep_cache={deep_cache!r} needs enable_deepcache() first")
         lay = ViewLayout.parse(views, objects)
         V, O, counts = lay
         if cross_attention_kwargs:
@@ -394,13 +432,26 @@ class MultiViewUNet(nn.Module):
             key = (source_image_latents.data_ptr(), source_image_latents._version, tuple(source_image_latents.shape),
                    encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape), B) + tuple(lay)
             glob = self.reference_stats_group is not None
-            hit = (self.cache_reference and self._ref_key == key
+            deep_key = key
+            if deep_cache == "reuse":
+                # the shallow forward never runs the encoder pass: the K/V the refresh call left are what a recomputation from the
+                # same tensors would give -- and from nothing else
+                if self._deep_key != key:
+                    raise L.MvdError('deep_cache="reuse": source_image_latents / encoder_hidden_states (or the batch layout) are not '
+                                     'those of the preceding deep_cache="refresh" forward' if self._deep_key is not False else
+                                     'deep_cache="reuse" without a preceding deep_cache="refresh" forward')
+                if self._ref_key != key:
+                    raise L.MvdError('deep_cache="reuse": the reference cache was reset since the deep_cache="refresh" forward')
+            hit = ((self.cache_reference or deep_cache == "reuse") and self._ref_key == key
                    and eng.reference_cache_valid(B, x.shape[2], x.shape[3], text.shape[1], bs, **lay.kwargs()))
             if glob and self.cache_reference:
                 # the recompute path below contains a collective: the decision must be the same on every rank of the group
                 # (a re-bound workspace or a fresh tensor on ONE rank would otherwise leave the others out of the all-gather)
                 from .distributed import any_rank
                 hit = not any_rank(not hit, None if self.reference_stats_group is True else self.reference_stats_group, dev)
+            if deep_cache == "reuse" and not hit:
+                raise L.MvdError('deep_cache="reuse": the engine holds no valid reference K/V for this forward (its buffers were re-bound '
+                                 'since the deep_cache="refresh" forward)')
             if hit:
                 img = dict(reuse_ref=True, keep_features=glob)
             else:
@@ -414,7 +465,16 @@ class MultiViewUNet(nn.Module):
                     local = eng.reference_encode(img["source_latents"], img["encoder_text"], B)
                     eng.reference_finish(merge_reference_stats(local, group))
                     img = dict(reuse_ref=True, keep_features=True)
-        out = eng.forward(x, t, text, **cam, **img, **lay.kwargs())
+        elif deep_cache == "reuse" and self._deep_key is not None:
+            raise L.MvdError('deep_cache="reuse" without a preceding deep_cache="refresh" forward' if self._deep_key is False else
+                             'deep_cache="reuse": the preceding deep_cache="refresh" forward had image conditioning, this one has none')
+        if deep_cache == "refresh":
+            self._deep_key, self._deep_hold = False, None
+        out = eng.forward(x, t, text, **cam, **img, **lay.kwargs(), **({"deep_cache": deep_cache} if deep_cache is not None else {}))
+        if deep_cache == "refresh":
+            # (held like _ref_hold: the allocator must not hand these addresses to other data while the key is live)
+            self._deep_key = deep_key if img else None
+            self._deep_hold = (source_image_latents, encoder_hidden_states) if img else None
         if cam:
             self.current_camera_embedding = eng.camera_embedding(cam["target_camera"].shape[0])
         hidden_states = out.to(out_dtype)
@@ -432,6 +492,22 @@ class MultiViewUNet(nn.Module):
 
     def _manage_modulation_hooks(self, register: bool):
         pass
+
+
+def check_deepcache(cache_interval, cache_branch_id, layers_per_block: int):
+    """``(cache_interval, cache_branch_id)`` as two ints, or ValueError: the interval >= 1, the branch in [0, layers_per_block)."""
+    try:
+        ok = float(cache_interval) == int(cache_interval) and float(cache_branch_id) == int(cache_branch_id)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or isinstance(cache_interval, bool) or isinstance(cache_branch_id, bool):
+        raise ValueError(f"DeepCache: cache_interval and cache_branch_id must be integers, got {cache_interval!r}, {cache_branch_id!r}")
+    interval, branch = int(cache_interval), int(cache_branch_id)
+    if interval < 1:
+        raise ValueError(f"DeepCache: cache_interval must be >= 1, got {interval}")
+    if not 0 <= branch < layers_per_block:
+        raise ValueError(f"DeepCache: cache_branch_id must lie in [0, {layers_per_block}) (layers_per_block), got {branch}")
+    return interval, branch
 
 
 def create_mvd_pipeline(pretrained_model_name_or_path: str, dtype: torch.dtype = torch.float16,

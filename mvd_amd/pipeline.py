@@ -65,7 +65,12 @@ class MVDDenoiser:
         (MVDPipeline.generate_views_batch): O prompts and O source rows, ``latents`` and the cameras O * views rows, object-major;
         every step is one object forward (``MultiViewUNet.forward(..., views=, objects=)``).  ``views`` a sequence
         ``(V_0, .., V_{O-1})``: ragged view counts -- O prompts and O source rows, ``latents`` and the cameras sum(V_o) rows,
-        object-major; every step is one ragged forward (``MultiViewUNet.forward(..., views=(V_0, ..))``)."""
+        object-major; every step is one ragged forward (``MultiViewUNet.forward(..., views=(V_0, ..))``).
+
+        DeepCache (``unet.enable_deepcache(cache_interval, cache_branch_id)``): step i (0-based) is a refresh
+        step iff ``i % cache_interval == 0`` -- the whole UNet, which also stores its deep feature -- and a shallow step otherwise;
+        under guidance the ``[uncond | cond]`` rows are one forward and share one stored feature.  Disabled, or
+        ``cache_interval=1``: the loop issues the launches it always did."""
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale={guidance_rescale!r} must lie in [0, 1]")
         rescale = float(guidance_rescale) if guidance_scale > 1.0 else 0.0      # without guidance it is ignored, as in diffusers
@@ -119,12 +124,14 @@ class MVDDenoiser:
                 if apg_step is None and apg.space != "output":
                     raise L.MvdError('apg: space="x0" needs a scheduler with step_guided(..., apg=) or step_guided_apg '
                                      f"({type(self.scheduler).__name__} has neither)")
+        deep = deepcache_schedule(getattr(self.unet, "deepcache", None), len(self.scheduler.timesteps))
         ts_host = self.scheduler.timesteps.tolist()                             # host ints for the scheduler's coefficients
         ts_dev = torch.tensor(ts_host, dtype=torch.float32, device=dev)         # ONE upload: a per-step scalar upload would make
         for i, t in enumerate(ts_host):                                         # the host wait for the previous step's kernels
             x_in = torch.cat([latents] * 2) if guidance_scale > 1.0 else latents  # pipeline.py:141
             out = self.unet(sample=x_in, timestep=ts_dev[i], encoder_hidden_states=embeds,
-                            cross_attention_kwargs=cross_attention_kwargs, **extra).sample.float().contiguous()
+                            cross_attention_kwargs=cross_attention_kwargs, **extra,
+                            **({"deep_cache": deep[i]} if deep is not None else {})).sample.float().contiguous()
             nz = None if noise_per_step is None else noise_per_step[i]
             if guidance_scale > 1.0 and guided_step is not None:
                 # DDIM / DPM-Solver++: the guidance combine (pipeline.py:156-158) and the step in ONE fused launch; with guidance
@@ -149,6 +156,15 @@ class MVDDenoiser:
             if callback is not None and i % callback_steps == 0:                # pipeline.py:165-166
                 callback(i, t, latents)
         return latents
+
+
+def deepcache_schedule(setting, steps: int):
+    """The ``deep_cache`` keyword of every step of a loop of ``steps`` steps under ``setting`` = ``(cache_interval, cache_branch_id)``:
+    ``"refresh"`` where ``i % cache_interval == 0``, else ``"reuse"``.  ``None`` -- no keyword at all, the loop as it always was --
+    without a setting or with ``cache_interval == 1``."""
+    if setting is None or int(setting[0]) == 1:
+        return None
+    return ["refresh" if i % int(setting[0]) == 0 else "reuse" for i in range(steps)]
 
 
 logger = logging.getLogger(__name__)
@@ -190,6 +206,15 @@ class MVDPipeline:
 
     def disable_freeu(self):
         self.unet.disable_freeu()
+
+    def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):
+        """DeepCache (``DeepCacheSDHelper``'s parameters) for every call that follows -- ``__call__``, ``generate_views`` and
+        ``generate_views_batch`` alike: every ``cache_interval``-th step runs the whole UNet, the steps in between only its
+        outermost layers around the deep feature that step stored (``MultiViewUNet.enable_deepcache``)."""
+        self.unet.enable_deepcache(cache_interval, cache_branch_id)
+
+    def disable_deepcache(self):
+        self.unet.disable_deepcache()
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
         """StableDiffusionPipeline.prepare_latents: N(0,1) of the latent shape times ``init_noise_sigma``."""

@@ -15,7 +15,7 @@ Configuration keys read (the reference ships no ``config/infer_config.yaml``; th
 architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics``, ``metric_weights`` (a
 mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
 pipeline's argument of that name, ``--guidance-rescale``) and ``freeu`` (default absent: off; ``"s1,s2,b1,b2"`` or four numbers in
-diffusers' ``enable_freeu`` order, ``--freeu``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
+diffusers' ``enable_freeu`` order, ``--freeu``) and ``deepcache`` (default absent: off; ``"N"`` or ``"N,branch"``, ``--deepcache``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
 sequence or a mapping, ``--apg``: adaptive projected guidance, the pipeline's argument of that name).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
@@ -268,6 +268,10 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     freeu = parse_freeu(config.get("freeu"))
     if freeu is not None:
         pipeline.enable_freeu(*freeu)
+    # DeepCache: absent (the default), the pipeline is not touched
+    deepcache = parse_deepcache(config.get("deepcache"))
+    if deepcache is not None:
+        pipeline.enable_deepcache(*deepcache)
     # adaptive projected guidance: absent (the default), the pipeline calls carry no such argument; it rides with the rescale's
     apg = parse_apg(config.get("apg"))
     if apg is not None:
@@ -425,6 +429,29 @@ def parse_freeu(value):
     return check_freeu(*parts)
 
 
+def parse_deepcache(value):
+    """The ``deepcache`` config key / ``--deepcache`` flag: ``"N"`` or ``"N,branch"``, an int, or a sequence of one or two ints ->
+    ``(cache_interval, cache_branch_id)`` (the branch defaults to 0); ``None`` / empty -> ``None`` (off).  ValueError for anything
+    else; the branch's upper limit (the UNet's layers_per_block) is checked by ``enable_deepcache``."""
+    if value is None or value == "" or value is False:
+        return None
+    if isinstance(value, bool):
+        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}")
+    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
+    if len(parts) not in (1, 2):
+        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}")
+    try:
+        nums = [float(p) for p in parts]
+    except (TypeError, ValueError):
+        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}") from None
+    if any(n != int(n) for n in nums):
+        raise ValueError(f"deepcache: the interval and the branch are integers, got {value!r}")
+    interval, branch = int(nums[0]), int(nums[1]) if len(nums) == 2 else 0
+    if interval < 1 or branch < 0:
+        raise ValueError(f"deepcache: the interval must be >= 1 and the branch >= 0, got {value!r}")
+    return interval, branch
+
+
 def parse_apg(value):
     """The ``apg`` config key / ``--apg`` flag: ``"eta,norm_threshold,momentum[,space]"``, a sequence in that order or a mapping of
     those names -> ``mvd_amd.scheduler.APG``; ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
@@ -453,6 +480,10 @@ def main(argv=None) -> int:
     ap.add_argument("--freeu", type=str, default=None, metavar="s1,s2,b1,b2",
                     help="FreeU on the UNet's main pass, diffusers' enable_freeu order (SD-2.1: 0.9,0.2,1.4,1.6; default: the config's "
                          "freeu, else off)")
+    ap.add_argument("--deepcache", type=str, default=None, metavar="N[,branch]",
+                    help="DeepCache (Ma et al. 2024): the whole UNet at every N-th step, the outermost layers around its stored deep "
+                         "feature in between; branch = DeepCache's cache_branch_id, default 0 (e.g. 3 or 3,0; default: the config's "
+                         "deepcache, else off)")
     ap.add_argument("--apg", type=str, default=None, metavar="eta,norm_threshold,momentum[,space]",
                     help="adaptive projected guidance (Sadat et al. 2025): eta in [0, 1], norm_threshold >= 0 (0: off), momentum in "
                          "(-1, 1), space output|x0 (e.g. 0,15,-0.5; default: the config's apg, else off)")
@@ -467,6 +498,11 @@ def main(argv=None) -> int:
             parse_freeu(args.freeu)
         except ValueError as e:
             ap.error(str(e))
+    if args.deepcache is not None:
+        try:
+            parse_deepcache(args.deepcache)
+        except ValueError as e:
+            ap.error(str(e))
     try:
         config = load_config(args.config)
     except Exception as e:  # noqa: BLE001
@@ -478,6 +514,8 @@ def main(argv=None) -> int:
         config["guidance_rescale"] = args.guidance_rescale
     if args.freeu is not None:
         config["freeu"] = args.freeu
+    if args.deepcache is not None:
+        config["deepcache"] = args.deepcache
     if args.apg is not None:
         config["apg"] = args.apg
     device =torch.device("cuda" if torch.cuda.is_available() else "cpu")
