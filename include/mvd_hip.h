@@ -448,6 +448,47 @@ int64_t mvd_debug_attention_pair_ws_bytes(const int* dims, const int* table0, co
                                           int nsplit);
 int mvd_debug_attention_pair(const void* const* ptrs, const int* dims, const int* table0, const int* table1, int batch, int heads,
                              float scale, int nsplit, void* ws, void* stream);
+/* The CLIP towers' and the VAE's own kernels one by one (text.hip, vision.hip, clip_layer.h, vae.hip), each a thin launch of the
+ * kernel the tower launches, on caller buffers; tests/test_clip_ops_gpu.py holds them to fp64 references and
+ * tests/test_clip_replay_gpu.py composes the towers from them bit for bit.  Every fp32 pointer is 16-byte aligned.
+ *
+ * Residual add + LayerNorm in one pass: x[rows][H] += delta[rows][H] in place (delta NULL: x is not written), then y = LN(x; gamma,
+ * beta, eps) with the two-pass variance, as bf16 (y_bf16) or fp32 (y_f32): exactly one of the two is given.  H % 4 == 0,
+ * 4 <= H <= 2048.  clip_layer.h is compiled into both towers' translation units: the two entries reach the two copies. */
+int mvd_op_text_add_ln(float* x, const float* delta, const float* gamma, const float* beta, int rows, int H, float eps, void* y_bf16,
+                       float* y_f32, void* stream);
+int mvd_op_vision_add_ln(float* x, const float* delta, const float* gamma, const float* beta, int rows, int H, float eps, void* y_bf16,
+                         float* y_f32, void* stream);
+/* The MLP's activation pass, fp32 x[n] -> bf16 y[n]: act 0 gelu (erf form), 1 quick_gelu = x * sigmoid(1.702 x).  n % 8 == 0. */
+int mvd_op_text_act(const float* x, int64_t n, int act, void* y_bf16, void* stream);
+int mvd_op_vision_act(const float* x, int64_t n, int act, void* y_bf16, void* stream);
+/* x[row] = tok[ids[row]] + pos[row % T], rows = batch * T; tok [vocab][H], pos [>= T][H] fp32.  An id outside [0, vocab) is clamped
+ * into it (below 0: row 0; vocab and above: row vocab - 1) for address safety only: range validation is the caller's.  H % 4 == 0. */
+int mvd_op_text_embed(const int32_t* ids, const float* tok, const float* pos, int rows, int T, int H, int vocab, float* x, void* stream);
+/* pixel_values [batch][3][image_size][image_size] fp32 -> bf16 patch rows [batch * (image_size / patch_size)^2][roundup(3 patch_size^2,
+ * 64)] in (c, py, px) order, pad columns zero: the rows mvd_vision_encode builds when it is handed pixel_values. */
+int mvd_op_vit_patchify(const float* pixel_values, int batch, int image_size, int patch_size, void* patches_bf16, void* stream);
+/* x[b][0] = cls + pos[0], x[b][1 + i] = patch_out[b][i] + pos[1 + i], then x = LN(x; gamma, beta, eps) (pre_layrnorm), fp32;
+ * patch_out [batch][tokens - 1][H], pos [tokens][H], x [batch][tokens][H].  H as for add_ln. */
+int mvd_op_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, int batch,
+                        int tokens, int H, float eps, float* x, void* stream);
+/* out[i] = x[i] + delta[i], fp32 (the image tower's last hidden state: the last fc2 result folded into the stream).  n % 4 == 0. */
+int mvd_op_vit_fold(const float* x, const float* delta, int64_t n, float* out, void* stream);
+/* x[r][:] /= ||x[r]||_2 in place, x [rows][dim] fp32, dim <= 2048: the second launch of mvd_op_clip_pool_project on its own. */
+int mvd_op_clip_l2norm(float* x, int rows, int dim, void* stream);
+/* quant_conv / post_quant_conv: y[b][o][p] = bias[o] + sum_c w[o][c] x[b][c][p] (fma in channel order), NCHW fp32, hw pixels per
+ * plane.  cin, cout <= 8: the kernel keeps a pixel's channels in eight registers, and more is refused before the launch. */
+int mvd_op_vae_pointwise(const float* x, int batch, int cin, int cout, int hw, const float* w, const float* bias, float* y, void* stream);
+/* Test hooks of the replay tests.  clip_linear: out[M][N] = a[M][K] . w[N][K]^T + bias through the towers' own routing (ClipCtx::linear:
+ * the small-M planner with its in-kernel split-K, else the tiled kernels with mvd_gemm_pick_splitk); a, w bf16, out bf16 or
+ * (out_f32) fp32; N, K multiples of 64.  ws: _ws_bytes(...) bytes of 256-byte aligned device memory, [split-K tile counters |
+ * partials]; the call zeroes the counters as the towers do at the head of an encode.  route_out (nullable, host): {small-M tile, or -1 for
+ * the tiled kernels; split-K factor}.  clip_attention: the image tower's
+ * attention launch over fused rows qkv [batch * tokens][3 * heads * 64] bf16 (q prescaled) -> out [batch * tokens][heads * 64]. */
+int64_t mvd_debug_clip_linear_ws_bytes(int M, int N, int K, int out_f32);
+int mvd_debug_clip_linear(const void* a, int K, int M, const void* w, const float* bias, int N, void* out, int out_f32, void* ws,
+                          int64_t ws_bytes, int* route_out, void* stream);
+int mvd_debug_clip_attention(const void* qkv_bf16, void* out_bf16, int batch, int heads, int tokens, void* stream);
 /* Measurement / bisection switches (bench.py --debug-flags, tools/, A/B tests): OR them into mvd_debug_set_flags.  Every switch
  * is read per launch or per forward unless it says otherwise, so 0 restores the product's behaviour.  The values are quoted
  * by DESIGN.md and profiles/ and never change; mvd_amd/_lib.py DebugFlag mirrors them (tests/test_cabi_cpu.py compares). */

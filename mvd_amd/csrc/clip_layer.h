@@ -68,8 +68,10 @@ __global__ __launch_bounds__(256) void text_add_ln_kernel(float* __restrict__ x,
 
 // ---------------------------------------------------------------- activation pass: fp32 pre-activations -> bf16
 // act 0: gelu (erf form), 1: quick_gelu = x * sigmoid(1.702 x).  8 elements per thread (2 x 16-byte loads, one 16-byte store).
+// gelu as 0.5 x erfc(-x / sqrt 2): the same function as 0.5 x (1 + erf(x / sqrt 2)) without its cancellation -- 1 + erf loses every
+// digit below x = -3 (10 % off at -5, flushed to 0 from -5.7 on, where the value is still a normal bf16 number).
 MVD_DEVINL float text_act(float x, int act) {
-  return act ? x / (1.0f + __expf(-1.702f * x)) : 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+  return act ? x / (1.0f + __expf(-1.702f * x)) : 0.5f * x * erfcf(x * -0.70710678118654752f);
 }
 __global__ __launch_bounds__(256) void text_act_kernel(const float* __restrict__ x, long n8, int act, bf16_t* __restrict__ y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -78,6 +80,36 @@ __global__ __launch_bounds__(256) void text_act_kernel(const float* __restrict__
   const u32x4 o = {pack2bf(text_act(a[0], act), text_act(a[1], act)), pack2bf(text_act(a[2], act), text_act(a[3], act)),
                    pack2bf(text_act(b[0], act), text_act(b[1], act)), pack2bf(text_act(b[2], act), text_act(b[3], act))};
   reinterpret_cast<u32x4*>(y)[i] = o;
+}
+
+// ---------------------------------------------------------------- the two launches, shared by the schedule and the operator entries
+int launch_add_ln(float* x, const float* delta, const float* g, const float* b, int rows, int H, float eps, bf16_t* y_bf, float* y_f32,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(text_add_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, delta, g, b, rows, H, eps, y_bf, y_f32);
+  return launch_check("add+layernorm");
+}
+int launch_act(const float* x, long n8, int act, bf16_t* y, hipStream_t s) {
+  hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, x, n8, act, y);
+  return launch_check("activation");
+}
+// the operator entries of a translation unit (mvd_op_text_* / mvd_op_vision_*): what the kernels cannot take is refused here
+int op_add_ln(const char* who, float* x, const float* delta, const float* g, const float* b, int rows, int H, float eps, void* y_bf,
+              float* y_f32, hipStream_t s) {
+  if (!x || !g || !b) { mvd_set_error("%s: null argument", who); return -1; }
+  if ((y_bf == nullptr) == (y_f32 == nullptr)) { mvd_set_error("%s: exactly one of y_bf16 and y_f32 must be given", who); return -1; }
+  if (rows <= 0 || rows > (1 << 24) || !(eps > 0.f)) { mvd_set_error("%s: bad rows %d / eps", who, rows); return -1; }
+  if (H < 4 || H % 4 || H > LN_MAXCH * 256) { mvd_set_error("%s: H = %d must be a multiple of 4 in 4..%d", who, H, LN_MAXCH * 256); return -1; }
+  if ((((uintptr_t)x | (uintptr_t)delta | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y_f32) & 15) || ((uintptr_t)y_bf & 7)) {
+    mvd_set_error("%s: x, delta, gamma, beta and y_f32 must be 16-byte aligned, y_bf16 8-byte aligned", who); return -1;
+  }
+  return launch_add_ln(x, delta, g, b, rows, H, eps, (bf16_t*)y_bf, y_f32, s);
+}
+int op_act(const char* who, const float* x, int64_t n, int act, void* y, hipStream_t s) {
+  if (!x || !y) { mvd_set_error("%s: null argument", who); return -1; }
+  if (n <= 0 || n % 8 || n > ((int64_t)1 << 40)) { mvd_set_error("%s: n = %lld must be a positive multiple of 8 (at most 2^40)", who, (long long)n); return -1; }
+  if (act != 0 && act != 1) { mvd_set_error("%s: act %d (0 gelu, 1 quick_gelu)", who, act); return -1; }
+  if (((uintptr_t)x | (uintptr_t)y) & 15) { mvd_set_error("%s: x and y must be 16-byte aligned", who); return -1; }
+  return launch_act(x, (long)(n / 8), act, (bf16_t*)y, s);
 }
 
 // ---------------------------------------------------------------- host side of one tower's schedule
@@ -92,6 +124,7 @@ struct ClipCtx {
   unsigned int* cnt_base = nullptr;
   int cnt_used = 0;
   int err = 0;
+  int last_tile = -1, last_splitk = 1;   // route of the last linear(): small-M tile (-1: the tiled kernels) and split-K factor
 
   template <class T> T* alloc(size_t n) { return ar.alloc_n<T>(n); }
   const void* W(const std::string& name, int dtype, int64_t numel) { return check_w ? w->find(name, dtype, numel, &err, prefix) : nullptr; }
@@ -118,15 +151,16 @@ struct ClipCtx {
       S = mvd_gemm_pick_splitk(g);
       if (S > 1) { g.splitk = S; g.part = alloc<float>((size_t)S * M * N); } else g.splitk = 1;
       if (!dry) r = launch_tiled(g, s);
+      tile = -1;
     }
+    last_tile = tile; last_splitk = S;
     ar.off = mark;
     return r;
   }
   int add_ln(float* x, const float* delta, const float* g, const float* b, int rows, int H, bf16_t* y_bf, float* y_f32) {
     if (err) return err;
     if (dry) return 0;
-    hipLaunchKernelGGL(text_add_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, delta, g, b, rows, H, eps, y_bf, y_f32);
-    return launch_check("add+layernorm");
+    return launch_add_ln(x, delta, g, b, rows, H, eps, y_bf, y_f32, s);
   }
 };
 
@@ -168,11 +202,7 @@ int clip_layers(ClipCtx& x, const ClipBufs& b, int layers, int H, int I, int M, 
     CHECK(x.linear(b.at, H, M, wo, bo, H, b.dl, true));
     CHECK(x.add_ln(b.xs, b.dl, g2w, b2w, M, H, b.h, nullptr));
     CHECK(x.linear(b.h, H, M, w1, bf1, I, b.f1, true));
-    if (!x.dry) {
-      const long n8 = (long)M * I / 8;
-      hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, x.s, b.f1, n8, act, b.g1);
-      CHECK(launch_check("activation"));
-    }
+    if (!x.dry) CHECK(launch_act(b.f1, (long)M * I / 8, act, b.g1, x.s));
     CHECK(x.linear(b.g1, I, M, w2, bf2, H, b.dl, true));
   }
   return x.err;

@@ -231,6 +231,27 @@ int check_shape(mvd_text* t, int batch, int seq_len, const char* who) {
   return 0;
 }
 
+// ClipCtx::linear on caller buffers: ws = [split-K tile counters | partials], the counters zeroed as encode_impl zeroes them
+int debug_linear(const bf16_t* a, int K, int M, const bf16_t* w, const float* bias, int N, void* out, bool out_f32, void* ws, hipStream_t s,
+                        bool dry, int cnt, size_t* bytes_out, int* cnt_out, int* route_out = nullptr) {
+  ClipCtx x{nullptr, "clip_linear: ", 1e-5f, s, dry};
+  x.check_w = false; x.ar.dry = dry;
+  if (!dry) {
+    x.cnt_base = reinterpret_cast<unsigned int*>(ws);
+    x.ar.base = reinterpret_cast<char*>(ws) + cnt_bytes(cnt);
+    if (cnt > 0 && hipMemsetAsync(x.cnt_base, 0, (size_t)cnt * 4, s) != hipSuccess) { mvd_set_error("clip_linear: hipMemsetAsync failed"); return -3; }
+  }
+  CHECK(x.linear(a, K, M, w, bias, N, out, out_f32));
+  if (bytes_out) *bytes_out = cnt_bytes(x.cnt_used) + x.ar.high;
+  if (cnt_out) *cnt_out = x.cnt_used;
+  if (route_out) { route_out[0] = x.last_tile; route_out[1] = x.last_splitk; }
+  return 0;
+}
+int debug_linear_shape(int M, int N, int K) {
+  if (M <= 0 || M > (1 << 20) || N <= 0 || N % 64 || K <= 0 || K % 64) { mvd_set_error("clip_linear: bad shape (M %d, N %d, K %d): N and K must be multiples of 64", M, N, K); return -1; }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -280,6 +301,39 @@ int mvd_op_attention_causal(const void* q, const void* k, const void* v, void* o
                             int ldo, float scale, void* stream) {
   return launch_attn_causal((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, batch, heads, n, ldq, ldk, ldv, ldo, scale,
                             (hipStream_t)stream);
+}
+
+int mvd_op_text_add_ln(float* x, const float* delta, const float* gamma, const float* beta, int rows, int H, float eps, void* y_bf16, float* y_f32,
+                       void* stream) {
+  return op_add_ln("text_add_ln", x, delta, gamma, beta, rows, H, eps, y_bf16, y_f32, (hipStream_t)stream);
+}
+
+int mvd_op_text_act(const float* x, int64_t n, int act, void* y_bf16, void* stream) { return op_act("text_act", x, n, act, y_bf16, (hipStream_t)stream); }
+
+int mvd_op_text_embed(const int32_t* ids, const float* tok, const float* pos, int rows, int T, int H, int vocab, float* x, void* stream) {
+  if (!ids || !tok || !pos || !x) { mvd_set_error("text_embed: null argument"); return -1; }
+  if (rows <= 0 || rows > (1 << 24) || T <= 0 || vocab <= 0 || H < 4 || H % 4) { mvd_set_error("text_embed: bad shape (rows %d, T %d, H %d, vocab %d): H must be a multiple of 4", rows, T, H, vocab); return -1; }
+  if (((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)x) & 15) { mvd_set_error("text_embed: tok, pos and x must be 16-byte aligned"); return -1; }
+  hipLaunchKernelGGL(text_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, tok, pos, rows, T, H, vocab, x);
+  return launch_check("text embedding");
+}
+
+int64_t mvd_debug_clip_linear_ws_bytes(int M, int N, int K, int out_f32) {
+  CHECK(debug_linear_shape(M, N, K));
+  size_t bytes = 0;
+  CHECK(debug_linear((const bf16_t*)0x1000, K, M, (const bf16_t*)0x1000, nullptr, N, (void*)0x1000, out_f32 != 0, nullptr, nullptr, true, 0, &bytes, nullptr));
+  return (int64_t)bytes + 256;
+}
+
+int mvd_debug_clip_linear(const void* a, int K, int M, const void* w, const float* bias, int N, void* out, int out_f32, void* ws, int64_t ws_bytes,
+                          int* route_out, void* stream) {
+  if (!a || !w || !out) { mvd_set_error("clip_linear: null argument"); return -1; }
+  CHECK(debug_linear_shape(M, N, K));
+  if (((uintptr_t)a | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)out) & 15) { mvd_set_error("clip_linear: a, w, bias and out must be 16-byte aligned"); return -1; }
+  size_t bytes = 0; int cnt = 0;
+  CHECK(debug_linear((const bf16_t*)a, K, M, (const bf16_t*)w, bias, N, out, out_f32 != 0, nullptr, nullptr, true, 0, &bytes, &cnt));
+  if (bytes > 0 && (!ws || ((uintptr_t)ws & 255) || (size_t)ws_bytes < bytes)) { mvd_set_error("clip_linear: workspace: need %zu bytes, 256-byte aligned (given %lld)", bytes, (long long)ws_bytes); return -4; }
+  return debug_linear((const bf16_t*)a, K, M, (const bf16_t*)w, bias, N, out, out_f32 != 0, ws, (hipStream_t)stream, false, cnt, nullptr, nullptr, route_out);
 }
 
 }  // extern "C"

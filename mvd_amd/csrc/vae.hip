@@ -76,6 +76,18 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, const floa
   out[i] = (mean + __expf(0.5f * lv) * noise[i]) * scale;
 }
 
+// the kernel keeps one pixel's input channels in float v[8]: more is refused before the launch
+int pointwise_shape(int B, int cin, int cout, int hw) {
+  if (B <= 0 || hw <= 0 || cin <= 0 || cout <= 0) { mvd_set_error("vae pointwise: bad shape (batch %d, cin %d, cout %d, hw %d)", B, cin, cout, hw); return -1; }
+  if (cin > 8 || cout > 8) { mvd_set_error("vae pointwise: cin %d / cout %d: at most 8 channels in and out", cin, cout); return -1; }
+  return 0;
+}
+int launch_pointwise(const float* x, int B, int cin, int cout, int hw, const float* w, const float* b, float* y, hipStream_t s) {
+  const long total = (long)B * hw;
+  hipLaunchKernelGGL(pointwise_small_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, cin, cout, hw, w, b, y, total);
+  return launch_check("vae pointwise");
+}
+
 }  // namespace
 
 struct mvd_vae : ModuleBase {
@@ -190,12 +202,11 @@ struct VCtx {
     return err;
   }
   int pointwise(const std::string& key, const float* x, int B, int cin, int cout, int hw, float* y) {
+    CHECK(pointwise_shape(B, cin, cout, hw));
     const float* w = WF(key + ".w", (int64_t)cout * cin);
     const float* b = WF(key + ".b", cout);
     if (dry || err) return err;
-    const long total = (long)B * hw;
-    hipLaunchKernelGGL(pointwise_small_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, cin, cout, hw, w, b, y, total);
-    return launch_check("vae pointwise");
+    return launch_pointwise(x, B, cin, cout, hw, w, b, y, s);
   }
 };
 
@@ -357,6 +368,12 @@ int mvd_op_gaussian_sample(const float* moments, const float* noise, int batch, 
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, moments, noise, channels, hw,
                      scale, out, total);
   return launch_check("gaussian_sample");
+}
+
+int mvd_op_vae_pointwise(const float* x, int batch, int cin, int cout, int hw, const float* w, const float* bias, float* y, void* stream) {
+  if (!x || !w || !bias || !y) { mvd_set_error("vae_pointwise: null argument"); return -1; }
+  CHECK(pointwise_shape(batch, cin, cout, hw));
+  return launch_pointwise(x, batch, cin, cout, hw, w, bias, y, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -370,6 +370,15 @@ struct mvd_vision : ModuleBase {      // (ar unused: the arena of a run lives in
 
 namespace {
 
+// the tower's attention: bidirectional over the fused [B * T][3H] q | k | v rows (q prescaled at pack time) -> at [B * T][H]
+int vit_attention(const bf16_t* qkv, bf16_t* at, int B, int heads, int T, hipStream_t s) {
+  const int H = heads * 64;
+  MvdAttnArgs a; memset(&a, 0, sizeof(a));
+  a.nprob = 1; a.batch = B; a.heads = heads; a.prescaled = 1;
+  a.p[0] = {qkv, qkv + H, qkv + 2 * H, at, 3 * H, 3 * H, 3 * H, H, (int64_t)T * 3 * H, (int64_t)T * 3 * H, (int64_t)T * 3 * H, (int64_t)T * H, T, T};
+  return mvd_launch_attention(a, s);
+}
+
 // dry: sizes only; otherwise `cnt` = the counter words the dry run asked for.  Workspace behind the patch rows:
 // [split-K tile counters | activations].
 int vencode_impl(mvd_vision* v, const float* pixel_values, int B, float* last_hidden, float* embeds, float* embeds_norm, hipStream_t s,
@@ -404,12 +413,7 @@ int vencode_impl(mvd_vision* v, const float* pixel_values, int B, float* last_hi
     hipLaunchKernelGGL(vit_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, po, cls, pos, gp, bp, M, T, H, c.layer_norm_eps, b.xs);
     CHECK(launch_check("vision embedding"));
   }
-  CHECK(clip_layers(x, b, c.num_layers, H, I, M, c.act, [&](const bf16_t* qkv, bf16_t* at) {
-    MvdAttnArgs a; memset(&a, 0, sizeof(a));
-    a.nprob = 1; a.batch = B; a.heads = c.num_heads; a.prescaled = 1;     // q rows prescaled at pack time
-    a.p[0] = {qkv, qkv + H, qkv + 2 * H, at, 3 * H, 3 * H, 3 * H, H, (int64_t)T * 3 * H, (int64_t)T * 3 * H, (int64_t)T * 3 * H, (int64_t)T * H, T, T};
-    return mvd_launch_attention(a, s);
-  }));
+  CHECK(clip_layers(x, b, c.num_layers, H, I, M, c.act, [&](const bf16_t* qkv, bf16_t* at) { return vit_attention(qkv, at, B, c.num_heads, T, s); }));
   if (!dry) {
     const float* dl = c.num_layers ? b.dl : nullptr;
     if (last_hidden) {
@@ -573,6 +577,55 @@ int mvd_op_clip_cosine(const float* a, const float* b, int batch, int dim, float
   if (!a || !b || (!per_row_out && !mean_out) || batch <= 0 || dim <= 0) { mvd_set_error("clip_cosine: bad argument"); return -1; }
   hipLaunchKernelGGL(clip_cosine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, b, batch, dim, per_row_out, mean_out);
   return launch_check("clip_cosine");
+}
+
+int mvd_op_vision_add_ln(float* x, const float* delta, const float* gamma, const float* beta, int rows, int H, float eps, void* y_bf16, float* y_f32,
+                         void* stream) {
+  return op_add_ln("vision_add_ln", x, delta, gamma, beta, rows, H, eps, y_bf16, y_f32, (hipStream_t)stream);
+}
+
+int mvd_op_vision_act(const float* x, int64_t n, int act, void* y_bf16, void* stream) { return op_act("vision_act", x, n, act, y_bf16, (hipStream_t)stream); }
+
+int mvd_op_vit_patchify(const float* pixel_values, int batch, int image_size, int patch_size, void* patches_bf16, void* stream) {
+  if (!pixel_values || !patches_bf16) { mvd_set_error("vit_patchify: null argument"); return -1; }
+  if (batch <= 0 || patch_size <= 0 || patch_size > 64 || image_size <= 0 || image_size > 4096 || image_size % patch_size) { mvd_set_error("vit_patchify: bad shape (batch %d, image_size %d, patch_size %d)", batch, image_size, patch_size); return -1; }
+  const int g = image_size / patch_size, Kp = (3 * patch_size * patch_size + 63) / 64 * 64;
+  const long total = (long)batch * g * g * Kp;
+  if (total >= (1L << 31) || (long)batch * 3 * image_size * image_size >= (1L << 31)) { mvd_set_error("vit_patchify: batch too large for one call"); return -1; }
+  hipLaunchKernelGGL(vit_patchify_kernel, dim3((unsigned)blocks_of(total)), dim3(256), 0, (hipStream_t)stream, pixel_values, total, image_size, patch_size, Kp,
+                     (bf16_t*)patches_bf16);
+  return launch_check("vision patchify");
+}
+
+int mvd_op_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, int batch, int tokens, int H,
+                        float eps, float* x, void* stream) {
+  if (!cls || !pos || !gamma || !beta || !x || (tokens > 1 && !patch_out)) { mvd_set_error("vit_embed_ln: null argument"); return -1; }
+  if (batch <= 0 || tokens <= 0 || (long)batch * tokens > (1L << 20) || !(eps > 0.f)) { mvd_set_error("vit_embed_ln: bad batch %d / tokens %d / eps", batch, tokens); return -1; }
+  if (H < 4 || H % 4 || H > LN_MAXCH * 256) { mvd_set_error("vit_embed_ln: H = %d must be a multiple of 4 in 4..%d", H, LN_MAXCH * 256); return -1; }
+  if (((uintptr_t)patch_out | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)x) & 15) { mvd_set_error("vit_embed_ln: every pointer must be 16-byte aligned"); return -1; }
+  const int M = batch * tokens;
+  hipLaunchKernelGGL(vit_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, patch_out, cls, pos, gamma, beta, M, tokens, H, eps, x);
+  return launch_check("vision embedding");
+}
+
+int mvd_op_vit_fold(const float* x, const float* delta, int64_t n, float* out, void* stream) {
+  if (!x || !delta || !out) { mvd_set_error("vit_fold: null argument"); return -1; }
+  if (n <= 0 || n % 4 || n > ((int64_t)1 << 38)) { mvd_set_error("vit_fold: n = %lld must be a positive multiple of 4 (at most 2^38)", (long long)n); return -1; }
+  if (((uintptr_t)x | (uintptr_t)delta | (uintptr_t)out) & 15) { mvd_set_error("vit_fold: x, delta and out must be 16-byte aligned"); return -1; }
+  const long n4 = (long)(n / 4);
+  hipLaunchKernelGGL(vit_fold_kernel, dim3((unsigned)blocks_of(n4)), dim3(256), 0, (hipStream_t)stream, x, delta, n4, out);
+  return launch_check("vision last hidden state");
+}
+
+int mvd_op_clip_l2norm(float* x, int rows, int dim, void* stream) {
+  if (!x || rows <= 0 || dim <= 0 || dim > PP_MAXH) { mvd_set_error("clip_l2norm: bad argument (rows %d, dim %d: at most %d)", rows, dim, PP_MAXH); return -1; }
+  hipLaunchKernelGGL(clip_l2norm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, dim);
+  return launch_check("clip L2 normalisation");
+}
+
+int mvd_debug_clip_attention(const void* qkv, void* out, int batch, int heads, int tokens, void* stream) {
+  if (!qkv || !out || batch <= 0 || heads <= 0 || tokens <= 0) { mvd_set_error("clip_attention: bad argument"); return -1; }
+  return vit_attention((const bf16_t*)qkv, (bf16_t*)out, batch, heads, tokens, (hipStream_t)stream);
 }
 
 }  // extern "C"

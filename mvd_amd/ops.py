@@ -626,6 +626,130 @@ def softmax_rows(s):
     return out
 
 
+def vae_pointwise(x, w, bias):
+    """quant_conv / post_quant_conv (vae.hip): x (B, cin, hw) fp32, w (cout, cin), bias (cout,) -> (B, cout, hw); cin, cout <= 8."""
+    assert x.dtype == torch.float32 and x.dim() == 3 and w.dtype == torch.float32 and w.shape[1] == x.shape[1] and bias.shape == w.shape[:1]
+    B, cin, hw = x.shape
+    y = torch.empty(B, w.shape[0], hw, device=x.device, dtype=torch.float32)
+    L.call("mvd_op_vae_pointwise", _p(x), B, cin, w.shape[0], hw, _p(w), _p(bias), _p(y), _s())
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ the CLIP towers' own kernels
+def _f32(*ts):
+    for t in ts:
+        if t is not None:
+            assert t.dtype == torch.float32, "expected fp32"
+
+
+def clip_add_ln(x, delta, gamma, beta, eps=1e-5, out_f32=False, tower="text", rows=None, out=None):
+    """Residual add + LayerNorm of the CLIP layers (clip_layer.h; ``tower``: the translation unit whose copy runs): x (R, H) fp32
+    += delta IN PLACE (delta None: x is not written), -> LN(x) as bf16 or (``out_f32``) fp32.  ``rows`` < R leaves the rows behind
+    it alone (tests); ``out``: a caller buffer of the output's type."""
+    _f32(x, delta, gamma, beta)
+    R, H = x.shape
+    rows = R if rows is None else rows
+    if out is None:
+        out = torch.empty(R, H, device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16) and rows <= R and out.numel() >= rows * H
+    assert gamma.shape == (H,) and beta.shape == (H,) and (delta is None or delta.numel() >= rows * H)
+    L.call(f"mvd_op_{tower}_add_ln", _p(x), _p(delta), _p(gamma), _p(beta), rows, H, float(eps), None if out_f32 else _p(out),
+           _p(out) if out_f32 else None, _s())
+    return out
+
+
+def clip_act(x, act, tower="text", n=None, out=None):
+    """The CLIP MLP's activation pass: fp32 -> bf16, act 0 gelu (erf), 1 quick_gelu; ``n`` (default: all) elements, n % 8 == 0."""
+    _f32(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    n = x.numel() if n is None else n
+    assert out.dtype == torch.bfloat16 and n <= x.numel() and n <= out.numel()
+    L.call(f"mvd_op_{tower}_act", _p(x), n, int(act), _p(out), _s())
+    return out
+
+
+def text_embed(ids, tok, pos, T, out=None):
+    """x[row] = tok[ids[row]] + pos[row % T]: ids (rows,) int32, tok (vocab, H), pos (>= T, H) fp32 -> (rows, H) fp32."""
+    _f32(tok, pos)
+    assert ids.dtype == torch.int32 and ids.dim() == 1 and pos.shape[0] >= T and pos.shape[1] == tok.shape[1]
+    rows, (vocab, H) = ids.shape[0], tok.shape
+    if out is None:
+        out = torch.empty(rows, H, device=tok.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() >= rows * H
+    L.call("mvd_op_text_embed", _p(ids), _p(tok), _p(pos), rows, T, H, vocab, _p(out), _s())
+    return out
+
+
+def vit_patchify(pixel_values, patch_size):
+    """(B, 3, S, S) fp32 -> (B * (S / P)^2, roundup(3 P^2, 64)) bf16 patch rows in (c, py, px) order, pad columns zero."""
+    _f32(pixel_values)
+    B, c, S, S2 = pixel_values.shape
+    assert c == 3 and S == S2
+    kp = (3 * patch_size ** 2 + 63) // 64 * 64
+    out = torch.empty(B * (S // patch_size) ** 2, kp, device=pixel_values.device, dtype=torch.bfloat16)
+    L.call("mvd_op_vit_patchify", _p(pixel_values), B, S, patch_size, _p(out), _s())
+    return out
+
+
+def vit_embed_ln(patch_out, cls, pos, gamma, beta, batch, eps=1e-5):
+    """[class | patches] + position, then pre_layrnorm: patch_out (batch * (T - 1), H), cls (H,), pos (T, H) -> (batch * T, H) fp32."""
+    _f32(patch_out, cls, pos, gamma, beta)
+    T, H = pos.shape
+    assert patch_out.shape == (batch * (T - 1), H) and cls.shape == (H,) and gamma.shape == (H,) and beta.shape == (H,)
+    out = torch.empty(batch * T, H, device=pos.device, dtype=torch.float32)
+    L.call("mvd_op_vit_embed_ln", _p(patch_out), _p(cls), _p(pos), _p(gamma), _p(beta), batch, T, H, float(eps), _p(out), _s())
+    return out
+
+
+def vit_fold(x, delta, n=None, out=None):
+    """out = x + delta over the first ``n`` (default: all) fp32 elements, n % 4 == 0."""
+    _f32(x, delta)
+    if out is None:
+        out = torch.empty_like(x)
+    n = x.numel() if n is None else n
+    assert out.dtype == torch.float32 and n <= min(x.numel(), delta.numel(), out.numel())
+    L.call("mvd_op_vit_fold", _p(x), _p(delta), n, _p(out), _s())
+    return out
+
+
+def clip_l2norm(x, rows=None):
+    """x (R, dim) fp32: the first ``rows`` rows divided by their L2 norm IN PLACE."""
+    _f32(x)
+    assert x.dim() == 2 and (rows is None or rows <= x.shape[0])
+    L.call("mvd_op_clip_l2norm", _p(x), x.shape[0] if rows is None else rows, x.shape[1], _s())
+    return x
+
+
+def clip_linear(a, w, bias=None, out_f32=False, route=None):
+    """a (M, K) . w (N, K)^T + bias through the CLIP towers' own GEMM routing (``mvd_debug_clip_linear``) -> (M, N) bf16 / fp32.
+    ``route``: a list that receives (small-M tile or -1 for the tiled kernels, split-K factor) of the launch."""
+    _bf16(a, w)
+    _f32(bias)
+    (M, K), N = a.shape, w.shape[0]
+    assert w.shape[1] == K
+    need = L.lib().mvd_debug_clip_linear_ws_bytes(M, N, K, int(out_f32))
+    if need < 0:
+        raise L.MvdError(f"mvd_debug_clip_linear_ws_bytes: {L.last_error()}")
+    ws = torch.empty(need, device=a.device, dtype=torch.uint8)
+    out = torch.empty(M, N, device=a.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    got = (C.c_int * 2)()
+    L.call("mvd_debug_clip_linear", _p(a), K, M, _p(w), _p(bias), N, _p(out), int(out_f32), _p(ws), ws.numel(), got, _s())
+    if route is not None:
+        route.append((got[0], got[1]))
+    return out
+
+
+def clip_attention(qkv, batch, heads):
+    """The image tower's attention launch (``mvd_debug_clip_attention``): qkv (batch * T, 3 * heads * 64) bf16, q prescaled -> (batch * T, heads * 64)."""
+    _bf16(qkv)
+    M, w = qkv.shape
+    assert w == 3 * heads * 64 and M % batch == 0
+    out = torch.empty(M, heads * 64, device=qkv.device, dtype=torch.bfloat16)
+    L.call("mvd_debug_clip_attention", _p(qkv), _p(out), batch, heads, M // batch, _s())
+    return out
+
+
 def ddpm_step(model_out, sample, noise, c0, c1, c2, c3, sigma):
     """fp32: x0 = c0*model_out + c1*sample ; prev = c2*x0 + c3*sample + sigma*noise (noise may be None iff sigma == 0)."""
     assert model_out.dtype == torch.float32 and sample.dtype == torch.float32
