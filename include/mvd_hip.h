@@ -199,6 +199,21 @@ int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable);
 int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2);
 int mvd_engine_clear_freeu(mvd_engine_t* e);
 
+/* Token merging (mvd_op_tome_* below) in front of attn1 of the MAIN pass's transformer blocks whose map
+ * H x W of a latent H0 x W0 has ceil(sqrt((H0 W0) / (H W))) <= max_downsample, with r = min(ns, int(H W ratio)) > 0: LayerNorm1,
+ * match + select, merge, the plain attn1.qkv GEMM on B N' rows, the one- or two-problem attention with nq = nk_self = N' (the
+ * adapter's Q_ref from merged rows, the reference K/V at full length), the out-projection into a temporary, un-merge + add.  attn2
+ * and the feed-forward are as they were; the encoder pass and the reference K/V never merge.  ratio in [0, 0.75], max_downsample
+ * one of 1, 2, 4, 8, else -1.  ratio 0, or no eligible block: the launches of a forward are what they were.  A merging block
+ * whose map is above the select kernel's limit or whose channels are no multiple of 64 fails the forward before anything is
+ * launched.  Both entries drop the captured hipGraphs; the workspace entries size the forward of the current setting.
+ * keep_tables (test plumbing): every merging block's slot table [batch][H W] stays in the workspace after the forward;
+ * mvd_engine_tome_table copies that of feature `feature_idx` of the last issued forward to the device array `out` and returns
+ * its length (0: the block did not merge; out null: the length alone). */
+int mvd_engine_set_tome(mvd_engine_t* e, double ratio, int max_downsample, int keep_tables);
+int mvd_engine_clear_tome(mvd_engine_t* e);
+int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* stream);
+
 /* DeepCache (Ma et al., CVPR 2024; the DeepCacheSDHelper used with diffusers, restated): the deep, low-resolution features of
  * the main pass change little between neighbouring denoising steps, so a step may reuse them.  With n = num_levels,
  * Lb = layers_per_block, a branch b in [0, Lb) (DeepCache's cache_branch_id) and j0 = Lb - 1 - b, the DEEP FEATURE is the hidden
@@ -598,6 +613,30 @@ int mvd_debug_apg_plan(int64_t n_row, int* out);
  * finite, a pointer that is null or not 16-byte aligned, or an output that overlaps an input or the other output. */
 int mvd_op_freeu(const void* hidden, int C, const void* skip, int Cs, int B, int H, int W, float b, float s, void* hidden_out,
                  void* skip_out, void* stream);
+
+/* Token merging (Bolya & Hoffman 2023; tomesd 0.1.x with use_rand = False, sx = sy = 2, restated) on a token-major bf16 map
+ * x [B][H*W][C], every image on its own.  dst tokens: the top-left token of every complete 2 x 2 cell, nd = (H/2)(W/2), numbered in
+ * raster order of the cells; src tokens: every other token (a last odd row / column included), ns = H W - nd, numbered in ascending
+ * token order.  score(s, d) = x_s . x_d / (|x_s| |x_d|): exact bf16 products, fp32 sums, the division on the fp32 result;
+ * best(s) = argmax over d, a tie to the lowest d.  The r src with the largest score(s, best(s)) are merged, ties to the lower index.
+ *   mvd_op_tome_match        slot [B][H W] int32: the row of every token in the merged sequence of N' = H W - r rows (dst d -> d, a
+ *                            merged src -> best(s), the p-th kept src in ascending token order -> nd + p); members [B][H W] and
+ *                            starts [B][N' + 1] int32: the tokens of row j are members[starts[j] .. starts[j + 1]), ascending.
+ *                            score / best [B][ns] (fp32 / int32) may be null: they then live in ws (mvd_op_tome_workspace_bytes,
+ *                            256-byte aligned).  Two launches (match, select); nothing is synchronised.
+ *   mvd_op_tome_merge        out [B][N'][C] = bf16(fp32 sum of the row's members in ascending token order / count); a row of one
+ *                            member is copied bit for bit.
+ *   mvd_op_tome_unmerge_add  h [B][H W][C] += t [B][N'][C] rows by slot, in place: bf16(float(h) + float(t)).
+ * -1 (mvd_last_error) before anything is launched for H or W < 2, H W above the select kernel's limit (mvd_debug_tome_plan out[7]),
+ * C no positive multiple of 64, r outside [0, ns], a null or misaligned pointer.
+ * mvd_debug_tome_plan: out[8] = nd, ns, N', score sort keys, member sort keys, match workgroups per image, select LDS bytes, the
+ * token limit (out[7] is written even when the shape is refused). */
+int64_t mvd_op_tome_workspace_bytes(int B, int H, int W);
+int mvd_op_tome_match(const void* x, int B, int H, int W, int C, int r, int* slot, int* members, int* starts, float* score_or_null,
+                      int* best_or_null, void* ws, int64_t ws_bytes, void* stream);
+int mvd_op_tome_merge(const void* x, int B, int H, int W, int C, int r, const int* members, const int* starts, void* out, void* stream);
+int mvd_op_tome_unmerge_add(void* h, const void* t, int B, int H, int W, int C, int r, const int* slot, void* stream);
+int mvd_debug_tome_plan(int H, int W, int C, int r, int64_t* out);
 
 /* ---- checkpoint scoring around the UNet, fp32 ------------------------------------------------ */
 /* Conventions of the helpers above; in addition every quantity that depends on a sample's timestep is read ON THE DEVICE

@@ -214,6 +214,15 @@ _SIGS = {
     "mvd_debug_apg_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
     "mvd_engine_set_freeu": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mvd_engine_clear_freeu": (C.c_int, [C.c_void_p]),
+    "mvd_engine_set_tome": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int]),
+    "mvd_engine_clear_tome": (C.c_int, [C.c_void_p]),
+    "mvd_engine_tome_table": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_op_tome_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mvd_op_tome_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mvd_op_tome_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mvd_op_tome_unmerge_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_debug_tome_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mvd_engine_set_deepcache": (C.c_int, [C.c_void_p, C.c_int]),
     "mvd_engine_clear_deepcache": (C.c_int, [C.c_void_p]),
     "mvd_engine_deepcache_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

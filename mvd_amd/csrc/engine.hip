@@ -80,6 +80,11 @@ struct mvd_engine {
   bool share_encoder = false;       // N4: the encoder pass reads weight set 0 (base UNet == image-encoder UNet)
   // FreeU (mvd_engine_set_freeu): the main pass's up blocks 0 and 1 read re-weighted hidden / skip inputs; freeu_b / freeu_s by block
   bool freeu_on = false; float freeu_b[2] = {1.f, 1.f}, freeu_s[2] = {1.f, 1.f};
+  // Token merging (mvd_engine_set_tome): the main pass's eligible transformer blocks run attn1 on the merged sequence.  tome_tab: with
+  // tome_keep, the slot table of every feature's block in the last issued forward (workspace memory; rows 0: the block did not merge)
+  double tome_ratio = 0.0; int tome_maxds = 1; bool tome_keep = false;
+  struct TomeTable { int* p = nullptr; int64_t n = 0; };
+  std::vector<TomeTable> tome_tab;
   // DeepCache (mvd_engine_set_deepcache; include/mvd_hip.h): the stored deep feature lives in a buffer of its own (the reference
   // cache's allocator is reset by every cold forward) and carries the record of the refresh forward that wrote it.  The record is
   // NOT part of HostState: it is written by unet_forward once a refresh forward has been issued (launched, captured or replayed),
@@ -547,6 +552,8 @@ struct PassOpts {
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
   const ViewLayout* layout = nullptr;   // the forward's batch layout (ragged.h): the adapter pass's K/V maps, the encoder pass's statistics
   bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
+  double tome_ratio = 0.0;    // main pass with token merging set on the engine (0: off); blocks down to tome_maxds merge
+  int tome_maxds = 1;
   int deep = 0;               // main pass, DeepCache: MVD_DEEPCACHE_REFRESH (store the deep feature) / _SHALLOW (start from it); 0: neither
   int deep_branch = 0;        // the branch b: down_blocks.0 layers 0..b and up_blocks.{n-1} layers Lb-1-b..Lb are the shallow forward
   bf16_t* deep_buf = nullptr; // the bound buffer: [B][H0][W0][C of the deep feature]
@@ -618,7 +625,36 @@ struct UNetPass {
     // (dual-stream forwards: this feature's adapter K/V come from the encoder pass on the side stream)
     if (ad && c.e->dual_now && !c.dry && !c.err && hipStreamWaitEvent(c.s, c.e->feat_ev[feat_idx], 0) != hipSuccess) { mvd_set_error("forward: hipStreamWaitEvent failed"); return -3; }
     // ---- attn1 (self) + adapter branch "<feature>_self"
-    {
+    const int tome_r = tome_merged(x.H, x.W);
+    if (tome_r > 0) {
+      // token merging (include/mvd_hip.h mvd_engine_set_tome): attn1 on the N' = hw - r merged rows of every image
+      if (hw > MVD_TOME_MAX_TOKENS || (C & 63)) { mvd_set_error("forward: token merging in %s: a %d x %d map of %d channels (the select kernel takes at most %d tokens, channels in multiples of 64)", key.c_str(), x.H, x.W, C, MVD_TOME_MAX_TOKENS); return c.err = -1; }
+      const int Nm = hw - tome_r, Mm = B_ * Nm;
+      const int nq = ad ? 4 * C : 3 * C;
+      CHECK(c.layernorm(h, M, C, c.WF(key + ".ln1.g", C), c.WF(key + ".ln1.b", C), ln));
+      int* slot = c.e->tome_keep ? c.aalloc<int>((size_t)M) : c.talloc<int>((size_t)M);
+      int* members = c.talloc<int>((size_t)M);
+      int* starts = c.talloc<int>((size_t)B_ * (Nm + 1));
+      const int64_t wsb = mvd_tome_workspace_bytes(B_, x.H, x.W);
+      void* tws = c.e->tmp.alloc((size_t)wsb);
+      bf16_t* lnm = c.talloc<bf16_t>((size_t)Mm * C);      // the merged rows; after the q/k/v GEMM, the out-projection's result
+      bf16_t* qkv = c.talloc<bf16_t>((size_t)Mm * nq);
+      if (!c.dry && !c.err) {
+        if (c.e->tome_keep && feat_idx < (int)c.e->tome_tab.size()) c.e->tome_tab[feat_idx] = {slot, (int64_t)M};
+        CHECK(mvd_launch_tome_match(ln, B_, x.H, x.W, C, tome_r, slot, members, starts, nullptr, nullptr, tws, wsb, c.s));
+        CHECK(mvd_launch_tome_merge(ln, B_, x.H, x.W, C, tome_r, members, starts, lnm, c.s));
+      }
+      CHECK(c.linear(lnm, nullptr, C, 0, Mm, c.WB(key + ".attn1.qkv.w", (int64_t)(packed ? 4 : 3) * C * C), nullptr, nq, nullptr, 0, qkv, nq));
+      MvdAttnArgs a; memset(&a, 0, sizeof(a));
+      a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
+      a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)Nm * nq, (int64_t)Nm * nq, (int64_t)Nm * nq, (int64_t)Nm * C, Nm, Nm};
+      if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)Nm * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)Nm * C, Nm, ref_nk};
+      if (ad) o.layout->fill_map(true, &a.kv_group[1], &a.kv_objects[1], &a.kv_index[1]);
+      CHECK(c.attention(a));
+      CHECK(c.linear(o_self, o_ref, C, ad ? C : 0, Mm, c.WB(key + ".attn1.out.w", (int64_t)C * ld_out), c.WF(key + ".attn1" + bias_slot, C), C, nullptr, 0, lnm, C, false, false, ld_out,
+                     ad ? std::string() : key + ".attn1.out.wx"));
+      if (!c.dry && !c.err) CHECK(mvd_launch_tome_unmerge_add(h, lnm, B_, x.H, x.W, C, tome_r, slot, c.s));
+    } else {
       const int nq = ad ? 4 * C : 3 * C;
       bf16_t* qkv = c.talloc<bf16_t>((size_t)M * nq);
       CHECK(c.ln_linear(h, M, C, key + ".ln1", key + ".attn1.qkv", (int64_t)(packed ? 4 : 3) * C, nq, nullptr, ln, qkv, nq, false));
@@ -688,6 +724,18 @@ struct UNetPass {
     }
     ++feat_idx;
     return c.err;
+  }
+
+  // merged src per image of a block whose map is H x W; 0: the block does not merge (tomesd: `down <= max_downsample`, r = int(N ratio))
+  int tome_merged(int H, int W) const {
+    if (!(o.tome_ratio > 0.0) || o.capture || H < 2 || W < 2) return 0;
+    const long q = ((long)H0 * W0) / ((long)H * W);
+    long down = 0;
+    while (down * down < q) ++down;
+    if (down > o.tome_maxds) return 0;
+    const int ns = H * W - (H / 2) * (W / 2);
+    const int r = (int)((double)(H * W) * o.tome_ratio);
+    return r < ns ? r : ns;
   }
 
   int film(const std::string& name, const Act& x, Act& out) {
@@ -1202,6 +1250,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   po.layout = &lay;
   po.freeu = e->freeu_on;
+  po.tome_ratio = e->tome_ratio; po.tome_maxds = e->tome_maxds;
+  if (e->tome_keep && !dry) e->tome_tab.assign(e->feats.size(), {});
   po.deep = deep; po.deep_branch = e->dc_branch; po.deep_buf = (bf16_t*)e->dc_ptr;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
@@ -1674,6 +1724,32 @@ int mvd_engine_clear_freeu(mvd_engine_t* e) {
   e->drop_graphs();
   e->freeu_on = false;
   return 0;
+}
+
+// Token merging on the main pass (include/mvd_hip.h).  Both drop the captured graphs, as FreeU's do
+int mvd_engine_set_tome(mvd_engine_t* e, double ratio, int max_downsample, int keep_tables) {
+  if (!e) { mvd_set_error("set_tome: null engine"); return -1; }
+  if (!(ratio >= 0.0) || !(ratio <= 0.75)) { mvd_set_error("set_tome: ratio must lie in [0, 0.75] (a quarter of the tokens are dst and stay), got %g", ratio); return -1; }
+  if (max_downsample != 1 && max_downsample != 2 && max_downsample != 4 && max_downsample != 8) { mvd_set_error("set_tome: max_downsample must be one of 1, 2, 4, 8, got %d", max_downsample); return -1; }
+  e->drop_graphs();
+  e->tome_ratio = ratio; e->tome_maxds = max_downsample; e->tome_keep = keep_tables != 0;
+  e->tome_tab.clear();
+  return 0;
+}
+int mvd_engine_clear_tome(mvd_engine_t* e) {
+  if (!e) { mvd_set_error("clear_tome: null engine"); return -1; }
+  e->drop_graphs();
+  e->tome_ratio = 0.0; e->tome_maxds = 1; e->tome_keep = false;
+  e->tome_tab.clear();
+  return 0;
+}
+int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* stream) {
+  if (!e || feature_idx < 0 || feature_idx >= (int)e->feats.size()) { mvd_set_error("tome_table: bad argument"); return -1; }
+  if (!e->tome_keep) { mvd_set_error("tome_table: tables are not kept (mvd_engine_set_tome with keep_tables)"); return -1; }
+  if (feature_idx >= (int)e->tome_tab.size() || !e->tome_tab[feature_idx].p) return 0;
+  const auto& t = e->tome_tab[feature_idx];
+  if (out && hipMemcpyAsync(out, t.p, (size_t)t.n * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("tome_table: copy failed"); return -3; }
+  return t.n;
 }
 
 // DeepCache (include/mvd_hip.h).  Setting, clearing and binding drop the captured graphs (their nodes hold the branch's schedule and

@@ -212,6 +212,14 @@ int mvd_launch_film(const bf16_t* x, int batch, int hw, int c, const float* scal
 // frequencies {0, -1} x {0, -1} times s.  One launch; every argument is checked before it (-1 and a message)
 int mvd_launch_freeu(const bf16_t* hidden, int C, const bf16_t* skip, int Cs, int B, int H, int W, float b, float s, bf16_t* hidden_out,
                      bf16_t* skip_out, hipStream_t stream);
+// Token merging (tome.hip; include/mvd_hip.h mvd_op_tome_*): match + select build the tables of a [B][H*W][C] map for r merged src per
+// image, merge writes the [B][H*W - r][C] sequence, unmerge_add adds t[slot] to h in place.  Every argument is checked before a launch
+constexpr int MVD_TOME_MAX_TOKENS = 9216;      // H * W of a merging map: the select kernel's two sorts live in LDS (96 x 96 latents fit)
+int64_t mvd_tome_workspace_bytes(int B, int H, int W);
+int mvd_launch_tome_match(const bf16_t* x, int B, int H, int W, int C, int r, int* slot, int* members, int* starts, float* score, int* best,
+                          void* ws, int64_t ws_bytes, hipStream_t stream);
+int mvd_launch_tome_merge(const bf16_t* x, int B, int H, int W, int C, int r, const int* members, const int* starts, bf16_t* out, hipStream_t stream);
+int mvd_launch_tome_unmerge_add(bf16_t* h, const bf16_t* t, int B, int H, int W, int C, int r, const int* slot, hipStream_t stream);
 // conv_in: 3x3 pad 1, tiny Cin (<=8) -> Cout, NHWC bf16 in/out, weights fp32 [Cout][3][3][Cin]
 int mvd_launch_conv_in(const bf16_t* x, int batch, int h, int w, int cin, const float* wt, const float* bias,
                        int cout, bf16_t* y, hipStream_t s);

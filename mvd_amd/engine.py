@@ -56,6 +56,8 @@ class MVDEngine:
         self._ws_args = None
         self.freeu = None                                         # (s1, s2, b1, b2) while FreeU is set
         self.deepcache = None                                     # the branch while DeepCache is set
+        self.tome = None                                          # (ratio, max_downsample) while token merging is set
+        self._tome_keep = False
         self._dc = None                                           # the bound buffer of the stored deep feature
 
     def __del__(self):
@@ -339,6 +341,40 @@ class MVDEngine:
         if self._ws_key is not None and self._ws_args is not None:
             # now, not in the next forward: whoever asks reference_cache_valid first gets the answer that holds
             self._ensure_workspace(*self._ws_args)
+
+    def set_tome(self, ratio: float = 0.5, max_downsample: int = 1, keep_tables: bool = False) -> None:
+        """Token merging in front of self-attention on the main UNet pass (``mvd_engine_set_tome``; tomesd's ``apply_patch`` names):
+        blocks whose map is at most ``max_downsample`` times coarser than the latent run ``attn1`` on ``N - int(N * ratio)`` rows.
+        ``keep_tables``: ``tome_tables()`` reads the blocks' slot tables after a forward (test plumbing)."""
+        L.call("mvd_engine_set_tome", self._h, float(ratio), int(max_downsample), int(bool(keep_tables)))
+        self.tome, self._tome_keep = (float(ratio), int(max_downsample)), bool(keep_tables)
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            self._ensure_workspace(*self._ws_args)
+
+    def clear_tome(self) -> None:
+        """Back to the forward without token merging (``mvd_engine_clear_tome``): the launches it made before."""
+        L.call("mvd_engine_clear_tome", self._h)
+        self.tome, self._tome_keep = None, False
+        # (the forward without merging needs MORE scratch than the merging one: a workspace sized while it was on is too small)
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            self._ensure_workspace(*self._ws_args)
+
+    def tome_tables(self):
+        """``{feature name: slot table (batch, H*W) int32}`` of the blocks that merged in the last issued forward (needs
+        ``set_tome(..., keep_tables=True)``)."""
+        out = {}
+        for i, (_, name, _, _) in enumerate(self.cfg.transformers()):
+            n = L.lib().mvd_engine_tome_table(self._h, i, None, None)
+            if n < 0:
+                raise L.MvdError(f"tome_table: {L.last_error()}")
+            if n:
+                t = torch.empty(n, dtype=torch.int32, device=self.device)
+                if L.lib().mvd_engine_tome_table(self._h, i, _ptr(t), C.c_void_p(torch.cuda.current_stream().cuda_stream)) != n:
+                    raise L.MvdError(f"tome_table: {L.last_error()}")
+                out[name] = t
+        return out
 
     def set_deepcache(self, branch: int = 0) -> None:
         """DeepCache on the main UNet pass (``mvd_engine_set_deepcache``): ``forward(..., deep_cache="refresh")`` stores the hidden

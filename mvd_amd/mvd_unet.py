@@ -290,6 +290,12 @@ class MultiViewUNet(nn.Module):
                 self._engine.clear_freeu()
             else:
                 self._engine.set_freeu(*self.freeu)
+        tome = self.tome if self.tome is not None and self.tome[0] > 0.0 else None
+        if tome != getattr(self._engine, "tome", None) or (tome is not None and self.tome_keep_tables != getattr(self._engine, "_tome_keep", False)):
+            if tome is None:
+                self._engine.clear_tome()
+            else:
+                self._engine.set_tome(*tome, keep_tables=self.tome_keep_tables)
         branch = None if self.deepcache is None else self.deepcache[1]
         if branch != getattr(self._engine, "deepcache", None):
             self._deep_key, self._deep_hold = False, None
@@ -315,6 +321,25 @@ class MultiViewUNet(nn.Module):
 
     def disable_freeu(self):
         self.base_unet.disable_freeu()
+
+    # ------------------------------------------------------------------ token merging (tomesd's parameter names)
+    tome_keep_tables = False        # test plumbing: keep the blocks' slot tables for ``_engine.tome_tables()``
+
+    @property
+    def tome(self):
+        """``(ratio, max_downsample)`` while token merging is enabled, else ``None``; kept on ``base_unet``
+        (``tomesd.apply_patch(pipe.unet.base_unet, ...)`` is the call the reference's users would make)."""
+        return self.base_unet.tome
+
+    def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1):
+        """Token Merging for Stable Diffusion (Bolya & Hoffman 2023; ``tomesd.apply_patch(model, ratio=, max_downsample=)`` with
+        ``use_rand=False``) on the main UNet pass: the transformer blocks whose map is at most ``max_downsample`` times coarser than
+        the latent merge ``int(N * ratio)`` of their ``N`` tokens in front of ``attn1`` and un-merge behind it (DESIGN.md section 9
+        N21).  ``attn2``, the feed-forward, the image-encoder pass and the cached reference do not depend on it."""
+        self.base_unet.enable_tome(ratio, max_downsample)
+
+    def disable_tome(self):
+        self.base_unet.disable_tome()
 
     # ------------------------------------------------------------------ DeepCache (DeepCacheSDHelper's parameter names)
     def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):

@@ -930,6 +930,68 @@ def freeu(hidden, skip, H, W, b, s, hidden_out=None, skip_out=None):
     return hidden_out, skip_out
 
 
+def _tome_shape(x, H, W, who):
+    _bf16(x)
+    if x.dim() != 3 or x.shape[1] != int(H) * int(W):
+        raise L.MvdError(f"{who}: expected a (B, H*W, C) bf16 map with H*W = {int(H) * int(W)}, got {tuple(x.shape)}")
+
+
+def tome_match(x, H, W, r, want_scores=False):
+    """Token merging, the decisions (``mvd_op_tome_match``: the match and the select launch) for ``x`` (B, H*W, C) bf16 -- a block's
+    LayerNorm1 output -- with ``r`` merged src per image.  Returns ``(slot, members, starts)`` int32 -- the merged row of every token
+    (B, H*W), the tokens of every merged row in ascending order (B, H*W) and where each row's list starts (B, H*W - r + 1) -- and,
+    with ``want_scores``, also ``(score, best)`` (B, #src) of every src token in ascending token order."""
+    _tome_shape(x, H, W, "tome_match")
+    B, HW, Cc = x.shape
+    i32 = dict(dtype=torch.int32, device=x.device)
+    slot, members = torch.empty(B, HW, **i32), torch.empty(B, HW, **i32)
+    starts = torch.empty(B, max(HW - int(r), 0) + 1, **i32)
+    ns = HW - (int(H) // 2) * (int(W) // 2)
+    score = torch.empty(B, ns, dtype=torch.float32, device=x.device) if want_scores else None
+    best = torch.empty(B, ns, **i32) if want_scores else None
+    nws = 0 if want_scores else max(int(L.lib().mvd_op_tome_workspace_bytes(B, int(H), int(W))), 0)
+    ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
+    L.call("mvd_op_tome_match", _p(x), B, int(H), int(W), Cc, int(r), _p(slot), _p(members), _p(starts), _p(score), _p(best), _p(ws), nws, _s())
+    return (slot, members, starts, score, best) if want_scores else (slot, members, starts)
+
+
+def tome_merge(x, H, W, r, members, starts, out=None):
+    """The merged sequence (B, H*W - r, C) of ``x`` (B, H*W, C) bf16 under ``tome_match``'s tables (``mvd_op_tome_merge``): every row the
+    fp32 mean of its members, summed in ascending token order, one rounding to bf16."""
+    _tome_shape(x, H, W, "tome_merge")
+    B, HW, Cc = x.shape
+    assert members.dtype == torch.int32 and starts.dtype == torch.int32 and members.is_contiguous() and starts.is_contiguous()
+    if out is None:
+        out = torch.empty(B, max(HW - int(r), 0), Cc, dtype=torch.bfloat16, device=x.device)
+    _bf16(out)
+    if tuple(out.shape) != (B, HW - int(r), Cc) or tuple(members.shape) != (B, HW) or tuple(starts.shape) != (B, HW - int(r) + 1):
+        raise L.MvdError(f"tome_merge: expected out {(B, HW - int(r), Cc)}, members {(B, HW)}, starts {(B, HW - int(r) + 1)}, got "
+                         f"{tuple(out.shape)}, {tuple(members.shape)}, {tuple(starts.shape)}")
+    L.call("mvd_op_tome_merge", _p(x), B, int(H), int(W), Cc, int(r), _p(members), _p(starts), _p(out), _s())
+    return out
+
+
+def tome_unmerge_add(h, t, H, W, r, slot):
+    """``h`` (B, H*W, C) += ``t`` (B, H*W - r, C) rows by ``slot``, in place (``mvd_op_tome_unmerge_add``): bf16(float(h) + float(t))."""
+    _tome_shape(h, H, W, "tome_unmerge_add")
+    _bf16(t)
+    B, HW, Cc = h.shape
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and tuple(slot.shape) == (B, HW)
+    if tuple(t.shape) != (B, HW - int(r), Cc):
+        raise L.MvdError(f"tome_unmerge_add: expected t {(B, HW - int(r), Cc)}, got {tuple(t.shape)}")
+    L.call("mvd_op_tome_unmerge_add", _p(h), _p(t), B, int(H), int(W), Cc, int(r), _p(slot), _s())
+    return h
+
+
+def tome_plan(H, W, C_, r):
+    """What the token-merging kernels do with an H x W map of C_ channels and r merged src (``mvd_debug_tome_plan``); MvdError, with
+    ``max_tokens`` in the message, for a shape they refuse."""
+    out = (C.c_int64 * 8)()
+    L.call("mvd_debug_tome_plan", int(H), int(W), int(C_), int(r), out)
+    return dict(dst=out[0], src=out[1], rows=out[2], score_keys=out[3], member_keys=out[4], match_workgroups=out[5], select_lds=out[6],
+                max_tokens=out[7])
+
+
 PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")       # prediction_type of mvd_op_noise_loss, by index
 
 

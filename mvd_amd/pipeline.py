@@ -207,6 +207,14 @@ class MVDPipeline:
     def disable_freeu(self):
         self.unet.disable_freeu()
 
+    def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1):
+        """``tomesd.apply_patch(pipe, ratio=, max_downsample=)``: token merging in front of the UNet's self-attention for every call
+        that follows (``MultiViewUNet.enable_tome``)."""
+        self.unet.enable_tome(ratio, max_downsample)
+
+    def disable_tome(self):
+        self.unet.disable_tome()
+
     def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):
         """DeepCache (``DeepCacheSDHelper``'s parameters) for every call that follows -- ``__call__``, ``generate_views`` and
         ``generate_views_batch`` alike: every ``cache_interval``-th step runs the whole UNet, the steps in between only its

@@ -169,6 +169,47 @@ class UNet2DConditionParams(_NoForward):
     def disable_freeu(self):
         self.freeu = None
 
+    # tomesd's apply_patch(model, ratio=, max_downsample=) / remove_patch as a pair of the same kind
+    tome = None                 # (ratio, max_downsample) while enabled
+
+    def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1):
+        if not self._freeu_main:
+            raise ValueError("enable_tome: token merging applies to the main pass only -- call it on MultiViewUNet.base_unet (the "
+                             "image encoder's pass and the cached reference K/V never merge)")
+        self.tome = check_tome(ratio, max_downsample)
+
+    def disable_tome(self):
+        self.tome = None
+
+
+def check_tome(ratio, max_downsample=1):
+    """(ratio, max_downsample); ValueError unless 0 <= ratio <= 0.75 and max_downsample is one of 1, 2, 4, 8 (tomesd's)."""
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 0.75:
+        raise ValueError(f"token merging: ratio must lie in [0, 0.75] (a quarter of the tokens are dst and stay), got {ratio}")
+    if isinstance(max_downsample, bool) or max_downsample not in (1, 2, 4, 8):
+        raise ValueError(f"token merging: max_downsample must be one of 1, 2, 4, 8, got {max_downsample!r}")
+    return ratio, int(max_downsample)
+
+
+def tome_blocks(cfg, height, width, ratio, max_downsample=1):
+    """``{feature name: (H, W, r)}`` of the transformer blocks that merge at a latent of ``height`` x ``width``: tomesd's rule
+    ``ceil(sqrt(N0 // N)) <= max_downsample`` with ``r = min(#src, int(N * ratio)) > 0``."""
+    import math
+    out = {}
+    for _, name, _, _ in cfg.transformers():
+        part = name.split("_")          # down_block_{i}_attn_{j} | mid_block_attn_0 | up_block_{i}_attn_{j}
+        level = int(part[2]) if part[0] == "down" else cfg.num_levels - 1 - (int(part[2]) if part[0] == "up" else 0)
+        H, W = height >> level, width >> level
+        if H < 2 or W < 2:
+            continue
+        q = (height * width) // (H * W)
+        down = math.isqrt(q - 1) + 1 if q > 0 else 0            # ceil(sqrt(q))
+        r = min(H * W - (H // 2) * (W // 2), int(H * W * float(ratio)))
+        if down <= max_downsample and r > 0:
+            out[name] = (H, W, r)
+    return out
+
 
 def check_freeu(s1, s2, b1, b2):
     """(s1, s2, b1, b2) as floats; ValueError unless all four are positive and finite."""

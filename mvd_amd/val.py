@@ -15,7 +15,8 @@ Configuration keys read (the reference ships no ``config/infer_config.yaml``; th
 architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device"), ``extra_metrics``, ``metric_weights`` (a
 mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
 pipeline's argument of that name, ``--guidance-rescale``) and ``freeu`` (default absent: off; ``"s1,s2,b1,b2"`` or four numbers in
-diffusers' ``enable_freeu`` order, ``--freeu``) and ``deepcache`` (default absent: off; ``"N"`` or ``"N,branch"``, ``--deepcache``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
+diffusers' ``enable_freeu`` order, ``--freeu``) and ``tome`` (default absent: off; ``"ratio"`` or ``"ratio,max_downsample"``,
+``--tome``: token merging, tomesd's ``apply_patch`` names) and ``deepcache`` (default absent: off; ``"N"`` or ``"N,branch"``, ``--deepcache``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
 sequence or a mapping, ``--apg``: adaptive projected guidance, the pipeline's argument of that name).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
@@ -268,6 +269,10 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     freeu = parse_freeu(config.get("freeu"))
     if freeu is not None:
         pipeline.enable_freeu(*freeu)
+    # token merging: absent (the default), the pipeline is not touched
+    tome = parse_tome(config.get("tome"))
+    if tome is not None:
+        pipeline.enable_tome(*tome)
     # DeepCache: absent (the default), the pipeline is not touched
     deepcache = parse_deepcache(config.get("deepcache"))
     if deepcache is not None:
@@ -429,6 +434,27 @@ def parse_freeu(value):
     return check_freeu(*parts)
 
 
+def parse_tome(value):
+    """The ``tome`` config key / ``--tome`` flag: ``"ratio"`` or ``"ratio,max_downsample"``, a number, or a sequence of one or two
+    numbers, in tomesd's ``apply_patch`` order -> ``(ratio, max_downsample)`` (max_downsample defaults to 1); ``None`` / empty ->
+    ``None`` (off).  ValueError for anything else."""
+    if value is None or value == "" or value is False:
+        return None
+    if isinstance(value, bool):
+        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}")
+    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
+    if len(parts) not in (1, 2):
+        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}")
+    try:
+        ratio, mds = float(parts[0]), float(parts[1]) if len(parts) == 2 else 1.0
+    except (TypeError, ValueError):
+        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}") from None
+    if mds != int(mds):
+        raise ValueError(f"tome: max_downsample is one of 1, 2, 4, 8, got {value!r}")
+    from .unet_params import check_tome
+    return check_tome(ratio, int(mds))
+
+
 def parse_deepcache(value):
     """The ``deepcache`` config key / ``--deepcache`` flag: ``"N"`` or ``"N,branch"``, an int, or a sequence of one or two ints ->
     ``(cache_interval, cache_branch_id)`` (the branch defaults to 0); ``None`` / empty -> ``None`` (off).  ValueError for anything
@@ -480,6 +506,9 @@ def main(argv=None) -> int:
     ap.add_argument("--freeu", type=str, default=None, metavar="s1,s2,b1,b2",
                     help="FreeU on the UNet's main pass, diffusers' enable_freeu order (SD-2.1: 0.9,0.2,1.4,1.6; default: the config's "
                          "freeu, else off)")
+    ap.add_argument("--tome", type=str, default=None, metavar="ratio[,max_downsample]",
+                    help="token merging in front of the UNet's self-attention, tomesd's apply_patch names: ratio in [0, 0.75], "
+                         "max_downsample one of 1, 2, 4, 8, default 1 (e.g. 0.5; default: the config's tome, else off)")
     ap.add_argument("--deepcache", type=str, default=None, metavar="N[,branch]",
                     help="DeepCache (Ma et al. 2024): the whole UNet at every N-th step, the outermost layers around its stored deep "
                          "feature in between; branch = DeepCache's cache_branch_id, default 0 (e.g. 3 or 3,0; default: the config's "
@@ -498,6 +527,11 @@ def main(argv=None) -> int:
             parse_freeu(args.freeu)
         except ValueError as e:
             ap.error(str(e))
+    if args.tome is not None:
+        try:
+            parse_tome(args.tome)
+        except ValueError as e:
+            ap.error(str(e))
     if args.deepcache is not None:
         try:
             parse_deepcache(args.deepcache)
@@ -514,6 +548,8 @@ def main(argv=None) -> int:
         config["guidance_rescale"] = args.guidance_rescale
     if args.freeu is not None:
         config["freeu"] = args.freeu
+    if args.tome is not None:
+        config["tome"] = args.tome
     if args.deepcache is not None:
         config["deepcache"] = args.deepcache
     if args.apg is not None:
