@@ -257,6 +257,27 @@ int mvd_engine_profile_summary(mvd_engine_t* e, int cap, int* cls, int* launches
  * Returns the number of bytes written (<0 on error). */
 int mvd_engine_profile_shapes(mvd_engine_t* e, char* buf_host, int cap);
 
+/* Main-pass taps (test plumbing, off by default).  With taps on, a forward records every block output of its MAIN pass, in
+ * execution order, under these names:
+ *   conv_in; down_blocks.i.resnets.j, down_blocks.i.attentions.j, down_blocks.i.downsamplers.0; mid_block.resnets.0,
+ *   mid_block.attentions.0, mid_block.resnets.1; up_blocks.i.resnets.j, up_blocks.i.attentions.j, up_blocks.i.upsamplers.0;
+ *   film.down_i / film.up_i, the output of each FiLM hook (MVD_USE_CAMERA; "mid_0" is the identity and has none);
+ *   conv_norm_out.in, the hidden state that enters conv_norm_out (the tensor of the last tap before it).
+ * A DeepCache shallow forward records the blocks it executes.  The encoder pass has no taps (mvd_engine_get_feature reads its
+ * outputs).  The tapped tensors are the pass's own activations, which stay in the workspace until the next call that uses it;
+ * the FiLM hooks of the mid and up blocks, which otherwise modulate in place, write a tensor of their own while taps are on
+ * (the same launch; the block output in front of the hook stays readable), and the mvd_engine_workspace_bytes* entries count
+ * it.  No launch and no synchronisation is added, the forward's output is bit for bit what it is with taps off, and with taps
+ * off a forward and its workspace size are what they were.  mvd_engine_set_taps drops the captured hipGraphs and the records;
+ * a replayed graph restores the records of the forward it captured.
+ *   mvd_engine_num_taps   the number of records of the last issued forward (-1 with taps off)
+ *   mvd_engine_tap_info   name (a host buffer of `cap` bytes) and shape of record `idx`
+ *   mvd_engine_get_tap    the tensor [batch][height][width][channels] bf16 as out_nchw [batch][channels][height][width] fp32 */
+int mvd_engine_set_taps(mvd_engine_t* e, int enable);
+int mvd_engine_num_taps(mvd_engine_t* e);
+int mvd_engine_tap_info(mvd_engine_t* e, int idx, char* name, int cap, int* batch, int* channels, int* height, int* width);
+int mvd_engine_get_tap(mvd_engine_t* e, int idx, float* out_nchw, void* stream);
+
 /* Number / shape / copy-out (NCHW fp32) of the encoder feature maps (image_encoder.py:36-84). */
 int mvd_engine_num_features(mvd_engine_t* e);
 int mvd_engine_feature_shape(mvd_engine_t* e, int idx, int* channels, int* height, int* width);

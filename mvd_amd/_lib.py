@@ -223,6 +223,11 @@ _SIGS = {
     "mvd_op_tome_merge": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mvd_op_tome_unmerge_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_debug_tome_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "mvd_engine_set_taps": (C.c_int, [C.c_void_p, C.c_int]),
+    "mvd_engine_num_taps": (C.c_int, [C.c_void_p]),
+    "mvd_engine_tap_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int)]),
+    "mvd_engine_get_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_engine_set_deepcache": (C.c_int, [C.c_void_p, C.c_int]),
     "mvd_engine_clear_deepcache": (C.c_int, [C.c_void_p]),
     "mvd_engine_deepcache_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

@@ -91,6 +91,12 @@ struct mvd_engine {
   // so replaying some other forward's graph cannot roll it back.
   bool dc_on = false; int dc_branch = 0;
   void* dc_ptr = nullptr; int64_t dc_bytes = 0;
+  // Main-pass taps (mvd_engine_set_taps; include/mvd_hip.h): with taps_on, the record of every block output of the last issued
+  // forward's main pass, in execution order.  The tensors are the pass's own activations (workspace memory, like tome_tab: nothing
+  // of the main pass is freed before the forward ends); only a FiLM hook that runs in place gets an output of its own.
+  struct Tap { std::string name; const bf16_t* p; int B, H, W, C; };
+  bool taps_on = false;
+  std::vector<Tap> taps;
   uint64_t weight_gen = 0;          // bumped by mvd_engine_set_weight / mvd_engine_clear_weights
   struct DeepRecord { bool valid = false; int batch = 0, h = 0, w = 0, cam = 0, img = 0, branch = 0; uint64_t wgen = 0; std::vector<int> layout; } dc_rec;
   bool dc_sizing = false;           // a sizing entry's dry run of a shallow forward: no stored feature is needed to size one
@@ -101,11 +107,12 @@ struct mvd_engine {
     int rc_batch, rc_h, rc_w; bool rc_valid, rc_keep;
     float* cam_emb; int cam_batch;
     std::vector<int> rc_layout;
+    std::vector<Tap> taps;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_layout}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_layout, taps}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
-    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_layout = h.rc_layout;
+    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_layout = h.rc_layout; taps = h.taps;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -745,6 +752,23 @@ struct UNetPass {
     return mvd_launch_film(x.p, x.B, x.hw(), x.C, it->second.first, it->second.second, x.C, out.p, c.s);
   }
 
+  // main-pass taps (mvd_engine::taps): the record of a block output; nothing is launched
+  bool tapping() const { return c.e->taps_on && !o.capture; }
+  void tap(const std::string& name, const Act& a) {
+    if (tapping() && !c.dry && !c.err) c.e->taps.push_back({name, a.p, a.B, a.H, a.W, a.C});
+  }
+  // a FiLM hook of the mid / up blocks, which modulates h in place -- with taps on into a tensor of its own (the same launch, the
+  // same values), so that the block output in front of it stays readable
+  int film_hook(const std::string& name, Act& h) {
+    Act res = h;
+    const bool known = o.film_ss->find(name) != o.film_ss->end();
+    if (known && tapping()) res = c.new_act(h.B, h.H, h.W, h.C, true);
+    CHECK(film(name, h, res));
+    h = res;
+    if (known) tap("film." + name, h);
+    return c.err;
+  }
+
   // positions of a layer in the FULL schedule (the order of enumerate_resnets / enumerate_features): what temb_off, tkv_off, refkv
   // and feat_ev are indexed by.  run() SETS resnet_idx / feat_idx from these in front of every layer it executes -- a shallow
   // (DeepCache) pass skips layers, and a count from 0 would hand its up block the down blocks' slices.
@@ -773,6 +797,7 @@ struct UNetPass {
     Act h = c.new_act(B, H0, W0, C0, true);
     // conv_in: x_in holds im2col rows [B*H*W][64] (k = tap*Cin + ch, zero padded) -> one K=64 MFMA GEMM
     CHECK(c.linear(x_in.p, nullptr, 64, 0, B * H0 * W0, c.WB("conv_in.w", (int64_t)C0 * 64), c.WF("conv_in.b", C0), C0, nullptr, 0, h.p, C0));
+    tap("conv_in", h);
     skips.push_back(h);
     for (int i = 0; i < (shallow ? 1 : n); ++i) {
       const int co = cfg.block_out_channels[i];
@@ -782,11 +807,13 @@ struct UNetPass {
         resnet_idx = down_resnet_pos(i, j);
         CHECK(resnet(bk + ".resnets." + std::to_string(j), h, nullptr, co, r));
         h = r;
+        tap(bk + ".resnets." + std::to_string(j), h);
         if (i + 1 < n) {
           Act t = c.new_act(B, h.H, h.W, co, true);
           feat_idx = down_feat_pos(i, j);
           CHECK(transformer(bk + ".attentions." + std::to_string(j), h, cfg.num_heads[i], t));
           h = t;
+          tap(bk + ".attentions." + std::to_string(j), h);
         }
         skips.push_back(h);
       }
@@ -795,6 +822,7 @@ struct UNetPass {
         Act d = c.new_act(B, (h.H + 1) / 2, (h.W + 1) / 2, co, true);
         CHECK(c.conv3(h, 2, 0, c.WB(bk + ".down.w", (int64_t)co * 9 * co), c.WF(bk + ".down.b", co), nullptr, 0, nullptr, nullptr, nullptr, 0, 0, d));
         h = d;
+        tap(bk + ".downsamplers.0", h);
         skips.push_back(h);
       }
       if (o.film) {  // hook modulates the block's returned hidden_states only; skips stay unmodulated (Q6)
@@ -802,6 +830,7 @@ struct UNetPass {
         Act res = m;
         CHECK(film("down_" + std::to_string(i), h, res));
         h = res;
+        tap("film.down_" + std::to_string(i), h);
       }
     }
     if (!shallow) {
@@ -809,14 +838,17 @@ struct UNetPass {
       Act r = c.new_act(B, h.H, h.W, cm, true);
       resnet_idx = mid_resnet_pos(0);
       CHECK(resnet("mid_block.resnets.0", h, nullptr, cm, r));
+      tap("mid_block.resnets.0", r);
       Act t = c.new_act(B, h.H, h.W, cm, true);
       feat_idx = mid_feat_pos();
       CHECK(transformer("mid_block.attentions.0", r, cfg.num_heads[n - 1], t));
+      tap("mid_block.attentions.0", t);
       Act r2 = c.new_act(B, h.H, h.W, cm, true);
       resnet_idx = mid_resnet_pos(1);
       CHECK(resnet("mid_block.resnets.1", t, nullptr, cm, r2));
       h = r2;
-      if (o.film) { Act res = h; CHECK(film("mid_0", h, res)); h = res; }
+      tap("mid_block.resnets.1", h);
+      if (o.film) CHECK(film_hook("mid_0", h));
     } else {
       // the stored deep feature, read where it lies (nothing below writes its hidden input: the resnet and FreeU only read it)
       h = Act{o.deep_buf, B, H0, W0, c.e->dc_hidden_channels()};
@@ -845,21 +877,25 @@ struct UNetPass {
           CHECK(resnet(bk + ".resnets." + std::to_string(j), h, &skip, co, r));
         }
         h = r;
+        tap(bk + ".resnets." + std::to_string(j), h);
         if (i > 0) {
           Act t = c.new_act(B, h.H, h.W, co, true);
           feat_idx = up_feat_pos(i, j);
           CHECK(transformer(bk + ".attentions." + std::to_string(j), h, cfg.num_heads[n - 1 - i], t));
           h = t;
+          tap(bk + ".attentions." + std::to_string(j), h);
         }
       }
       if (i + 1 < n) {
         Act u = c.new_act(B, h.H * 2, h.W * 2, co, true);
         CHECK(c.conv3(h, 1, 1, c.WB(bk + ".up.w", (int64_t)co * 9 * co), c.WF(bk + ".up.b", co), nullptr, 0, nullptr, nullptr, nullptr, 0, 0, u, bk + ".up.ws", bk + ".up.w4"));
         h = u;
+        tap(bk + ".upsamplers.0", h);
       }
-      if (o.film) { Act res = h; CHECK(film("up_" + std::to_string(i), h, res)); h = res; }
+      if (o.film) CHECK(film_hook("up_" + std::to_string(i), h));
     }
     if (out_nchw) {
+      tap("conv_norm_out.in", h);
       Act t = c.new_act(B, h.H, h.W, C0, false);
       CHECK(c.groupnorm(h.p, nullptr, C0, 0, B, h.hw(), cfg.norm_eps, c.WF("conv_norm_out.g", C0), c.WF("conv_norm_out.b", C0), 1, t.p));
       const bf16_t* wo = c.WB("conv_out.w", (int64_t)cfg.out_channels * 9 * C0);
@@ -1252,6 +1288,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   po.freeu = e->freeu_on;
   po.tome_ratio = e->tome_ratio; po.tome_maxds = e->tome_maxds;
   if (e->tome_keep && !dry) e->tome_tab.assign(e->feats.size(), {});
+  if (!dry) e->taps.clear();
   po.deep = deep; po.deep_branch = e->dc_branch; po.deep_buf = (bf16_t*)e->dc_ptr;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
@@ -1435,6 +1472,7 @@ int mvd_engine_bind_workspace(mvd_engine_t* e, void* ws, int64_t ws_bytes, void*
   e->rc_ptr = refcache; e->rc_bytes = refcache_bytes;
   e->persist.base = (char*)refcache; e->persist.cap = (size_t)(refcache ? refcache_bytes : 0);
   e->rc_valid = false; e->rc_pending = false;
+  e->taps.clear();
   return 0;
 }
 
@@ -1779,6 +1817,35 @@ int mvd_engine_bind_deepcache(mvd_engine_t* e, void* ptr, int64_t bytes) {
   if ((uintptr_t)ptr & 255) { mvd_set_error("bind_deepcache: the buffer must be 256-byte aligned"); return -1; }
   e->dc_ptr = ptr; e->dc_bytes = ptr ? bytes : 0;
   return 0;
+}
+
+// Main-pass taps (include/mvd_hip.h).  Switching drops the captured graphs (a FiLM hook's output moves) and the records
+int mvd_engine_set_taps(mvd_engine_t* e, int enable) {
+  if (!e) { mvd_set_error("set_taps: null engine"); return -1; }
+  e->drop_graphs();
+  e->taps_on = enable != 0;
+  e->taps.clear();
+  return 0;
+}
+int mvd_engine_num_taps(mvd_engine_t* e) {
+  if (!e) { mvd_set_error("num_taps: null engine"); return -1; }
+  if (!e->taps_on) { mvd_set_error("num_taps: taps are not kept (mvd_engine_set_taps)"); return -1; }
+  return (int)e->taps.size();
+}
+int mvd_engine_tap_info(mvd_engine_t* e, int idx, char* name, int cap, int* batch, int* channels, int* height, int* width) {
+  if (!e || !name || cap <= 0 || !batch || !channels || !height || !width) { mvd_set_error("tap_info: bad argument"); return -1; }
+  if (!e->taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("tap_info: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->taps_on ? (int)e->taps.size() : 0); return -1; }
+  const mvd_engine::Tap& t = e->taps[idx];
+  if ((int)t.name.size() >= cap) { mvd_set_error("tap_info: the name '%s' needs %d bytes, the buffer has %d", t.name.c_str(), (int)t.name.size() + 1, cap); return -1; }
+  memcpy(name, t.name.c_str(), t.name.size() + 1);
+  *batch = t.B; *channels = t.C; *height = t.H; *width = t.W;
+  return 0;
+}
+int mvd_engine_get_tap(mvd_engine_t* e, int idx, float* out_nchw, void* stream) {
+  if (!e || !out_nchw) { mvd_set_error("get_tap: bad argument"); return -1; }
+  if (!e->taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("get_tap: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->taps_on ? (int)e->taps.size() : 0); return -1; }
+  const mvd_engine::Tap& t = e->taps[idx];
+  return mvd_launch_nhwc_to_nchw_f32(t.p, t.B, t.H * t.W, t.C, out_nchw, (hipStream_t)stream);
 }
 
 int mvd_engine_num_features(mvd_engine_t* e) { return e ? (int)e->feats.size() : -1; }

@@ -58,6 +58,7 @@ class MVDEngine:
         self.deepcache = None                                     # the branch while DeepCache is set
         self.tome = None                                          # (ratio, max_downsample) while token merging is set
         self._tome_keep = False
+        self._taps = False                                        # main-pass taps are kept (set_taps)
         self._dc = None                                           # the bound buffer of the stored deep feature
 
     def __del__(self):
@@ -374,6 +375,31 @@ class MVDEngine:
                 if L.lib().mvd_engine_tome_table(self._h, i, _ptr(t), C.c_void_p(torch.cuda.current_stream().cuda_stream)) != n:
                     raise L.MvdError(f"tome_table: {L.last_error()}")
                 out[name] = t
+        return out
+
+    def set_taps(self, enable: bool = True) -> None:
+        """Main-pass taps (``mvd_engine_set_taps``; test plumbing): with them on, ``taps()`` reads every block output of the last
+        forward's main pass.  The forward's output does not depend on the switch; its workspace may grow."""
+        L.call("mvd_engine_set_taps", self._h, int(bool(enable)))
+        self._taps = bool(enable)
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            self._ensure_workspace(*self._ws_args)
+
+    def taps(self) -> Dict[str, torch.Tensor]:
+        """``{name: (B, C, H, W) fp32}`` of the block outputs of the last issued forward's main pass, in execution order (the names:
+        include/mvd_hip.h; needs ``set_taps()``)."""
+        n = L.lib().mvd_engine_num_taps(self._h)
+        if n < 0:
+            raise L.MvdError(f"num_taps: {L.last_error()}")
+        out = {}
+        name = C.create_string_buffer(128)
+        b, c, h, w = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        for i in range(n):
+            L.call("mvd_engine_tap_info", self._h, i, name, len(name), C.byref(b), C.byref(c), C.byref(h), C.byref(w))
+            t = torch.empty(b.value, c.value, h.value, w.value, dtype=torch.float32, device=self.device)
+            L.call("mvd_engine_get_tap", self._h, i, _ptr(t), L.stream())
+            out[name.value.decode()] = t
         return out
 
     def set_deepcache(self, branch: int = 0) -> None:

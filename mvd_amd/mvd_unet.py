@@ -296,6 +296,8 @@ class MultiViewUNet(nn.Module):
                 self._engine.clear_tome()
             else:
                 self._engine.set_tome(*tome, keep_tables=self.tome_keep_tables)
+        if bool(getattr(self, "keep_taps", False)) != bool(getattr(self._engine, "_taps", False)):
+            self._engine.set_taps(bool(self.keep_taps))
         branch = None if self.deepcache is None else self.deepcache[1]
         if branch != getattr(self._engine, "deepcache", None):
             self._deep_key, self._deep_hold = False, None
@@ -340,6 +342,17 @@ class MultiViewUNet(nn.Module):
 
     def disable_tome(self):
         self.base_unet.disable_tome()
+
+    # ------------------------------------------------------------------ main-pass taps (test plumbing)
+    keep_taps = False               # keep every block output of the main pass for ``taps()``
+    keep_reference_features = False  # keep the encoder pass's feature maps of a forward for ``_engine.features()``
+
+    def taps(self) -> Dict[str, torch.Tensor]:
+        """``{block name: (B, C, H, W) fp32}`` of the last forward's main pass, in execution order (``keep_taps = True`` before
+        the forward; the names: include/mvd_hip.h ``mvd_engine_set_taps``)."""
+        if self._engine is None:
+            raise L.MvdError("taps(): no forward yet")
+        return self._engine.taps()
 
     # ------------------------------------------------------------------ DeepCache (DeepCacheSDHelper's parameter names)
     def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):
@@ -478,9 +491,10 @@ class MultiViewUNet(nn.Module):
                 raise L.MvdError('deep_cache="reuse": the engine holds no valid reference K/V for this forward (its buffers were re-bound '
                                  'since the deep_cache="refresh" forward)')
             if hit:
-                img = dict(reuse_ref=True, keep_features=glob)
+                img = dict(reuse_ref=True, keep_features=glob or bool(getattr(self, "keep_reference_features", False)))
             else:
-                img = dict(source_latents=self._f32(source_image_latents, dev), encoder_text=enc_text.contiguous())
+                img = dict(source_latents=self._f32(source_image_latents, dev), encoder_text=enc_text.contiguous(),
+                           keep_features=bool(getattr(self, "keep_reference_features", False)))
                 self._ref_key = key
                 self._ref_hold = (source_image_latents, encoder_hidden_states) if self.cache_reference else None
                 if glob:

@@ -315,9 +315,12 @@ def multiview_unet_forward(
     use_image_conditioning: bool = True,
     simple_cam_encoder: bool = False,
     features_out: Optional[Dict[str, torch.Tensor]] = None,
+    trace: Optional[Dict[str, tuple]] = None,
 ) -> torch.Tensor:
     """Full reference-faithful forward.  ``params`` uses the wrapper's key prefixes
-    ``base_unet.``, ``camera_encoder.``, ``image_encoder.unet.``."""
+    ``base_unet.``, ``camera_encoder.``, ``image_encoder.unet.``.  ``trace``: the main
+    pass's blocks (``sd21_unet.unet_forward``); ``sample`` names the caller's sample,
+    in front of the ``output`` modulation."""
     p_base = _sub(params, "base_unet.")
     B = sample.shape[0]
     # mvd_unet.py:233-237 -- CFG: repeat text to the sample batch
@@ -369,7 +372,8 @@ def multiview_unet_forward(
             return x
         return apply_modulation(p_cam, name, x, emb, cam_modulation_strength)  # "mid_0" -> identity (Q3)
 
-    return U.unet_forward(p_base, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook)
+    kw = {} if trace is None else {"trace": trace}      # (callers that wrap unet_forward need not know the argument)
+    return U.unet_forward(p_base, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, **kw)
 
 
 def init_mvd_params(cfg: U.UNetConfig, seed=0, cam_dim=1024, cam_hidden=512, simple=False,

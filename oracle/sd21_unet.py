@@ -21,6 +21,10 @@ reference re-enters diffusers:
   the ``nn.Module`` forward hooks of /root/reference/src/models/mvd_unet.py:354-380.
 * ``capture`` dict -- filled with every Transformer2DModel output (NCHW), i.e.
   the 16 hooks of /root/reference/src/models/image_encoder.py:36-84.
+* ``trace`` dict -- filled, in execution order, with ``name -> (output, names of
+  the inputs)`` of every block under the engine's tap names (include/mvd_hip.h
+  ``mvd_engine_set_taps``), plus ``conv_out``; ``sample`` names the input of
+  ``conv_in``.  An up-block resnet has two inputs: the hidden state and the skip.
 """
 from __future__ import annotations
 
@@ -294,6 +298,7 @@ def unet_forward(
     attn_hook: Optional[AttnHook] = None,
     block_hook: Optional[Callable[[str, torch.Tensor], torch.Tensor]] = None,
     capture: Optional[Dict[str, torch.Tensor]] = None,
+    trace: Optional[Dict[str, Tuple[torch.Tensor, Tuple[str, ...]]]] = None,
 ) -> torch.Tensor:
     """One UNet forward.  ``sample`` (B,Cin,H,W), ``text`` (B,L,xdim), ``timestep`` 0-d or (B,)."""
     G, eps = cfg.norm_num_groups, cfg.norm_eps
@@ -312,50 +317,72 @@ def unet_forward(
             capture[name] = x
         return x
 
-    def bh(name, x):
-        return block_hook(name, x) if block_hook is not None else x
+    last = ["sample"]        # trace: the name of the tensor h holds
 
-    h = F.conv2d(sample, p["conv_in.weight"], p["conv_in.bias"], padding=1)
+    def tr(name, x, *inputs):
+        if trace is not None:
+            trace[name] = (x, inputs if inputs else (last[0],))
+            last[0] = name
+        return x
+
+    def bh(name, x):
+        if block_hook is None:
+            return x
+        y = block_hook(name, x)
+        return y if y is x else tr(f"film.{name}", y)      # (an unknown modulator is the identity and no block)
+
+    h = tr("conv_in", F.conv2d(sample, p["conv_in.weight"], p["conv_in.bias"], padding=1))
     skips = [h]
+    skip_names = ["conv_in"]
     for i in range(cfg.num_levels):
         for j in range(cfg.layers_per_block):
-            h = resnet_block(p, f"down_blocks.{i}.resnets.{j}", h, temb_act, G, eps)
+            h = tr(f"down_blocks.{i}.resnets.{j}", resnet_block(p, f"down_blocks.{i}.resnets.{j}", h, temb_act, G, eps))
             if cfg.down_has_attn(i):
                 name = f"down_block_{i}_attn_{j}"
                 h = cap(name, transformer_2d(p, f"down_blocks.{i}.attentions.{j}", h, text,
                                              cfg.num_heads[i], G, attn_hook, name))
+                tr(f"down_blocks.{i}.attentions.{j}", h)
             skips.append(h)
+            skip_names.append(last[0])
         if i < cfg.num_levels - 1:
             h = F.conv2d(h, p[f"down_blocks.{i}.downsamplers.0.conv.weight"],
                          p[f"down_blocks.{i}.downsamplers.0.conv.bias"], stride=2, padding=1)
+            tr(f"down_blocks.{i}.downsamplers.0", h)
             skips.append(h)
+            skip_names.append(last[0])
         # forward hook modulates the returned hidden_states only, never the skip tuple (Q6)
         h = bh(f"down_{i}", h)
 
-    h = resnet_block(p, "mid_block.resnets.0", h, temb_act, G, eps)
+    h = tr("mid_block.resnets.0", resnet_block(p, "mid_block.resnets.0", h, temb_act, G, eps))
     h = cap("mid_block_attn_0", transformer_2d(p, "mid_block.attentions.0", h, text,
                                                cfg.num_heads[-1], G, attn_hook, "mid_block_attn_0"))
-    h = resnet_block(p, "mid_block.resnets.1", h, temb_act, G, eps)
+    tr("mid_block.attentions.0", h)
+    h = tr("mid_block.resnets.1", resnet_block(p, "mid_block.resnets.1", h, temb_act, G, eps))
     h = bh("mid_0", h)
 
     rev_heads = list(reversed(cfg.num_heads))
     for i in range(cfg.num_levels):
         for j in range(cfg.layers_per_block + 1):
             skip = skips.pop()
+            skip_name = skip_names.pop()
             h = torch.cat([h, skip], dim=1)
             h = resnet_block(p, f"up_blocks.{i}.resnets.{j}", h, temb_act, G, eps)
+            tr(f"up_blocks.{i}.resnets.{j}", h, last[0], skip_name)
             if cfg.up_has_attn(i):
                 name = f"up_block_{i}_attn_{j}"
                 h = cap(name, transformer_2d(p, f"up_blocks.{i}.attentions.{j}", h, text,
                                              rev_heads[i], G, attn_hook, name))
+                tr(f"up_blocks.{i}.attentions.{j}", h)
         if i < cfg.num_levels - 1:
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")
             h = F.conv2d(h, p[f"up_blocks.{i}.upsamplers.0.conv.weight"],
                          p[f"up_blocks.{i}.upsamplers.0.conv.bias"], padding=1)
+            tr(f"up_blocks.{i}.upsamplers.0", h)
         h = bh(f"up_{i}", h)
 
+    tr("conv_norm_out.in", h)
     h = F.silu(_gn(h, p, "conv_norm_out", G, eps))
-    return F.conv2d(h, p["conv_out.weight"], p["conv_out.bias"], padding=1)
+    return tr("conv_out", F.conv2d(h, p["conv_out.weight"], p["conv_out.bias"], padding=1))
 
 
 def feature_names(cfg: UNetConfig) -> List[str]:

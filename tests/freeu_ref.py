@@ -107,11 +107,11 @@ def freeu_oracle(s1, s2, b1, b2, *, blocks=(0, 1), use_b=True, use_s=True, flip_
     orig_forward, orig_resnet = OU.unet_forward, OU.resnet_block
     state = {"cfg": None}
 
-    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None):
+    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None, **kw):
         prev = state["cfg"]
         state["cfg"] = cfg if capture is None else None
         try:
-            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture)
+            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture, **kw)
         finally:
             state["cfg"] = prev
 
