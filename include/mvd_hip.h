@@ -214,6 +214,24 @@ int mvd_engine_set_tome(mvd_engine_t* e, double ratio, int max_downsample, int k
 int mvd_engine_clear_tome(mvd_engine_t* e);
 int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* stream);
 
+/* Token downsampling (ToDo: Smith, Saxena and Saha, IJCAI 2024, restated; mvd_op_todo_downsample below)
+ * of the keys and values of attn1 in the MAIN pass's transformer blocks.  A block whose map is H x W of a latent H0 x W0 has
+ * down = ceil(sqrt((H0 W0) / (H W))) (token merging's rule); down 1 takes `factor`, down 2 `factor_level_2`, a deeper block is never
+ * downsampled.  With a factor f in {2, 3, 4} and H / f >= 1, W / f >= 1 the block runs the fused LayerNorm + q/k/v GEMM as ever, ONE
+ * pooling launch of the K and V columns into a compact [batch][Nk][2C] buffer, Nk = (H / f)(W / f), and the attention launch with
+ * nq = H W queries against nk = Nk keys; the adapter's self branch (Q_ref of all H W rows against the reference K/V at full
+ * length, every layout map), the out-projection with the residual, attn2, the feed-forward, the encoder pass and the cached
+ * reference are what they were.  method 0: nearest (the top-left token of each cell), 1: area (the cell's mean).
+ * A factor outside [1, 4] or a method outside {0, 1}: -1.  While token merging is set (ratio > 0) set_todo with a factor above 1 is
+ * refused, and mvd_engine_set_tome with a ratio above 0 is refused while a factor is above 1: -1 and a message, nothing changes.
+ * Both factors 1, or clear: the launches of a forward are what they were.  Both entries drop the captured hipGraphs and invalidate
+ * DeepCache's stored feature (a deep feature of another setting is stale); the workspace entries size the forward of the current
+ * setting.  mvd_engine_todo_keys: out[i], i < min(n, features) = Nk of feature i's block in the last issued forward (0: it was not
+ * downsampled, or no forward yet); host memory; returns the number of features. */
+int mvd_engine_set_todo(mvd_engine_t* e, int factor, int factor_level_2, int method);
+int mvd_engine_clear_todo(mvd_engine_t* e);
+int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n);
+
 /* DeepCache (Ma et al., CVPR 2024; the DeepCacheSDHelper used with diffusers, restated): the deep, low-resolution features of
  * the main pass change little between neighbouring denoising steps, so a step may reuse them.  With n = num_levels,
  * Lb = layers_per_block, a branch b in [0, Lb) (DeepCache's cache_branch_id) and j0 = Lb - 1 - b, the DEEP FEATURE is the hidden
@@ -658,6 +676,16 @@ int mvd_op_tome_match(const void* x, int B, int H, int W, int C, int r, int* slo
 int mvd_op_tome_merge(const void* x, int B, int H, int W, int C, int r, const int* members, const int* starts, void* out, void* stream);
 int mvd_op_tome_unmerge_add(void* h, const void* t, int B, int H, int W, int C, int r, const int* slot, void* stream);
 int mvd_debug_tome_plan(int H, int W, int C, int r, int64_t* out);
+
+/* Token downsampling (ToDo, restated) of K and V rows: k and v point at the K and V columns of token-major bf16 rows
+ * [B][H*W] that share the row stride ld (elements; the fused q/k/v buffer: 3C or 4C) and the batch stride H W ld.  The key map is
+ * Hk x Wk = (H / f) x (W / f); tokens of an incomplete last row or column of cells are in no key.
+ *   method 0 (nearest)  key (i, j) = the row of token (i f, j f), bit for bit
+ *   method 1 (area)     key (i, j) = bf16(fp32 sum of the cell's f*f rows in row-major order / float(f*f)), RNE
+ * out [B][Hk Wk][2C] bf16: K in columns [0, C), V in [C, 2C).  One launch.  -1 (mvd_last_error) before it for f outside {2, 3, 4},
+ * a method outside {0, 1}, C no positive multiple of 8, ld no multiple of 8 or below C, a null or not 16-byte aligned pointer,
+ * H / f or W / f = 0, or out overlapping the input rows. */
+int mvd_op_todo_downsample(const void* k, const void* v, int ld, int B, int H, int W, int C, int f, int method, void* out, void* stream);
 
 /* ---- checkpoint scoring around the UNet, fp32 ------------------------------------------------ */
 /* Conventions of the helpers above; in addition every quantity that depends on a sample's timestep is read ON THE DEVICE

@@ -228,6 +228,10 @@ _SIGS = {
     "mvd_engine_tap_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
     "mvd_engine_get_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "mvd_engine_set_todo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mvd_engine_clear_todo": (C.c_int, [C.c_void_p]),
+    "mvd_engine_todo_keys": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "mvd_op_todo_downsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mvd_engine_set_deepcache": (C.c_int, [C.c_void_p, C.c_int]),
     "mvd_engine_clear_deepcache": (C.c_int, [C.c_void_p]),
     "mvd_engine_deepcache_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

@@ -85,6 +85,10 @@ struct mvd_engine {
   double tome_ratio = 0.0; int tome_maxds = 1; bool tome_keep = false;
   struct TomeTable { int* p = nullptr; int64_t n = 0; };
   std::vector<TomeTable> tome_tab;
+  // Token downsampling (mvd_engine_set_todo): attn1 of the main pass's eligible blocks reads pooled K/V.  todo_f[0] / [1]: the factor at
+  // the latent's own level / one level below (1: off); todo_nk: the keys of every feature's block in the last issued forward (0: full)
+  int todo_f[2] = {1, 1}, todo_method = 0;
+  std::vector<int> todo_nk;
   // DeepCache (mvd_engine_set_deepcache; include/mvd_hip.h): the stored deep feature lives in a buffer of its own (the reference
   // cache's allocator is reset by every cold forward) and carries the record of the refresh forward that wrote it.  The record is
   // NOT part of HostState: it is written by unet_forward once a refresh forward has been issued (launched, captured or replayed),
@@ -108,11 +112,12 @@ struct mvd_engine {
     float* cam_emb; int cam_batch;
     std::vector<int> rc_layout;
     std::vector<Tap> taps;
+    std::vector<int> todo_nk;
   };
-  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_layout, taps}; }
+  HostState host_state() const { return {refkv, feat_keep, rc_batch, rc_h, rc_w, rc_valid, rc_keep, cam_emb, cam_batch, rc_layout, taps, todo_nk}; }
   void set_host_state(const HostState& h) {
     refkv = h.refkv; feat_keep = h.feat_keep; rc_batch = h.rc_batch; rc_h = h.rc_h; rc_w = h.rc_w; rc_valid = h.rc_valid;
-    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_layout = h.rc_layout; taps = h.taps;
+    rc_keep = h.rc_keep; cam_emb = h.cam_emb; cam_batch = h.cam_batch; rc_layout = h.rc_layout; taps = h.taps; todo_nk = h.todo_nk;
   }
   struct GraphEntry { std::string key; hipGraph_t g; hipGraphExec_t x; HostState after; };
   bool dual_late = false;                   // set by the main pass once it runs (mostly) alone again: single-stream launch policy
@@ -561,6 +566,8 @@ struct PassOpts {
   bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
   double tome_ratio = 0.0;    // main pass with token merging set on the engine (0: off); blocks down to tome_maxds merge
   int tome_maxds = 1;
+  int todo_f[2] = {1, 1};     // main pass with token downsampling set on the engine: the K/V factor by level (1: off), and the method
+  int todo_method = 0;
   int deep = 0;               // main pass, DeepCache: MVD_DEEPCACHE_REFRESH (store the deep feature) / _SHALLOW (start from it); 0: neither
   int deep_branch = 0;        // the branch b: down_blocks.0 layers 0..b and up_blocks.{n-1} layers Lb-1-b..Lb are the shallow forward
   bf16_t* deep_buf = nullptr; // the bound buffer: [B][H0][W0][C of the deep feature]
@@ -668,6 +675,18 @@ struct UNetPass {
       MvdAttnArgs a; memset(&a, 0, sizeof(a));
       a.batch = B_; a.heads = heads; a.scale = scale; a.prescaled = 1; a.nprob = ad ? 2 : 1;
       a.p[0] = {qkv, qkv + C, qkv + 2 * C, o_self, nq, nq, nq, C, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * nq, (int64_t)hw * C, hw, hw};
+      const int todo_f = todo_factor(x.H, x.W);
+      if (todo_f > 1) {
+        // token downsampling (include/mvd_hip.h mvd_engine_set_todo): the self problem's keys and values from the pooled K/V rows;
+        // the queries, the adapter's problem and the out-projection are untouched
+        const int Nk = (x.H / todo_f) * (x.W / todo_f);
+        bf16_t* kv = c.talloc<bf16_t>((size_t)B_ * Nk * 2 * C);
+        if (!c.dry && !c.err) {
+          if (feat_idx < (int)c.e->todo_nk.size()) c.e->todo_nk[feat_idx] = Nk;
+          CHECK(mvd_launch_todo_downsample(qkv + C, qkv + 2 * C, nq, B_, x.H, x.W, C, todo_f, o.todo_method, kv, c.s));
+        }
+        a.p[0].k = kv; a.p[0].v = kv + C; a.p[0].ldk = a.p[0].ldv = 2 * C; a.p[0].bsk = a.p[0].bsv = (int64_t)Nk * 2 * C; a.p[0].nk = Nk;
+      }
       if (ad) a.p[1] = {qkv + 3 * C, rkv, rkv + C, o_ref, nq, 4 * C, 4 * C, C, (int64_t)hw * nq, (int64_t)ref_nk * 4 * C, (int64_t)ref_nk * 4 * C, (int64_t)hw * C, hw, ref_nk};
       if (ad) o.layout->fill_map(true, &a.kv_group[1], &a.kv_objects[1], &a.kv_index[1]);
       CHECK(c.attention(a));
@@ -743,6 +762,17 @@ struct UNetPass {
     const int ns = H * W - (H / 2) * (W / 2);
     const int r = (int)((double)(H * W) * o.tome_ratio);
     return r < ns ? r : ns;
+  }
+
+  // the K/V factor of a block whose map is H x W; 1: attn1 reads its own K/V rows (down as in tome_merged; deeper than 2: never)
+  int todo_factor(int H, int W) const {
+    if (o.capture || (o.todo_f[0] <= 1 && o.todo_f[1] <= 1)) return 1;
+    const long q = ((long)H0 * W0) / ((long)H * W);
+    long down = 0;
+    while (down * down < q) ++down;
+    if (down < 1 || down > 2) return 1;
+    const int f = o.todo_f[down - 1];
+    return (f > 1 && H / f >= 1 && W / f >= 1) ? f : 1;
   }
 
   int film(const std::string& name, const Act& x, Act& out) {
@@ -1288,6 +1318,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   po.freeu = e->freeu_on;
   po.tome_ratio = e->tome_ratio; po.tome_maxds = e->tome_maxds;
   if (e->tome_keep && !dry) e->tome_tab.assign(e->feats.size(), {});
+  po.todo_f[0] = e->todo_f[0]; po.todo_f[1] = e->todo_f[1]; po.todo_method = e->todo_method;
+  if (!dry) e->todo_nk.assign(e->feats.size(), 0);
   if (!dry) e->taps.clear();
   po.deep = deep; po.deep_branch = e->dc_branch; po.deep_buf = (bf16_t*)e->dc_ptr;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
@@ -1769,6 +1801,7 @@ int mvd_engine_set_tome(mvd_engine_t* e, double ratio, int max_downsample, int k
   if (!e) { mvd_set_error("set_tome: null engine"); return -1; }
   if (!(ratio >= 0.0) || !(ratio <= 0.75)) { mvd_set_error("set_tome: ratio must lie in [0, 0.75] (a quarter of the tokens are dst and stay), got %g", ratio); return -1; }
   if (max_downsample != 1 && max_downsample != 2 && max_downsample != 4 && max_downsample != 8) { mvd_set_error("set_tome: max_downsample must be one of 1, 2, 4, 8, got %d", max_downsample); return -1; }
+  if (ratio > 0.0 && (e->todo_f[0] > 1 || e->todo_f[1] > 1)) { mvd_set_error("set_tome: token downsampling is set (factors %d, %d): the two are alternatives, clear it first (mvd_engine_clear_todo)", e->todo_f[0], e->todo_f[1]); return -1; }
   e->drop_graphs();
   e->tome_ratio = ratio; e->tome_maxds = max_downsample; e->tome_keep = keep_tables != 0;
   e->tome_tab.clear();
@@ -1788,6 +1821,33 @@ int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* 
   const auto& t = e->tome_tab[feature_idx];
   if (out && hipMemcpyAsync(out, t.p, (size_t)t.n * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("tome_table: copy failed"); return -3; }
   return t.n;
+}
+
+// Token downsampling on the main pass (include/mvd_hip.h).  Both drop the captured graphs and invalidate DeepCache's stored feature
+int mvd_engine_set_todo(mvd_engine_t* e, int factor, int factor_level_2, int method) {
+  if (!e) { mvd_set_error("set_todo: null engine"); return -1; }
+  if (factor < 1 || factor > 4 || factor_level_2 < 1 || factor_level_2 > 4) { mvd_set_error("set_todo: factor and factor_level_2 must lie in [1, 4], got %d and %d", factor, factor_level_2); return -1; }
+  if (method != 0 && method != 1) { mvd_set_error("set_todo: the method is 0 (nearest) or 1 (area), got %d", method); return -1; }
+  if ((factor > 1 || factor_level_2 > 1) && e->tome_ratio > 0.0) { mvd_set_error("set_todo: token merging is set (ratio %g): the two are alternatives, clear it first (mvd_engine_clear_tome)", e->tome_ratio); return -1; }
+  e->drop_graphs();
+  e->dc_rec.valid = false;
+  e->todo_f[0] = factor; e->todo_f[1] = factor_level_2; e->todo_method = method;
+  e->todo_nk.clear();
+  return 0;
+}
+int mvd_engine_clear_todo(mvd_engine_t* e) {
+  if (!e) { mvd_set_error("clear_todo: null engine"); return -1; }
+  e->drop_graphs();
+  e->dc_rec.valid = false;
+  e->todo_f[0] = e->todo_f[1] = 1; e->todo_method = 0;
+  e->todo_nk.clear();
+  return 0;
+}
+int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n) {
+  if (!e || !out || n < 0) { mvd_set_error("todo_keys: bad argument"); return -1; }
+  const int nf = (int)e->feats.size();
+  for (int i = 0; i < n && i < nf; ++i) out[i] = i < (int)e->todo_nk.size() ? e->todo_nk[i] : 0;
+  return nf;
 }
 
 // DeepCache (include/mvd_hip.h).  Setting, clearing and binding drop the captured graphs (their nodes hold the branch's schedule and

@@ -220,6 +220,11 @@ int mvd_launch_tome_match(const bf16_t* x, int B, int H, int W, int C, int r, in
                           void* ws, int64_t ws_bytes, hipStream_t stream);
 int mvd_launch_tome_merge(const bf16_t* x, int B, int H, int W, int C, int r, const int* members, const int* starts, bf16_t* out, hipStream_t stream);
 int mvd_launch_tome_unmerge_add(bf16_t* h, const bf16_t* t, int B, int H, int W, int C, int r, const int* slot, hipStream_t stream);
+// Token downsampling of the self-attention keys (todo.hip; include/mvd_hip.h mvd_op_todo_downsample): the K and V columns of the
+// fused q/k/v rows (row stride ld, batch stride H*W*ld) of an H x W map -> out [B][(H/f)(W/f)][2C], K | V.  method 0: the top-left
+// token of every complete f x f cell; 1: the cell's mean.  One launch; every argument is checked before it (-1 and a message)
+int mvd_launch_todo_downsample(const bf16_t* k, const bf16_t* v, int ld, int B, int H, int W, int C, int f, int method, bf16_t* out,
+                               hipStream_t stream);
 // conv_in: 3x3 pad 1, tiny Cin (<=8) -> Cout, NHWC bf16 in/out, weights fp32 [Cout][3][3][Cin]
 int mvd_launch_conv_in(const bf16_t* x, int batch, int h, int w, int cin, const float* wt, const float* bias,
                        int cout, bf16_t* y, hipStream_t s);

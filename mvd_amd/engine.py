@@ -58,6 +58,7 @@ class MVDEngine:
         self.deepcache = None                                     # the branch while DeepCache is set
         self.tome = None                                          # (ratio, max_downsample) while token merging is set
         self._tome_keep = False
+        self.todo = None                                          # (factor, factor_level_2, method) while token downsampling is set
         self._taps = False                                        # main-pass taps are kept (set_taps)
         self._dc = None                                           # the bound buffer of the stored deep feature
 
@@ -376,6 +377,34 @@ class MVDEngine:
                     raise L.MvdError(f"tome_table: {L.last_error()}")
                 out[name] = t
         return out
+
+    def set_todo(self, factor: int = 2, factor_level_2: int = 1, method: str = "nearest") -> None:
+        """Token downsampling of the self-attention keys and values on the main UNet pass (``mvd_engine_set_todo``): blocks at the
+        latent's own resolution pool K/V by ``factor``, blocks one level below by ``factor_level_2`` (1: untouched); ``method`` is
+        ``"nearest"`` or ``"area"``.  Refused while token merging is set."""
+        from .unet_params import TODO_METHODS, check_todo
+        factor, factor_level_2, method = check_todo(factor, factor_level_2, method)
+        L.call("mvd_engine_set_todo", self._h, factor, factor_level_2, TODO_METHODS.index(method))
+        self.todo = (factor, factor_level_2, method)
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            self._ensure_workspace(*self._ws_args)
+
+    def clear_todo(self) -> None:
+        """Back to the forward without token downsampling (``mvd_engine_clear_todo``): the launches it made before."""
+        L.call("mvd_engine_clear_todo", self._h)
+        self.todo = None
+        self._ws_resize = True
+        if self._ws_key is not None and self._ws_args is not None:
+            self._ensure_workspace(*self._ws_args)
+
+    def todo_keys(self) -> Dict[str, int]:
+        """``{feature name: Nk}`` of the blocks whose self-attention ran on downsampled keys in the last issued forward."""
+        names = [name for _, name, _, _ in self.cfg.transformers()]
+        out = (C.c_int * len(names))()
+        if L.lib().mvd_engine_todo_keys(self._h, out, len(names)) < 0:
+            raise L.MvdError(f"todo_keys: {L.last_error()}")
+        return {name: int(nk) for name, nk in zip(names, out) if nk}
 
     def set_taps(self, enable: bool = True) -> None:
         """Main-pass taps (``mvd_engine_set_taps``; test plumbing): with them on, ``taps()`` reads every block output of the last

@@ -290,12 +290,21 @@ class MultiViewUNet(nn.Module):
                 self._engine.clear_freeu()
             else:
                 self._engine.set_freeu(*self.freeu)
+        # (token merging and token downsampling are alternatives and the engine refuses one while the other is set: whichever is
+        #  being switched off goes first)
+        todo = self.todo if self.todo is not None and (self.todo[0] > 1 or self.todo[1] > 1) else None
+        if todo is None and getattr(self._engine, "todo", None) is not None:
+            self._deep_key, self._deep_hold = False, None
+            self._engine.clear_todo()
         tome = self.tome if self.tome is not None and self.tome[0] > 0.0 else None
         if tome != getattr(self._engine, "tome", None) or (tome is not None and self.tome_keep_tables != getattr(self._engine, "_tome_keep", False)):
             if tome is None:
                 self._engine.clear_tome()
             else:
                 self._engine.set_tome(*tome, keep_tables=self.tome_keep_tables)
+        if todo is not None and todo != getattr(self._engine, "todo", None):
+            self._deep_key, self._deep_hold = False, None       # (a deep feature stored under another setting is stale)
+            self._engine.set_todo(*todo)
         if bool(getattr(self, "keep_taps", False)) != bool(getattr(self._engine, "_taps", False)):
             self._engine.set_taps(bool(self.keep_taps))
         branch = None if self.deepcache is None else self.deepcache[1]
@@ -342,6 +351,24 @@ class MultiViewUNet(nn.Module):
 
     def disable_tome(self):
         self.base_unet.disable_tome()
+
+    # ------------------------------------------------------------------ token downsampling (ToDo)
+    @property
+    def todo(self):
+        """``(factor, factor_level_2, method)`` while token downsampling is enabled, else ``None``; kept on ``base_unet``."""
+        return self.base_unet.todo
+
+    def enable_todo(self, factor: int = 2, factor_level_2: int = 1, method: str = "nearest"):
+        """Token downsampling (ToDo: Smith, Saxena and Saha 2024) on the main UNet pass: the self-attention of the transformer
+        blocks at the latent's own resolution keeps every query and reads its keys and values from the token map downsampled by
+        ``factor`` (``method="nearest"``: the top-left token of each cell; ``"area"``: the cell's mean); blocks one level below
+        use ``factor_level_2``, deeper blocks are never touched.  The adapter's self branch, ``attn2``,
+        the feed-forward, the image-encoder pass and the cached reference do not depend on it.  The alternative to
+        ``enable_tome``: enabling one while the other is on raises."""
+        self.base_unet.enable_todo(factor, factor_level_2, method)
+
+    def disable_todo(self):
+        self.base_unet.disable_todo()
 
     # ------------------------------------------------------------------ main-pass taps (test plumbing)
     keep_taps = False               # keep every block output of the main pass for ``taps()``

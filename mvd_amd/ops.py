@@ -992,6 +992,51 @@ def tome_plan(H, W, C_, r):
                 max_tokens=out[7])
 
 
+TODO_METHODS = ("nearest", "area")          # method of mvd_op_todo_downsample, by index
+
+
+def todo_downsample(qkv_or_k, v, H, W, f, method, out=None, channels=None):
+    """Token downsampling of K and V rows (``mvd_op_todo_downsample``, one launch): the keys and values of an ``H`` x ``W`` token map
+    pooled by the factor ``f`` into ``out`` (B, (H // f) * (W // f), 2C) bf16, K in columns ``[0, C)`` and V in ``[C, 2C)``.
+    ``method``: ``"nearest"`` (the top-left token of every complete f x f cell, bit for bit) or ``"area"`` (the cell's mean: fp32 sum
+    in row-major order, divided by f*f, one rounding to bf16); 0 / 1 are taken too.
+    ``qkv_or_k`` and ``v`` are the K and V columns, (B, H*W, C) views with a shared row stride (slices of the fused q/k/v rows:
+    ``qkv[..., C:2*C]`` and ``qkv[..., 2*C:3*C]``).  With ``v=None`` the first argument is the fused (B, H*W, 3C or 4C) buffer itself,
+    q | k | v [| q_ref], of ``channels`` channels (default: a third of its width)."""
+    if v is None:
+        qkv = qkv_or_k
+        _bf16(qkv)
+        Cc = int(channels) if channels is not None else qkv.shape[-1] // 3
+        if qkv.dim() != 3 or qkv.shape[-1] < 3 * Cc or Cc <= 0:
+            raise L.MvdError(f"todo_downsample: expected fused (B, H*W, >= 3C) q/k/v rows, got {tuple(qkv.shape)} with C = {Cc}")
+        k, v = qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:3 * Cc]
+    else:
+        k = qkv_or_k
+    for t in (k, v):
+        if t.dtype != torch.bfloat16 or not t.is_cuda or t.dim() != 3:
+            raise L.MvdError(f"todo_downsample: k and v must be (B, H*W, C) bf16 tensors on the GPU, got {t.dtype} {tuple(t.shape)}")
+    B, HW, Cc = k.shape
+    if tuple(v.shape) != (B, HW, Cc) or HW != int(H) * int(W):
+        raise L.MvdError(f"todo_downsample: expected k and v (B, {int(H) * int(W)}, C), got {tuple(k.shape)} and {tuple(v.shape)}")
+    ld = k.stride(1)
+    if k.stride(2) != 1 or v.stride() != k.stride() or (B > 1 and k.stride(0) != HW * ld):
+        raise L.MvdError(f"todo_downsample: k and v must share a row stride and the batch stride H*W*ld, got strides {k.stride()} and {v.stride()}")
+    m = TODO_METHODS.index(method) if method in TODO_METHODS else method
+    if isinstance(m, bool) or not isinstance(m, int):
+        raise L.MvdError(f"todo_downsample: method must be one of {TODO_METHODS}, got {method!r}")
+    fi = int(f)
+    Nk = (int(H) // fi) * (int(W) // fi) if fi > 0 else 0
+    if out is None:
+        out = torch.empty(B, max(Nk, 1), 2 * Cc, dtype=torch.bfloat16, device=k.device)
+        if Nk < 1:
+            out = out[:, :0]
+    _bf16(out)
+    if Nk >= 1 and tuple(out.shape) != (B, Nk, 2 * Cc):
+        raise L.MvdError(f"todo_downsample: expected out {(B, Nk, 2 * Cc)}, got {tuple(out.shape)}")
+    L.call("mvd_op_todo_downsample", C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), int(ld), B, int(H), int(W), Cc, fi, int(m), _p(out), _s())
+    return out
+
+
 PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")       # prediction_type of mvd_op_noise_loss, by index
 
 

@@ -215,6 +215,14 @@ class MVDPipeline:
     def disable_tome(self):
         self.unet.disable_tome()
 
+    def enable_todo(self, factor: int = 2, factor_level_2: int = 1, method: str = "nearest"):
+        """Token downsampling of the UNet's self-attention keys and values (ToDo) for every call that follows -- ``__call__``,
+        ``generate_views`` and ``generate_views_batch`` alike (``MultiViewUNet.enable_todo``)."""
+        self.unet.enable_todo(factor, factor_level_2, method)
+
+    def disable_todo(self):
+        self.unet.disable_todo()
+
     def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0):
         """DeepCache (``DeepCacheSDHelper``'s parameters) for every call that follows -- ``__call__``, ``generate_views`` and
         ``generate_views_batch`` alike: every ``cache_interval``-th step runs the whole UNet, the steps in between only its

@@ -176,10 +176,28 @@ class UNet2DConditionParams(_NoForward):
         if not self._freeu_main:
             raise ValueError("enable_tome: token merging applies to the main pass only -- call it on MultiViewUNet.base_unet (the "
                              "image encoder's pass and the cached reference K/V never merge)")
-        self.tome = check_tome(ratio, max_downsample)
+        tome = check_tome(ratio, max_downsample)
+        if tome[0] > 0.0 and self.todo is not None and (self.todo[0] > 1 or self.todo[1] > 1):
+            raise ValueError("enable_tome: token downsampling is enabled and the two are alternatives -- disable_todo() first")
+        self.tome = tome
 
     def disable_tome(self):
         self.tome = None
+
+    # token downsampling of the self-attention keys (ToDo): the alternative to token merging
+    todo = None                 # (factor, factor_level_2, method) while enabled
+
+    def enable_todo(self, factor: int = 2, factor_level_2: int = 1, method: str = "nearest"):
+        if not self._freeu_main:
+            raise ValueError("enable_todo: token downsampling applies to the main pass only -- call it on MultiViewUNet.base_unet (the "
+                             "image encoder's pass and the cached reference K/V are never downsampled)")
+        todo = check_todo(factor, factor_level_2, method)
+        if (todo[0] > 1 or todo[1] > 1) and self.tome is not None and self.tome[0] > 0.0:
+            raise ValueError("enable_todo: token merging is enabled and the two are alternatives -- disable_tome() first")
+        self.todo = todo
+
+    def disable_todo(self):
+        self.todo = None
 
 
 def check_tome(ratio, max_downsample=1):
@@ -208,6 +226,39 @@ def tome_blocks(cfg, height, width, ratio, max_downsample=1):
         r = min(H * W - (H // 2) * (W // 2), int(H * W * float(ratio)))
         if down <= max_downsample and r > 0:
             out[name] = (H, W, r)
+    return out
+
+
+TODO_METHODS = ("nearest", "area")          # method of mvd_engine_set_todo / mvd_op_todo_downsample, by index
+
+
+def check_todo(factor=2, factor_level_2=1, method="nearest"):
+    """(factor, factor_level_2, method); ValueError unless both factors are integers in [1, 4] and the method is "nearest" or "area"."""
+    for name, f in (("factor", factor), ("factor_level_2", factor_level_2)):
+        if isinstance(f, bool) or not isinstance(f, int) or not 1 <= f <= 4:
+            raise ValueError(f"token downsampling: {name} must be an integer in [1, 4] (1: untouched), got {f!r}")
+    if method not in TODO_METHODS:
+        raise ValueError(f"token downsampling: method must be one of {TODO_METHODS}, got {method!r}")
+    return int(factor), int(factor_level_2), method
+
+
+def todo_blocks(cfg, height, width, factor=2, factor_level_2=1):
+    """``{feature name: (H, W, f, Nk)}`` of the transformer blocks whose self-attention reads downsampled keys at a latent of
+    ``height`` x ``width``: ``down = ceil(sqrt(N0 // N))`` (``tome_blocks``' rule) 1 takes ``factor``, 2 ``factor_level_2``, deeper
+    blocks none; a block with ``f == 1``, ``H // f < 1`` or ``W // f < 1`` is untouched.  ``Nk = (H // f) * (W // f)``."""
+    import math
+    out = {}
+    for _, name, _, _ in cfg.transformers():
+        part = name.split("_")          # down_block_{i}_attn_{j} | mid_block_attn_0 | up_block_{i}_attn_{j}
+        level = int(part[2]) if part[0] == "down" else cfg.num_levels - 1 - (int(part[2]) if part[0] == "up" else 0)
+        H, W = height >> level, width >> level
+        if H < 1 or W < 1:
+            continue
+        q = (height * width) // (H * W)
+        down = math.isqrt(q - 1) + 1 if q > 0 else 0            # ceil(sqrt(q))
+        f = factor if down == 1 else factor_level_2 if down == 2 else 1
+        if f > 1 and H // f >= 1 and W // f >= 1:
+            out[name] = (H, W, f, (H // f) * (W // f))
     return out
 
 

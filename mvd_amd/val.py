@@ -16,7 +16,8 @@ architecture and the CLIP snapshot), ``sampler``, ``frontend`` ("host" | "device
 mapping of the ``ValidationMetrics`` weight keywords to paths), ``group_sources`` and ``guidance_rescale`` (default 0.0: off; the
 pipeline's argument of that name, ``--guidance-rescale``) and ``freeu`` (default absent: off; ``"s1,s2,b1,b2"`` or four numbers in
 diffusers' ``enable_freeu`` order, ``--freeu``) and ``tome`` (default absent: off; ``"ratio"`` or ``"ratio,max_downsample"``,
-``--tome``: token merging, tomesd's ``apply_patch`` names) and ``deepcache`` (default absent: off; ``"N"`` or ``"N,branch"``, ``--deepcache``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
+``--tome``: token merging, tomesd's ``apply_patch`` names) and ``todo`` (default absent: off; ``"factor"``,
+``"factor,factor_level_2"`` or ``"factor,factor_level_2,method"``, ``--todo``: token downsampling of the self-attention keys) and ``deepcache`` (default absent: off; ``"N"`` or ``"N,branch"``, ``--deepcache``) and ``apg`` (default absent: off; ``"eta,norm_threshold,momentum[,space]"``, a
 sequence or a mapping, ``--apg``: adaptive projected guidance, the pipeline's argument of that name).
 
 What is kept from the reference on purpose: a metric that cannot be built is ``None`` and scores 0.0; values ``<= 0`` are left out
@@ -273,6 +274,10 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     tome = parse_tome(config.get("tome"))
     if tome is not None:
         pipeline.enable_tome(*tome)
+    # token downsampling: absent (the default), the pipeline is not touched
+    todo = parse_todo(config.get("todo"))
+    if todo is not None:
+        pipeline.enable_todo(*todo)
     # DeepCache: absent (the default), the pipeline is not touched
     deepcache = parse_deepcache(config.get("deepcache"))
     if deepcache is not None:
@@ -455,6 +460,28 @@ def parse_tome(value):
     return check_tome(ratio, int(mds))
 
 
+def parse_todo(value):
+    """The ``todo`` config key / ``--todo`` flag: ``"factor"``, ``"factor,factor_level_2"`` or ``"factor,factor_level_2,method"``, an
+    int, or a sequence of one to three such values -> ``(factor, factor_level_2, method)`` (factor_level_2 defaults to 1, the method
+    to ``"nearest"``); ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
+    if value is None or value == "" or value is False:
+        return None
+    what = "todo: expected factor[,factor_level_2[,method]] (e.g. 2 or 2,1,area)"
+    if isinstance(value, bool):
+        raise ValueError(f"{what}, got {value!r}")
+    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
+    if len(parts) not in (1, 2, 3):
+        raise ValueError(f"{what}, got {value!r}")
+    try:
+        fs = [float(p) for p in parts[:2]]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}, got {value!r}") from None
+    if any(f != int(f) for f in fs):
+        raise ValueError(f"todo: the factors are integers in [1, 4], got {value!r}")
+    from .unet_params import check_todo
+    return check_todo(int(fs[0]), int(fs[1]) if len(fs) == 2 else 1, str(parts[2]) if len(parts) == 3 else "nearest")
+
+
 def parse_deepcache(value):
     """The ``deepcache`` config key / ``--deepcache`` flag: ``"N"`` or ``"N,branch"``, an int, or a sequence of one or two ints ->
     ``(cache_interval, cache_branch_id)`` (the branch defaults to 0); ``None`` / empty -> ``None`` (off).  ValueError for anything
@@ -509,6 +536,10 @@ def main(argv=None) -> int:
     ap.add_argument("--tome", type=str, default=None, metavar="ratio[,max_downsample]",
                     help="token merging in front of the UNet's self-attention, tomesd's apply_patch names: ratio in [0, 0.75], "
                          "max_downsample one of 1, 2, 4, 8, default 1 (e.g. 0.5; default: the config's tome, else off)")
+    ap.add_argument("--todo", type=str, default=None, metavar="factor[,factor_level_2[,method]]",
+                    help="token downsampling (ToDo) of the UNet's self-attention keys and values: factors in [1, 4] for the blocks at "
+                         "the latent's resolution and one level below (default 1), method nearest (default) or area (e.g. 2 or "
+                         "2,1,area; default: the config's todo, else off)")
     ap.add_argument("--deepcache", type=str, default=None, metavar="N[,branch]",
                     help="DeepCache (Ma et al. 2024): the whole UNet at every N-th step, the outermost layers around its stored deep "
                          "feature in between; branch = DeepCache's cache_branch_id, default 0 (e.g. 3 or 3,0; default: the config's "
@@ -532,6 +563,11 @@ def main(argv=None) -> int:
             parse_tome(args.tome)
         except ValueError as e:
             ap.error(str(e))
+    if args.todo is not None:
+        try:
+            parse_todo(args.todo)
+        except ValueError as e:
+            ap.error(str(e))
     if args.deepcache is not None:
         try:
             parse_deepcache(args.deepcache)
@@ -550,6 +586,8 @@ def main(argv=None) -> int:
         config["freeu"] = args.freeu
     if args.tome is not None:
         config["tome"] = args.tome
+    if args.todo is not None:
+        config["todo"] = args.todo
     if args.deepcache is not None:
         config["deepcache"] = args.deepcache
     if args.apg is not None:
