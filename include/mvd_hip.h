@@ -188,14 +188,22 @@ int mvd_engine_set_graph(mvd_engine_t* e, int enable);
  * base UNet's (frozen base), the encoder pass can read weight set 0 and set 1 need not be registered at all. */
 int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable);
 
-/* FreeU (Si et al., CVPR 2024; diffusers-0.32.2 UNet2DConditionModel.enable_freeu(s1, s2, b1, b2), restated) on the MAIN UNet
+/* Main-pass options: what setting or clearing one invalidates.  FreeU, token merging, token downsampling, DeepCache and the taps
+ * (below) are state of the engine, beside the argument block; every forward entry honours them and the workspace entries size the
+ * forward of the CURRENT setting.  Every setter and clearer drops the captured hipGraphs, and besides:
+ *   set_freeu / clear_freeu                           nothing more
+ *   set_tome / clear_tome                             the kept slot tables
+ *   set_todo / clear_todo                             the key counts, DeepCache's stored feature
+ *   set_deepcache / clear_deepcache / bind_deepcache  DeepCache's stored feature
+ *   set_taps                                          the tap records
+ * (FreeU and token merging leave a stored deep feature valid.)  A refused call (-1 and a message) changes nothing.
+ *
+ * FreeU (Si et al., CVPR 2024; diffusers-0.32.2 UNet2DConditionModel.enable_freeu(s1, s2, b1, b2), restated) on the MAIN UNet
  * pass: in front of every resnet of up block 0 (b1, s1) and of up block 1 (b2, s2) the hidden input and the skip input are
  * replaced by mvd_op_freeu's two outputs (below); up blocks 2 and 3 are untouched.  The encoder pass, the Q2 statistics, the
- * reference K/V and the reference cache never depend on the setting (also with mvd_engine_share_encoder_weights).  The state
- * lives on the engine, beside the argument block, which is as it was; every forward entry honours it, and the four
- * mvd_engine_workspace_bytes* entries size the forward of the CURRENT setting (a workspace bound before FreeU was set may be
- * too small: the forward then says so before it launches anything).  All four values must be positive and finite, else -1.
- * Setting or clearing drops the captured hipGraphs.  Clear (the default): the launches of a forward are what they were. */
+ * reference K/V and the reference cache never depend on the setting (also with mvd_engine_share_encoder_weights).  A workspace
+ * bound before FreeU was set may be too small: the forward then says so before it launches anything.  All four values must be
+ * positive and finite, else -1.  Clear (the default): the launches of a forward are what they were. */
 int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2);
 int mvd_engine_clear_freeu(mvd_engine_t* e);
 
@@ -206,7 +214,7 @@ int mvd_engine_clear_freeu(mvd_engine_t* e);
  * and the feed-forward are as they were; the encoder pass and the reference K/V never merge.  ratio in [0, 0.75], max_downsample
  * one of 1, 2, 4, 8, else -1.  ratio 0, or no eligible block: the launches of a forward are what they were.  A merging block
  * whose map is above the select kernel's limit or whose channels are no multiple of 64 fails the forward before anything is
- * launched.  Both entries drop the captured hipGraphs; the workspace entries size the forward of the current setting.
+ * launched.  What setting or clearing invalidates: "main-pass options" above.
  * keep_tables (test plumbing): every merging block's slot table [batch][H W] stays in the workspace after the forward;
  * mvd_engine_tome_table copies that of feature `feature_idx` of the last issued forward to the device array `out` and returns
  * its length (0: the block did not merge; out null: the length alone). */
@@ -224,10 +232,9 @@ int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* 
  * reference are what they were.  method 0: nearest (the top-left token of each cell), 1: area (the cell's mean).
  * A factor outside [1, 4] or a method outside {0, 1}: -1.  While token merging is set (ratio > 0) set_todo with a factor above 1 is
  * refused, and mvd_engine_set_tome with a ratio above 0 is refused while a factor is above 1: -1 and a message, nothing changes.
- * Both factors 1, or clear: the launches of a forward are what they were.  Both entries drop the captured hipGraphs and invalidate
- * DeepCache's stored feature (a deep feature of another setting is stale); the workspace entries size the forward of the current
- * setting.  mvd_engine_todo_keys: out[i], i < min(n, features) = Nk of feature i's block in the last issued forward (0: it was not
- * downsampled, or no forward yet); host memory; returns the number of features. */
+ * Both factors 1, or clear: the launches of a forward are what they were.  What setting or clearing invalidates: "main-pass
+ * options" above (a deep feature of another setting is stale).  mvd_engine_todo_keys: out[i], i < min(n, features) = Nk of feature
+ * i's block in the last issued forward (0: it was not downsampled, or no forward yet); host memory; returns the number of features. */
 int mvd_engine_set_todo(mvd_engine_t* e, int factor, int factor_level_2, int method);
 int mvd_engine_clear_todo(mvd_engine_t* e);
 int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n);
@@ -253,11 +260,10 @@ int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n);
  * branch and a weight generation that mvd_engine_set_weight / mvd_engine_clear_weights bump -- and a shallow forward whose
  * arguments do not match it is rejected before any launch, in words that name the mismatch.  The timestep is not part of the
  * record: reusing the feature at another step is the point.  The bits are part of the argument block and so of the hipGraph key.
- *   mvd_engine_set_deepcache / _clear_deepcache   set the branch (outside [0, Lb): -1) / switch off; both drop the captured
- *                          hipGraphs and invalidate the stored feature.
+ *   mvd_engine_set_deepcache / _clear_deepcache   set the branch (outside [0, Lb): -1) / switch off
  *   mvd_engine_deepcache_bytes / _bind_deepcache  the buffer of the stored feature for a forward of this shape (any branch), apart
- *                          from the reference cache (whose allocator every cold forward resets); 256-byte aligned.  Binding drops
- *                          the captured hipGraphs and invalidates the stored feature.
+ *                          from the reference cache (whose allocator every cold forward resets); 256-byte aligned.
+ * What setting, clearing or binding invalidates: "main-pass options" above.
  * The mvd_engine_workspace_bytes_args / _objects / _ragged entries size the forward the bits describe; a shallow forward never
  * needs more than the full forward of the same arguments (checked there). */
 int mvd_engine_set_deepcache(mvd_engine_t* e, int branch);
@@ -286,8 +292,8 @@ int mvd_engine_profile_shapes(mvd_engine_t* e, char* buf_host, int cap);
  * the FiLM hooks of the mid and up blocks, which otherwise modulate in place, write a tensor of their own while taps are on
  * (the same launch; the block output in front of the hook stays readable), and the mvd_engine_workspace_bytes* entries count
  * it.  No launch and no synchronisation is added, the forward's output is bit for bit what it is with taps off, and with taps
- * off a forward and its workspace size are what they were.  mvd_engine_set_taps drops the captured hipGraphs and the records;
- * a replayed graph restores the records of the forward it captured.
+ * off a forward and its workspace size are what they were.  What mvd_engine_set_taps invalidates: "main-pass options" above
+ * (a graph's FiLM hooks write where they wrote when it was captured); a replayed graph restores the records of the forward it captured.
  *   mvd_engine_num_taps   the number of records of the last issued forward (-1 with taps off)
  *   mvd_engine_tap_info   name (a host buffer of `cap` bytes) and shape of record `idx`
  *   mvd_engine_get_tap    the tensor [batch][height][width][channels] bf16 as out_nchw [batch][channels][height][width] fp32 */

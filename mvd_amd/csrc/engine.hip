@@ -31,6 +31,19 @@ namespace {
 struct FeatureInfo { std::string name; int level; int C; int heads; std::string key; /* weight-slot prefix of the block */ };
 constexpr int MVD_REF_ONLY_INTERNAL = 1 << 30;   // set by mvd_engine_reference_encode only (rejected on the public entry)
 
+// The main-pass options (include/mvd_hip.h "main-pass options"): what the setters set, as one value.  mvd_engine::opt is assigned by
+// apply_main_opts alone; the main pass reads it through PassOpts::main, the encoder pass never sees it.
+struct MainOpts {
+  bool freeu_on = false; float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};   // FreeU: up blocks 0 and 1 read re-weighted hidden / skip inputs
+  double tome_ratio = 0.0; int tome_maxds = 1; bool tome_keep = false;              // token merging: attn1 of the eligible blocks on the merged sequence
+  int todo_f[2] = {1, 1}, todo_method = 0;    // token downsampling: the K/V factor at the latent's own level / one level below (1: off)
+  bool dc_on = false; int dc_branch = 0;      // DeepCache
+  bool taps_on = false;                       // main-pass taps
+  bool merges() const { return tome_ratio > 0.0; }
+  bool downsamples() const { return todo_f[0] > 1 || todo_f[1] > 1; }
+};
+enum MainOptField { OPT_FREEU, OPT_TOME, OPT_TODO, OPT_DEEPCACHE, OPT_TAPS };
+
 }  // namespace
 
 struct mvd_engine {
@@ -78,33 +91,26 @@ struct mvd_engine {
     return 0;
   }
   bool share_encoder = false;       // N4: the encoder pass reads weight set 0 (base UNet == image-encoder UNet)
-  // FreeU (mvd_engine_set_freeu): the main pass's up blocks 0 and 1 read re-weighted hidden / skip inputs; freeu_b / freeu_s by block
-  bool freeu_on = false; float freeu_b[2] = {1.f, 1.f}, freeu_s[2] = {1.f, 1.f};
-  // Token merging (mvd_engine_set_tome): the main pass's eligible transformer blocks run attn1 on the merged sequence.  tome_tab: with
-  // tome_keep, the slot table of every feature's block in the last issued forward (workspace memory; rows 0: the block did not merge)
-  double tome_ratio = 0.0; int tome_maxds = 1; bool tome_keep = false;
+  MainOpts opt;                     // FreeU, token merging, token downsampling, DeepCache, taps: see MainOpts and apply_main_opts
+  // Records and buffers of the last issued forward (not options).  tome_tab: with opt.tome_keep, the slot table of every feature's
+  // block (workspace memory; rows 0: the block did not merge); todo_nk: the keys of every feature's block (0: full)
   struct TomeTable { int* p = nullptr; int64_t n = 0; };
   std::vector<TomeTable> tome_tab;
-  // Token downsampling (mvd_engine_set_todo): attn1 of the main pass's eligible blocks reads pooled K/V.  todo_f[0] / [1]: the factor at
-  // the latent's own level / one level below (1: off); todo_nk: the keys of every feature's block in the last issued forward (0: full)
-  int todo_f[2] = {1, 1}, todo_method = 0;
   std::vector<int> todo_nk;
-  // DeepCache (mvd_engine_set_deepcache; include/mvd_hip.h): the stored deep feature lives in a buffer of its own (the reference
-  // cache's allocator is reset by every cold forward) and carries the record of the refresh forward that wrote it.  The record is
-  // NOT part of HostState: it is written by unet_forward once a refresh forward has been issued (launched, captured or replayed),
-  // so replaying some other forward's graph cannot roll it back.
-  bool dc_on = false; int dc_branch = 0;
+  // DeepCache (include/mvd_hip.h): the stored deep feature lives in a buffer of its own (the reference cache's allocator is reset by
+  // every cold forward) and carries the record of the refresh forward that wrote it.  The record is NOT part of HostState: it is
+  // written by unet_forward once a refresh forward has been issued (launched, captured or replayed), so replaying some other
+  // forward's graph cannot roll it back.
   void* dc_ptr = nullptr; int64_t dc_bytes = 0;
-  // Main-pass taps (mvd_engine_set_taps; include/mvd_hip.h): with taps_on, the record of every block output of the last issued
-  // forward's main pass, in execution order.  The tensors are the pass's own activations (workspace memory, like tome_tab: nothing
-  // of the main pass is freed before the forward ends); only a FiLM hook that runs in place gets an output of its own.
+  // Main-pass taps (include/mvd_hip.h): with opt.taps_on, the record of every block output of the last issued forward's main pass,
+  // in execution order.  The tensors are the pass's own activations (workspace memory, like tome_tab: nothing of the main pass is
+  // freed before the forward ends); only a FiLM hook that runs in place gets an output of its own.
   struct Tap { std::string name; const bf16_t* p; int B, H, W, C; };
-  bool taps_on = false;
   std::vector<Tap> taps;
   uint64_t weight_gen = 0;          // bumped by mvd_engine_set_weight / mvd_engine_clear_weights
   struct DeepRecord { bool valid = false; int batch = 0, h = 0, w = 0, cam = 0, img = 0, branch = 0; uint64_t wgen = 0; std::vector<int> layout; } dc_rec;
   bool dc_sizing = false;           // a sizing entry's dry run of a shallow forward: no stored feature is needed to size one
-  int dc_hidden_channels() const { return cfg.layers_per_block - 1 - dc_branch >= 1 ? cfg.block_out_channels[0] : cfg.block_out_channels[1]; }
+  int dc_hidden_channels() const { return cfg.layers_per_block - 1 - opt.dc_branch >= 1 ? cfg.block_out_channels[0] : cfg.block_out_channels[1]; }
   // hipGraph replay of whole forwards (mvd_engine_set_graph): one instantiated graph per distinct (arguments, cache state)
   struct HostState {                  // what a forward leaves behind on the host side
     std::vector<bf16_t*> refkv, feat_keep;
@@ -563,13 +569,8 @@ struct PassOpts {
   float* stats = nullptr;     // kept raw and normalisation + K/V projection wait for mvd_engine_reference_finish
   int ref_batch = 0;          // batch of the reference features (Q4 re-chunking)
   const ViewLayout* layout = nullptr;   // the forward's batch layout (ragged.h): the adapter pass's K/V maps, the encoder pass's statistics
-  bool freeu = false;         // main pass with FreeU set on the engine: up blocks 0 and 1 read mvd_launch_freeu's outputs
-  double tome_ratio = 0.0;    // main pass with token merging set on the engine (0: off); blocks down to tome_maxds merge
-  int tome_maxds = 1;
-  int todo_f[2] = {1, 1};     // main pass with token downsampling set on the engine: the K/V factor by level (1: off), and the method
-  int todo_method = 0;
+  const MainOpts* main = nullptr;   // the main pass: the engine's options; null for the encoder pass, which none of them touches
   int deep = 0;               // main pass, DeepCache: MVD_DEEPCACHE_REFRESH (store the deep feature) / _SHALLOW (start from it); 0: neither
-  int deep_branch = 0;        // the branch b: down_blocks.0 layers 0..b and up_blocks.{n-1} layers Lb-1-b..Lb are the shallow forward
   bf16_t* deep_buf = nullptr; // the bound buffer: [B][H0][W0][C of the deep feature]
   int late_from = 99;         // main pass of a two-stream forward: up-block index from which it takes the single-stream launch policy (99: never)
   const std::unordered_map<std::string, std::pair<float*, float*>>* film_ss = nullptr;  // name -> (scale, shift) [B][dim]
@@ -646,7 +647,7 @@ struct UNetPass {
       const int Nm = hw - tome_r, Mm = B_ * Nm;
       const int nq = ad ? 4 * C : 3 * C;
       CHECK(c.layernorm(h, M, C, c.WF(key + ".ln1.g", C), c.WF(key + ".ln1.b", C), ln));
-      int* slot = c.e->tome_keep ? c.aalloc<int>((size_t)M) : c.talloc<int>((size_t)M);
+      int* slot = o.main->tome_keep ? c.aalloc<int>((size_t)M) : c.talloc<int>((size_t)M);
       int* members = c.talloc<int>((size_t)M);
       int* starts = c.talloc<int>((size_t)B_ * (Nm + 1));
       const int64_t wsb = mvd_tome_workspace_bytes(B_, x.H, x.W);
@@ -654,7 +655,7 @@ struct UNetPass {
       bf16_t* lnm = c.talloc<bf16_t>((size_t)Mm * C);      // the merged rows; after the q/k/v GEMM, the out-projection's result
       bf16_t* qkv = c.talloc<bf16_t>((size_t)Mm * nq);
       if (!c.dry && !c.err) {
-        if (c.e->tome_keep && feat_idx < (int)c.e->tome_tab.size()) c.e->tome_tab[feat_idx] = {slot, (int64_t)M};
+        if (o.main->tome_keep && feat_idx < (int)c.e->tome_tab.size()) c.e->tome_tab[feat_idx] = {slot, (int64_t)M};
         CHECK(mvd_launch_tome_match(ln, B_, x.H, x.W, C, tome_r, slot, members, starts, nullptr, nullptr, tws, wsb, c.s));
         CHECK(mvd_launch_tome_merge(ln, B_, x.H, x.W, C, tome_r, members, starts, lnm, c.s));
       }
@@ -683,7 +684,7 @@ struct UNetPass {
         bf16_t* kv = c.talloc<bf16_t>((size_t)B_ * Nk * 2 * C);
         if (!c.dry && !c.err) {
           if (feat_idx < (int)c.e->todo_nk.size()) c.e->todo_nk[feat_idx] = Nk;
-          CHECK(mvd_launch_todo_downsample(qkv + C, qkv + 2 * C, nq, B_, x.H, x.W, C, todo_f, o.todo_method, kv, c.s));
+          CHECK(mvd_launch_todo_downsample(qkv + C, qkv + 2 * C, nq, B_, x.H, x.W, C, todo_f, o.main->todo_method, kv, c.s));
         }
         a.p[0].k = kv; a.p[0].v = kv + C; a.p[0].ldk = a.p[0].ldv = 2 * C; a.p[0].bsk = a.p[0].bsv = (int64_t)Nk * 2 * C; a.p[0].nk = Nk;
       }
@@ -752,26 +753,28 @@ struct UNetPass {
     return c.err;
   }
 
-  // merged src per image of a block whose map is H x W; 0: the block does not merge (tomesd: `down <= max_downsample`, r = int(N ratio))
-  int tome_merged(int H, int W) const {
-    if (!(o.tome_ratio > 0.0) || o.capture || H < 2 || W < 2) return 0;
+  // how many times coarser than the latent a block's H x W map is: ceil(sqrt(N0 / N)) (tomesd's `down`)
+  long down_of(int H, int W) const {
     const long q = ((long)H0 * W0) / ((long)H * W);
     long down = 0;
     while (down * down < q) ++down;
-    if (down > o.tome_maxds) return 0;
+    return down;
+  }
+
+  // merged src per image of a block whose map is H x W; 0: the block does not merge (tomesd: `down <= max_downsample`, r = int(N ratio))
+  int tome_merged(int H, int W) const {
+    if (!o.main || !o.main->merges() || H < 2 || W < 2 || down_of(H, W) > o.main->tome_maxds) return 0;
     const int ns = H * W - (H / 2) * (W / 2);
-    const int r = (int)((double)(H * W) * o.tome_ratio);
+    const int r = (int)((double)(H * W) * o.main->tome_ratio);
     return r < ns ? r : ns;
   }
 
-  // the K/V factor of a block whose map is H x W; 1: attn1 reads its own K/V rows (down as in tome_merged; deeper than 2: never)
+  // the K/V factor of a block whose map is H x W; 1: attn1 reads its own K/V rows (deeper than down 2: never)
   int todo_factor(int H, int W) const {
-    if (o.capture || (o.todo_f[0] <= 1 && o.todo_f[1] <= 1)) return 1;
-    const long q = ((long)H0 * W0) / ((long)H * W);
-    long down = 0;
-    while (down * down < q) ++down;
+    if (!o.main || !o.main->downsamples()) return 1;
+    const long down = down_of(H, W);
     if (down < 1 || down > 2) return 1;
-    const int f = o.todo_f[down - 1];
+    const int f = o.main->todo_f[down - 1];
     return (f > 1 && H / f >= 1 && W / f >= 1) ? f : 1;
   }
 
@@ -783,7 +786,7 @@ struct UNetPass {
   }
 
   // main-pass taps (mvd_engine::taps): the record of a block output; nothing is launched
-  bool tapping() const { return c.e->taps_on && !o.capture; }
+  bool tapping() const { return o.main && o.main->taps_on; }
   void tap(const std::string& name, const Act& a) {
     if (tapping() && !c.dry && !c.err) c.e->taps.push_back({name, a.p, a.B, a.H, a.W, a.C});
   }
@@ -815,7 +818,7 @@ struct UNetPass {
     // DeepCache (include/mvd_hip.h): `shallow` runs down_blocks.0 layers 0..b and up_blocks.{n-1} layers j0..Lb around the stored
     // deep feature; `refresh` is the full pass, which copies that feature out where the shallow pass will put it in
     const bool shallow = o.deep == MVD_DEEPCACHE_SHALLOW, refresh = o.deep == MVD_DEEPCACHE_REFRESH;
-    const int j0 = Lb - 1 - o.deep_branch;
+    const int branch = o.main ? o.main->dc_branch : 0, j0 = Lb - 1 - branch;   // (o.deep is set on the main pass only)
     std::vector<Act> skips;
     // text K/V for all attn2 sites of this pass: one [B*L][xdim] x [tkv_total][xdim]^T GEMM instead of 16 small ones
     // (a shallow pass computes all of it as well: the GEMM is small, and the executed sites read the slices of their full-schedule
@@ -832,7 +835,7 @@ struct UNetPass {
     for (int i = 0; i < (shallow ? 1 : n); ++i) {
       const int co = cfg.block_out_channels[i];
       const std::string bk = "down_blocks." + std::to_string(i);
-      for (int j = 0; j < (shallow ? o.deep_branch + 1 : Lb); ++j) {
+      for (int j = 0; j < (shallow ? branch + 1 : Lb); ++j) {
         Act r = c.new_act(B, h.H, h.W, co, true);
         resnet_idx = down_resnet_pos(i, j);
         CHECK(resnet(bk + ".resnets." + std::to_string(j), h, nullptr, co, r));
@@ -896,11 +899,11 @@ struct UNetPass {
           CHECK((int)hipMemcpyAsync(o.deep_buf, h.p, (size_t)h.rows() * h.C * sizeof(bf16_t), hipMemcpyDeviceToDevice, c.s));
         Act r = c.new_act(B, h.H, h.W, co, true);
         resnet_idx = up_resnet_pos(i, j);
-        if (o.freeu && i < 2) {
+        if (o.main && o.main->freeu_on && i < 2) {
           // FreeU: the resnet (GroupNorm and the folded 1x1 shortcut alike) reads the re-weighted pair; h and skip stay as they were
           const size_t fm = c.e->tmp.off;
           Act hf = c.new_act(B, h.H, h.W, h.C, false), sf = c.new_act(B, skip.H, skip.W, skip.C, false);
-          if (!c.dry && !c.err) CHECK(mvd_launch_freeu(h.p, h.C, skip.p, skip.C, B, h.H, h.W, c.e->freeu_b[i], c.e->freeu_s[i], hf.p, sf.p, c.s));
+          if (!c.dry && !c.err) CHECK(mvd_launch_freeu(h.p, h.C, skip.p, skip.C, B, h.H, h.W, o.main->freeu_b[i], o.main->freeu_s[i], hf.p, sf.p, c.s));
           CHECK(resnet(bk + ".resnets." + std::to_string(j), hf, &sf, co, r));
           c.e->tmp.off = fm;
         } else {
@@ -1138,8 +1141,8 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   const bool shallow = deep == MVD_DEEPCACHE_SHALLOW;
   if (deep) {
     if (deep == (MVD_DEEPCACHE_REFRESH | MVD_DEEPCACHE_SHALLOW)) { mvd_set_error("forward: MVD_DEEPCACHE_REFRESH and MVD_DEEPCACHE_SHALLOW are one or the other, got both"); return -1; }
-    if (!e->dc_on) { mvd_set_error("forward: %s without mvd_engine_set_deepcache", shallow ? "MVD_DEEPCACHE_SHALLOW" : "MVD_DEEPCACHE_REFRESH"); return -1; }
-    if (e->dc_branch < 0 || e->dc_branch >= cfg.layers_per_block) { mvd_set_error("forward: DeepCache branch %d outside [0, %d)", e->dc_branch, cfg.layers_per_block); return -1; }
+    if (!e->opt.dc_on) { mvd_set_error("forward: %s without mvd_engine_set_deepcache", shallow ? "MVD_DEEPCACHE_SHALLOW" : "MVD_DEEPCACHE_REFRESH"); return -1; }
+    if (e->opt.dc_branch < 0 || e->opt.dc_branch >= cfg.layers_per_block) { mvd_set_error("forward: DeepCache branch %d outside [0, %d)", e->opt.dc_branch, cfg.layers_per_block); return -1; }
     if (shallow && use_img && !reuse) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW with MVD_USE_IMAGE needs MVD_REUSE_REF (a shallow forward never runs the encoder pass)"); return -1; }
     if (shallow && !e->dc_sizing) {
       const mvd_engine::DeepRecord& r = e->dc_rec;
@@ -1151,7 +1154,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
         mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of a forward with camera conditioning %s and image conditioning %s, this one has them %s and %s",
                       r.cam ? "on" : "off", r.img ? "on" : "off", use_cam ? "on" : "off", use_img ? "on" : "off"); return -1;
       }
-      if (r.branch != e->dc_branch) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of branch %d, the engine is set to branch %d", r.branch, e->dc_branch); return -1; }
+      if (r.branch != e->opt.dc_branch) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: the stored deep feature is of branch %d, the engine is set to branch %d", r.branch, e->opt.dc_branch); return -1; }
       if (r.wgen != e->weight_gen) { mvd_set_error("forward: MVD_DEEPCACHE_SHALLOW: weights were registered or cleared since the deep feature was stored"); return -1; }
     }
     if (!e->dc_sizing) {
@@ -1171,7 +1174,7 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   char msg[256];
   if (lay.validate(a.flags & MVD_SHARE_REF, use_img, a.batch, a.ref_batch, use_cam ? a.cam_batch : INT_MIN, a.height, a.width, cfg.num_levels, msg, sizeof(msg))) { mvd_set_error("%s", msg); return -1; }
   // FreeU filters the maps of up blocks 0 and 1 (levels n - 1 and n - 2): a map of one row or column has no frequency -1
-  if (e->freeu_on && !ref_only && ((a.height >> (cfg.num_levels - 1)) < 2 || (a.width >> (cfg.num_levels - 1)) < 2)) {
+  if (e->opt.freeu_on && !ref_only && ((a.height >> (cfg.num_levels - 1)) < 2 || (a.width >> (cfg.num_levels - 1)) < 2)) {
     mvd_set_error("forward: FreeU needs maps of at least 2 x 2 in up block 0, latent %dx%d gives %dx%d", a.height, a.width, a.height >> (cfg.num_levels - 1), a.width >> (cfg.num_levels - 1)); return -1;
   }
   if (use_cam && a.cam_batch > 0 && (a.cam_batch > a.batch || a.batch % a.cam_batch)) { mvd_set_error("forward: camera batch %d must divide the sample batch %d", a.cam_batch, a.batch); return -1; }
@@ -1315,13 +1318,11 @@ int forward_body(mvd_engine* e, const mvd_forward_args_t& a, hipStream_t s, bool
   static const int late_dflt = MVD_ENV_INT("MVD_DUAL_LATE_FROM", 99);
   po.late_from = (g_debug_flags & MVD_DBG_LATE_FROM_UP1) ? 1 : late_dflt;
   po.layout = &lay;
-  po.freeu = e->freeu_on;
-  po.tome_ratio = e->tome_ratio; po.tome_maxds = e->tome_maxds;
-  if (e->tome_keep && !dry) e->tome_tab.assign(e->feats.size(), {});
-  po.todo_f[0] = e->todo_f[0]; po.todo_f[1] = e->todo_f[1]; po.todo_method = e->todo_method;
+  po.main = &e->opt;
+  if (e->opt.tome_keep && !dry) e->tome_tab.assign(e->feats.size(), {});
   if (!dry) e->todo_nk.assign(e->feats.size(), 0);
   if (!dry) e->taps.clear();
-  po.deep = deep; po.deep_branch = e->dc_branch; po.deep_buf = (bf16_t*)e->dc_ptr;
+  po.deep = deep; po.deep_buf = (bf16_t*)e->dc_ptr;
   UNetPass pass{c, cfg, po, B, H, Wd, L, tx, tproj};
   pass.text_rows = TB;
   CHECK(pass.run(xin, a.out));
@@ -1673,7 +1674,7 @@ static int unet_forward(mvd_engine_t* e, const mvd_forward_args_t* args, const V
     mvd_engine::DeepRecord& d = e->dc_rec;
     d.batch = args->batch; d.h = args->height; d.w = args->width; d.layout = host.key();
     d.cam = (args->flags & MVD_USE_CAMERA) ? 1 : 0; d.img = (args->flags & MVD_USE_IMAGE) ? 1 : 0;
-    d.branch = e->dc_branch; d.wgen = e->weight_gen; d.valid = true;
+    d.branch = e->opt.dc_branch; d.wgen = e->weight_gen; d.valid = true;
   }
   return r;
 }
@@ -1780,68 +1781,75 @@ int mvd_engine_share_encoder_weights(mvd_engine_t* e, int enable) {
   return 0;
 }
 
-// FreeU on the main pass (include/mvd_hip.h).  A graph captured under one setting is never replayed under another: both drop them
+// The main-pass options (include/mvd_hip.h "main-pass options: what setting or clearing one invalidates").  The only code that assigns
+// e->opt: every setter and clearer below builds `next` from e->opt and names the option it changes.  A refused call changes nothing.
+static int apply_main_opts(mvd_engine* e, const MainOpts& next, MainOptField what) {
+  // token merging and token downsampling are alternatives (only one of the two changes per call: the other's state is e->opt's)
+  if (what == OPT_TOME && next.merges() && next.downsamples()) { mvd_set_error("set_tome: token downsampling is set (factors %d, %d): the two are alternatives, clear it first (mvd_engine_clear_todo)", next.todo_f[0], next.todo_f[1]); return -1; }
+  if (what == OPT_TODO && next.merges() && next.downsamples()) { mvd_set_error("set_todo: token merging is set (ratio %g): the two are alternatives, clear it first (mvd_engine_clear_tome)", next.tome_ratio); return -1; }
+  // what a change of each option invalidates beside the captured graphs, which every one drops (a graph captured under one setting is
+  // never replayed under another).  FreeU and token merging leave a stored deep feature valid: recorded as found.
+  static const struct { bool dc_rec, tome_tab, todo_nk, taps; } invalidates[] = {
+    /* OPT_FREEU     */ {false, false, false, false},
+    /* OPT_TOME      */ {false, true,  false, false},
+    /* OPT_TODO      */ {true,  false, true,  false},
+    /* OPT_DEEPCACHE */ {true,  false, false, false},
+    /* OPT_TAPS      */ {false, false, false, true},
+  };
+  e->drop_graphs();
+  if (invalidates[what].dc_rec) e->dc_rec.valid = false;
+  if (invalidates[what].tome_tab) e->tome_tab.clear();
+  if (invalidates[what].todo_nk) e->todo_nk.clear();
+  if (invalidates[what].taps) e->taps.clear();
+  e->opt = next;
+  return 0;
+}
+
 int mvd_engine_set_freeu(mvd_engine_t* e, float s1, float s2, float b1, float b2) {
   if (!e) { mvd_set_error("set_freeu: null engine"); return -1; }
   const float v[4] = {s1, s2, b1, b2};
   for (float x : v) if (!(x > 0.f) || !(x < INFINITY)) { mvd_set_error("set_freeu: s1, s2, b1, b2 must be positive and finite, got %g, %g, %g, %g", (double)s1, (double)s2, (double)b1, (double)b2); return -1; }
-  e->drop_graphs();
-  e->freeu_on = true; e->freeu_s[0] = s1; e->freeu_s[1] = s2; e->freeu_b[0] = b1; e->freeu_b[1] = b2;
-  return 0;
+  MainOpts next = e->opt; next.freeu_on = true; next.freeu_s[0] = s1; next.freeu_s[1] = s2; next.freeu_b[0] = b1; next.freeu_b[1] = b2;
+  return apply_main_opts(e, next, OPT_FREEU);
 }
 int mvd_engine_clear_freeu(mvd_engine_t* e) {
   if (!e) { mvd_set_error("clear_freeu: null engine"); return -1; }
-  e->drop_graphs();
-  e->freeu_on = false;
-  return 0;
+  MainOpts next = e->opt; next.freeu_on = false;
+  return apply_main_opts(e, next, OPT_FREEU);
 }
 
-// Token merging on the main pass (include/mvd_hip.h).  Both drop the captured graphs, as FreeU's do
 int mvd_engine_set_tome(mvd_engine_t* e, double ratio, int max_downsample, int keep_tables) {
   if (!e) { mvd_set_error("set_tome: null engine"); return -1; }
   if (!(ratio >= 0.0) || !(ratio <= 0.75)) { mvd_set_error("set_tome: ratio must lie in [0, 0.75] (a quarter of the tokens are dst and stay), got %g", ratio); return -1; }
   if (max_downsample != 1 && max_downsample != 2 && max_downsample != 4 && max_downsample != 8) { mvd_set_error("set_tome: max_downsample must be one of 1, 2, 4, 8, got %d", max_downsample); return -1; }
-  if (ratio > 0.0 && (e->todo_f[0] > 1 || e->todo_f[1] > 1)) { mvd_set_error("set_tome: token downsampling is set (factors %d, %d): the two are alternatives, clear it first (mvd_engine_clear_todo)", e->todo_f[0], e->todo_f[1]); return -1; }
-  e->drop_graphs();
-  e->tome_ratio = ratio; e->tome_maxds = max_downsample; e->tome_keep = keep_tables != 0;
-  e->tome_tab.clear();
-  return 0;
+  MainOpts next = e->opt; next.tome_ratio = ratio; next.tome_maxds = max_downsample; next.tome_keep = keep_tables != 0;
+  return apply_main_opts(e, next, OPT_TOME);
 }
 int mvd_engine_clear_tome(mvd_engine_t* e) {
   if (!e) { mvd_set_error("clear_tome: null engine"); return -1; }
-  e->drop_graphs();
-  e->tome_ratio = 0.0; e->tome_maxds = 1; e->tome_keep = false;
-  e->tome_tab.clear();
-  return 0;
+  MainOpts next = e->opt; next.tome_ratio = 0.0; next.tome_maxds = 1; next.tome_keep = false;
+  return apply_main_opts(e, next, OPT_TOME);
 }
 int64_t mvd_engine_tome_table(mvd_engine_t* e, int feature_idx, int* out, void* stream) {
   if (!e || feature_idx < 0 || feature_idx >= (int)e->feats.size()) { mvd_set_error("tome_table: bad argument"); return -1; }
-  if (!e->tome_keep) { mvd_set_error("tome_table: tables are not kept (mvd_engine_set_tome with keep_tables)"); return -1; }
+  if (!e->opt.tome_keep) { mvd_set_error("tome_table: tables are not kept (mvd_engine_set_tome with keep_tables)"); return -1; }
   if (feature_idx >= (int)e->tome_tab.size() || !e->tome_tab[feature_idx].p) return 0;
   const auto& t = e->tome_tab[feature_idx];
   if (out && hipMemcpyAsync(out, t.p, (size_t)t.n * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) { mvd_set_error("tome_table: copy failed"); return -3; }
   return t.n;
 }
 
-// Token downsampling on the main pass (include/mvd_hip.h).  Both drop the captured graphs and invalidate DeepCache's stored feature
 int mvd_engine_set_todo(mvd_engine_t* e, int factor, int factor_level_2, int method) {
   if (!e) { mvd_set_error("set_todo: null engine"); return -1; }
   if (factor < 1 || factor > 4 || factor_level_2 < 1 || factor_level_2 > 4) { mvd_set_error("set_todo: factor and factor_level_2 must lie in [1, 4], got %d and %d", factor, factor_level_2); return -1; }
   if (method != 0 && method != 1) { mvd_set_error("set_todo: the method is 0 (nearest) or 1 (area), got %d", method); return -1; }
-  if ((factor > 1 || factor_level_2 > 1) && e->tome_ratio > 0.0) { mvd_set_error("set_todo: token merging is set (ratio %g): the two are alternatives, clear it first (mvd_engine_clear_tome)", e->tome_ratio); return -1; }
-  e->drop_graphs();
-  e->dc_rec.valid = false;
-  e->todo_f[0] = factor; e->todo_f[1] = factor_level_2; e->todo_method = method;
-  e->todo_nk.clear();
-  return 0;
+  MainOpts next = e->opt; next.todo_f[0] = factor; next.todo_f[1] = factor_level_2; next.todo_method = method;
+  return apply_main_opts(e, next, OPT_TODO);
 }
 int mvd_engine_clear_todo(mvd_engine_t* e) {
   if (!e) { mvd_set_error("clear_todo: null engine"); return -1; }
-  e->drop_graphs();
-  e->dc_rec.valid = false;
-  e->todo_f[0] = e->todo_f[1] = 1; e->todo_method = 0;
-  e->todo_nk.clear();
-  return 0;
+  MainOpts next = e->opt; next.todo_f[0] = next.todo_f[1] = 1; next.todo_method = 0;
+  return apply_main_opts(e, next, OPT_TODO);
 }
 int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n) {
   if (!e || !out || n < 0) { mvd_set_error("todo_keys: bad argument"); return -1; }
@@ -1850,20 +1858,18 @@ int mvd_engine_todo_keys(mvd_engine_t* e, int* out, int n) {
   return nf;
 }
 
-// DeepCache (include/mvd_hip.h).  Setting, clearing and binding drop the captured graphs (their nodes hold the branch's schedule and
-// the buffer's address) and invalidate the stored feature
+// (binding a buffer changes no option, but a graph's nodes hold the buffer's address and the stored feature lies in it: it takes
+//  DeepCache's row of the table)
 int mvd_engine_set_deepcache(mvd_engine_t* e, int branch) {
   if (!e) { mvd_set_error("set_deepcache: null engine"); return -1; }
   if (branch < 0 || branch >= e->cfg.layers_per_block) { mvd_set_error("set_deepcache: branch %d outside [0, %d) (layers_per_block)", branch, e->cfg.layers_per_block); return -1; }
-  e->drop_graphs();
-  e->dc_on = true; e->dc_branch = branch; e->dc_rec.valid = false;
-  return 0;
+  MainOpts next = e->opt; next.dc_on = true; next.dc_branch = branch;
+  return apply_main_opts(e, next, OPT_DEEPCACHE);
 }
 int mvd_engine_clear_deepcache(mvd_engine_t* e) {
   if (!e) { mvd_set_error("clear_deepcache: null engine"); return -1; }
-  e->drop_graphs();
-  e->dc_on = false; e->dc_branch = 0; e->dc_rec.valid = false;
-  return 0;
+  MainOpts next = e->opt; next.dc_on = false; next.dc_branch = 0;
+  return apply_main_opts(e, next, OPT_DEEPCACHE);
 }
 int64_t mvd_engine_deepcache_bytes(mvd_engine_t* e, int batch, int height, int width) {
   if (!e || batch <= 0 || height <= 0 || width <= 0) { mvd_set_error("deepcache_bytes: bad argument"); return -1; }
@@ -1872,29 +1878,26 @@ int64_t mvd_engine_deepcache_bytes(mvd_engine_t* e, int batch, int height, int w
   return (((int64_t)batch * height * width * c * (int64_t)sizeof(bf16_t)) + 255) & ~(int64_t)255;
 }
 int mvd_engine_bind_deepcache(mvd_engine_t* e, void* ptr, int64_t bytes) {
-  if (e) { e->drop_graphs(); e->dc_rec.valid = false; }
+  if (e) (void)apply_main_opts(e, e->opt, OPT_DEEPCACHE);
   if (!e || (ptr && bytes <= 0)) { mvd_set_error("bind_deepcache: bad argument"); return -1; }
   if ((uintptr_t)ptr & 255) { mvd_set_error("bind_deepcache: the buffer must be 256-byte aligned"); return -1; }
   e->dc_ptr = ptr; e->dc_bytes = ptr ? bytes : 0;
   return 0;
 }
 
-// Main-pass taps (include/mvd_hip.h).  Switching drops the captured graphs (a FiLM hook's output moves) and the records
 int mvd_engine_set_taps(mvd_engine_t* e, int enable) {
   if (!e) { mvd_set_error("set_taps: null engine"); return -1; }
-  e->drop_graphs();
-  e->taps_on = enable != 0;
-  e->taps.clear();
-  return 0;
+  MainOpts next = e->opt; next.taps_on = enable != 0;
+  return apply_main_opts(e, next, OPT_TAPS);
 }
 int mvd_engine_num_taps(mvd_engine_t* e) {
   if (!e) { mvd_set_error("num_taps: null engine"); return -1; }
-  if (!e->taps_on) { mvd_set_error("num_taps: taps are not kept (mvd_engine_set_taps)"); return -1; }
+  if (!e->opt.taps_on) { mvd_set_error("num_taps: taps are not kept (mvd_engine_set_taps)"); return -1; }
   return (int)e->taps.size();
 }
 int mvd_engine_tap_info(mvd_engine_t* e, int idx, char* name, int cap, int* batch, int* channels, int* height, int* width) {
   if (!e || !name || cap <= 0 || !batch || !channels || !height || !width) { mvd_set_error("tap_info: bad argument"); return -1; }
-  if (!e->taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("tap_info: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->taps_on ? (int)e->taps.size() : 0); return -1; }
+  if (!e->opt.taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("tap_info: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->opt.taps_on ? (int)e->taps.size() : 0); return -1; }
   const mvd_engine::Tap& t = e->taps[idx];
   if ((int)t.name.size() >= cap) { mvd_set_error("tap_info: the name '%s' needs %d bytes, the buffer has %d", t.name.c_str(), (int)t.name.size() + 1, cap); return -1; }
   memcpy(name, t.name.c_str(), t.name.size() + 1);
@@ -1903,7 +1906,7 @@ int mvd_engine_tap_info(mvd_engine_t* e, int idx, char* name, int cap, int* batc
 }
 int mvd_engine_get_tap(mvd_engine_t* e, int idx, float* out_nchw, void* stream) {
   if (!e || !out_nchw) { mvd_set_error("get_tap: bad argument"); return -1; }
-  if (!e->taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("get_tap: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->taps_on ? (int)e->taps.size() : 0); return -1; }
+  if (!e->opt.taps_on || idx < 0 || idx >= (int)e->taps.size()) { mvd_set_error("get_tap: no tap %d (%d kept; mvd_engine_set_taps, then a forward)", idx, e->opt.taps_on ? (int)e->taps.size() : 0); return -1; }
   const mvd_engine::Tap& t = e->taps[idx];
   return mvd_launch_nhwc_to_nchw_f32(t.p, t.B, t.H * t.W, t.C, out_nchw, (hipStream_t)stream);
 }

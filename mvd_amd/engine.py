@@ -12,6 +12,7 @@ import torch
 from . import _lib as L
 from .config import UNetConfig
 from .layout import ViewLayout
+from .main_options import TODO_METHODS, MainOptions, check_todo
 from .packing import pack_camera, pack_unet
 
 
@@ -54,13 +55,12 @@ class MVDEngine:
         self._ws_key = None
         self._ws_resize = False
         self._ws_args = None
-        self.freeu = None                                         # (s1, s2, b1, b2) while FreeU is set
-        self.deepcache = None                                     # the branch while DeepCache is set
-        self.tome = None                                          # (ratio, max_downsample) while token merging is set
-        self._tome_keep = False
-        self.todo = None                                          # (factor, factor_level_2, method) while token downsampling is set
-        self._taps = False                                        # main-pass taps are kept (set_taps)
+        self.options = MainOptions()                              # what the set_* / clear_* methods below have set the main pass to
         self._dc = None                                           # the bound buffer of the stored deep feature
+
+    # what callers and tests read off an engine: views of ``options``, which is the only state
+    freeu, tome = property(lambda self: self.options.freeu), property(lambda self: self.options.tome)
+    todo, deepcache = property(lambda self: self.options.todo), property(lambda self: self.options.deepcache)
 
     def __del__(self):
         try:
@@ -338,7 +338,17 @@ class MVDEngine:
         the lower half of its backbone channels by ``b1`` and the lowest spatial frequencies of its skip maps by ``s1``, up block 1
         by ``b2`` / ``s2``.  The encoder pass and the cached reference do not depend on it."""
         L.call("mvd_engine_set_freeu", self._h, float(s1), float(s2), float(b1), float(b2))
-        self.freeu = (float(s1), float(s2), float(b1), float(b2))
+        self._options_changed(freeu=(s1, s2, b1, b2))
+
+    def clear_freeu(self) -> None:
+        """Back to the forward without FreeU (``mvd_engine_clear_freeu``): the launches it made before."""
+        L.call("mvd_engine_clear_freeu", self._h)
+        self._options_changed(freeu=None)
+
+    def _options_changed(self, **fields) -> None:
+        """The tail of the setters whose option moves the workspace's size: the same shape may now need more (or, token merging
+        cleared, more than while it was on)."""
+        self.options = self.options._replace(**fields)
         self._ws_resize = True
         if self._ws_key is not None and self._ws_args is not None:
             # now, not in the next forward: whoever asks reference_cache_valid first gets the answer that holds
@@ -349,19 +359,12 @@ class MVDEngine:
         blocks whose map is at most ``max_downsample`` times coarser than the latent run ``attn1`` on ``N - int(N * ratio)`` rows.
         ``keep_tables``: ``tome_tables()`` reads the blocks' slot tables after a forward (test plumbing)."""
         L.call("mvd_engine_set_tome", self._h, float(ratio), int(max_downsample), int(bool(keep_tables)))
-        self.tome, self._tome_keep = (float(ratio), int(max_downsample)), bool(keep_tables)
-        self._ws_resize = True
-        if self._ws_key is not None and self._ws_args is not None:
-            self._ensure_workspace(*self._ws_args)
+        self._options_changed(tome=(ratio, max_downsample), tome_keep=keep_tables)
 
     def clear_tome(self) -> None:
         """Back to the forward without token merging (``mvd_engine_clear_tome``): the launches it made before."""
         L.call("mvd_engine_clear_tome", self._h)
-        self.tome, self._tome_keep = None, False
-        # (the forward without merging needs MORE scratch than the merging one: a workspace sized while it was on is too small)
-        self._ws_resize = True
-        if self._ws_key is not None and self._ws_args is not None:
-            self._ensure_workspace(*self._ws_args)
+        self._options_changed(tome=None)
 
     def tome_tables(self):
         """``{feature name: slot table (batch, H*W) int32}`` of the blocks that merged in the last issued forward (needs
@@ -382,21 +385,14 @@ class MVDEngine:
         """Token downsampling of the self-attention keys and values on the main UNet pass (``mvd_engine_set_todo``): blocks at the
         latent's own resolution pool K/V by ``factor``, blocks one level below by ``factor_level_2`` (1: untouched); ``method`` is
         ``"nearest"`` or ``"area"``.  Refused while token merging is set."""
-        from .unet_params import TODO_METHODS, check_todo
         factor, factor_level_2, method = check_todo(factor, factor_level_2, method)
         L.call("mvd_engine_set_todo", self._h, factor, factor_level_2, TODO_METHODS.index(method))
-        self.todo = (factor, factor_level_2, method)
-        self._ws_resize = True
-        if self._ws_key is not None and self._ws_args is not None:
-            self._ensure_workspace(*self._ws_args)
+        self._options_changed(todo=(factor, factor_level_2, method))
 
     def clear_todo(self) -> None:
         """Back to the forward without token downsampling (``mvd_engine_clear_todo``): the launches it made before."""
         L.call("mvd_engine_clear_todo", self._h)
-        self.todo = None
-        self._ws_resize = True
-        if self._ws_key is not None and self._ws_args is not None:
-            self._ensure_workspace(*self._ws_args)
+        self._options_changed(todo=None)
 
     def todo_keys(self) -> Dict[str, int]:
         """``{feature name: Nk}`` of the blocks whose self-attention ran on downsampled keys in the last issued forward."""
@@ -410,10 +406,7 @@ class MVDEngine:
         """Main-pass taps (``mvd_engine_set_taps``; test plumbing): with them on, ``taps()`` reads every block output of the last
         forward's main pass.  The forward's output does not depend on the switch; its workspace may grow."""
         L.call("mvd_engine_set_taps", self._h, int(bool(enable)))
-        self._taps = bool(enable)
-        self._ws_resize = True
-        if self._ws_key is not None and self._ws_args is not None:
-            self._ensure_workspace(*self._ws_args)
+        self._options_changed(taps=enable)
 
     def taps(self) -> Dict[str, torch.Tensor]:
         """``{name: (B, C, H, W) fp32}`` of the block outputs of the last issued forward's main pass, in execution order (the names:
@@ -436,13 +429,13 @@ class MVDEngine:
         input of ``up_blocks.{n-1}.resnets.{Lb-1-branch}``, ``deep_cache="reuse"`` runs only ``down_blocks.0`` layers ``0..branch``
         and the last ``branch + 2`` layers of the last up block around it.  Setting invalidates a stored feature."""
         L.call("mvd_engine_set_deepcache", self._h, int(branch))
-        self.deepcache = int(branch)
+        self.options = self.options._replace(deepcache=branch)
 
     def clear_deepcache(self) -> None:
         """Back to the engine without DeepCache (``mvd_engine_clear_deepcache``); the buffer is released."""
         L.call("mvd_engine_clear_deepcache", self._h)
         L.call("mvd_engine_bind_deepcache", self._h, None, 0)
-        self.deepcache, self._dc = None, None
+        self.options, self._dc = self.options._replace(deepcache=None), None
 
     def _ensure_deepcache(self, batch, h, w):
         # (a buffer that is large enough stays bound: binding invalidates the stored feature)
@@ -453,11 +446,6 @@ class MVDEngine:
             self._dc = None
             self._dc = torch.empty(need, dtype=torch.uint8, device=self.device)
             L.call("mvd_engine_bind_deepcache", self._h, _ptr(self._dc), self._dc.numel())
-
-    def clear_freeu(self) -> None:
-        """Back to the forward without FreeU (``mvd_engine_clear_freeu``): the launches it made before."""
-        L.call("mvd_engine_clear_freeu", self._h)
-        self.freeu = None
 
     def _staged(self, name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
         shape = tuple(t.shape) if shape is None else tuple(shape)

@@ -21,6 +21,7 @@ from .attention import get_attention_processor_for_module
 from .camera_encoder import CameraEncoder
 from .config import UNetConfig
 from .layout import ViewLayout
+from .main_options import MainOptions, check_deepcache, transitions  # noqa: F401
 from .unet_params import UNet2DConditionParams
 
 logger = logging.getLogger(__name__)
@@ -171,7 +172,7 @@ class MultiViewUNet(nn.Module):
         self.unet_config = cfg
         self.base_unet = _build_unet(cfg, init)
         _load_named_unet(self.base_unet, pretrained_model_name_or_path, snapshot, "MultiViewUNet")
-        self.base_unet._freeu_main = True       # base_unet.enable_freeu(...) is the reference's call site
+        self.base_unet._main_pass = True       # base_unet.enable_freeu(...) is the reference's call site
         self.config = self.base_unet.config
         self.device = torch.device("cpu")
         self.dtype = dtype
@@ -285,36 +286,17 @@ class MultiViewUNet(nn.Module):
             self.reset_reference_cache()
         if bool(getattr(self, "use_hip_graph", False)) != bool(getattr(self._engine, "_graph", False)):
             self._engine.set_graph(bool(getattr(self, "use_hip_graph", False)))
-        if self.freeu != self._engine.freeu:
-            if self.freeu is None:
-                self._engine.clear_freeu()
-            else:
-                self._engine.set_freeu(*self.freeu)
-        # (token merging and token downsampling are alternatives and the engine refuses one while the other is set: whichever is
-        #  being switched off goes first)
-        todo = self.todo if self.todo is not None and (self.todo[0] > 1 or self.todo[1] > 1) else None
-        if todo is None and getattr(self._engine, "todo", None) is not None:
-            self._deep_key, self._deep_hold = False, None
-            self._engine.clear_todo()
-        tome = self.tome if self.tome is not None and self.tome[0] > 0.0 else None
-        if tome != getattr(self._engine, "tome", None) or (tome is not None and self.tome_keep_tables != getattr(self._engine, "_tome_keep", False)):
-            if tome is None:
-                self._engine.clear_tome()
-            else:
-                self._engine.set_tome(*tome, keep_tables=self.tome_keep_tables)
-        if todo is not None and todo != getattr(self._engine, "todo", None):
+        eng, want = self._engine, self.main_options()
+        if (want.todo, want.deepcache) != (eng.options.todo, eng.options.deepcache):
             self._deep_key, self._deep_hold = False, None       # (a deep feature stored under another setting is stale)
-            self._engine.set_todo(*todo)
-        if bool(getattr(self, "keep_taps", False)) != bool(getattr(self._engine, "_taps", False)):
-            self._engine.set_taps(bool(self.keep_taps))
-        branch = None if self.deepcache is None else self.deepcache[1]
-        if branch != getattr(self._engine, "deepcache", None):
-            self._deep_key, self._deep_hold = False, None
-            if branch is None:
-                self._engine.clear_deepcache()
-            else:
-                self._engine.set_deepcache(branch)
+        for name, args, kw in transitions(eng.options, want):
+            getattr(eng, name)(*args, **kw)
         return self._engine
+
+    def main_options(self) -> MainOptions:
+        """What the engine's main pass is to be set to: the switches kept on ``base_unet``, the test plumbing and DeepCache's branch."""
+        return MainOptions(self.freeu, self.tome, self.tome_keep_tables, self.todo, self.keep_taps,
+                           None if self.deepcache is None else self.deepcache[1])
 
     # ------------------------------------------------------------------ FreeU (diffusers' names and argument order)
     @property
@@ -558,22 +540,6 @@ class MultiViewUNet(nn.Module):
 
     def _manage_modulation_hooks(self, register: bool):
         pass
-
-
-def check_deepcache(cache_interval, cache_branch_id, layers_per_block: int):
-    """``(cache_interval, cache_branch_id)`` as two ints, or ValueError: the interval >= 1, the branch in [0, layers_per_block)."""
-    try:
-        ok = float(cache_interval) == int(cache_interval) and float(cache_branch_id) == int(cache_branch_id)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok or isinstance(cache_interval, bool) or isinstance(cache_branch_id, bool):
-        raise ValueError(f"DeepCache: cache_interval and cache_branch_id must be integers, got {cache_interval!r}, {cache_branch_id!r}")
-    interval, branch = int(cache_interval), int(cache_branch_id)
-    if interval < 1:
-        raise ValueError(f"DeepCache: cache_interval must be >= 1, got {interval}")
-    if not 0 <= branch < layers_per_block:
-        raise ValueError(f"DeepCache: cache_branch_id must lie in [0, {layers_per_block}) (layers_per_block), got {branch}")
-    return interval, branch
 
 
 def create_mvd_pipeline(pretrained_model_name_or_path: str, dtype: torch.dtype = torch.float16,

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .attention import AttnProcessor2_0HIP
 from .config import UNetConfig
+from .main_options import TODO_METHODS, check_alternatives, check_freeu, check_todo, check_tome, todo_blocks, tome_blocks  # noqa: F401
 
 
 class _NoForward(nn.Module):
@@ -158,10 +159,10 @@ class UNet2DConditionParams(_NoForward):
     # diffusers' UNet2DConditionModel.enable_freeu / disable_freeu (same names and argument order).  The mirror only keeps the
     # setting: the MultiViewUNet that owns this module as its ``base_unet`` hands it to the engine before its next forward.
     freeu = None                # (s1, s2, b1, b2) while enabled
-    _freeu_main = False         # set by MultiViewUNet on its base_unet: the UNet of the main pass
+    _main_pass = False          # set by MultiViewUNet on its base_unet: the UNet of the main pass, which the three switches are for
 
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
-        if not self._freeu_main:
+        if not self._main_pass:
             raise ValueError("enable_freeu: FreeU applies to the main pass only -- call it on MultiViewUNet.base_unet (the image "
                              "encoder's UNet runs without it, as in the reference)")
         self.freeu = check_freeu(s1, s2, b1, b2)
@@ -173,12 +174,11 @@ class UNet2DConditionParams(_NoForward):
     tome = None                 # (ratio, max_downsample) while enabled
 
     def enable_tome(self, ratio: float = 0.5, max_downsample: int = 1):
-        if not self._freeu_main:
+        if not self._main_pass:
             raise ValueError("enable_tome: token merging applies to the main pass only -- call it on MultiViewUNet.base_unet (the "
                              "image encoder's pass and the cached reference K/V never merge)")
         tome = check_tome(ratio, max_downsample)
-        if tome[0] > 0.0 and self.todo is not None and (self.todo[0] > 1 or self.todo[1] > 1):
-            raise ValueError("enable_tome: token downsampling is enabled and the two are alternatives -- disable_todo() first")
+        check_alternatives(tome, self.todo, "enable_tome")
         self.tome = tome
 
     def disable_tome(self):
@@ -188,84 +188,13 @@ class UNet2DConditionParams(_NoForward):
     todo = None                 # (factor, factor_level_2, method) while enabled
 
     def enable_todo(self, factor: int = 2, factor_level_2: int = 1, method: str = "nearest"):
-        if not self._freeu_main:
+        if not self._main_pass:
             raise ValueError("enable_todo: token downsampling applies to the main pass only -- call it on MultiViewUNet.base_unet (the "
                              "image encoder's pass and the cached reference K/V are never downsampled)")
         todo = check_todo(factor, factor_level_2, method)
-        if (todo[0] > 1 or todo[1] > 1) and self.tome is not None and self.tome[0] > 0.0:
-            raise ValueError("enable_todo: token merging is enabled and the two are alternatives -- disable_tome() first")
+        check_alternatives(self.tome, todo, "enable_todo")
         self.todo = todo
 
     def disable_todo(self):
         self.todo = None
 
-
-def check_tome(ratio, max_downsample=1):
-    """(ratio, max_downsample); ValueError unless 0 <= ratio <= 0.75 and max_downsample is one of 1, 2, 4, 8 (tomesd's)."""
-    ratio = float(ratio)
-    if not 0.0 <= ratio <= 0.75:
-        raise ValueError(f"token merging: ratio must lie in [0, 0.75] (a quarter of the tokens are dst and stay), got {ratio}")
-    if isinstance(max_downsample, bool) or max_downsample not in (1, 2, 4, 8):
-        raise ValueError(f"token merging: max_downsample must be one of 1, 2, 4, 8, got {max_downsample!r}")
-    return ratio, int(max_downsample)
-
-
-def tome_blocks(cfg, height, width, ratio, max_downsample=1):
-    """``{feature name: (H, W, r)}`` of the transformer blocks that merge at a latent of ``height`` x ``width``: tomesd's rule
-    ``ceil(sqrt(N0 // N)) <= max_downsample`` with ``r = min(#src, int(N * ratio)) > 0``."""
-    import math
-    out = {}
-    for _, name, _, _ in cfg.transformers():
-        part = name.split("_")          # down_block_{i}_attn_{j} | mid_block_attn_0 | up_block_{i}_attn_{j}
-        level = int(part[2]) if part[0] == "down" else cfg.num_levels - 1 - (int(part[2]) if part[0] == "up" else 0)
-        H, W = height >> level, width >> level
-        if H < 2 or W < 2:
-            continue
-        q = (height * width) // (H * W)
-        down = math.isqrt(q - 1) + 1 if q > 0 else 0            # ceil(sqrt(q))
-        r = min(H * W - (H // 2) * (W // 2), int(H * W * float(ratio)))
-        if down <= max_downsample and r > 0:
-            out[name] = (H, W, r)
-    return out
-
-
-TODO_METHODS = ("nearest", "area")          # method of mvd_engine_set_todo / mvd_op_todo_downsample, by index
-
-
-def check_todo(factor=2, factor_level_2=1, method="nearest"):
-    """(factor, factor_level_2, method); ValueError unless both factors are integers in [1, 4] and the method is "nearest" or "area"."""
-    for name, f in (("factor", factor), ("factor_level_2", factor_level_2)):
-        if isinstance(f, bool) or not isinstance(f, int) or not 1 <= f <= 4:
-            raise ValueError(f"token downsampling: {name} must be an integer in [1, 4] (1: untouched), got {f!r}")
-    if method not in TODO_METHODS:
-        raise ValueError(f"token downsampling: method must be one of {TODO_METHODS}, got {method!r}")
-    return int(factor), int(factor_level_2), method
-
-
-def todo_blocks(cfg, height, width, factor=2, factor_level_2=1):
-    """``{feature name: (H, W, f, Nk)}`` of the transformer blocks whose self-attention reads downsampled keys at a latent of
-    ``height`` x ``width``: ``down = ceil(sqrt(N0 // N))`` (``tome_blocks``' rule) 1 takes ``factor``, 2 ``factor_level_2``, deeper
-    blocks none; a block with ``f == 1``, ``H // f < 1`` or ``W // f < 1`` is untouched.  ``Nk = (H // f) * (W // f)``."""
-    import math
-    out = {}
-    for _, name, _, _ in cfg.transformers():
-        part = name.split("_")          # down_block_{i}_attn_{j} | mid_block_attn_0 | up_block_{i}_attn_{j}
-        level = int(part[2]) if part[0] == "down" else cfg.num_levels - 1 - (int(part[2]) if part[0] == "up" else 0)
-        H, W = height >> level, width >> level
-        if H < 1 or W < 1:
-            continue
-        q = (height * width) // (H * W)
-        down = math.isqrt(q - 1) + 1 if q > 0 else 0            # ceil(sqrt(q))
-        f = factor if down == 1 else factor_level_2 if down == 2 else 1
-        if f > 1 and H // f >= 1 and W // f >= 1:
-            out[name] = (H, W, f, (H // f) * (W // f))
-    return out
-
-
-def check_freeu(s1, s2, b1, b2):
-    """(s1, s2, b1, b2) as floats; ValueError unless all four are positive and finite."""
-    import math
-    vals = tuple(float(v) for v in (s1, s2, b1, b2))
-    if not all(math.isfinite(v) and v > 0.0 for v in vals):
-        raise ValueError(f"FreeU: s1, s2, b1, b2 must be positive and finite, got {vals}")
-    return vals

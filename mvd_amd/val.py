@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from ._lib import MvdError
+from .main_options import check_freeu, check_todo, check_tome
 
 logger = logging.getLogger(__name__)
 
@@ -266,22 +267,11 @@ def run_validation(pipeline, dataset, config: Dict, device, output_dir: Path, *,
     all_results, batch_metrics = [], []
     # off (0.0, the default): the pipeline calls are the ones made before the key existed, argument for argument
     rescale = {"guidance_rescale": float(config["guidance_rescale"])} if float(config.get("guidance_rescale", 0.0) or 0.0) != 0.0 else {}
-    # FreeU: absent (the default), the pipeline is not touched
-    freeu = parse_freeu(config.get("freeu"))
-    if freeu is not None:
-        pipeline.enable_freeu(*freeu)
-    # token merging: absent (the default), the pipeline is not touched
-    tome = parse_tome(config.get("tome"))
-    if tome is not None:
-        pipeline.enable_tome(*tome)
-    # token downsampling: absent (the default), the pipeline is not touched
-    todo = parse_todo(config.get("todo"))
-    if todo is not None:
-        pipeline.enable_todo(*todo)
-    # DeepCache: absent (the default), the pipeline is not touched
-    deepcache = parse_deepcache(config.get("deepcache"))
-    if deepcache is not None:
-        pipeline.enable_deepcache(*deepcache)
+    # FreeU, token merging, token downsampling, DeepCache: absent (the default), the pipeline is not touched
+    for key, parse, method in FLAG_OPTIONS:
+        setting = parse(config.get(key)) if method else None
+        if setting is not None:
+            getattr(pipeline, method)(*setting)
     # adaptive projected guidance: absent (the default), the pipeline calls carry no such argument; it rides with the rescale's
     apg = parse_apg(config.get("apg"))
     if apg is not None:
@@ -427,36 +417,40 @@ def save_results(all_results: List[Dict], overall_metrics: Dict, output_dir: Pat
             w.writerow([metric, value])
 
 
+def _flag_parts(value, what: str, counts, nums: int = 0):
+    """The shared front of the ``parse_*`` below: ``None`` / empty / ``False`` -> ``None`` (off); a string's comma-separated parts, a
+    number alone or a sequence's items, the first ``nums`` of them as floats.  ValueError(``what``, got ...) for ``True``, a count
+    outside ``counts`` or a part that is no number."""
+    if value is None or value == "" or value is False:
+        return None
+    if isinstance(value, bool):
+        raise ValueError(f"{what}, got {value!r}")
+    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
+    if len(parts) not in counts:
+        raise ValueError(f"{what}, got {value!r}")
+    try:
+        return [float(p) for p in parts[:nums]] + parts[nums:]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}, got {value!r}") from None
+
+
 def parse_freeu(value):
     """The ``freeu`` config key / ``--freeu`` flag: ``"s1,s2,b1,b2"`` or a sequence of four numbers, in diffusers' ``enable_freeu``
     order -> ``(s1, s2, b1, b2)``; ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
-    if value is None or value == "" or value is False:
-        return None
-    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else list(value)
-    if len(parts) != 4:
-        raise ValueError(f"freeu: expected four values s1,s2,b1,b2 (SD-2.1: 0.9,0.2,1.4,1.6), got {value!r}")
-    from .unet_params import check_freeu
-    return check_freeu(*parts)
+    parts = _flag_parts(value, "freeu: expected four values s1,s2,b1,b2 (SD-2.1: 0.9,0.2,1.4,1.6)", (4,))
+    return parts and check_freeu(*parts)
 
 
 def parse_tome(value):
     """The ``tome`` config key / ``--tome`` flag: ``"ratio"`` or ``"ratio,max_downsample"``, a number, or a sequence of one or two
     numbers, in tomesd's ``apply_patch`` order -> ``(ratio, max_downsample)`` (max_downsample defaults to 1); ``None`` / empty ->
     ``None`` (off).  ValueError for anything else."""
-    if value is None or value == "" or value is False:
+    parts = _flag_parts(value, "tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2)", (1, 2), nums=2)
+    if parts is None:
         return None
-    if isinstance(value, bool):
-        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}")
-    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
-    if len(parts) not in (1, 2):
-        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}")
-    try:
-        ratio, mds = float(parts[0]), float(parts[1]) if len(parts) == 2 else 1.0
-    except (TypeError, ValueError):
-        raise ValueError(f"tome: expected ratio[,max_downsample] (e.g. 0.5 or 0.5,2), got {value!r}") from None
+    ratio, mds = parts[0], parts[1] if len(parts) == 2 else 1.0
     if mds != int(mds):
         raise ValueError(f"tome: max_downsample is one of 1, 2, 4, 8, got {value!r}")
-    from .unet_params import check_tome
     return check_tome(ratio, int(mds))
 
 
@@ -464,21 +458,12 @@ def parse_todo(value):
     """The ``todo`` config key / ``--todo`` flag: ``"factor"``, ``"factor,factor_level_2"`` or ``"factor,factor_level_2,method"``, an
     int, or a sequence of one to three such values -> ``(factor, factor_level_2, method)`` (factor_level_2 defaults to 1, the method
     to ``"nearest"``); ``None`` / empty -> ``None`` (off).  ValueError for anything else."""
-    if value is None or value == "" or value is False:
+    parts = _flag_parts(value, "todo: expected factor[,factor_level_2[,method]] (e.g. 2 or 2,1,area)", (1, 2, 3), nums=2)
+    if parts is None:
         return None
-    what = "todo: expected factor[,factor_level_2[,method]] (e.g. 2 or 2,1,area)"
-    if isinstance(value, bool):
-        raise ValueError(f"{what}, got {value!r}")
-    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
-    if len(parts) not in (1, 2, 3):
-        raise ValueError(f"{what}, got {value!r}")
-    try:
-        fs = [float(p) for p in parts[:2]]
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}, got {value!r}") from None
+    fs = parts[:2]
     if any(f != int(f) for f in fs):
         raise ValueError(f"todo: the factors are integers in [1, 4], got {value!r}")
-    from .unet_params import check_todo
     return check_todo(int(fs[0]), int(fs[1]) if len(fs) == 2 else 1, str(parts[2]) if len(parts) == 3 else "nearest")
 
 
@@ -486,17 +471,9 @@ def parse_deepcache(value):
     """The ``deepcache`` config key / ``--deepcache`` flag: ``"N"`` or ``"N,branch"``, an int, or a sequence of one or two ints ->
     ``(cache_interval, cache_branch_id)`` (the branch defaults to 0); ``None`` / empty -> ``None`` (off).  ValueError for anything
     else; the branch's upper limit (the UNet's layers_per_block) is checked by ``enable_deepcache``."""
-    if value is None or value == "" or value is False:
+    nums = _flag_parts(value, "deepcache: expected N[,branch] (e.g. 3 or 3,0)", (1, 2), nums=2)
+    if nums is None:
         return None
-    if isinstance(value, bool):
-        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}")
-    parts = [p.strip() for p in value.split(",")] if isinstance(value, str) else ([value] if isinstance(value, (int, float)) else list(value))
-    if len(parts) not in (1, 2):
-        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}")
-    try:
-        nums = [float(p) for p in parts]
-    except (TypeError, ValueError):
-        raise ValueError(f"deepcache: expected N[,branch] (e.g. 3 or 3,0), got {value!r}") from None
     if any(n != int(n) for n in nums):
         raise ValueError(f"deepcache: the interval and the branch are integers, got {value!r}")
     interval, branch = int(nums[0]), int(nums[1]) if len(nums) == 2 else 0
@@ -514,6 +491,11 @@ def parse_apg(value):
     if isinstance(value, str) and len(value.split(",")) not in (3, 4):
         raise ValueError(f"apg: expected eta,norm_threshold,momentum[,space] (e.g. 0,15,-0.5), got {value!r}")
     return APG.of(value)
+
+
+# (config key and flag name, its parser, the pipeline method that takes the parsed value's items; apg rides with the pipeline calls)
+FLAG_OPTIONS = (("apg", parse_apg, None), ("freeu", parse_freeu, "enable_freeu"), ("tome", parse_tome, "enable_tome"),
+                ("todo", parse_todo, "enable_todo"), ("deepcache", parse_deepcache, "enable_deepcache"))
 
 
 def main(argv=None) -> int:
@@ -548,31 +530,12 @@ def main(argv=None) -> int:
                     help="adaptive projected guidance (Sadat et al. 2025): eta in [0, 1], norm_threshold >= 0 (0: off), momentum in "
                          "(-1, 1), space output|x0 (e.g. 0,15,-0.5; default: the config's apg, else off)")
     args = ap.parse_args(argv)
-    if args.apg is not None:
-        try:
-            parse_apg(args.apg)
-        except ValueError as e:
-            ap.error(str(e))
-    if args.freeu is not None:
-        try:
-            parse_freeu(args.freeu)
-        except ValueError as e:
-            ap.error(str(e))
-    if args.tome is not None:
-        try:
-            parse_tome(args.tome)
-        except ValueError as e:
-            ap.error(str(e))
-    if args.todo is not None:
-        try:
-            parse_todo(args.todo)
-        except ValueError as e:
-            ap.error(str(e))
-    if args.deepcache is not None:
-        try:
-            parse_deepcache(args.deepcache)
-        except ValueError as e:
-            ap.error(str(e))
+    for key, parse, _ in FLAG_OPTIONS:
+        if getattr(args, key) is not None:
+            try:
+                parse(getattr(args, key))
+            except ValueError as e:
+                ap.error(str(e))
     try:
         config = load_config(args.config)
     except Exception as e:  # noqa: BLE001
@@ -582,16 +545,9 @@ def main(argv=None) -> int:
         config["group_sources"] = True
     if args.guidance_rescale is not None:
         config["guidance_rescale"] = args.guidance_rescale
-    if args.freeu is not None:
-        config["freeu"] = args.freeu
-    if args.tome is not None:
-        config["tome"] = args.tome
-    if args.todo is not None:
-        config["todo"] = args.todo
-    if args.deepcache is not None:
-        config["deepcache"] = args.deepcache
-    if args.apg is not None:
-        config["apg"] = args.apg
+    for key, _, _ in FLAG_OPTIONS:
+        if getattr(args, key) is not None:
+            config[key] = getattr(args, key)
     device =torch.device("cuda" if torch.cuda.is_available() else "cpu")
     output_dir = Path(args.output_dir) / datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     output_dir.mkdir(exist_ok=True, parents=True)

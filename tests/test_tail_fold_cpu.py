@@ -145,7 +145,8 @@ def test_encoder_weight_dedup_detects_equal_and_differing_weights(monkeypatch, f
     log = []
 
     class FakeEngine:
-        freeu = None
+        from mvd_amd.main_options import MainOptions
+        options = MainOptions()
         _graph = False
 
         def __init__(self, *a, device=None, **kw):

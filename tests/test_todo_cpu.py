@@ -348,31 +348,31 @@ def test_val_flag_reaches_the_config_and_the_pipeline(monkeypatch, tmp_path, fla
 class _StubEngine:
     """records what ``MultiViewUNet._ensure_engine`` hands down and every forward"""
     device = torch.device("cpu")
-    freeu = tome = todo = deepcache = None
-    _graph = _taps = _tome_keep = False
+    _graph = False
 
     def __init__(self):
-        self.log = []
+        from mvd_amd.main_options import MainOptions
+        self.log, self.options = [], MainOptions()
 
     def set_todo(self, *a):
         self.log.append(("set_todo",) + a)
-        self.todo = a
+        self.options = self.options._replace(todo=a)
 
     def clear_todo(self):
         self.log.append(("clear_todo",))
-        self.todo = None
+        self.options = self.options._replace(todo=None)
 
     def set_tome(self, *a, **kw):
-        assert self.todo is None, "set_tome while token downsampling is set: the engine would refuse"
+        assert self.options.todo is None, "set_tome while token downsampling is set: the engine would refuse"
         self.log.append(("set_tome",) + a)
-        self.tome = a
+        self.options = self.options._replace(tome=a)
 
     def clear_tome(self):
         self.log.append(("clear_tome",))
-        self.tome = None
+        self.options = self.options._replace(tome=None)
 
     def forward(self, x, t, text, **kw):
-        self.log.append(("forward", self.todo))
+        self.log.append(("forward", self.options.todo))
         return torch.zeros_like(x)
 
     def reference_cache_valid(self, *a, **kw):
