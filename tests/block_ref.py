@@ -19,7 +19,19 @@ A batch is a list of ``Group``s: the rows that one oracle call computes together
 the views / objects / ragged forwards are, by definition, independent calls of g rows with a one-row reference each.
 
 ``wrong=`` names a wiring fault (``VARIANTS``); ``block_want`` then returns what an engine with that fault would compute, or None
-where the fault does not apply to the block.  Plain helper module, no fixtures; nothing here touches the code under test."""
+where the fault does not apply to the block.
+
+Token merging and token downsampling (``Cond(tome=, todo=)``): a transformer block that the setting makes eligible
+(``unet_params.tome_blocks`` / ``todo_blocks``, held against what the option oracle records) is the OPTION ORACLE's function
+(tests/tome_ref.py, tests/todo_ref.py) of the block input -- token merging under the slot tables given (the engine's own decisions,
+``MVDEngine.tome_tables()``), token downsampling by its definition.  The adapter's "self" branch stays ``adapter_branch``: on the
+merged rows under token merging, on the full rows and the un-pooled reference under token downsampling.  ``OPTION_VARIANTS`` are
+the faults of ONE block under an option, expressed through the oracles' own wrong-on-purpose switches.  DeepCache needs nothing
+here: a shallow forward's blocks are the same functions, the first re-run up-block resnet reading the stored tensor
+(``check_taps(extra=)``).
+
+Plain helper module, no fixtures; nothing here touches the code under test."""
+import contextlib
 import re
 from types import SimpleNamespace
 
@@ -37,6 +49,10 @@ TOL = {"conv_in": 1e-2, "resnet": 1e-2, "resnet_sc": 1e-2, "attention": 1e-2, "d
 VARIANTS = ("adapter_self_dropped", "adapter_cross_dropped", "adapter_self_other_ref", "adapter_cross_other_ref",
             "adapter_procs_swapped", "adapter_self_out_bias0", "adapter_cross_out_bias0", "text_other_row", "temb_other_row",
             "temb_neighbour_slice", "cat_swapped", "skip_post_film", "film_other_row", "film_neighbour", "freeu_dropped")
+# faults of one eligible transformer block under token merging / token downsampling: "<option>_<the oracle's switch>", and
+# ``tome_stale_table``: the slot table of the nearest eligible block of the same map in front of this one
+OPTION_VARIANTS = {"tome": ("tome_stale_table", "tome_roll_tables", "tome_zero_merged", "tome_merge_cross", "tome_neighbour_row"),
+                   "todo": ("todo_corner", "todo_also_ref", "todo_factor_off", "todo_swap_method")}
 
 
 def bf16(x):
@@ -76,11 +92,25 @@ class Cond:
     """The conditioning of one forward.  ``t`` (B,) timesteps; ``text`` the text rows as the forward's caller passes them to the
     ENGINE's main pass (one per row, or per guidance half and object in a layout forward); ``cams`` = (src, tgt, proj) or None;
     ``feats`` {feature: (Br, C, H, W)} or None; ``groups``: see the module docstring (default: one group of all rows, every
-    reference row)."""
+    reference row).  ``tome`` / ``todo``: the setting (the keywords of ``enable_tome`` / ``enable_todo``) or None, with
+    ``latent_hw``; ``tome_tables``: {feature: slot (B, H*W)}, None for the definition's own decisions."""
 
     def __init__(self, cfg, params, batch, t, text, cams=None, feats=None, groups=None, freeu=None, img_ref_scale=0.3, strength=0.2,
-                 round_text=True):
+                 round_text=True, tome=None, todo=None, tome_tables=None, latent_hw=None):
         self.cfg, self.B = cfg, batch
+        self.tome, self.todo, self.tables, self.latent_hw = tome, todo, tome_tables, latent_hw
+        self.merging, self.pooling = {}, {}
+        if tome is not None or todo is not None:
+            from mvd_amd.config import UNetConfig as HostConfig
+            from mvd_amd.unet_params import todo_blocks, tome_blocks
+            assert (tome is None or todo is None) and latent_hw is not None
+            host = HostConfig(block_out_channels=tuple(cfg.block_out_channels), layers_per_block=cfg.layers_per_block,
+                              num_heads=tuple(cfg.num_heads))
+            h, w = latent_hw
+            if tome is not None:
+                self.merging = tome_blocks(host, h, w, tome["ratio"], tome.get("max_downsample", 1))
+            else:
+                self.pooling = todo_blocks(host, h, w, todo.get("factor", 2), todo.get("factor_level_2", 1))
         self.p = OM._sub(params, "base_unet.")
         self.p_cam = OM._sub(params, "camera_encoder.") if cams is not None else None
         self.scale, self.strength, self.freeu = img_ref_scale, strength, freeu
@@ -141,6 +171,23 @@ class Cond:
             if text_all.shape[0] < 2:
                 return None
             text_all = text_all.roll(1, 0)
+        option = wrong is not None and wrong.startswith(("tome_", "todo_"))
+        if option and feature not in (self.merging if wrong.startswith("tome_") else self.pooling):
+            return None
+        if wrong == "todo_corner" and self.todo.get("method", "nearest") == "area":         # (a mean has no corner)
+            return None
+        tables = None
+        if feature in self.merging and self.tables is not None:
+            tables = self.tables[feature]
+            if wrong == "tome_stale_table":
+                names = list(self.merging)
+                same = [n for n in names[:names.index(feature)] if self.merging[n][:2] == self.merging[feature][:2]]
+                if not same:
+                    return None
+                tables = self.tables[same[-1]]
+            tables = tables.long().cpu().reshape(self.B, -1)
+        elif wrong == "tome_stale_table":
+            return None
         out = torch.empty_like(x)
         pos = {r: i for i, r in enumerate(rows)}
         for grp in self.groups:
@@ -157,11 +204,41 @@ class Cond:
                         return None
                 ref = ref_all[grp.ref_rows]
                 ref_wrong = ref_all.roll(1, 0)[grp.ref_rows]
-                hook = self._adapter_hook(feature, heads, len(grp.rows), sel, ref, ref_wrong, wrong)
-            out[here] = U.transformer_2d(self.p, name, x[here], text, heads, cfg.norm_num_groups, hook, feature)
+            if wrong == "tome_roll_tables" and len(sel) < 2:
+                return None
+            rec = {}
+            with self._option(feature, tables, [grp.rows[i] for i in sel], wrong if option else None, rec) as pool:
+                if ad:
+                    hook = self._adapter_hook(feature, heads, len(grp.rows), sel, ref, ref_wrong, wrong, pool)
+                out[here] = U.transformer_2d(self.p, name, x[here], text, heads, cfg.norm_num_groups, hook, feature)
+            self._check_record(feature, rec, tuple(x.shape[-2:]), wrong)
         return out
 
-    def _adapter_hook(self, feature, heads, Bh, sel, ref, ref_wrong, wrong):
+    def _option(self, feature, tables, rows, wrong, rec):
+        """the option oracle's context around one block call of batch rows ``rows`` (yields todo_oracle's ``pool_ref`` or None)"""
+        sw = {wrong[5:]: True} if wrong is not None and wrong != "tome_stale_table" else {}
+        if self.tome is not None:
+            from tests.tome_ref import tome_oracle
+            tb = None if tables is None else {feature: tables[rows]}
+            return tome_oracle(**self.tome, tables=tb, record=rec, latent_hw=self.latent_hw, **sw)
+        if self.todo is not None:
+            from tests.todo_ref import todo_oracle
+            return todo_oracle(**self.todo, record=rec, latent_hw=self.latent_hw, **sw)
+        return contextlib.nullcontext()
+
+    def _check_record(self, feature, rec, hw, wrong):
+        """what the oracle did to the block is what ``tome_blocks`` / ``todo_blocks`` say of it"""
+        assert set(rec) == ({feature} if feature in self.merging or feature in self.pooling else set()), (feature, sorted(rec))
+        if feature in self.merging:
+            from tests.tome_ref import geometry
+            H, W, r = self.merging[feature]
+            dst, src = geometry(H, W)
+            slot = rec[feature]
+            assert hw == (H, W) and ((slot >= 0) & (slot < H * W - r)).all() and ((slot[:, src] < dst.numel()).sum(dim=1) == r).all(), feature
+        if feature in self.pooling and wrong != "todo_factor_off":
+            assert hw == self.pooling[feature][:2] and rec[feature] == self.pooling[feature][3], (feature, rec, self.pooling[feature])
+
+    def _adapter_hook(self, feature, heads, Bh, sel, ref, ref_wrong, wrong, pool=None):
         def hook(_feature, kind, hidden, attn_out):
             if wrong == f"adapter_{kind}_dropped":
                 return attn_out
@@ -173,6 +250,8 @@ class Cond:
                 w = dict(w)
                 w["to_out_ref.0.bias"] = torch.zeros_like(w["to_out_ref.0.bias"])
             r = ref_wrong if wrong == f"adapter_{kind}_other_ref" else ref
+            if pool is not None:                # (todo_also_ref, inside the self hook: the pooled reference; else r itself)
+                r = pool(r)
             return attn_out + self.scale * adapter_branch(w, hidden, r, heads, Bh, sel)
         return hook
 
@@ -230,7 +309,7 @@ def block_want(cond, name, ins, rows=None, wrong=None, taps=None, inputs=None):
     NA = (None, None)
     applies = {"conv_in": ("film_other_row", "film_neighbour"),
                "film": ("film_other_row", "film_neighbour"),
-               "attention": tuple(v for v in VARIANTS if v.startswith("adapter")) + ("text_other_row",),
+               "attention": tuple(v for v in VARIANTS if v.startswith("adapter")) + ("text_other_row",) + OPTION_VARIANTS["tome"] + OPTION_VARIANTS["todo"],
                "resnet": ("temb_other_row", "temb_neighbour_slice", "cat_swapped", "skip_post_film", "freeu_dropped")}
     kind = kind_of(name)
     if wrong is not None and wrong not in applies.get(kind, ()):
@@ -295,19 +374,26 @@ def branch_error(got, want, x, tol, slack=SLACK):
     return (got - want).norm().item(), tol * bnorm + slack * rnd, bnorm
 
 
-def check_taps(cond, taps, inputs, sample, out, rows=None, tol=None, what="", sliced=False):
+def check_taps(cond, taps, inputs, sample, out, rows=None, tol=None, what="", sliced=False, only=None, extra=None, need=None):
     """Every tap of one forward against ``block_want`` on the taps that feed it.  ``taps`` {name: (B, C, H, W) fp32} in execution
     order; ``inputs`` {name: input names} (the oracle's trace gives them; ``sample`` names the sample); ``out``: the forward's
-    output, the tap ``conv_out``.  ``rows``: the rows to compare (default: all); ``sliced``: the tensors hold these rows only.  Returns {kind: (worst error / bound, name, error / branch)}; raises on the first block beyond
+    output, the tap ``conv_out``.  ``rows``: the rows to compare (default: all); ``sliced``: the tensors hold these rows only; ``only``: the blocks to check
+    (default: all); ``extra``: {name: tensor} that blocks may read and that are not themselves checked (the stored deep feature of a
+    DeepCache shallow forward, whose ``taps`` / ``inputs`` hold the blocks it runs); ``need``: a dict that receives {kind: (the
+    tolerance the worst block of the kind needs, (error - slack * rounding term) / ||branch||, its name, its error / ||branch||)},
+    the transformer blocks that token merging / token downsampling changes under a kind of their own.  Returns {kind: (worst error / bound, name, error / branch)}; raises on the first block beyond
     its bound, by name."""
     tol = TOL if tol is None else tol
     rows_ = list(range(cond.B)) if rows is None else list(rows)
-    tensors = dict(taps)
+    tensors = dict(extra or {})
+    tensors.update(taps)
     tensors["sample"], tensors["conv_out"] = sample, out
     worst = {}
     pick = (lambda x: x) if sliced else (lambda x: x[rows_])
     assert list(taps) == [n for n in inputs if n != "conv_out"], f"{what}: taps {list(taps)} are not the blocks {list(inputs)}"
     for name in list(taps) + ["conv_out"]:
+        if only is not None and name not in only:
+            continue
         got = pick(tensors[name])
         if name == "conv_norm_out.in":
             assert torch.equal(got, pick(tensors[inputs[name][0]])), f"{what}: {name} is not the tensor of {inputs[name][0]}"
@@ -318,6 +404,12 @@ def check_taps(cond, taps, inputs, sample, out, rows=None, tol=None, what="", sl
         assert torch.isfinite(got).all(), f"{what}: {name}: non-finite output"
         err, bound, bnorm = branch_error(got, want, x, tol[kind])
         assert bnorm > 0, f"{what}: {name}: the reference branch is zero"
+        if need is not None:
+            changed = kind == "attention" and (feature_of(name) in cond.merging or feature_of(name) in cond.pooling)
+            key = kind + (" (merged)" if cond.merging else " (pooled)") if changed else kind
+            needs = (err - (bound - tol[kind] * bnorm)) / bnorm
+            if key not in need or needs > need[key][0]:
+                need[key] = (needs, name, err / bnorm)
         assert err <= bound, (f"{what}: first failing block {name} ({kind}): branch error {err / bnorm:.4g} of ||branch|| > bound "
                               f"{bound / bnorm:.4g} (tol {tol[kind]:g})")
         if kind not in worst or err / bound > worst[kind][0]:
@@ -325,15 +417,35 @@ def check_taps(cond, taps, inputs, sample, out, rows=None, tol=None, what="", sl
     return worst
 
 
-def report(what, worst):
+def eligible_and_readers(cond, inputs):
+    """the transformer blocks that ``cond``'s option changes and the blocks that read their outputs directly"""
+    own = {n for n in inputs if ".attentions." in n and (feature_of(n) in cond.merging or feature_of(n) in cond.pooling)}
+    return own | {n for n, ins in inputs.items() if own & set(ins)}
+
+
+def shallow_blocks(cfg, inputs, branch):
+    """(names, deep): the blocks of ``inputs`` that a DeepCache shallow forward of ``branch`` runs, in order -- conv_in, layers
+    0..branch of down_blocks.0, the last branch + 2 layers of the last up block, what follows them -- and the name of the tensor the
+    refresh forward stores: the hidden input of ``deepcache_ref.deep_key``"""
+    from tests.deepcache_ref import deep_key
+    n, j0 = cfg.num_levels, cfg.layers_per_block - 1 - branch
+    keep = {"conv_in", f"film.up_{n - 1}", "conv_norm_out.in", "conv_out"}
+    keep |= {f"down_blocks.0.{k}.{j}" for j in range(branch + 1) for k in ("resnets", "attentions")}
+    keep |= {f"up_blocks.{n - 1}.{k}.{j}" for j in range(j0, cfg.layers_per_block + 1) for k in ("resnets", "attentions")}
+    return [x for x in inputs if x in keep], inputs[deep_key(cfg, branch)][0]
+
+
+def report(what, worst, need=None):
     print(f"{what}: worst branch error per block kind, as a fraction of its bound")
     for kind, (frac, name, rel) in sorted(worst.items()):
         print(f"  {kind:<12} {frac:6.3f} of the bound ({rel:.3e} of ||branch||) at {name}")
+    for kind, (tol, name, rel) in sorted((need or {}).items()):
+        print(f"  {kind:<18} needs tol {tol:9.2e} (error {rel:.3e} of ||branch||) at {name}")
 
 
 # ---------------------------------------------------------------------------------------------- the cases of the two test files
 def make_case(name, cfg, params, batch, hw, text_len, *, cam=True, img=True, ref_batch=None, layout=None, freeu=None, seed=0,
-              cam_dim=96):
+              cam_dim=96, tome=None, todo=None):
     """Inputs of one forward, built as parity_util.make_inputs builds them, with one timestep per row.  ``layout``: None, or
     ("views", V, g) / ("objects", O, V, g) / ("ragged", counts, g) -- ``batch`` is then ignored.  ``ref_batch`` (ordinary
     forward): rows of the reference, default ``batch``; half of it is the guidance form."""
@@ -363,7 +475,7 @@ def make_case(name, cfg, params, batch, hw, text_len, *, cam=True, img=True, ref
     # one timestep per row, neighbours far apart (another row's time projection is then a different vector, not a near copy)
     t = torch.tensor([(981, 21, 501, 261, 741, 141, 621, 381)[b % 8] for b in range(batch)], dtype=torch.float32)
     c = SimpleNamespace(name=name, cfg=cfg, params=params, B=batch, sample=inp["sample"][:batch], t=t, freeu=freeu, kw=kw, groups=groups,
-                        cams=(inp["src"][:batch], inp["tgt"][:batch], inp["proj"]) if cam else None, lat=None, text=inp["text"][:batch])
+                        cams=(inp["src"][:batch], inp["tgt"][:batch], inp["proj"]) if cam else None, lat=None, text=inp["text"][:batch], tome=tome, todo=todo)
     if layout is not None:
         c.text, c.lat = inp["text"][:g * O], inp["lat"][:O]
     elif img:
@@ -371,18 +483,63 @@ def make_case(name, cfg, params, batch, hw, text_len, *, cam=True, img=True, ref
     return c
 
 
-def case_cond(c, feats, round_text=True):
-    """the conditioning of case ``c`` around the encoder maps ``feats`` (the engine's kept ones; the oracle's own on the CPU)"""
-    return Cond(c.cfg, c.params, c.B, c.t, c.text, c.cams, feats, c.groups, c.freeu, round_text=round_text)
+def case_cond(c, feats, round_text=True, tome_tables=None, t=None):
+    """the conditioning of case ``c`` around the encoder maps ``feats`` (the engine's kept ones; the oracle's own on the CPU);
+    ``tome_tables``: the slot tables of the forward (token merging); ``t``: other timesteps than the case's"""
+    return Cond(c.cfg, c.params, c.B, c.t if t is None else t, c.text, c.cams, feats, c.groups, c.freeu, round_text=round_text,
+                tome=getattr(c, "tome", None), todo=getattr(c, "todo", None), tome_tables=tome_tables, latent_hw=tuple(c.sample.shape[-2:]))
 
 
-def oracle_forward(c, _in_freeu=False):
+def oracle_forward(c, _in_freeu=False, tables_out=None, fault=None):
     """(out, taps, inputs, feats) of case ``c`` by the ORACLE's forward: one call, or -- a layout forward -- the independent
-    calls of its definition, rows scattered.  ``taps`` {name: tensor} without ``conv_out``; ``inputs`` {name: input names}."""
+    calls of its definition, rows scattered.  ``taps`` {name: tensor} without ``conv_out``; ``inputs`` {name: input names}.
+    A case with ``tome`` / ``todo`` runs under the option oracle; ``tables_out``: a dict that receives the slot tables token
+    merging used, {feature: (B, H*W)}.  ``fault`` = (block name, variant of ``OPTION_VARIANTS``, Cond): that one block computes
+    the variant, the rest of the forward is right (what a single-block fault does to the OUTPUT)."""
     if c.freeu is not None and not _in_freeu:
         from tests.freeu_ref import freeu_oracle
         with freeu_oracle(**c.freeu):
-            return oracle_forward(c, True)
+            return oracle_forward(c, True, tables_out, fault)
+    option, rec = contextlib.nullcontext(), {}
+    if getattr(c, "tome", None) is not None:
+        from tests.tome_ref import tome_oracle
+        option = tome_oracle(**c.tome, record=rec)
+    elif getattr(c, "todo", None) is not None:
+        from tests.todo_ref import todo_oracle
+        option = todo_oracle(**c.todo)
+    with option, _one_block_fault(fault):
+        return _oracle_forward(c, rec, tables_out)
+
+
+@contextlib.contextmanager
+def _one_block_fault(fault):
+    """``oracle.sd21_unet.transformer_2d`` answers block ``fault[0]`` with ``Cond.transformer(wrong=fault[1])`` on the rows of the
+    call (found by the call's input: the case's rows in order, or -- a layout forward -- the rows of the group being computed)"""
+    if fault is None:
+        yield
+        return
+    block, variant, cond = fault
+    inner = U.transformer_2d
+    calls = {"n": 0}
+
+    def transformer(p, key, x, text, heads, groups, attn_hook, hook_name):
+        if key != block or attn_hook is None and cond.feats is not None:          # (the encoder pass has no adapter hook)
+            return inner(p, key, x, text, heads, groups, attn_hook, hook_name)
+        rows = cond.groups[calls["n"]].rows if len(cond.groups) > 1 else list(range(cond.B))
+        calls["n"] += 1
+        U.transformer_2d = inner
+        try:
+            return cond.transformer(block, x, rows, variant)
+        finally:
+            U.transformer_2d = transformer
+    U.transformer_2d = transformer
+    try:
+        yield
+    finally:
+        U.transformer_2d = inner
+
+
+def _oracle_forward(c, rec, tables_out):
     kw = dict(img_ref_scale=0.3, cam_modulation_strength=0.2)
     if c.cams is not None:
         kw["fourier_proj"] = c.cams[2]
@@ -398,6 +555,8 @@ def oracle_forward(c, _in_freeu=False):
 
     if c.groups is None:
         out, trace, feats = call(list(range(c.B)), c.text, c.lat)
+        if tables_out is not None:
+            tables_out.update(rec)
         inputs = {n: i for n, (_, i) in trace.items()}
         taps = {n: x for n, (x, _) in trace.items() if n != "conv_out"}
         return out, taps, inputs, (feats or None)
@@ -416,6 +575,9 @@ def oracle_forward(c, _in_freeu=False):
             inputs[n] = i
         for n, x in f.items():
             feats.setdefault(n, torch.empty(nref, *x.shape[1:]))[grp.ref_rows] = x
+        if tables_out is not None:
+            for n, s in rec.items():
+                tables_out.setdefault(n, torch.zeros(c.B, s.shape[1], dtype=torch.long))[grp.rows] = s
     return out, taps, inputs, feats
 
 
@@ -449,6 +611,27 @@ def tiny_cases(cfg, params):
         mk("objects_o2_v2_g2", 0, 16, 7, cam=False, layout=("objects", 2, 2, 2)),
         mk("ragged_2_1_g2", 0, 16, 7, cam=False, layout=("ragged", (2, 1), 2)),
         mk("freeu_b2_img", 2, 16, 7, cam=False, freeu=dict(SD21)),
+    ])
+
+
+AREA22 = dict(factor=2, factor_level_2=2, method="area")
+
+
+def option_cases(cfg, params):
+    """the tiny token-merging / token-downsampling cases of tests/test_block_parity_options_gpu.py, by name: the smallest shapes
+    at which level 0 merges and level 1 still has a 2 x 2 map"""
+    from tests.freeu_ref import SD21
+    from tests.todo_ref import PARITY_SETTING as TODO
+    from tests.tome_ref import PARITY_SETTING as TOME
+    mk = lambda name, *a, **k: (name, make_case(name, cfg, params, *a, **k))      # noqa: E731
+    return dict([
+        mk("tome_b2", 2, 16, 7, tome=dict(TOME)), mk("tome_b2_md2", 2, 16, 7, tome=dict(ratio=0.5, max_downsample=2)),
+        mk("tome_wide_b2", 2, (8, 24), 7, tome=dict(TOME)),
+        mk("todo_b2", 2, 16, 7, todo=dict(TODO)), mk("todo_b2_area22", 2, 16, 7, todo=dict(AREA22)),
+        mk("todo_wide_b2", 2, (8, 24), 7, todo=dict(TODO)),
+        mk("tome_views_v2_g2", 0, 16, 7, cam=False, layout=("views", 2, 2), tome=dict(TOME)),
+        mk("todo_objects_o2_v2_g2", 0, 16, 7, cam=False, layout=("objects", 2, 2, 2), todo=dict(TODO)),
+        mk("todo_freeu_b2", 2, 16, 7, cam=False, freeu=dict(SD21), todo=dict(AREA22)),
     ])
 
 

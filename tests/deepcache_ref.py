@@ -40,7 +40,7 @@ def deepcache_oracle(mode, store: dict, branch: int = 0):
     orig_forward, orig_resnet = OU.unet_forward, OU.resnet_block
     state = {"cfg": None}
 
-    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None):
+    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None, **kw):
         prev = state["cfg"]
         state["cfg"] = cfg if capture is None else None
         if capture is None and callable(mode):
@@ -48,7 +48,7 @@ def deepcache_oracle(mode, store: dict, branch: int = 0):
             assert count["mode"] in ("record", "replay"), count["mode"]
             count["k"] += 1
         try:
-            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture)
+            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture, **kw)
         finally:
             state["cfg"] = prev
 

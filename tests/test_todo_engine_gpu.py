@@ -20,6 +20,13 @@ the switch-off forward / to the plain oracle):
   ragged (2, 1), g = 2:    off 1.263e-2 -> 1.894e-2, on 1.266e-2 (rows 1.13e-2 .. 1.52e-2); 1.877e-1 / 1.879e-1
   FreeU (SD-2.1 setting) + (2, 2, area): off 1.293e-2 -> 1.940e-2, on 1.226e-2; 2.176e-1 / 2.178e-1
 
+What this bound cannot judge is judged block by block in tests/test_block_parity_options_gpu.py: every block of a ToDo forward
+against the ToDo oracle's function of that block on the engine's own input.  ``also_ref`` is the example -- 2.17e-2 from the
+engine's result here, beside a bound of 1.97e-2, and in ONE block it moves the oracle's output by 1.3e-2 .. 1.4e-2, inside the
+bound; at the block it is 2.8e-2 of the branch and more, two block bounds away and more (tests/test_block_parity_options_cpu.py),
+so an engine that pooled the reference K/V in one block would fail there.  The same file runs ToDo at the SD-2.1 topology (5 and
+10 heads, batch 1 and 8), which no test here does.
+
 The inputs are ``parity_util.make_inputs``' at seed 0, as in the token-merging engine test, with one exception that
 ``todo_ref.parity_inputs`` states and tests/test_todo_cpu.py justifies on the ORACLE alone: under white noise the distance between
 downsampling on and off falls like 1 / sqrt(keys) -- the oracle's own two results are 5.6e-2 apart at 48 x 48 (576 keys), the engine's

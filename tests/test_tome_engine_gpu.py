@@ -15,6 +15,13 @@ share of slots that differ from the oracle's own decisions -- one flipped src mo
   max_downsample 2: off 1.314e-2 -> 1.970e-2, on 1.316e-2, 15.7 %;  ragged (2, 1), g = 2: off 1.263e-2 -> 1.894e-2, on 1.280e-2;
   every ToMe result 1.5e-1 .. 2.0e-1 from the plain oracle.
 
+What this bound cannot judge: a fault in ONE eligible block.  Every wrong variant priced in tests/test_tome_cpu.py is wrong in all
+five blocks at once; a stale or another image's table, ``attn2`` merged as well or an un-merge through the neighbouring row in one
+block alone moves the output by 6.6e-2 .. 1.2e-1 on the oracle, and milder faults of one block stay inside 2e-2 (the ``also_ref``
+variant of tests/test_todo_engine_gpu.py does).  tests/test_block_parity_options_gpu.py holds every block of a ToMe forward to the
+oracle's function of that block on the engine's own input and tables (a single-block fault is 7 bounds away and more there:
+tests/test_block_parity_options_cpu.py), also at the SD-2.1 topology, batch 1 and 8, which no test here runs.
+
 The pipeline: ``generate_views`` adds nothing to a forward but the samplers' fused steps, which never see the setting, and the
 oracle loop under forced tables would need the tables of every step's forward; the wrapper path it uses
 (``MultiViewUNet._ensure_engine``, the cached reference, hipGraph replay) is what the forward tests below exercise, and

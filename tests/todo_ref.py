@@ -172,17 +172,20 @@ ORACLE_WRONG = ("levels_shift", "corner", "also_ref", "factor_off", "swap_method
 
 @contextlib.contextmanager
 def todo_oracle(factor=2, factor_level_2=1, method="nearest", *, levels_shift=0, corner=False, also_ref=False, factor_off=False,
-                swap_method=False, record=None):
+                swap_method=False, record=None, latent_hw=None):
     """Inside the block every MAIN-pass oracle forward (the forwards that do not pass ``capture``) runs ``attn1`` of the eligible
     transformer blocks as ``attention(n, ctx=downsample(n))``: every query, the keys and values of the downsampled LayerNorm rows.
     The adapter's "self" hook gets the full ``n``; everything else is the plain block.  ``record``: a dict that receives
-    ``{feature name: Nk}``.
+    ``{feature name: Nk}``.  ``latent_hw``: the latent size of a ``transformer_2d`` call made OUTSIDE ``unet_forward`` (one block
+    on its own, tests/block_ref.py); inside a forward the forward's own sample decides, as ever.  Yields ``pool_ref``: what the
+    reference feature map (Br, C, H, W) behind the adapter's self branch becomes -- itself, but for ``also_ref`` inside the self hook
+    of a downsampled block (a hook that does not go through ``oracle.mvd.image_cross_attention`` asks it).
     WRONG on purpose: ``levels_shift`` -- the level rule sees a latent 2^shift times coarser per side (the blocks of THAT level take
     ``factor``, the level below ``factor_level_2``, the finer ones nothing); ``corner`` -- nearest takes the cell's bottom-right token; ``also_ref`` -- the reference feature map behind the adapter's self
     branch is downsampled the same way, so the reference K/V are pooled too; ``factor_off`` -- f + 1; ``swap_method`` -- the other method."""
     from oracle import mvd as OM
     orig_forward, orig_tf, orig_ica = OU.unet_forward, OU.transformer_2d, OM.image_cross_attention
-    state = {"latent": None, "ref_pool": None}
+    state = {"latent": None if latent_hw is None else tuple(latent_hw), "ref_pool": None}      # (outside a forward)
     meth = METHODS[1 - METHODS.index(method)] if swap_method else method
 
     def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None, **kw):
@@ -193,12 +196,15 @@ def todo_oracle(factor=2, factor_level_2=1, method="nearest", *, levels_shift=0,
         finally:
             state["latent"] = prev
 
-    def ref_attention(w, hidden, ref_nchw, heads, *a, **kw):
+    def pool_ref(ref_nchw):
         if state["ref_pool"] is not None:
             fr, Br, Cr, Hr, Wr = (state["ref_pool"],) + tuple(ref_nchw.shape)
             rows = downsample(ref_nchw.permute(0, 2, 3, 1).reshape(Br, Hr * Wr, Cr), Hr, Wr, fr, meth, corner=corner)
             ref_nchw = rows.reshape(Br, Hr // fr, Wr // fr, Cr).permute(0, 3, 1, 2)
-        return orig_ica(w, hidden, ref_nchw, heads, *a, **kw)
+        return ref_nchw
+
+    def ref_attention(w, hidden, ref_nchw, heads, *a, **kw):
+        return orig_ica(w, hidden, pool_ref(ref_nchw), heads, *a, **kw)
 
     def transformer(p, key, x, text, heads, groups, attn_hook, hook_name):
         lat = state["latent"]
@@ -244,6 +250,6 @@ def todo_oracle(factor=2, factor_level_2=1, method="nearest", *, levels_shift=0,
 
     OU.unet_forward, OU.transformer_2d, OM.image_cross_attention = forward, transformer, ref_attention
     try:
-        yield
+        yield pool_ref
     finally:
         OU.unet_forward, OU.transformer_2d, OM.image_cross_attention = orig_forward, orig_tf, orig_ica

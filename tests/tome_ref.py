@@ -175,22 +175,25 @@ def block_merges(latent_hw, H, W, ratio, max_downsample):
 
 @contextlib.contextmanager
 def tome_oracle(ratio, max_downsample=1, tables=None, *, merge_cross=False, levels_shift=0, roll_tables=False, zero_merged=False,
-                record=None):
+                neighbour_row=False, record=None, latent_hw=None):
     """Inside the block every MAIN-pass oracle forward (the forwards that do not pass ``capture``) merges in front of ``attn1`` of
     the eligible transformer blocks: n -> merge(n), attn1 (and the adapter's "self" hook) on the merged rows, un-merge, residual.
     ``tables``: ``{feature name: slot (B, H*W)}`` forces the decisions (the engine's own, from ``MVDEngine.tome_tables()``);
     otherwise they are the definition's on the oracle's own LayerNorm output.  ``record``: a dict that receives the tables used.
+    ``latent_hw``: the latent size of a ``transformer_2d`` call made OUTSIDE ``unet_forward`` (one block on its own,
+    tests/block_ref.py); inside a forward the forward's own sample decides, as ever, and the encoder pass never merges.
     WRONG on purpose: ``merge_cross`` -- attn2 runs on merged rows as well; ``levels_shift`` -- the eligibility test sees a latent
     2^shift times coarser per side: only the blocks of THAT level merge; ``roll_tables`` -- every image uses
-    the table of the next image of the batch; ``zero_merged`` -- merged src get no attention output."""
+    the table of the next image of the batch; ``zero_merged`` -- merged src get no attention output; ``neighbour_row`` -- every
+    token un-merges from the row of the token after it (``unmerge(neighbour_row=True)``)."""
     orig_forward, orig_tf = OU.unet_forward, OU.transformer_2d
-    state = {"latent": None}
+    state = {"latent": None if latent_hw is None else tuple(latent_hw)}      # (outside a forward; a forward sets its own)
 
-    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None):
+    def forward(p, cfg, sample, timestep, text, attn_hook=None, block_hook=None, capture=None, **kw):
         prev = state["latent"]
         state["latent"] = tuple(sample.shape[-2:]) if capture is None else None
         try:
-            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture)
+            return orig_forward(p, cfg, sample, timestep, text, attn_hook=attn_hook, block_hook=block_hook, capture=capture, **kw)
         finally:
             state["latent"] = prev
 
@@ -228,7 +231,7 @@ def tome_oracle(ratio, max_downsample=1, tables=None, *, merge_cross=False, leve
             a = OU.attention(p, f"{b}.{attn}", m, m if ctx_self else text, heads)
             if attn_hook is not None:
                 a = attn_hook(hook_name, kind, m, a)
-            a = unmerge(a, slot)
+            a = unmerge(a, slot, neighbour_row=neighbour_row)
             if zero_merged:
                 a = torch.where(((slot < nd) & ~is_dst[None])[:, :, None], torch.zeros_like(a), a)
             return a
