@@ -646,6 +646,25 @@ int mvd_op_sampler_step_apg(const float* model_out, float guidance_scale, float 
                             float* x0_out, int64_t rows, int64_t n_row, void* stream);
 /* The partition of a row by the two entry points above, out[4] as mvd_debug_cfg_rescale_plan. */
 int mvd_debug_apg_plan(int64_t n_row, int* out);
+/* One UniPC step (Zhao et al., NeurIPS 2023; diffusers-0.32.2 UniPCMultistepScheduler with predict_x0, restated; SURVEY.md 8f row
+ * N23): the corrector of the previous step and the predictor of this one in ONE launch.  mvd_amd/scheduler.py computes the
+ * per-step scalars on the host; nothing is uploaded.  Per element:
+ *   m  = guided ? u + guidance_scale*(c - u) : model_out   ([uncond | cond] stacked on the batch dim: 2n floats when guided)
+ *   x0 = a0*m + a1*sample                                  (sample: this step's input, the uncorrected prediction)
+ *   xc = corr ? cx*last_sample + c0*h0 + c1*h1 + c2*h2 + ct*x0 : sample
+ *   out = px*xc + p0*x0 + p1*h0 + p2*h1 ;  if (xc_out) xc_out = xc ;  if (x0_out) x0_out = x0
+ * last_sample is the previous step's (corrected) sample, h0, h1, h2 the previous x0 predictions, newest first.  Every operation is
+ * one fp32 rounding, in this order: m = fma(c - u, g, u); x0 = fma(a0, m, a1*sample); xc = cx*last_sample, then fma(c0, h0, .),
+ * fma(c1, h1, .), fma(c2, h2, .), fma(ct, x0, .); out = px*xc, then fma(p0, x0, .), fma(p1, h0, .), fma(p2, h1, .).  A term whose
+ * coefficient is 0 is skipped and its pointer, which may be NULL, is never read; corr == 0 zeroes cx .. ct.  n % 4 == 0;
+ * last_sample is required with corr; h0 when c0 != 0 or p1 != 0, h1 when c1 != 0 or p2 != 0, h2 when c2 != 0.  In place is allowed
+ * for out == sample, xc_out == last_sample and x0_out == any one of h0 .. h2 (every element is read and then written by the same
+ * thread); an output that overlaps model_out or another output is an error; otherwise -1 (mvd_last_error), before anything is
+ * launched.  The history rotates on the host by rotating buffer roles: the kernel writes only the newest x0. */
+int mvd_op_unipc_step(const float* model_out, int guided, float guidance_scale, const float* sample, const float* last_sample,
+                      const float* h0, const float* h1, const float* h2, float a0, float a1, int corr, float cx, float c0, float c1,
+                      float c2, float ct, float px, float p0, float p1, float p2, float* out, float* xc_out, float* x0_out, int64_t n,
+                      void* stream);
 
 /* FreeU on the two inputs of an up-block resnet, ONE launch.  hidden [B][H*W][C] and skip [B][H*W][Cs] are bf16, token-major:
  *   hidden_out = hidden with channels [0, C / 2) multiplied by b (fp32 product, one rounding to bf16), the rest bit for bit;

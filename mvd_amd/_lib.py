@@ -212,6 +212,9 @@ _SIGS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "mvd_debug_apg_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int)]),
+    "mvd_op_unipc_step": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mvd_engine_set_freeu": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "mvd_engine_clear_freeu": (C.c_int, [C.c_void_p]),
     "mvd_engine_set_tome": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int]),

@@ -553,7 +553,7 @@ def create_mvd_pipeline(pretrained_model_name_or_path: str, dtype: torch.dtype =
     interpolated SNR-shifted DDPM scheduler (``scheduler_config`` is accepted and ignored like the reference, :401,
     420-421).  Text encoder / VAE are attached when a local snapshot directory provides them; nothing is downloaded.
     ``unet_config`` / ``init`` are keyword-only extensions for checkpoint-free construction (tests, synthetic weights);
-    ``sampler`` (keyword-only) picks the scheduler class of the shifted schedule: "ddpm" (default), "ddim", "dpmsolver++";
+    ``sampler`` (keyword-only) picks the scheduler class of the shifted schedule: "ddpm" (default), "ddim", "dpmsolver++", "unipc";
     ``text_encoder`` (keyword-only): "transformers" (default, today's optional component) or "hip" (``CLIPTextModelHIP`` and the
     native CLIP tokenizer from the snapshot: prompt strings without the transformers package; missing files are an error)."""
     from .pipeline import build_pipeline

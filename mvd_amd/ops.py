@@ -911,6 +911,32 @@ def apg_plan(n_row):
     return dict(threads=out[0], vec=out[1], wave=out[2], keep=out[3], passes=-(-int(n_row) // per_pass))
 
 
+def unipc_step(model_out, sample, a0, a1, px, p0, p1=0.0, p2=0.0, corr=False, cx=0.0, c0=0.0, c1=0.0, c2=0.0, ct=0.0,
+               last_sample=None, h0=None, h1=None, h2=None, guidance_scale=None, out=None, xc_out=None, x0_out=None):
+    """fp32 UniPC step, corrector and predictor in ONE launch: m = model_out, or u + g*(c - u) of the stacked (2B, ...)
+    [uncond | cond] when ``guidance_scale`` is given; x0 = a0*m + a1*sample ; xc = cx*last_sample + c0*h0 + c1*h1 + c2*h2 + ct*x0
+    when ``corr``, else sample ; out = px*xc + p0*x0 + p1*h0 + p2*h1 ; xc_out = xc ; x0_out = x0.  ``h0`` .. ``h2`` are the previous
+    x0 predictions, newest first; one whose coefficients are all 0 is not passed on (and may be None), ``last_sample`` goes only
+    with ``corr``.  ``out`` may be ``sample``, ``xc_out`` may be ``last_sample`` and ``x0_out`` may be one of ``h0`` .. ``h2``; no
+    output may overlap ``model_out``."""
+    guided = guidance_scale is not None
+    assert model_out.dtype == torch.float32 and sample.dtype == torch.float32
+    assert model_out.numel() == sample.numel() * (2 if guided else 1), (tuple(model_out.shape), tuple(sample.shape))
+    for t in (last_sample, h0, h1, h2, out, xc_out, x0_out):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == sample.numel())
+    corr = bool(corr)
+    if not corr:
+        cx = c0 = c1 = c2 = ct = 0.0
+    if out is None:
+        out = torch.empty_like(sample)
+    L.call("mvd_op_unipc_step", _p(model_out), int(guided), float(guidance_scale) if guided else 0.0, _p(sample),
+           _p(last_sample if corr else None), _p(h0 if (c0 != 0.0 or p1 != 0.0) else None),
+           _p(h1 if (c1 != 0.0 or p2 != 0.0) else None), _p(h2 if c2 != 0.0 else None), float(a0), float(a1), int(corr), float(cx),
+           float(c0), float(c1), float(c2), float(ct), float(px), float(p0), float(p1), float(p2), _p(out), _p(xc_out), _p(x0_out),
+           sample.numel(), _s())
+    return out
+
+
 def freeu(hidden, skip, H, W, b, s, hidden_out=None, skip_out=None):
     """FreeU (diffusers' ``apply_freeu``, threshold 1) on the two inputs of an up-block resnet, ONE launch (``mvd_op_freeu``).
     ``hidden`` (B, H*W, C) and ``skip`` (B, H*W, Cs) bf16, token-major -> ``(hidden', skip')``: channels [0, C // 2) of

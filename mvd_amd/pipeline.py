@@ -526,7 +526,7 @@ def _scheduler_from_snapshot(path) -> "Any":
     return DDPMScheduler(**cfg)
 
 
-SAMPLERS = ("ddpm", "ddim", "dpmsolver++")
+SAMPLERS = ("ddpm", "ddim", "dpmsolver++", "unipc")
 
 
 def _sampler_config_from_snapshot(path) -> Dict[str, Any]:
@@ -542,7 +542,7 @@ def _sampler_config_from_snapshot(path) -> Dict[str, Any]:
 def _make_scheduler(path, sampler: str):
     """The interpolated SNR shift (scale 6, mvd_unet.py:420-428) of the snapshot's schedule, handed to the chosen
     sampler's class (``ShiftSNRScheduler.from_scheduler(..., scheduler_class=)``)."""
-    from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, ShiftSNRScheduler
+    from .scheduler import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, ShiftSNRScheduler, UniPCMultistepScheduler
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler={sampler!r}: expected one of {SAMPLERS}")
     base_scheduler = _scheduler_from_snapshot(path)
@@ -550,7 +550,7 @@ def _make_scheduler(path, sampler: str):
         return ShiftSNRScheduler.from_scheduler(noise_scheduler=base_scheduler, shift_mode="interpolated", shift_scale=6.0,
                                                 scheduler_class=DDPMScheduler)
     base_scheduler.config = SimpleNamespace(**{**vars(base_scheduler.config), **_sampler_config_from_snapshot(path)})
-    cls = DDIMScheduler if sampler == "ddim" else DPMSolverMultistepScheduler
+    cls = {"ddim": DDIMScheduler, "dpmsolver++": DPMSolverMultistepScheduler, "unipc": UniPCMultistepScheduler}[sampler]
     return ShiftSNRScheduler.from_scheduler(noise_scheduler=base_scheduler, shift_mode="interpolated", shift_scale=6.0,
                                             scheduler_class=cls)
 
@@ -625,7 +625,7 @@ def build_pipeline(pretrained_model_name_or_path, dtype, use_camera_conditioning
     """``create_mvd_pipeline`` (mvd_unet.py:388-453): scheduler swap to the interpolated SNR shift (scale 6, hard-coded
     there, :420-428), ``MultiViewUNet`` as ``pipeline.unet``, the three attributes of :449-451.  Nothing is fetched: the
     name resolves to local snapshot files (hub.resolve_snapshot) or the call raises.  ``sampler``: "ddpm" (the
-    reference's ancestral DDPM, the default), "ddim" or "dpmsolver++" -- the same shifted schedule in another class.
+    reference's ancestral DDPM, the default), "ddim", "dpmsolver++" or "unipc" -- the same shifted schedule in another class.
     ``text_encoder``: "transformers" (the default: transformers' CLIP when the package and the snapshot files exist, else none)
     or "hip" (``CLIPTextModelHIP`` + the native tokenizer from the snapshot; an error when they are missing)."""
     from .hub import resolve_snapshot

@@ -27,12 +27,15 @@ the device.
   the setting, the update itself is in the docstring of ``ops.apg``.  Applied only when guidance is active; the projection, the
   norm cap, the momentum update, the optional rescale and the step are ONE launch (``mvd_op_sampler_step_apg``).  The schedulers
   hold no APG state: the momentum buffer is the caller's.  Unpinned against diffusers; pinned by tests/apg_ref.py.
+* ``UniPCMultistepScheduler`` (Zhao et al., NeurIPS 2023) restates diffusers-0.32.2's class of that name for
+  data prediction, orders 1 - 3, bh1 / bh2: the corrector of the previous step and the predictor of this one are ONE launch
+  (``mvd_op_unipc_step``).  Unpinned against diffusers; pinned by tests/unipc_ref.py and the identity UniP-2 (bh2) == DPM-Solver++ 2M.
 """
 from __future__ import annotations
 
 import math
 from types import SimpleNamespace
-from typing import Any, Optional
+from typing import Any, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -585,6 +588,245 @@ class DPMSolverMultistepScheduler(_SolverSchedule):
         ``apg`` / ``momentum_buffer``: as ``DDIMScheduler.step_guided``."""
         return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample, guidance_rescale, apg,
                                                       momentum_buffer))
+
+
+class UniPCCoefficients(NamedTuple):
+    """The scalars of one ``mvd_op_unipc_step`` launch: x0 = a0*m + a1*x ; xc = cx*xl + c0*h0 + c1*h1 + c2*h2 + ct*x0 when ``corr``,
+    else x ; y = px*xc + p0*x0 + p1*h0 + p2*h1 (xl: the previous step's corrected sample; h0, h1, h2: the previous x0 predictions,
+    newest first)."""
+    a0: float
+    a1: float
+    corr: bool
+    cx: float
+    c0: float
+    c1: float
+    c2: float
+    ct: float
+    px: float
+    p0: float
+    p1: float
+    p2: float
+
+
+class UniPCMultistepScheduler(_SolverSchedule):
+    """diffusers-0.32.2 ``UniPCMultistepScheduler`` (Zhao et al., NeurIPS 2023) for ``predict_x0=True`` (data prediction),
+    ``solver_order`` 1 / 2 / 3, ``solver_type`` bh2 / bh1, epsilon / v_prediction, ``lower_order_final``, ``disable_corrector`` (step
+    indices after which no corrector runs), ``timestep_spacing`` leading / linspace / trailing with ``steps_offset``,
+    ``final_sigmas_type="zero"``.  Defaults are SD-2.1's betas and v_prediction, as ``DDPMScheduler`` here; the grid is
+    DPM-Solver++'s; the sigmas are kept in float64.  Unpinned against diffusers (absent here); pinned by the textbook restatement
+    tests/unipc_ref.py and by identities (tests/test_unipc_cpu.py: UniP order 2 bh2 IS DPM-Solver++ 2M midpoint).
+
+    Call i corrects the sample the previous call predicted (UniC, from sigma_{i-1} to sigma_i, with this call's model output) and
+    predicts the next one (UniP, from sigma_i to sigma_{i+1}).  Both are affine in (model output, sample, last sample, x0 history),
+    so a call is ONE launch (``mvd_op_unipc_step``) whose coefficients ``step_coefficients`` computes on the host in fp64.  The
+    state is ``solver_order`` x0 buffers and one last-sample buffer per (shape, device); the history rotates by rotating the
+    buffers' roles, the kernel writes the newest x0 into the oldest slot.  ``set_timesteps`` resets everything."""
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "scaled_linear", trained_betas=None, solver_order: int = 2,
+                 prediction_type: str = "v_prediction", thresholding: bool = False, predict_x0: bool = True,
+                 solver_type: str = "bh2", lower_order_final: bool = True, disable_corrector=(), solver_p=None,
+                 use_karras_sigmas: bool = False, use_exponential_sigmas: bool = False, use_beta_sigmas: bool = False,
+                 timestep_spacing: str = "linspace", steps_offset: int = 0, final_sigmas_type: str = "zero",
+                 rescale_betas_zero_snr: bool = False, **_ignored):
+        if solver_order not in (1, 2, 3):
+            _unsupported(f"UniPC solver_order={solver_order}")
+        if solver_type not in ("bh1", "bh2"):
+            _unsupported(f"UniPC solver_type={solver_type!r}")
+        if not predict_x0:
+            _unsupported("UniPC predict_x0=False")
+        if solver_p is not None:
+            _unsupported("UniPC solver_p")
+        if thresholding or use_karras_sigmas or use_exponential_sigmas or use_beta_sigmas:
+            _unsupported("UniPC thresholding / Karras, exponential, beta sigmas")
+        if final_sigmas_type != "zero" or rescale_betas_zero_snr:
+            _unsupported("UniPC final_sigmas_type != 'zero' / rescale_betas_zero_snr")
+        disable_corrector = sorted({int(v) for v in disable_corrector})
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                                      thresholding=thresholding, predict_x0=predict_x0, solver_type=solver_type,
+                                      lower_order_final=lower_order_final, disable_corrector=disable_corrector, solver_p=solver_p,
+                                      use_karras_sigmas=use_karras_sigmas, use_exponential_sigmas=use_exponential_sigmas,
+                                      use_beta_sigmas=use_beta_sigmas, timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      final_sigmas_type=final_sigmas_type, rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._init_solver(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas, prediction_type,
+                          timestep_spacing)
+        self.disable_corrector = disable_corrector
+        self.sigmas = None
+        self._bufs = {}             # (shape, device) -> ([x0 buffers, newest first], the last-sample buffer)
+        self._state_key = None      # the buffers the previous step of this schedule wrote
+        self._step_index = None
+        self.lower_order_nums = 0
+        self.this_order = 0         # the predictor order of the previous step: the order of the next corrector
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
+        """The spaced grid of ``num_inference_steps`` timesteps, or an explicit integer grid ``timesteps``."""
+        if (num_inference_steps is None) == (timesteps is None):
+            raise ValueError("pass exactly one of num_inference_steps / timesteps")
+        T = self.config.num_train_timesteps
+        if timesteps is not None:
+            ts = np.asarray(timesteps).astype(np.int64)
+            if ts.ndim != 1 or ts.size == 0 or ts.min() < 0 or ts.max() >= T:
+                raise ValueError(f"timesteps must be a non-empty 1-D grid in [0, {T - 1}]")
+        else:
+            ts = self._grid(int(num_inference_steps), 1)
+        acp = self._acp[ts]
+        self._sig = [float(s) for s in np.sqrt((1.0 - acp) / acp)] + [0.0]       # final_sigmas_type "zero"
+        self.sigmas = torch.tensor(self._sig, dtype=torch.float64)
+        self.timesteps = torch.from_numpy(ts.copy())
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self._ts_host = ts.tolist()
+        self.num_inference_steps = len(ts)
+        self._step_index = None
+        self.lower_order_nums = 0
+        self.this_order = 0
+        self._state_key = None
+
+    def _order(self, i: int, lower_order_nums: int) -> int:
+        so = self.config.solver_order
+        return min(so, len(self._ts_host) - i if self.config.lower_order_final else so, lower_order_nums + 1)
+
+    def _point(self, k: int):
+        """(alpha, sigma_bar, lambda) at sigma_k"""
+        s = self._sig[k]
+        alpha = 1.0 / math.sqrt(s * s + 1.0)
+        sb = s * alpha
+        return alpha, sb, (math.inf if sb == 0.0 else math.log(alpha) - math.log(sb))
+
+    def _update(self, s0: int, order: int, corrector: bool):
+        """One UniP / UniC update from sigma_{s0} to sigma_{s0 + 1} of order ``order``, as (coefficient of the sample at s0,
+        coefficient of m0 = the x0 at s0, [coefficients of the x0 at s0 - 1, s0 - 2, ..], coefficient of the x0 at s0 + 1 (UniC))."""
+        alpha_t, sb_t, lam_t = self._point(s0 + 1)
+        _, sb_s0, lam_s0 = self._point(s0)
+        h = lam_t - lam_s0
+        hh = -h
+        phi1 = math.expm1(hh)                                   # -1 at the zero final sigma, h = +inf
+        cx, c_m0 = sb_t / sb_s0, -alpha_t * phi1
+        if order == 1 and not corrector:                        # UniP-1 is the DDIM step: no B(h) term
+            return cx, c_m0, [], 0.0
+        if sb_t == 0.0:
+            raise ValueError("a UniPC step of order > 1 onto the zero final sigma is undefined (lower_order_final=True takes "
+                             "order 1 there)")
+        if s0 - (order - 1) < 0:
+            raise ValueError(f"a UniPC update of order {order} at sigma index {s0} needs {order - 1} earlier points")
+        rks = [(self._point(s0 - k)[2] - lam_s0) / h for k in range(1, order)] + [1.0]
+        B = phi1 if self.config.solver_type == "bh2" else hh
+        R, b, h_phi_k, fact = [], [], phi1 / hh - 1.0, 1.0
+        for j in range(1, order + 1):                           # diffusers' recurrence: b[j - 1] = phi_{j + 1} * j! / B
+            R.append([r ** (j - 1) for r in rks])
+            b.append(h_phi_k * fact / B)
+            fact *= j + 1
+            h_phi_k = h_phi_k / hh - 1.0 / fact
+        if corrector:
+            rhos = [0.5] if order == 1 else np.linalg.solve(np.array(R), np.array(b)).tolist()
+        else:                                                   # rhos_p of order 2 is diffusers' literal 0.5, not the solve
+            rhos = [0.5] if order == 2 else np.linalg.solve(np.array(R)[:-1, :-1], np.array(b)[:-1]).tolist()
+            rhos = rhos + [0.0]
+        # x_t = cx*x - alpha_t*phi1*m0 - alpha_t*B*(sum_k rho_k (m_k - m0) / r_k + rho_last (m_t - m0))
+        hist = [-alpha_t * B * rho / r for rho, r in zip(rhos[:-1], rks[:-1])]
+        c_t = -alpha_t * B * rhos[-1]
+        return cx, c_m0 - sum(hist) - c_t, hist, c_t
+
+    def step_coefficients(self, step_index: int, order: Optional[int] = None, corrector: Optional[bool] = None,
+                          corrector_order: Optional[int] = None) -> UniPCCoefficients:
+        """The ``UniPCCoefficients`` of call ``step_index``.  ``order`` (the predictor's), ``corrector`` (whether UniC runs) and
+        ``corrector_order`` default to what a run from step 0 uses."""
+        if self.sigmas is None:
+            raise ValueError("call set_timesteps first")
+        i = int(step_index)
+        if not 0 <= i < len(self._ts_host):
+            raise ValueError(f"step_index={i} outside the schedule of {len(self._ts_host)} steps")
+        so = self.config.solver_order
+        if order is None:
+            order = self._order(i, min(i, so))
+        if corrector is None:
+            corrector = i > 0 and (i - 1) not in self.disable_corrector
+        if corrector and i == 0:
+            raise ValueError("the first step has no corrector")
+        alpha_s0, sb_s0, _ = self._point(i)
+        a0, a1 = self._x0_coefficients(alpha_s0, sb_s0)
+        cx = ct = 0.0
+        c = [0.0, 0.0, 0.0]
+        if corrector:
+            if corrector_order is None:
+                corrector_order = self._order(i - 1, min(i - 1, so))
+            cx, c[0], hist, ct = self._update(i - 1, int(corrector_order), True)
+            c[1:1 + len(hist)] = hist
+        px, p0, hist, _ = self._update(i, int(order), False)
+        p = (hist + [0.0, 0.0])[:2]
+        return UniPCCoefficients(a0, a1, bool(corrector), cx, c[0], c[1], c[2], ct, px, p0, p[0], p[1])
+
+    def _launch_unipc(self, model_out, guidance_scale, c: UniPCCoefficients, sample, last, hist, xc_out, x0_out):
+        """One ``mvd_op_unipc_step``.  ``guidance_scale`` None: a plain step of ``model_out``; else of the stacked [uncond | cond]."""
+        from . import ops
+        h = (list(hist) + [None] * 3)[:3]
+        return ops.unipc_step(model_out, sample, c.a0, c.a1, c.px, c.p0, c.p1, c.p2, corr=c.corr, cx=c.cx, c0=c.c0, c1=c.c1, c2=c.c2,
+                              ct=c.ct, last_sample=last, h0=h[0], h1=h[1], h2=h[2], guidance_scale=guidance_scale, xc_out=xc_out,
+                              x0_out=x0_out)
+
+    def _step(self, model_output, guidance_scale, timestep, sample):
+        if self.sigmas is None:
+            raise ValueError("call set_timesteps first")
+        if self._step_index is None:                           # diffusers' index_for_timestep
+            hits = [k for k, v in enumerate(self._ts_host) if v == int(timestep)]
+            self._step_index = len(self._ts_host) - 1 if not hits else hits[1] if len(hits) > 1 else hits[0]
+        i, n = self._step_index, len(self._ts_host)
+        if i >= n:
+            raise ValueError("step called more often than the schedule has timesteps: call set_timesteps again")
+        key = (tuple(sample.shape), sample.device)
+        if self._state_key is not None and self._state_key != key:
+            raise ValueError("a UniPC step needs the previous steps' x0 and last sample of the same shape and device: "
+                             "call set_timesteps to start a new trajectory")
+        # without a previous step of this run (a first call in mid-schedule) there is no last sample: no corrector, as in diffusers
+        corrector = i > 0 and (i - 1) not in self.disable_corrector and self._state_key is not None
+        order = self._order(i, self.lower_order_nums)
+        c = self.step_coefficients(i, order, corrector, self.this_order if corrector else None)
+        if key not in self._bufs:
+            new = lambda: torch.empty(sample.shape, device=sample.device, dtype=torch.float32)      # noqa: E731
+            self._bufs[key] = ([new() for _ in range(self.config.solver_order)], new())
+        hist, last = self._bufs[key]
+        # the next call's corrector reads this call's corrected sample; where none runs, it is not written
+        keep_last = i + 1 < n and i not in self.disable_corrector
+        out = self._launch_unipc(model_output, guidance_scale, c, sample, last, hist, last if keep_last else None, hist[-1])
+        hist.insert(0, hist.pop())                             # the slot just written is the newest: rotate the roles
+        self._state_key = key
+        self.this_order = order
+        self.lower_order_nums = min(self.lower_order_nums + 1, self.config.solver_order)
+        self._step_index = i + 1
+        return out
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator: Optional[torch.Generator] = None,
+             noise: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """One UniPC call on the GPU: the corrector of the previous step and the predictor of this one in ONE fused HIP kernel,
+        which also stores this step's x0 and corrected sample for the next; returns an object with ``prev_sample``.
+        Deterministic: ``generator`` / ``noise`` are accepted and unused."""
+        return SimpleNamespace(prev_sample=self._step(model_output, None, timestep, sample))
+
+    def step_guided(self, uncond_cond: torch.Tensor, guidance_scale: float, timestep, sample: torch.Tensor,
+                    noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                    guidance_rescale: float = 0.0, apg=None, momentum_buffer: Optional[torch.Tensor] = None):
+        """``step`` of uncond + guidance_scale*(cond - uncond), [uncond | cond] stacked on the batch dim: ONE launch.  With
+        ``guidance_rescale`` > 0 or ``apg`` (and ``guidance_scale`` > 1) TWO launches: ``ops.cfg_rescale`` / ``ops.apg``, then the
+        unguided step.  APG in ``space="x0"`` is not offered by UniPC (its step has no x0-space entry)."""
+        from . import ops
+        _check_rescale(guidance_rescale)
+        apg = _check_apg(apg, guidance_rescale)
+        if apg is not None and apg.space == "x0":
+            raise ValueError('apg: space="x0" is not implemented for UniPC (UniPCMultistepScheduler applies APG to the model output '
+                             'in a launch of its own); use space="output" or another sampler')
+        active = guidance_scale is not None and guidance_scale > 1.0
+        if active and apg is not None:
+            m = ops.apg(uncond_cond, guidance_scale, **apg.kwargs(), guidance_rescale=guidance_rescale, momentum_buffer=momentum_buffer)
+            return SimpleNamespace(prev_sample=self._step(m, None, timestep, sample))
+        if active and guidance_rescale > 0.0:
+            m = ops.cfg_rescale(uncond_cond, guidance_scale, guidance_rescale)
+            return SimpleNamespace(prev_sample=self._step(m, None, timestep, sample))
+        return SimpleNamespace(prev_sample=self._step(uncond_cond, guidance_scale, timestep, sample))
 
 
 class ShiftSNRScheduler:
